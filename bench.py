@@ -6,7 +6,9 @@ A step = one pass of the hot path over one batch of synthetic input: a batch of 
 three streams.  (Rounds 1-2 counted ONE MSM as a step, round 3 a batch of 32: the driver's 20 steps were 26 ms, then 0.8 s of a
 13 s run, and its sampler never saw the GPU busy; with 256 they are ~6 s.  `config.ms_per_msm` is the figure rounds 1-2 called
 ms_per_step; `value` -- pairs per second -- does not depend on the batch.)
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+(--dump-outputs: the points the last timed step returned, as canonical affine coordinates in DIR/msm_results.npy; the inputs are
+seeded, so two builds of the library can be compared output for output.)
 For N > 1 the driver launches one rank per GPU with torch.distributed.run; every rank owns its
 own 2^20 points of one N*2^20-point MSM (weak scaling), the 96-byte partial sums are exchanged
 with an RCCL all-gather and added on the device (RCCL has no elliptic-curve reduction).
@@ -80,7 +82,17 @@ def parse():
                         "ncclSend/ncclRecv on a single-process RCCL communicator)")
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                    help="nccl = RCCL over xGMI (default); gloo = host-staged gather (debug / boxes without RCCL), labelled as such")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed region, write what its last step computed to DIR/<name>.npy (float64; see dump_outputs): the same "
+                        "arguments give the same inputs, so two builds can be compared output for output")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    if a.warmup < 0:
+        p.error("--warmup must not be negative")
+    if a.dump_outputs and a.single_process:
+        p.error("--dump-outputs covers the torchrun path (without --single-process)")
+    return a
 
 
 def dlog_of_msm(curve_name, canon, k0, d, offset):
@@ -102,6 +114,38 @@ def point_of_dlog(curve_name, k):
     from oracle.pasta_oracle import CURVES
     C = CURVES[curve_name]
     return C.compress(C.mul(k % C.order, C.gen))
+
+
+def affine_limbs(curve_name, jac):
+    """(m, 12) uint64 Jacobian points in Montgomery form (reef_jacobian) -> (m, 2, 8) float64: the affine x and y in canonical form as
+    little-endian 32-bit limbs (exact in float64); the identity is (0, 0).  The form does not depend on the representative the library
+    returned, so the outputs of two builds compare limb for limb."""
+    import numpy as np
+    from oracle.pasta_oracle import CURVES, R256
+    p = CURVES[curve_name].base
+    rinv = pow(R256, -1, p)
+    rows = np.ascontiguousarray(jac, dtype=np.uint64).reshape(-1, 12)
+    out = np.zeros((rows.shape[0], 2, 8), dtype=np.float64)
+    for i, row in enumerate(rows):
+        x_, y_, z_ = (sum(int(row[4 * c + j]) << (64 * j) for j in range(4)) * rinv % p for c in range(3))
+        if z_ == 0:
+            continue
+        zi = pow(z_, -1, p)
+        for k, v in enumerate((x_ * zi * zi % p, y_ * zi * zi * zi % p)):
+            out[i, k] = [(v >> (32 * j)) & 0xFFFFFFFF for j in range(8)]
+    return out
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 or float64 only, 64 MB at most in all."""
+    import numpy as np
+    total = sum(v.nbytes for v in arrays.values())
+    if total > 64 << 20:
+        raise ValueError(f"--dump-outputs: {total} bytes is more than 64 MB")
+    os.makedirs(dirpath, exist_ok=True)
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        np.save(os.path.join(dirpath, name + ".npy"), v)
 
 
 def cpu_quota():
@@ -805,6 +849,11 @@ def main():
     last = (a.steps * MPS - 1) % nctx
     final_parts = parts[last].cpu().numpy().copy()
     final_result = results[last].cpu().numpy().copy()
+    if a.dump_outputs and rank == 0:
+        # what the callers of the last step received: each of its final min(MPS, nctx) MSMs still holds its result buffer (B points each)
+        held = range(a.steps * MPS - min(MPS, nctx), a.steps * MPS)
+        jac = np.stack([results[i % nctx].cpu().numpy().view(np.uint64).reshape(B, 12) for i in held])
+        dump_outputs(a.dump_outputs, {"msm_results": affine_limbs(a.curve, jac.reshape(-1, 12)).reshape(len(held), B, 2, 8)})
     single = None
     host_ms = None
     host_pageable = None

@@ -33,23 +33,31 @@ def test_hand_counts_of_the_brca_regexes():
 
 
 def test_the_literals_are_the_ones_the_reference_holds():
-    """The regexes are the reference's (tests/scripts/dna.sh), and its 1 MB documents hold the literals where the re-basing rule says."""
+    """The regexes are the reference's (tests/scripts/dna.sh), and its 1 MB documents hold the literals where the re-basing rule says.
+    Read from tests/golden/dna_fixture.json (oracle/gen_dna_fixture.py): the script's regex lines, and of each document its length and
+    the 10 000 characters after the 1 000 000-character base, where the literals sit."""
+    import json
     import os
+    import re
     from oracle.gen_replay_shapes import BRCA1_A, BRCA1_B, BRCA2_LENS
-    ref = "/root/reference/tests"
-    if not os.path.isdir(ref):
-        pytest.skip("the reference tree is not on this box")
-    sh = open(os.path.join(ref, "scripts", "dna.sh")).read().splitlines()
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dna_fixture.json")) as f:
+        fx = json.load(f)
+    sh = {int(k) - 1: v for k, v in fx["dna_sh"].items()}
     assert ("^.{43052424}" + BRCA1_A) in sh[5] and ("^.{43052424}" + BRCA1_A) in sh[7]                 # dna.sh:6 and :8
     assert ("^.{43050079}" + ".*".join(BRCA1_B)) in sh[6] and ("^.{43050079}" + ".*".join(BRCA1_B)) in sh[10]   # :7 and :11
-    import re
     lits = re.search(r'--re "\^\.\{32317478\}([ACGT.*]+)"', sh[12]).group(1).split(".*")                # :13
+
+    def find(doc, lit):                                                                               # position in the whole document
+        i = doc["tail"].find(lit)
+        return -1 if i < 0 else doc["tail_offset"] + i
     assert tuple(len(x) for x in lits) == BRCA2_LENS
-    doc = open(os.path.join(ref, "docs", "BRCA1_base1m+primary")).read()
-    assert len(doc) == 1010000 and doc.find(BRCA1_A) == 1000000 + 8129 and doc.find(BRCA1_B[0]) == 1000000 + 5784
+    doc = fx["docs"]["BRCA1_base1m+primary"]
+    assert doc["tail_offset"] == 1000000 and doc["tail_offset"] + len(doc["tail"]) == doc["length"]
+    assert doc["length"] == 1010000 and find(doc, BRCA1_A) == 1000000 + 8129 and find(doc, BRCA1_B[0]) == 1000000 + 5784
     assert 43052424 - 8129 == 43050079 - 5784                                                        # one base document, two offsets into the gene region
-    doc2 = open(os.path.join(ref, "docs", "BRCA2_base1m+primary")).read()
-    assert doc2.find(lits[0]) == 1000000 + 1970
+    doc2 = fx["docs"]["BRCA2_base1m+primary"]
+    assert doc2["tail_offset"] == 1000000 and doc2["tail_offset"] + len(doc2["tail"]) == doc2["length"] == 1010000
+    assert find(doc2, lits[0]) == 1000000 + 1970
 
 
 def test_outside_the_family_is_refused():
