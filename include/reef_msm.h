@@ -21,6 +21,8 @@
  * (it owns one HIP stream and one workspace); use one ctx (or clone) per concurrent caller.
  *
  * ABI changelog (reef_abi_version()):
+ *   7  the NIFS fold of a folding step on the device (reef_nifs_*, section 3f): R1CS cross term T, comm_T, the folds of W, E, u, X,
+ *      and the relaxed-R1CS check.  Nothing else changed.
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -40,7 +42,7 @@
  */
 #ifndef REEF_MSM_H
 #define REEF_MSM_H
-#define REEF_ABI_VERSION 6
+#define REEF_ABI_VERSION 7
 
 #include <stdbool.h>
 #include <stddef.h>
@@ -389,6 +391,43 @@ reef_status reef_derive_generators(int curve, const uint8_t *label, size_t label
                                    bool is_mont, reef_affine *out, int out_loc);
 /* SHAKE256(in) -> out_len bytes: the host half of the derivation, exported for tests and for callers that want the stream. */
 void reef_shake256(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_len);
+
+/* ---------------------------------------------------------------------------------------------
+ * (3f) Row N6: the vector work of one folding step, nova-snark's NIFS::prove [R] (Reef: RecursiveSNARK::prove_step,
+ * src/backend/framework.rs:668-675), over the SCALAR field of the curve (Pallas: Fq, Vesta: Fp).  Per step and curve:
+ *   T      = AZ1 o BZ2 + AZ2 o BZ1 - u1 CZ2 - CZ1          (o: entry-wise; the fresh instance has u2 = 1, E2 = 0)
+ *   comm_T = MSM(T, key)                                   (the existing MSM path, T never leaves the device)
+ *   W = W1 + r W2,  E = E1 + r T,  u = u1 + r,  X = X1 + r X2
+ * Recalled layouts [R]: z = W || u || X (num_vars + 1 + num_io entries; column num_vars is u), and the matrices as
+ * (row, col, value) triples, duplicates summed (R1CSShape::multiply_vec).  The points comm_W, comm_E of the folded
+ * instance (two scalar multiplications) stay with the caller.
+ *
+ * reef_nifs_create      one context per curve and R1CS shape, on `device`; every vector stays resident there.
+ * reef_nifs_set_matrix  which: 0 A, 1 B, 2 C.  Host triples in any order, row < num_cons, col < num_vars + 1 + num_io
+ *                       (REEF_ERR_ARG otherwise).  The device form (CSR, coefficient classes) is built once per call.
+ * reef_nifs_set_running the running relaxed instance: W (num_vars), E (num_cons; NULL: zeros), u (1), X (num_io), all
+ *                       in `loc` memory.  nova's first step: E = 0, u = 1.
+ * reef_nifs_commit_T    the fresh W2, X2 (loc memory): T on the device, kept resident with z2; *comm_T (HOST) = MSM of T
+ *                       over `key`: a reef_msm_ctx of the same curve and device holding at least num_cons points.  The
+ *                       MSM runs on the key ctx's stream (reef_msm_ctx_stream: the key ctx stays on that stream).
+ * reef_nifs_fold        the four folds with the host's challenge r; valid once after every commit_T (REEF_ERR_ARG else).
+ * reef_nifs_read        which: 0 W, 1 E, 2 T, 3 u, 4 X; the first `count` entries to the host, Montgomery form if to_mont.
+ * reef_nifs_check_relaxed  AZ o BZ == u CZ + E on the running instance (nova's is_sat_relaxed without the commitment
+ *                       check): *violations = rows that fail, *first_bad_row = the lowest of them (UINT64_MAX: none).
+ * is_mont: inputs in pasta Montgomery form, else canonical integers.  Calls on one context are serialised and return
+ * with their work done. */
+typedef struct reef_nifs_ctx reef_nifs_ctx;
+reef_status reef_nifs_create(reef_nifs_ctx **out, int curve, size_t num_cons, size_t num_vars, size_t num_io, int device);
+void reef_nifs_destroy(reef_nifs_ctx *ctx);
+reef_status reef_nifs_set_matrix(reef_nifs_ctx *ctx, int which, const uint32_t *row, const uint32_t *col, const reef_fe *val, size_t nnz,
+                                 bool is_mont);
+reef_status reef_nifs_set_running(reef_nifs_ctx *ctx, const reef_fe *W, const reef_fe *E, const reef_fe *u, const reef_fe *X, int loc,
+                                  bool is_mont);
+reef_status reef_nifs_commit_T(reef_nifs_ctx *ctx, reef_msm_ctx *key, const reef_fe *W2, const reef_fe *X2, int loc, bool is_mont,
+                               reef_jacobian *comm_T);
+reef_status reef_nifs_fold(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont);
+reef_status reef_nifs_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont);
+reef_status reef_nifs_check_relaxed(reef_nifs_ctx *ctx, uint64_t *violations, uint64_t *first_bad_row);
 
 /* ---------------------------------------------------------------------------------------------
  * (4) Runtime plumbing.

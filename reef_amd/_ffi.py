@@ -68,7 +68,7 @@ class KeyCacheStats(ctypes.Structure):
     _fields_ = [(n, c_uint64) for n in ("entries", "resident_keys", "resident_bytes", "builds", "hits", "clones", "misspeculated", "spares")]
 
 
-ABI_VERSION = 6     # REEF_ABI_VERSION of include/reef_msm.h this binding was written against
+ABI_VERSION = 7     # REEF_ABI_VERSION of include/reef_msm.h this binding was written against
 
 
 def build(force: bool = False, jobs: int = 4) -> str:
@@ -157,6 +157,14 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_sc_read": (c_int, [vp, c_int, c_size_t, vp]),
         "reef_sc_reset_table": (c_int, [vp]),
         "reef_sc_sync": (c_int, [vp]),
+        "reef_nifs_create": (c_int, [POINTER(vp), c_int, c_size_t, c_size_t, c_size_t, c_int]),
+        "reef_nifs_destroy": (None, [vp]),
+        "reef_nifs_set_matrix": (c_int, [vp, c_int, vp, vp, vp, c_size_t, c_bool]),
+        "reef_nifs_set_running": (c_int, [vp, vp, vp, vp, vp, c_int, c_bool]),
+        "reef_nifs_commit_T": (c_int, [vp, vp, vp, vp, c_int, c_bool, vp]),
+        "reef_nifs_fold": (c_int, [vp, vp, c_bool]),
+        "reef_nifs_read": (c_int, [vp, c_int, c_size_t, vp, c_bool]),
+        "reef_nifs_check_relaxed": (c_int, [vp, POINTER(c_uint64), POINTER(c_uint64)]),
         "reef_merkle_nodes": (c_uint64, [c_uint64]),
         "reef_merkle_commit": (c_int, [c_int, vp, vp, c_size_t, c_int, c_bool, vp, c_int, vp]),
         "reef_merkle_commit_devices": (c_int, [c_int, vp, vp, c_size_t, c_bool, vp, c_size_t, vp, vp, vp]),

@@ -478,6 +478,53 @@ reef_status reef_sc_sync(reef_sc_ctx *ctx) {
     return vt(ctx->curve)->sc_sync(ctx->impl);
 }
 
+// ---- row N6: the NIFS fold of one step
+struct reef_nifs_ctx {
+    int curve;
+    void *impl;
+};
+static const NifsVTable *nvt(int curve) { return curve == REEF_PALLAS ? pallas_nifs_vtable() : vesta_nifs_vtable(); }
+reef_status reef_nifs_create(reef_nifs_ctx **out, int curve, size_t num_cons, size_t num_vars, size_t num_io, int device) {
+    if (!out) { set_error("null argument"); return REEF_ERR_ARG; }
+    STATELESS_PROLOGUE(curve);
+    (void)v;
+    void *impl = nullptr;
+    REEF_TRY(guarded([&] { return nvt(curve)->create(&impl, num_cons, num_vars, num_io, device); }));
+    *out = new reef_nifs_ctx{curve, impl};
+    return REEF_OK;
+}
+void reef_nifs_destroy(reef_nifs_ctx *ctx) {
+    if (!ctx) return;
+    nvt(ctx->curve)->destroy(ctx->impl);
+    delete ctx;
+}
+reef_status reef_nifs_set_matrix(reef_nifs_ctx *ctx, int which, const uint32_t *row, const uint32_t *col, const reef_fe *val, size_t nnz, bool is_mont) {
+    SC_CHECK(ctx);
+    return guarded([&] { return nvt(ctx->curve)->set_matrix(ctx->impl, which, row, col, val, nnz, is_mont); });
+}
+reef_status reef_nifs_set_running(reef_nifs_ctx *ctx, const reef_fe *W, const reef_fe *E, const reef_fe *u, const reef_fe *X, int loc, bool is_mont) {
+    SC_CHECK(ctx);
+    return nvt(ctx->curve)->set_running(ctx->impl, W, E, u, X, loc, is_mont);
+}
+reef_status reef_nifs_commit_T(reef_nifs_ctx *ctx, reef_msm_ctx *key, const reef_fe *W2, const reef_fe *X2, int loc, bool is_mont, reef_jacobian *comm_T) {
+    SC_CHECK(ctx);
+    if (!key) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (key->curve != ctx->curve) { set_error("reef_nifs_commit_T: the key is of curve %d, the NIFS ctx of curve %d", key->curve, ctx->curve); return REEF_ERR_ARG; }
+    return guarded([&] { return nvt(ctx->curve)->commit_t(ctx->impl, key->impl, W2, X2, loc, is_mont, comm_T); });
+}
+reef_status reef_nifs_fold(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont) {
+    SC_CHECK(ctx);
+    return nvt(ctx->curve)->fold(ctx->impl, r, is_mont);
+}
+reef_status reef_nifs_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont) {
+    SC_CHECK(ctx);
+    return nvt(ctx->curve)->read(ctx->impl, which, count, out, to_mont);
+}
+reef_status reef_nifs_check_relaxed(reef_nifs_ctx *ctx, uint64_t *violations, uint64_t *first_bad_row) {
+    SC_CHECK(ctx);
+    return nvt(ctx->curve)->check(ctx->impl, violations, first_bad_row);
+}
+
 uint64_t reef_merkle_nodes(uint64_t n) {
     uint64_t total = 0, m = (n + 1) / 2;
     for (;;) {

@@ -397,4 +397,19 @@ struct CurveVTable {
 const CurveVTable *pallas_vtable();
 const CurveVTable *vesta_vtable();
 
+// Row N6: the NIFS fold of one step over the curve's scalar field (nifs_engine.inc; include/reef_msm.h 3f).  Its own table: make_vtable
+// (engine.inc) stays as it is.  key_impl: the impl of a reef_msm_ctx of the same curve.
+struct NifsVTable {
+    reef_status (*create)(void **impl, size_t num_cons, size_t num_vars, size_t num_io, int device);
+    void (*destroy)(void *impl);
+    reef_status (*set_matrix)(void *impl, int which, const uint32_t *row, const uint32_t *col, const reef_fe *val, size_t nnz, bool is_mont);
+    reef_status (*set_running)(void *impl, const reef_fe *W, const reef_fe *E, const reef_fe *u, const reef_fe *X, int loc, bool is_mont);
+    reef_status (*commit_t)(void *impl, void *key_impl, const reef_fe *W2, const reef_fe *X2, int loc, bool is_mont, reef_jacobian *comm_t);
+    reef_status (*fold)(void *impl, const reef_fe *r, bool is_mont);
+    reef_status (*read)(void *impl, int which, size_t count, reef_fe *out, bool to_mont);
+    reef_status (*check)(void *impl, uint64_t *violations, uint64_t *first_bad_row);
+};
+const NifsVTable *pallas_nifs_vtable();
+const NifsVTable *vesta_nifs_vtable();
+
 }  // namespace reef

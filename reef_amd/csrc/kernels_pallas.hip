@@ -5,10 +5,16 @@
 #include "mle_kernels.inc"
 #include "merkle_kernels.inc"
 #include "keygen_kernels.inc"
+#include "nifs_kernels.inc"
 #include "engine.inc"
+#include "nifs_engine.inc"
 namespace reef {
 const CurveVTable *pallas_vtable() {
     static const CurveVTable vt = make_vtable<0>();
+    return &vt;
+}
+const NifsVTable *pallas_nifs_vtable() {
+    static const NifsVTable vt = make_nifs_vtable<0>();
     return &vt;
 }
 }

@@ -1,0 +1,353 @@
+// Host side of row N6 (the NIFS fold of one step: nifs_kernels.inc); included after engine.inc.
+namespace reef {
+
+template <int C> struct NifsCtx {
+    static constexpr int F = 1 - C;      // scalar field of curve C
+    std::mutex mu;
+    int device = 0;
+    hipStream_t stream = nullptr;        // the pool stream of the call in progress (common.h: StreamLease)
+    StreamLease lease;
+    size_t num_cons = 0, num_vars = 0, num_io = 0, nz = 0;   // nz = num_vars + 1 + num_io
+    DevBuf rowptr[3], ent[3], side[3];   // CSR of A, B, C: row pointers, {col, class} per entry, general coefficients by entry
+    std::vector<u32> h_rowptr[3];        // host copies: the long-row list is made from them
+    bool has[3] = {false, false, false};
+    bool prepared = false;               // long_rows is up to date with the three matrices
+    DevBuf long_rows, seg_row, seg_first, part;   // long rows, their segments (nifs_kernels.inc: k_nifs_rows_long), partial sums
+    u32 nlong = 0, nseg = 0;
+    DevBuf z1, z2, E, T, stage, counters;
+    hipEvent_t ev = nullptr;             // orders the key ctx's stream after the upload of z2 (commit_T)
+    bool running = false, committed = false, have_t = false;
+    fe256 k254 = {};
+};
+
+// Every call enqueues on a pool stream and waits for it before it returns: the ctx holds no stream between calls.
+template <int C> struct NifsScope {
+    NifsCtx<C> *c;
+    explicit NifsScope(NifsCtx<C> *ctx) : c(ctx) {}
+    reef_status enter() { return c->lease.enter(c->device, &c->stream); }
+    ~NifsScope() {
+        if (!c->lease.counted) return;
+        (void)hipStreamSynchronize(c->stream);
+        c->lease.idle();
+    }
+};
+
+template <int C> static void nifs_free(NifsCtx<C> *c) {
+    if (!c) return;
+    if (c->lease.counted) (void)hipStreamSynchronize(c->stream);
+    c->lease.idle();
+    for (int k = 0; k < 3; ++k) { c->rowptr[k].release(); c->ent[k].release(); c->side[k].release(); }
+    for (DevBuf *b : {&c->long_rows, &c->seg_row, &c->seg_first, &c->part, &c->z1, &c->z2, &c->E, &c->T, &c->stage, &c->counters}) b->release();
+    if (c->ev) (void)hipEventDestroy(c->ev);
+    stream_pool().context_destroyed();
+    delete c;
+}
+
+template <int C> static reef_status v_nifs_create(void **impl, size_t num_cons, size_t num_vars, size_t num_io, int device) {
+    if (!impl || num_cons == 0 || num_cons >= (1ull << 31) || num_vars + 1 + num_io >= (1ull << 31)) {
+        set_error("reef_nifs_create: need 0 < num_cons < 2^31 and num_vars + 1 + num_io < 2^31");
+        return REEF_ERR_ARG;
+    }
+    int ndev = 0;
+    REEF_HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) { set_error("reef_nifs_create: no device %d", device); return REEF_ERR_ARG; }
+    REEF_ON_DEVICE(device);
+    NifsCtx<C> *c = new NifsCtx<C>();
+    c->device = device;
+    c->num_cons = num_cons;
+    c->num_vars = num_vars;
+    c->num_io = num_io;
+    c->nz = num_vars + 1 + num_io;
+    fe x254 = fe_zero();
+    x254.l[8] = 1u << 22;                // 2^(8 * 29 + 22)
+    REEF_SET_BOUND(x254, 1.0);
+    constexpr int F = NifsCtx<C>::F;
+    c->k254 = fe_to_table<F>(fe_mul<F>(x254, fe_const<F>(FC<F>::C_R2, 1.0)));     // 2^254 R'
+    reef_status st = stream_pool().context_created(device);
+    if (st != REEF_OK) { delete c; return st; }
+    for (DevBuf *b : {&c->z1, &c->z2}) if (st == REEF_OK) st = b->ensure(c->nz * sizeof(fe256));
+    for (DevBuf *b : {&c->E, &c->T}) if (st == REEF_OK) st = b->ensure(num_cons * sizeof(fe256));
+    if (st == REEF_OK) st = c->counters.ensure(2 * sizeof(u32));
+    if (st == REEF_OK && hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); st = REEF_ERR_HIP; }
+    if (st != REEF_OK) { nifs_free(c); return st; }
+    *impl = c;
+    return REEF_OK;
+}
+template <int C> static void v_nifs_destroy(void *impl) { nifs_free((NifsCtx<C> *)impl); }
+
+template <int C>
+static reef_status v_nifs_set_matrix(void *impl, int which, const uint32_t *row, const uint32_t *col, const reef_fe *val, size_t nnz, bool is_mont) {
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    if (which < 0 || which > 2) { set_error("reef_nifs_set_matrix: which must be 0 (A), 1 (B) or 2 (C)"); return REEF_ERR_ARG; }
+    if (nnz && (!row || !col || !val)) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (nnz >= (1ull << 32)) { set_error("reef_nifs_set_matrix: at most 2^32 - 1 entries per matrix"); return REEF_ERR_ARG; }
+    // counting sort by row on the host (any order in, CSR out; duplicates stay separate entries: a dot product sums them)
+    std::vector<u32> ptr(c->num_cons + 1, 0);
+    for (size_t e = 0; e < nnz; ++e) {
+        if (row[e] >= c->num_cons || col[e] >= c->nz) {
+            set_error("reef_nifs_set_matrix: entry %zu (row %u, col %u) outside %zu x %zu", e, row[e], col[e], c->num_cons, c->nz);
+            return REEF_ERR_ARG;
+        }
+        ++ptr[row[e] + 1];
+    }
+    for (size_t i = 0; i < c->num_cons; ++i) ptr[i + 1] += ptr[i];
+    std::vector<u32> fill(ptr.begin(), ptr.end() - 1), cols(nnz);
+    std::vector<reef_fe> vals(nnz);
+    for (size_t e = 0; e < nnz; ++e) {
+        const u32 p = fill[row[e]]++;
+        cols[p] = col[e];
+        vals[p] = val[e];
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    c->has[which] = false;
+    c->prepared = false;
+    REEF_TRY(c->rowptr[which].ensure(ptr.size() * sizeof(u32)));
+    REEF_TRY(c->ent[which].ensure(std::max<size_t>(1, nnz) * sizeof(uint2)));
+    REEF_TRY(c->side[which].ensure(std::max<size_t>(1, nnz) * sizeof(fe256)));
+    REEF_TRY(c->stage.ensure(std::max<size_t>(1, nnz) * sizeof(u32)));
+    REEF_HIP_TRY(hipMemcpyAsync(c->rowptr[which].p, ptr.data(), ptr.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+    if (nnz) {
+        REEF_HIP_TRY(hipMemcpyAsync(c->stage.p, cols.data(), nnz * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+        REEF_HIP_TRY(hipMemcpyAsync(c->side[which].p, vals.data(), nnz * sizeof(fe256), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_nifs_classify<NifsCtx<C>::F>, dim3(ceil_div(nnz, 256)), dim3(256), 0, c->stream, c->stage.template as<u32>(), (u32)nnz,
+                           (int)is_mont, c->ent[which].template as<uint2>(), c->side[which].template as<fe256>());
+        REEF_HIP_TRY(hipGetLastError());
+    }
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));   // the host vectors go out of scope
+    c->h_rowptr[which].swap(ptr);
+    c->has[which] = true;
+    return REEF_OK;
+}
+
+// the rows k_nifs_rows_short leaves to k_nifs_rows_long (after the matrices changed)
+template <int C> static reef_status nifs_prepare(NifsCtx<C> *c) {
+    if (!c->has[0] || !c->has[1] || !c->has[2]) { set_error("reef_nifs: set the matrices A, B and C first"); return REEF_ERR_ARG; }
+    if (c->prepared) return REEF_OK;
+    std::vector<u32> rows, seg_row, seg_first(1, 0);
+    for (size_t i = 0; i < c->num_cons; ++i) {
+        size_t len = 0, longest = 0;
+        for (int k = 0; k < 3; ++k) {
+            const size_t lk = c->h_rowptr[k][i + 1] - c->h_rowptr[k][i];
+            len += lk;
+            longest = std::max(longest, lk);
+        }
+        if (len <= NIFS_LONG_ROW) continue;
+        const u32 segs = (u32)((longest + NIFS_SEG - 1) / NIFS_SEG);
+        seg_row.insert(seg_row.end(), segs, (u32)rows.size());
+        rows.push_back((u32)i);
+        seg_first.push_back(seg_first.back() + segs);
+    }
+    c->nlong = (u32)rows.size();
+    c->nseg = (u32)seg_row.size();
+    REEF_TRY(c->long_rows.ensure(std::max<size_t>(1, rows.size()) * sizeof(u32)));
+    REEF_TRY(c->seg_row.ensure(std::max<size_t>(1, seg_row.size()) * sizeof(u32)));
+    REEF_TRY(c->seg_first.ensure(seg_first.size() * sizeof(u32)));
+    REEF_TRY(c->part.ensure(std::max<size_t>(1, seg_row.size()) * 6 * sizeof(fe_limbs)));
+    if (!rows.empty()) {
+        REEF_HIP_TRY(hipMemcpyAsync(c->long_rows.p, rows.data(), rows.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+        REEF_HIP_TRY(hipMemcpyAsync(c->seg_row.p, seg_row.data(), seg_row.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+        REEF_HIP_TRY(hipMemcpyAsync(c->seg_first.p, seg_first.data(), seg_first.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+        REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    c->prepared = true;
+    return REEF_OK;
+}
+
+template <int C> static NifsArgs nifs_args(NifsCtx<C> *c) {
+    NifsArgs a;
+    memset(&a, 0, sizeof a);
+    for (int k = 0; k < 3; ++k) a.m[k] = NifsMat{c->rowptr[k].template as<u32>(), c->ent[k].template as<uint2>(), c->side[k].template as<fe256>()};
+    a.z1 = c->z1.template as<fe256>();
+    a.z2 = c->z2.template as<fe256>();
+    a.E = c->E.template as<fe256>();
+    a.T = c->T.template as<fe256>();
+    a.num_cons = (u32)c->num_cons;
+    a.num_vars = (u32)c->num_vars;
+    a.k254 = c->k254;
+    a.viol = c->counters.template as<u32>();
+    a.first_bad = a.viol + 1;
+    a.long_rows = c->long_rows.template as<u32>();
+    a.nlong = c->nlong;
+    return a;
+}
+template <int C, int MODE> static reef_status nifs_row_pass(NifsCtx<C> *c, hipStream_t s) {
+    const NifsArgs a = nifs_args(c);
+    hipLaunchKernelGGL((k_nifs_rows_short<NifsCtx<C>::F, MODE>), dim3(ceil_div(c->num_cons, 256)), dim3(256), 0, s, a);
+    if (c->nlong) {
+        const u32 *seg_row = c->seg_row.template as<u32>(), *seg_first = c->seg_first.template as<u32>();
+        fe_limbs *part = c->part.template as<fe_limbs>();
+        hipLaunchKernelGGL((k_nifs_rows_long<NifsCtx<C>::F, MODE>), dim3(c->nseg), dim3(256), 0, s, a, seg_row, seg_first, part);
+        hipLaunchKernelGGL((k_nifs_rows_finish<NifsCtx<C>::F, MODE>), dim3(c->nlong), dim3(64), 0, s, a, seg_first, (const fe_limbs *)part);
+    }
+    REEF_HIP_TRY(hipGetLastError());
+    return REEF_OK;
+}
+
+// n elements of the caller's (host or device) buffer into dst, in the caller's form: dst holds them raw until k_nifs_import
+template <int C> static reef_status nifs_copy_in(NifsCtx<C> *c, fe256 *dst, const reef_fe *src, size_t n, int loc) {
+    if (!n) return REEF_OK;
+    REEF_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(fe256), loc == REEF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    return REEF_OK;
+}
+// z = w || 1 (or u) || x, raw, then converted in place
+template <int C>
+static reef_status nifs_load_z(NifsCtx<C> *c, fe256 *z, const reef_fe *w, const reef_fe *u, const reef_fe *x, int loc, bool is_mont) {
+    constexpr int F = NifsCtx<C>::F;
+    REEF_TRY(nifs_copy_in(c, z, w, c->num_vars, loc));
+    if (u) REEF_TRY(nifs_copy_in(c, z + c->num_vars, u, 1, loc));
+    else {
+        static fe256 one_raw[2];             // the one of z2 in either form: canonical 1, or pasta Montgomery form
+        static std::once_flag once;
+        std::call_once(once, [] {
+            memset(one_raw, 0, sizeof one_raw);
+            one_raw[0].w[0] = 1;
+            one_raw[1] = fe_to_abi<F>(fe_one<F>());
+        });
+        REEF_HIP_TRY(hipMemcpyAsync(z + c->num_vars, &one_raw[is_mont ? 1 : 0], sizeof(fe256), hipMemcpyHostToDevice, c->stream));
+    }
+    REEF_TRY(nifs_copy_in(c, z + c->num_vars + 1, x, c->num_io, loc));
+    hipLaunchKernelGGL(k_nifs_import<F>, dim3(ceil_div(c->nz, 256)), dim3(256), 0, c->stream, z, (u32)c->nz, (int)is_mont, z);
+    REEF_HIP_TRY(hipGetLastError());
+    return REEF_OK;
+}
+
+template <int C>
+static reef_status v_nifs_set_running(void *impl, const reef_fe *W, const reef_fe *E, const reef_fe *u, const reef_fe *X, int loc, bool is_mont) {
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    if ((c->num_vars && !W) || !u || (c->num_io && !X)) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    c->running = c->committed = false;
+    fe256 *dE = c->E.template as<fe256>();
+    REEF_TRY(nifs_load_z(c, c->z1.template as<fe256>(), W, u, X, loc, is_mont));
+    if (E) {
+        REEF_TRY(nifs_copy_in(c, dE, E, c->num_cons, loc));
+        hipLaunchKernelGGL(k_nifs_import<NifsCtx<C>::F>, dim3(ceil_div(c->num_cons, 256)), dim3(256), 0, c->stream, dE, (u32)c->num_cons, (int)is_mont, dE);
+        REEF_HIP_TRY(hipGetLastError());
+    } else {
+        REEF_HIP_TRY(hipMemsetAsync(dE, 0, c->num_cons * sizeof(fe256), c->stream));     // zero is zero in every form
+    }
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    c->running = true;
+    return REEF_OK;
+}
+
+// T of the running instance and the fresh one (u2 = 1, E2 = 0), then comm_T = MSM(T, key) on the key ctx's stream: the row pass
+// is enqueued there, behind the upload of z2, and the MSM reads T where the pass wrote it.
+template <int C>
+static reef_status v_nifs_commit_t(void *impl, void *key_impl, const reef_fe *W2, const reef_fe *X2, int loc, bool is_mont, reef_jacobian *comm_t) {
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    Ctx<C> *key = (Ctx<C> *)key_impl;
+    if (!key || !comm_t || (c->num_vars && !W2) || (c->num_io && !X2)) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->running) { set_error("reef_nifs_commit_T: no running instance (reef_nifs_set_running first)"); return REEF_ERR_ARG; }
+    int key_dev = 0;
+    size_t key_n = 0;
+    {
+        std::lock_guard<std::mutex> kl(key->mu);
+        key_dev = key->key->device;
+        key_n = key->key->n;
+    }
+    if (key_dev != c->device) { set_error("reef_nifs_commit_T: the key lives on device %d, the NIFS ctx on device %d", key_dev, c->device); return REEF_ERR_ARG; }
+    if (key_n < c->num_cons) { set_error("reef_nifs_commit_T: the key holds %zu points, T has %zu entries", key_n, c->num_cons); return REEF_ERR_ARG; }
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    REEF_TRY(nifs_prepare(c));
+    c->committed = false;
+    REEF_TRY(nifs_load_z(c, c->z2.template as<fe256>(), W2, nullptr, X2, loc, is_mont));
+    hipStream_t ks = (hipStream_t)v_ctx_stream<C>(key);
+    if (!ks) return REEF_ERR_HIP;
+    REEF_HIP_TRY(hipEventRecord(c->ev, c->stream));
+    REEF_HIP_TRY(hipStreamWaitEvent(ks, c->ev, 0));
+    REEF_TRY((nifs_row_pass<C, NIFS_MODE_T>(c, ks)));
+    c->have_t = true;
+    REEF_TRY(v_msm<C>(key, (const reef_fe *)c->T.p, c->num_cons, REEF_DEVICE, false, comm_t, REEF_HOST));
+    REEF_HIP_TRY(hipStreamSynchronize(ks));
+    c->committed = true;
+    return REEF_OK;
+}
+
+template <int C> static reef_status v_nifs_fold(void *impl, const reef_fe *r, bool is_mont) {
+    constexpr int F = NifsCtx<C>::F;
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    if (!r) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->committed) { set_error("reef_nifs_fold: no cross term of this step (reef_nifs_commit_T first)"); return REEF_ERR_ARG; }
+    fe256 rp;
+    memcpy(&rp, r, sizeof rp);
+    const fe ri = is_mont ? fe_from_abi<F>(rp) : fe_from_integer<F>(rp);                 // r R'
+    const fe256 r_int = fe_to_table<F>(ri);
+    const fe256 r_sq = fe_to_table<F>(fe_mul<F>(ri, fe_const<F>(FC<F>::C_R2, 1.0)));    // r R'^2: times an integer T gives r T R'
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    hipLaunchKernelGGL(k_nifs_axpy<F>, dim3(ceil_div(c->nz, 256)), dim3(256), 0, c->stream, c->z1.template as<fe256>(), (const fe256 *)c->z2.p, (u32)c->nz, r_int);
+    hipLaunchKernelGGL(k_nifs_axpy<F>, dim3(ceil_div(c->num_cons, 256)), dim3(256), 0, c->stream, c->E.template as<fe256>(), (const fe256 *)c->T.p,
+                       (u32)c->num_cons, r_sq);
+    REEF_HIP_TRY(hipGetLastError());
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    c->committed = false;                    // the next fold needs the next step's T
+    return REEF_OK;
+}
+
+// which: 0 W, 1 E, 2 T, 3 u, 4 X
+template <int C> static reef_status v_nifs_read(void *impl, int which, size_t count, reef_fe *out, bool to_mont) {
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    if (count && !out) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    const fe256 *src = nullptr;
+    size_t len = 0;
+    switch (which) {
+    case 0: src = c->z1.template as<fe256>(); len = c->num_vars; break;
+    case 1: src = c->E.template as<fe256>(); len = c->num_cons; break;
+    case 2: src = c->T.template as<fe256>(); len = c->num_cons; break;
+    case 3: src = c->z1.template as<fe256>() + c->num_vars; len = 1; break;
+    case 4: src = c->z1.template as<fe256>() + c->num_vars + 1; len = c->num_io; break;
+    default: set_error("reef_nifs_read: which must be 0 (W), 1 (E), 2 (T), 3 (u) or 4 (X)"); return REEF_ERR_ARG;
+    }
+    if (count > len) { set_error("reef_nifs_read: %zu entries asked, the vector has %zu", count, len); return REEF_ERR_ARG; }
+    if (which == 2 ? !c->have_t : !c->running) { set_error("reef_nifs_read: nothing to read yet"); return REEF_ERR_ARG; }
+    if (!count) return REEF_OK;
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    REEF_TRY(c->stage.ensure(count * sizeof(fe256)));
+    hipLaunchKernelGGL(k_nifs_export<NifsCtx<C>::F>, dim3(ceil_div(count, 256)), dim3(256), 0, c->stream, src, (u32)count, (int)(which == 2), (int)to_mont,
+                       c->stage.template as<fe256>());
+    REEF_HIP_TRY(hipGetLastError());
+    REEF_HIP_TRY(hipMemcpyAsync(out, c->stage.p, count * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    return REEF_OK;
+}
+
+template <int C> static reef_status v_nifs_check(void *impl, uint64_t *violations, uint64_t *first_bad_row) {
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->running) { set_error("reef_nifs_check_relaxed: no running instance (reef_nifs_set_running first)"); return REEF_ERR_ARG; }
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    REEF_TRY(nifs_prepare(c));
+    const u32 init[2] = {0u, 0xffffffffu};
+    REEF_HIP_TRY(hipMemcpyAsync(c->counters.p, init, sizeof init, hipMemcpyHostToDevice, c->stream));
+    REEF_TRY((nifs_row_pass<C, NIFS_MODE_CHECK>(c, c->stream)));
+    u32 got[2] = {0, 0};
+    REEF_HIP_TRY(hipMemcpyAsync(got, c->counters.p, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (violations) *violations = got[0];
+    if (first_bad_row) *first_bad_row = got[0] ? (uint64_t)got[1] : UINT64_MAX;
+    return REEF_OK;
+}
+
+template <int C> NifsVTable make_nifs_vtable() {
+    return NifsVTable{v_nifs_create<C>, v_nifs_destroy<C>, v_nifs_set_matrix<C>, v_nifs_set_running<C>, v_nifs_commit_t<C>, v_nifs_fold<C>,
+                      v_nifs_read<C>, v_nifs_check<C>};
+}
+
+}  // namespace reef

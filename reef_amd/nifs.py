@@ -1,0 +1,97 @@
+"""Python front-end of the NIFS fold of one folding step (row N6; include/reef_msm.h 3f).
+
+nova-snark's NIFS::prove (Reef: RecursiveSNARK::prove_step, src/backend/framework.rs:668-675) per curve and step:
+the cross term T of the running relaxed instance and a fresh one, comm_T = MSM(T, key), and the folds of W, E, u, X
+with the transcript's challenge r.  Vectors are numpy (n, 4) uint64 arrays of canonical limbs (or pasta Montgomery
+form with is_mont=True); the matrices are (row, col, value) triples.  All arithmetic runs in libreef_msm.so.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import _ffi
+from ._ffi import REEF_HOST, check
+from .msm import MsmContext, curve_id
+
+W, E, T, U, X = 0, 1, 2, 3, 4          # reef_nifs_read: which
+A, B, C = 0, 1, 2                      # reef_nifs_set_matrix: which
+
+
+def _fe(arr, n: Optional[int] = None) -> np.ndarray:
+    a = np.ascontiguousarray(arr, dtype=np.uint64).reshape(-1, 4)
+    if n is not None and a.shape[0] != n:
+        raise ValueError(f"expected {n} field elements, got {a.shape[0]}")
+    return a
+
+
+class Nifs:
+    """The resident running instance, the fresh witness and T of one R1CS shape over the scalar field of `curve`."""
+
+    def __init__(self, curve, num_cons: int, num_vars: int, num_io: int, device: int = 0):
+        self._lib = _ffi.load()
+        self.curve = curve_id(curve)
+        self.num_cons, self.num_vars, self.num_io = num_cons, num_vars, num_io
+        h = ctypes.c_void_p()
+        check(self._lib.reef_nifs_create(ctypes.byref(h), self.curve, num_cons, num_vars, num_io, device))
+        self._h = h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.reef_nifs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_matrix(self, which: int, rows, cols, vals, *, is_mont: bool = False) -> None:
+        """Matrix A, B or C from (row, col, value) triples in any order; duplicates are summed."""
+        r = np.ascontiguousarray(rows, dtype=np.uint32)
+        c = np.ascontiguousarray(cols, dtype=np.uint32)
+        v = _fe(vals, r.shape[0])
+        if c.shape[0] != r.shape[0]:
+            raise ValueError("rows and cols differ in length")
+        check(self._lib.reef_nifs_set_matrix(self._h, which, r.ctypes.data, c.ctypes.data, v.ctypes.data, r.shape[0], is_mont))
+
+    def set_running(self, w, e, u, x, *, is_mont: bool = False) -> None:
+        """The running relaxed instance (W, E, u, X); e=None: E = 0 (nova's first step, with u = 1)."""
+        wa, ua, xa = _fe(w, self.num_vars), _fe(u, 1), _fe(x, self.num_io)
+        ea = None if e is None else _fe(e, self.num_cons)
+        check(self._lib.reef_nifs_set_running(self._h, wa.ctypes.data, None if ea is None else ea.ctypes.data, ua.ctypes.data,
+                                              xa.ctypes.data, REEF_HOST, is_mont))
+
+    def commit_t(self, key: MsmContext, w2, x2, *, is_mont: bool = False) -> np.ndarray:
+        """T of the running and the fresh instance (W2, 1, X2) on the device; returns comm_T (uint64[12] Jacobian)."""
+        wa, xa = _fe(w2, self.num_vars), _fe(x2, self.num_io)
+        out = np.zeros(12, dtype=np.uint64)
+        check(self._lib.reef_nifs_commit_T(self._h, key._h, wa.ctypes.data, xa.ctypes.data, REEF_HOST, is_mont, out.ctypes.data))
+        return out
+
+    def fold(self, r: int, *, is_mont: bool = False) -> None:
+        """W, E, u, X of the running instance folded with the last commit_t's fresh instance and T."""
+        ra = np.array([(r >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+        check(self._lib.reef_nifs_fold(self._h, ra.ctypes.data, is_mont))
+
+    def read(self, which: int, count: Optional[int] = None, *, to_mont: bool = False) -> np.ndarray:
+        if count is None:
+            count = {W: self.num_vars, E: self.num_cons, T: self.num_cons, U: 1, X: self.num_io}[which]
+        out = np.zeros((count, 4), dtype=np.uint64)
+        check(self._lib.reef_nifs_read(self._h, which, count, out.ctypes.data, to_mont))
+        return out
+
+    def check_relaxed(self) -> Tuple[int, Optional[int]]:
+        """(rows violating AZ o BZ == u CZ + E, the first of them or None)."""
+        v, f = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.reef_nifs_check_relaxed(self._h, ctypes.byref(v), ctypes.byref(f)))
+        return v.value, (None if v.value == 0 else f.value)
