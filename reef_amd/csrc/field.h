@@ -12,8 +12,9 @@
 // The internal Montgomery radix is R' = 2^261 (9 x 29); keys are converted once at upload,
 // results once at output (field_consts.h: C_IN, C_OUT).  Both moduli are
 //      M = 2^254 + delta,  delta < 2^126   =>  limbs (1, M1, M2, M3, M4, 0, 0, 0, 2^22)
-// and M = 1 mod 2^29, so the Montgomery quotient digit is q = -t0 mod 2^29 and a reduction
-// round costs 6 MADs.
+// and M = 1 mod 2^29, so the Montgomery quotient digit is q = -t0 mod 2^29.  Every column that
+// gets reduced starts from the bias 2^29 - 1 (free: the addend of its first MAD), which turns
+// the round's carry (t0 + q) / 2^29 into a plain t0 >> 29 and leaves 5 MADs per round.
 //
 // Value bounds.  Limbs are "normalised" when l0..l7 <= 2^29 + 7 (l0 < 2^29 exactly) and the
 // top limb holds the rest.  A product needs (A/M)*(B/M) < 128 and returns a value < 2M with
@@ -197,8 +198,8 @@ REEF_HD void mad_acc_1(u64 &acc, u32 a) { acc += a; }
 #if !defined(__HIP_DEVICE_COMPILE__)
 // Host forms of the row operations (the gfx950 forms are whole rows of v_mad_u64_u32 in one
 // asm statement each: field_mad_gfx950.h).
-REEF_HD void mad_row_new(u64 (&t)[10], const u32 (&a)[9], u32 b) {
-    for (int j = 0; j < 9; ++j) t[j] = (u64)a[j] * b;
+REEF_HD void mad_row_new(u64 (&t)[10], const u32 (&a)[9], u32 b, u64 bias) {
+    for (int j = 0; j < 9; ++j) t[j] = (u64)a[j] * b + bias;
 }
 REEF_HD void mad_row_acc(u64 (&t)[10], const u32 (&a)[9], u32 b) {
     for (int j = 0; j < 8; ++j) t[j] += (u64)a[j] * b;
@@ -208,14 +209,13 @@ REEF_HD void mad_row_add(u64 (&t)[10], const u32 (&a)[9], u32 b) {
     for (int j = 0; j < 9; ++j) t[j] += (u64)a[j] * b;
 }
 REEF_HD void mad_reduce(u64 (&t)[10], u32 q, u32 m1, u32 m2, u32 m3, u32 m4, u32 top) {
-    t[0] += q;
     t[1] += (u64)q * m1; t[2] += (u64)q * m2; t[3] += (u64)q * m3; t[4] += (u64)q * m4;
     t[8] += (u64)q * top;
 }
-template <int I> REEF_HD void sqr_row(u64 (&t)[10], const u32 (&a)[9], const u32 (&a2)[9]) {
+template <int I> REEF_HD void sqr_row(u64 (&t)[10], const u32 (&a)[9], const u32 (&a2)[9], u64 bias) {
     if (I == 0) {
-        t[0] = (u64)a[0] * a[0];
-        for (int j = 1; j < 9; ++j) t[j] = (u64)a[0] * a2[j];
+        t[0] = (u64)a[0] * a[0] + bias;
+        for (int j = 1; j < 9; ++j) t[j] = (u64)a[0] * a2[j] + bias;
     } else if (I == 8) {
         t[8] = (u64)a[8] * a[8];
     } else {
@@ -228,8 +228,8 @@ template <int I> REEF_HD void sqr_row(u64 (&t)[10], const u32 (&a)[9], const u32
 }  // namespace reef
 #include "field_mad_gfx950.h"
 namespace reef {
-template <int I> __device__ __forceinline__ void sqr_row(u64 (&t)[10], const u32 (&a)[9], const u32 (&a2)[9]) {
-    if constexpr (I == 0) sqr_row0(t, a, a2);
+template <int I> __device__ __forceinline__ void sqr_row(u64 (&t)[10], const u32 (&a)[9], const u32 (&a2)[9], u64 bias) {
+    if constexpr (I == 0) sqr_row0(t, a, a2, bias);
     else if constexpr (I == 1) sqr_row1(t, a, a2);
     else if constexpr (I == 2) sqr_row2(t, a, a2);
     else if constexpr (I == 3) sqr_row3(t, a, a2);
@@ -238,14 +238,26 @@ template <int I> __device__ __forceinline__ void sqr_row(u64 (&t)[10], const u32
     else if constexpr (I == 6) sqr_row6(t, a, a2);
     else if constexpr (I == 7) sqr_row7(t, a, a2);
     else sqr_row8(t, a, a2);
+    (void)bias;
 }
 #endif
 
-// One Montgomery reduction round on the column accumulators t[0..8] (t[0] = current column):
-// q = -t0 mod 2^29, t += q*M, the (now zero) low 29 bits of t[0] are dropped into t[1], and the
+// Columns 0..8 of a product -- the ones the rounds reduce -- hold their value plus MONT_BIAS.
+// Seeded by the first row (mad_row_new, sqr_row<0>) at no cost, or by mont_bias() for callers
+// that build the columns themselves.
+static constexpr u64 MONT_BIAS = LIMB_MASK;
+REEF_HD void mont_bias(u64 (&t)[10]) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j) t[j] += MONT_BIAS;
+}
+
+// One Montgomery reduction round on the biased column accumulators t[0..8] (t[0] = current
+// column, value v = t0 - (2^29 - 1)): q = -v mod 2^29 = ~t0 mod 2^29, and t += q*M.  Limb 0 of M
+// is 1, so that term would only make the low 29 bits of t[0] zero; the carry it leads to,
+// (v + q) / 2^29 = ceil(v / 2^29), is already t0 >> 29.  The carry is dropped into t[1] and the
 // accumulators are renamed one column up (free after unrolling).
 template <int F> REEF_HD void mont_round(u64 (&t)[10]) {
-    const u32 q = (0u - (u32)t[0]) & LIMB_MASK;
+    const u32 q = ~(u32)t[0] & LIMB_MASK;
     mad_reduce(t, q, FC<F>::M1, FC<F>::M2, FC<F>::M3, FC<F>::M4, 1u << 22);
     t[1] += t[0] >> LIMB_BITS;
 #pragma unroll
@@ -279,7 +291,7 @@ template <int F> REEF_HD fe fe_mul(const fe &a, const fe &b) {
 #endif
     u64 t[10];
     t[9] = 0;
-    mad_row_new(t, a.l, b.l[0]);
+    mad_row_new(t, a.l, b.l[0], MONT_BIAS);
     mont_round<F>(t);
 #pragma unroll
     for (int i = 1; i < 9; ++i) {
@@ -303,7 +315,7 @@ template <int F> REEF_HD fe fe_mul2_add(const fe &a, const fe &b, const fe &c, c
 #endif
     u64 t[10];
     t[9] = 0;
-    mad_row_new(t, a.l, b.l[0]);
+    mad_row_new(t, a.l, b.l[0], MONT_BIAS);
     mad_row_add(t, c.l, d.l[0]);
     mont_round<F>(t);
 #pragma unroll
@@ -331,7 +343,7 @@ template <int F, int K> REEF_HD fe fe_mul_sub(const fe &a, const fe &b, const fe
 #endif
     u64 t[10];
     t[9] = 0;
-    mad_row_new(t, a.l, b.l[0]);
+    mad_row_new(t, a.l, b.l[0], MONT_BIAS);
     mont_round<F>(t);
 #pragma unroll
     for (int i = 1; i < 9; ++i) {
@@ -358,15 +370,15 @@ template <int F> REEF_HD fe fe_sqr(const fe &a) {
     for (int i = 0; i < 9; ++i) a2[i] = a.l[i] << 1;
     u64 t[10];
     t[9] = 0;
-    sqr_row<0>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<1>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<2>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<3>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<4>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<5>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<6>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<7>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<8>(t, a.l, a2); mont_round<F>(t);
+    sqr_row<0>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<1>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<2>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<3>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<4>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<5>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<6>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<7>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<8>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
     fe r = mont_finish<F>(t);
     REEF_SET_BOUND(r, 1.0 + REEF_GET_BOUND(a) * REEF_GET_BOUND(a) / 128.0);
     return r;
@@ -386,15 +398,15 @@ template <int F, int K> REEF_HD fe fe_sqr_sub(const fe &a, const fe &c) {
     for (int i = 0; i < 9; ++i) a2[i] = a.l[i] << 1;
     u64 t[10];
     t[9] = 0;
-    sqr_row<0>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<1>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<2>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<3>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<4>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<5>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<6>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<7>(t, a.l, a2); mont_round<F>(t);
-    sqr_row<8>(t, a.l, a2); mont_round<F>(t);
+    sqr_row<0>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<1>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<2>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<3>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<4>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<5>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<6>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<7>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
+    sqr_row<8>(t, a.l, a2, MONT_BIAS); mont_round<F>(t);
 #pragma unroll
     for (int i = 0; i < 9; ++i) mad_acc_1(t[i], fe_bias<F, K>()[i] - c.l[i]);
     fe r = mont_finish<F>(t);

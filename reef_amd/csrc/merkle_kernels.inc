@@ -36,7 +36,7 @@ template <int F> __device__ __forceinline__ fe wide18_reduce_small(fe_wide18 &w)
     wide18_carry(w);
     u64 t[10];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) t[i] = w.c[i];
+    for (int i = 0; i < 9; ++i) t[i] = w.c[i] + MONT_BIAS;
     t[9] = 0;
 #pragma unroll
     for (int r = 0; r < 9; ++r) {

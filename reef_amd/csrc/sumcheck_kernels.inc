@@ -93,6 +93,7 @@ template <int F> __device__ __forceinline__ fe fe_from_wide(const fe_wide &w) {
     for (int i = 0; i < 9; ++i) t[i] += (u64)m0 * FC<F>::ONE[i];
 #pragma unroll
     for (int i = 0; i < 8; ++i) t[i + 1] += (u64)c1 * FC<F>::ONE[i];
+    mont_bias(t);
 #pragma unroll
     for (int i = 0; i < 9; ++i) mont_round<F>(t);
     fe x = mont_finish<F>(t);
@@ -162,7 +163,7 @@ template <int F> __device__ __forceinline__ fe wide18_reduce(fe_wide18 &w) {
     wide18_carry(w);
     u64 t[10];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) t[i] = w.c[i];
+    for (int i = 0; i < 9; ++i) t[i] = w.c[i] + MONT_BIAS;
     t[9] = 0;
 #pragma unroll
     for (int r = 0; r < 9; ++r) {
