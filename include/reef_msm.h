@@ -23,6 +23,8 @@
  * ABI changelog (reef_abi_version()):
  *   7  the NIFS fold of a folding step on the device (reef_nifs_*, section 3f): R1CS cross term T, comm_T, the folds of W, E, u, X,
  *      and the relaxed-R1CS check.  Nothing else changed.
+ *      Later, still 7 (symbols added, none changed): the sum-checks of the final SNARK on a NIFS ctx's running instance
+ *      (reef_spartan_*, section 3g).  A caller that needs them checks for the symbol, not the version.
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -428,6 +430,48 @@ reef_status reef_nifs_commit_T(reef_nifs_ctx *ctx, reef_msm_ctx *key, const reef
 reef_status reef_nifs_fold(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont);
 reef_status reef_nifs_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont);
 reef_status reef_nifs_check_relaxed(reef_nifs_ctx *ctx, uint64_t *violations, uint64_t *first_bad_row);
+
+/* ---------------------------------------------------------------------------------------------
+ * (3g) Row N5: the two sum-checks of the final SNARK, nova-snark's RelaxedR1CSSNARK::prove [R] (Reef: S1 / S2,
+ * src/backend/framework.rs:7-8, called from CompressedSNARK::prove :695-698), run on the running relaxed instance (W, E, u, X)
+ * and the matrices of a reef_nifs_ctx as they stand at reef_spartan_begin.  Same field as 3f (the curve's SCALAR field).
+ * The Keccak transcript stays with the caller: every call takes the challenge the caller squeezed after the previous one.
+ *
+ * Recalled facts [R], in one place (spartan/snark.rs, spartan/sumcheck.rs, r1cs.rs; correct them here if they are wrong):
+ *   padding    R1CSShape::pad / RelaxedR1CSWitness::pad: the caller passes pk.S's num_cons_pad, num_vars_pad (powers of two);
+ *              matrix column c >= num_vars becomes c + num_vars_pad - num_vars (u lands at num_vars_pad); rows >= num_cons
+ *              are empty; W and E are zero-padded; z = W || 0 || u || X || 0 has 2 num_vars_pad entries.
+ *   eq         eq(t)[i] = prod_j (bit_j(i) ? t_j : 1 - t_j), t_0 pairing with the MOST significant bit of i (EqPolynomial::evals).
+ *   binding    a round binds the top variable: X[i] <- X[i] + r (X[i + n] - X[i]), i < n, n = half the table (bound_poly_var_top);
+ *              r_x, r_y list the challenges in call order, so r_x[0] is the most significant bit.
+ *   outer      prove_cubic_with_additive_term over eq(tau), AZ, BZ, D = u CZ + E with comb eq (AZ BZ - D), log2(num_cons_pad)
+ *              rounds; a round's evaluations are {e0, e2, e3}: the sums at t = 0, 2, 3 of lo + t (hi - lo); the verifier's
+ *              e1 = claim - e0; the CompressedUniPoly absorbed is the cubic through (0, e0), (1, e1), (2, e2), (3, e3) without
+ *              its linear coefficient.  claims_outer = {AZ(r_x), BZ(r_x), CZ(r_x), E(r_x)}.
+ *   inner      the joint claim AZ(r_x) + r BZ(r_x) + r^2 CZ(r_x); ABC[col] = sum_row eq(r_x)[row] (A + r B + r^2 C)[row][col] on
+ *              the renumbered columns (compute_eval_table_sparse); prove_quad over ABC and z, log2(2 num_vars_pad) rounds, each
+ *              {e0, e2} (t = 0, 2); then eval_W = W~(r_y[1..]) over num_vars_pad entries.
+ *
+ * reef_spartan_begin        num_cons_pad, num_vars_pad: powers of two in [2, 2^24], num_cons_pad >= num_cons, num_vars_pad >= num_vars,
+ *                           num_io < num_vars_pad; tau: log2(num_cons_pad) entries.  AZ, BZ, CZ, D and eq(tau) on the device;
+ *                           evals = round 0 of the outer sum-check.  May be called at any time: it starts a new prove.
+ * reef_spartan_outer_round  binds with r, evals = the next round; exactly log2(num_cons_pad) - 1 calls.
+ * reef_spartan_outer_claims binds with r_last; claims = {AZ(r_x), BZ(r_x), CZ(r_x), E(r_x)}.
+ * reef_spartan_inner_begin  r: the joint-claim challenge; builds ABC and z; evals = round 0 of the inner sum-check.
+ * reef_spartan_inner_round  binds with r, evals = the next round; exactly log2(num_vars_pad) calls.
+ * reef_spartan_inner_claims binds with r_last; claims = {ABC(r_y), z(r_y), eval_W}.
+ * Every challenge and tau entry must be below the modulus.  is_mont: inputs and outputs in pasta Montgomery form, else canonical
+ * integers.  Outputs are HOST memory.  A call out of order -- a round before begin, one round too many or too few, any call after
+ * reef_nifs_set_matrix / set_running / commit_T / fold changed the ctx since begin -- is REEF_ERR_ARG naming the call expected, and
+ * changes nothing.  The calls never modify W, E, u, X, T or the NIFS state: commit_T and fold stay valid.  The workspace (five
+ * tables of num_cons_pad entries, two of 2 num_vars_pad) is allocated by the first begin, grows, and is freed with the ctx. */
+reef_status reef_spartan_begin(reef_nifs_ctx *ctx, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *tau, bool is_mont,
+                               reef_fe evals[3]);
+reef_status reef_spartan_outer_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe evals[3]);
+reef_status reef_spartan_outer_claims(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe claims[4]);
+reef_status reef_spartan_inner_begin(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe evals[2]);
+reef_status reef_spartan_inner_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe evals[2]);
+reef_status reef_spartan_inner_claims(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe claims[3]);
 
 /* ---------------------------------------------------------------------------------------------
  * (4) Runtime plumbing.

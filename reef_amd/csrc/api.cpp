@@ -525,6 +525,33 @@ reef_status reef_nifs_check_relaxed(reef_nifs_ctx *ctx, uint64_t *violations, ui
     return nvt(ctx->curve)->check(ctx->impl, violations, first_bad_row);
 }
 
+// ---- row N5: the sum-checks of the final SNARK on a NIFS ctx
+static const SpartanVTable *svt(int curve) { return curve == REEF_PALLAS ? pallas_spartan_vtable() : vesta_spartan_vtable(); }
+reef_status reef_spartan_begin(reef_nifs_ctx *ctx, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *tau, bool is_mont, reef_fe evals[3]) {
+    SC_CHECK(ctx);
+    return guarded([&] { return svt(ctx->curve)->begin(ctx->impl, num_cons_pad, num_vars_pad, tau, is_mont, evals); });
+}
+reef_status reef_spartan_outer_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe evals[3]) {
+    SC_CHECK(ctx);
+    return svt(ctx->curve)->outer_round(ctx->impl, r, is_mont, evals);
+}
+reef_status reef_spartan_outer_claims(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe claims[4]) {
+    SC_CHECK(ctx);
+    return guarded([&] { return svt(ctx->curve)->outer_claims(ctx->impl, r_last, is_mont, claims); });
+}
+reef_status reef_spartan_inner_begin(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe evals[2]) {
+    SC_CHECK(ctx);
+    return guarded([&] { return svt(ctx->curve)->inner_begin(ctx->impl, r, is_mont, evals); });
+}
+reef_status reef_spartan_inner_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe evals[2]) {
+    SC_CHECK(ctx);
+    return svt(ctx->curve)->inner_round(ctx->impl, r, is_mont, evals);
+}
+reef_status reef_spartan_inner_claims(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe claims[3]) {
+    SC_CHECK(ctx);
+    return guarded([&] { return svt(ctx->curve)->inner_claims(ctx->impl, r_last, is_mont, claims); });
+}
+
 uint64_t reef_merkle_nodes(uint64_t n) {
     uint64_t total = 0, m = (n + 1) / 2;
     for (;;) {

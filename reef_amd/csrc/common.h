@@ -412,4 +412,16 @@ struct NifsVTable {
 const NifsVTable *pallas_nifs_vtable();
 const NifsVTable *vesta_nifs_vtable();
 
+// Row N5: the sum-checks of the final SNARK on a NIFS ctx's running instance (spartan_engine.inc; include/reef_msm.h 3g).  impl: a NIFS impl.
+struct SpartanVTable {
+    reef_status (*begin)(void *impl, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *tau, bool is_mont, reef_fe *evals);
+    reef_status (*outer_round)(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals);
+    reef_status (*outer_claims)(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *claims);
+    reef_status (*inner_begin)(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals);
+    reef_status (*inner_round)(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals);
+    reef_status (*inner_claims)(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *claims);
+};
+const SpartanVTable *pallas_spartan_vtable();
+const SpartanVTable *vesta_spartan_vtable();
+
 }  // namespace reef

@@ -6,8 +6,10 @@
 #include "merkle_kernels.inc"
 #include "keygen_kernels.inc"
 #include "nifs_kernels.inc"
+#include "spartan_kernels.inc"
 #include "engine.inc"
 #include "nifs_engine.inc"
+#include "spartan_engine.inc"
 namespace reef {
 const CurveVTable *pallas_vtable() {
     static const CurveVTable vt = make_vtable<0>();
@@ -15,6 +17,10 @@ const CurveVTable *pallas_vtable() {
 }
 const NifsVTable *pallas_nifs_vtable() {
     static const NifsVTable vt = make_nifs_vtable<0>();
+    return &vt;
+}
+const SpartanVTable *pallas_spartan_vtable() {
+    static const SpartanVTable vt = make_spartan_vtable<0>();
     return &vt;
 }
 }

@@ -1,6 +1,21 @@
 // Host side of row N6 (the NIFS fold of one step: nifs_kernels.inc); included after engine.inc.
 namespace reef {
 
+template <int C> struct SpartanState;                     // row N5 on the same ctx (spartan_engine.inc)
+template <int C> static void spartan_release(SpartanState<C> *s);
+
+// The lines of a matrix triple (rows of the CSR, or columns of the CSC copy) that k_nifs_rows_short leaves to k_nifs_rows_long:
+// their indices, their segments (nifs_kernels.inc) and the segments' partial sums.
+struct NifsSegs {
+    DevBuf long_rows, seg_row, seg_first, part;
+    u32 nlong = 0, nseg = 0;
+    bool prepared = false;               // up to date with the three matrices
+    void release() {
+        for (DevBuf *b : {&long_rows, &seg_row, &seg_first, &part}) b->release();
+        prepared = false;
+    }
+};
+
 template <int C> struct NifsCtx {
     static constexpr int F = 1 - C;      // scalar field of curve C
     std::mutex mu;
@@ -11,9 +26,12 @@ template <int C> struct NifsCtx {
     DevBuf rowptr[3], ent[3], side[3];   // CSR of A, B, C: row pointers, {col, class} per entry, general coefficients by entry
     std::vector<u32> h_rowptr[3];        // host copies: the long-row list is made from them
     bool has[3] = {false, false, false};
-    bool prepared = false;               // long_rows is up to date with the three matrices
-    DevBuf long_rows, seg_row, seg_first, part;   // long rows, their segments (nifs_kernels.inc: k_nifs_rows_long), partial sums
-    u32 nlong = 0, nseg = 0;
+    NifsSegs rows;                       // long rows of the CSR
+    DevBuf colptr[3], cent[3], cside[3]; // row N5: the column-major copy of A, B, C ({row, class} per entry), built by set_matrix
+    std::vector<u32> h_colptr[3];
+    NifsSegs cols;                       // long columns of the CSC
+    SpartanState<C> *sp = nullptr;       // row N5 workspace, made by the first reef_spartan_begin
+    u64 gen = 0;                         // bumped by every call that changes the matrices or the running instance (or commits T)
     DevBuf z1, z2, E, T, stage, counters;
     hipEvent_t ev = nullptr;             // orders the key ctx's stream after the upload of z2 (commit_T)
     bool running = false, committed = false, have_t = false;
@@ -36,8 +54,12 @@ template <int C> static void nifs_free(NifsCtx<C> *c) {
     if (!c) return;
     if (c->lease.counted) (void)hipStreamSynchronize(c->stream);
     c->lease.idle();
-    for (int k = 0; k < 3; ++k) { c->rowptr[k].release(); c->ent[k].release(); c->side[k].release(); }
-    for (DevBuf *b : {&c->long_rows, &c->seg_row, &c->seg_first, &c->part, &c->z1, &c->z2, &c->E, &c->T, &c->stage, &c->counters}) b->release();
+    for (int k = 0; k < 3; ++k)
+        for (DevBuf *b : {&c->rowptr[k], &c->ent[k], &c->side[k], &c->colptr[k], &c->cent[k], &c->cside[k]}) b->release();
+    c->rows.release();
+    c->cols.release();
+    spartan_release<C>(c->sp);
+    for (DevBuf *b : {&c->z1, &c->z2, &c->E, &c->T, &c->stage, &c->counters}) b->release();
     if (c->ev) (void)hipEventDestroy(c->ev);
     stream_pool().context_destroyed();
     delete c;
@@ -98,39 +120,63 @@ static reef_status v_nifs_set_matrix(void *impl, int which, const uint32_t *row,
         cols[p] = col[e];
         vals[p] = val[e];
     }
+    // and by column (row N5's ABC pass: one line per column of z), from the CSR so that a column's entries go by row
+    std::vector<u32> cptr(c->nz + 1, 0), crows(nnz);
+    std::vector<reef_fe> cvals(nnz);
+    for (size_t e = 0; e < nnz; ++e) ++cptr[cols[e] + 1];
+    for (size_t j = 0; j < c->nz; ++j) cptr[j + 1] += cptr[j];
+    {
+        std::vector<u32> cfill(cptr.begin(), cptr.end() - 1);
+        for (size_t i = 0; i < c->num_cons; ++i)
+            for (u32 e = ptr[i]; e < ptr[i + 1]; ++e) {
+                const u32 p = cfill[cols[e]]++;
+                crows[p] = (u32)i;
+                cvals[p] = vals[e];
+            }
+    }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_ON_DEVICE(c->device);
     NifsScope<C> scope(c);
     REEF_TRY(scope.enter());
     c->has[which] = false;
-    c->prepared = false;
+    c->rows.prepared = c->cols.prepared = false;
+    ++c->gen;
     REEF_TRY(c->rowptr[which].ensure(ptr.size() * sizeof(u32)));
     REEF_TRY(c->ent[which].ensure(std::max<size_t>(1, nnz) * sizeof(uint2)));
     REEF_TRY(c->side[which].ensure(std::max<size_t>(1, nnz) * sizeof(fe256)));
-    REEF_TRY(c->stage.ensure(std::max<size_t>(1, nnz) * sizeof(u32)));
+    REEF_TRY(c->colptr[which].ensure(cptr.size() * sizeof(u32)));
+    REEF_TRY(c->cent[which].ensure(std::max<size_t>(1, nnz) * sizeof(uint2)));
+    REEF_TRY(c->cside[which].ensure(std::max<size_t>(1, nnz) * sizeof(fe256)));
+    REEF_TRY(c->stage.ensure(std::max<size_t>(1, 2 * nnz) * sizeof(u32)));
     REEF_HIP_TRY(hipMemcpyAsync(c->rowptr[which].p, ptr.data(), ptr.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
     if (nnz) {
         REEF_HIP_TRY(hipMemcpyAsync(c->stage.p, cols.data(), nnz * sizeof(u32), hipMemcpyHostToDevice, c->stream));
         REEF_HIP_TRY(hipMemcpyAsync(c->side[which].p, vals.data(), nnz * sizeof(fe256), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_nifs_classify<NifsCtx<C>::F>, dim3(ceil_div(nnz, 256)), dim3(256), 0, c->stream, c->stage.template as<u32>(), (u32)nnz,
                            (int)is_mont, c->ent[which].template as<uint2>(), c->side[which].template as<fe256>());
+        u32 *srows = c->stage.template as<u32>() + nnz;
+        REEF_HIP_TRY(hipMemcpyAsync(srows, crows.data(), nnz * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+        REEF_HIP_TRY(hipMemcpyAsync(c->cside[which].p, cvals.data(), nnz * sizeof(fe256), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_nifs_classify<NifsCtx<C>::F>, dim3(ceil_div(nnz, 256)), dim3(256), 0, c->stream, (const u32 *)srows, (u32)nnz,
+                           (int)is_mont, c->cent[which].template as<uint2>(), c->cside[which].template as<fe256>());
         REEF_HIP_TRY(hipGetLastError());
     }
+    REEF_HIP_TRY(hipMemcpyAsync(c->colptr[which].p, cptr.data(), cptr.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));   // the host vectors go out of scope
     c->h_rowptr[which].swap(ptr);
+    c->h_colptr[which].swap(cptr);
     c->has[which] = true;
     return REEF_OK;
 }
 
-// the rows k_nifs_rows_short leaves to k_nifs_rows_long (after the matrices changed)
-template <int C> static reef_status nifs_prepare(NifsCtx<C> *c) {
-    if (!c->has[0] || !c->has[1] || !c->has[2]) { set_error("reef_nifs: set the matrices A, B and C first"); return REEF_ERR_ARG; }
-    if (c->prepared) return REEF_OK;
+// the lines k_nifs_rows_short leaves to k_nifs_rows_long (after the matrices changed): rows of the CSR, or columns of the CSC
+template <int C> static reef_status nifs_segments(NifsCtx<C> *c, const std::vector<u32> (&hptr)[3], size_t n, NifsSegs &sg) {
+    if (sg.prepared) return REEF_OK;
     std::vector<u32> rows, seg_row, seg_first(1, 0);
-    for (size_t i = 0; i < c->num_cons; ++i) {
+    for (size_t i = 0; i < n; ++i) {
         size_t len = 0, longest = 0;
         for (int k = 0; k < 3; ++k) {
-            const size_t lk = c->h_rowptr[k][i + 1] - c->h_rowptr[k][i];
+            const size_t lk = hptr[k][i + 1] - hptr[k][i];
             len += lk;
             longest = std::max(longest, lk);
         }
@@ -140,20 +186,24 @@ template <int C> static reef_status nifs_prepare(NifsCtx<C> *c) {
         rows.push_back((u32)i);
         seg_first.push_back(seg_first.back() + segs);
     }
-    c->nlong = (u32)rows.size();
-    c->nseg = (u32)seg_row.size();
-    REEF_TRY(c->long_rows.ensure(std::max<size_t>(1, rows.size()) * sizeof(u32)));
-    REEF_TRY(c->seg_row.ensure(std::max<size_t>(1, seg_row.size()) * sizeof(u32)));
-    REEF_TRY(c->seg_first.ensure(seg_first.size() * sizeof(u32)));
-    REEF_TRY(c->part.ensure(std::max<size_t>(1, seg_row.size()) * 6 * sizeof(fe_limbs)));
+    sg.nlong = (u32)rows.size();
+    sg.nseg = (u32)seg_row.size();
+    REEF_TRY(sg.long_rows.ensure(std::max<size_t>(1, rows.size()) * sizeof(u32)));
+    REEF_TRY(sg.seg_row.ensure(std::max<size_t>(1, seg_row.size()) * sizeof(u32)));
+    REEF_TRY(sg.seg_first.ensure(seg_first.size() * sizeof(u32)));
+    REEF_TRY(sg.part.ensure(std::max<size_t>(1, seg_row.size()) * 6 * sizeof(fe_limbs)));
     if (!rows.empty()) {
-        REEF_HIP_TRY(hipMemcpyAsync(c->long_rows.p, rows.data(), rows.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-        REEF_HIP_TRY(hipMemcpyAsync(c->seg_row.p, seg_row.data(), seg_row.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-        REEF_HIP_TRY(hipMemcpyAsync(c->seg_first.p, seg_first.data(), seg_first.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+        REEF_HIP_TRY(hipMemcpyAsync(sg.long_rows.p, rows.data(), rows.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+        REEF_HIP_TRY(hipMemcpyAsync(sg.seg_row.p, seg_row.data(), seg_row.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+        REEF_HIP_TRY(hipMemcpyAsync(sg.seg_first.p, seg_first.data(), seg_first.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
         REEF_HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    c->prepared = true;
+    sg.prepared = true;
     return REEF_OK;
+}
+template <int C> static reef_status nifs_prepare(NifsCtx<C> *c) {
+    if (!c->has[0] || !c->has[1] || !c->has[2]) { set_error("reef_nifs: set the matrices A, B and C first"); return REEF_ERR_ARG; }
+    return nifs_segments(c, c->h_rowptr, c->num_cons, c->rows);
 }
 
 template <int C> static NifsArgs nifs_args(NifsCtx<C> *c) {
@@ -169,22 +219,23 @@ template <int C> static NifsArgs nifs_args(NifsCtx<C> *c) {
     a.k254 = c->k254;
     a.viol = c->counters.template as<u32>();
     a.first_bad = a.viol + 1;
-    a.long_rows = c->long_rows.template as<u32>();
-    a.nlong = c->nlong;
+    a.long_rows = c->rows.long_rows.template as<u32>();
+    a.nlong = c->rows.nlong;
     return a;
 }
-template <int C, int MODE> static reef_status nifs_row_pass(NifsCtx<C> *c, hipStream_t s) {
-    const NifsArgs a = nifs_args(c);
-    hipLaunchKernelGGL((k_nifs_rows_short<NifsCtx<C>::F, MODE>), dim3(ceil_div(c->num_cons, 256)), dim3(256), 0, s, a);
-    if (c->nlong) {
-        const u32 *seg_row = c->seg_row.template as<u32>(), *seg_first = c->seg_first.template as<u32>();
-        fe_limbs *part = c->part.template as<fe_limbs>();
-        hipLaunchKernelGGL((k_nifs_rows_long<NifsCtx<C>::F, MODE>), dim3(c->nseg), dim3(256), 0, s, a, seg_row, seg_first, part);
-        hipLaunchKernelGGL((k_nifs_rows_finish<NifsCtx<C>::F, MODE>), dim3(c->nlong), dim3(64), 0, s, a, seg_first, (const fe_limbs *)part);
+// one pass over the lines of a (the rows, or for MODE_ABC the columns: a.num_cons lines) with the long ones of sg
+template <int C, int MODE> static reef_status nifs_line_pass(const NifsArgs &a, const NifsSegs &sg, hipStream_t s) {
+    hipLaunchKernelGGL((k_nifs_rows_short<NifsCtx<C>::F, MODE>), dim3(ceil_div(a.num_cons, 256)), dim3(256), 0, s, a);
+    if (sg.nlong) {
+        const u32 *seg_row = sg.seg_row.template as<u32>(), *seg_first = sg.seg_first.template as<u32>();
+        fe_limbs *part = sg.part.template as<fe_limbs>();
+        hipLaunchKernelGGL((k_nifs_rows_long<NifsCtx<C>::F, MODE>), dim3(sg.nseg), dim3(256), 0, s, a, seg_row, seg_first, part);
+        hipLaunchKernelGGL((k_nifs_rows_finish<NifsCtx<C>::F, MODE>), dim3(sg.nlong), dim3(64), 0, s, a, seg_first, (const fe_limbs *)part);
     }
     REEF_HIP_TRY(hipGetLastError());
     return REEF_OK;
 }
+template <int C, int MODE> static reef_status nifs_row_pass(NifsCtx<C> *c, hipStream_t s) { return nifs_line_pass<C, MODE>(nifs_args(c), c->rows, s); }
 
 // n elements of the caller's (host or device) buffer into dst, in the caller's form: dst holds them raw until k_nifs_import
 template <int C> static reef_status nifs_copy_in(NifsCtx<C> *c, fe256 *dst, const reef_fe *src, size_t n, int loc) {
@@ -223,6 +274,7 @@ static reef_status v_nifs_set_running(void *impl, const reef_fe *W, const reef_f
     NifsScope<C> scope(c);
     REEF_TRY(scope.enter());
     c->running = c->committed = false;
+    ++c->gen;
     fe256 *dE = c->E.template as<fe256>();
     REEF_TRY(nifs_load_z(c, c->z1.template as<fe256>(), W, u, X, loc, is_mont));
     if (E) {
@@ -260,6 +312,7 @@ static reef_status v_nifs_commit_t(void *impl, void *key_impl, const reef_fe *W2
     REEF_TRY(scope.enter());
     REEF_TRY(nifs_prepare(c));
     c->committed = false;
+    ++c->gen;
     REEF_TRY(nifs_load_z(c, c->z2.template as<fe256>(), W2, nullptr, X2, loc, is_mont));
     hipStream_t ks = (hipStream_t)v_ctx_stream<C>(key);
     if (!ks) return REEF_ERR_HIP;
@@ -287,6 +340,7 @@ template <int C> static reef_status v_nifs_fold(void *impl, const reef_fe *r, bo
     REEF_ON_DEVICE(c->device);
     NifsScope<C> scope(c);
     REEF_TRY(scope.enter());
+    ++c->gen;
     hipLaunchKernelGGL(k_nifs_axpy<F>, dim3(ceil_div(c->nz, 256)), dim3(256), 0, c->stream, c->z1.template as<fe256>(), (const fe256 *)c->z2.p, (u32)c->nz, r_int);
     hipLaunchKernelGGL(k_nifs_axpy<F>, dim3(ceil_div(c->num_cons, 256)), dim3(256), 0, c->stream, c->E.template as<fe256>(), (const fe256 *)c->T.p,
                        (u32)c->num_cons, r_sq);

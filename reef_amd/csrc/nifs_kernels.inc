@@ -6,7 +6,9 @@
 //   W, E, u, X = W1 + r W2, E1 + r T, u1 + r, X1 + r X2       (k_nifs_axpy: z1 += r z2 covers W, u and X at once)
 //   relaxed    : AZ o BZ == u CZ + E                           (the same row pass, MODE_CHECK)
 //
-// AZ, BZ and CZ are never written: one pass per row computes its dot products and the row's epilogue.
+// AZ, BZ and CZ are never written for these: one pass per row computes its dot products and the row's epilogue.  Row N5
+// (spartan_kernels.inc) adds two epilogues: MODE_SPARTAN writes AZ, BZ, CZ and D = u CZ + E of the running instance as
+// tables, and MODE_ABC runs the same kernels over the column-major copy of the matrices, with eq(r_x) in place of z.
 //
 // Device form of a matrix (nifs_engine.inc builds it once per shape): CSR row pointers and one 8-byte word per entry,
 // {col, class}.  The class says how the entry's coefficient multiplies z[col]:
@@ -22,7 +24,7 @@ namespace reef {
 
 static constexpr u32 NIFS_GENERAL = 1u << 31, NIFS_NEG = 1u << 30, NIFS_MAG = 0xffffu;
 static constexpr u32 NIFS_LONG_ROW = 128;        // rows with more entries (A + B + C) go to k_nifs_rows_long, one block each
-enum { NIFS_MODE_T = 0, NIFS_MODE_CHECK = 1 };
+enum { NIFS_MODE_T = 0, NIFS_MODE_CHECK = 1, NIFS_MODE_SPARTAN = 2, NIFS_MODE_ABC = 3 };
 
 struct NifsMat {
     const u32 *rowptr;       // num_cons + 1
@@ -39,6 +41,9 @@ struct NifsArgs {
     u32 *viol, *first_bad;   // MODE_CHECK counters
     const u32 *long_rows;
     u32 nlong;
+    fe256 *out[4];           // MODE_SPARTAN: AZ, BZ, CZ, D by row.  MODE_ABC: out[0] by renumbered column
+    fe256 r1, r2;            // MODE_ABC: r, r^2 (internal form)
+    u32 shift;               // MODE_ABC: a column >= num_vars lands at column + shift (num_vars_pad - num_vars)
 };
 
 // Host triples -> device form: the raw coefficient (ABI form or canonical integer) sits in side[e]; this writes ent[e] and,
@@ -154,14 +159,15 @@ __device__ __forceinline__ void nifs_dot(const NifsMat &m, u32 b, u32 e, u32 ste
     for (int v = 0; v < NV; ++v) out[v] = nifs_reduce<F>(acc[v], k254);
 }
 
-// The row's epilogue on its canonical dot products d: MODE_T d = {AZ1, AZ2, BZ1, BZ2, CZ1, CZ2}, MODE_CHECK d = {AZ, BZ, CZ}.
+// The row's epilogue on its canonical dot products d: MODE_T d = {AZ1, AZ2, BZ1, BZ2, CZ1, CZ2}, MODE_CHECK and MODE_SPARTAN
+// d = {AZ, BZ, CZ}.
 template <int F, int MODE>
 __device__ __forceinline__ void nifs_epilogue(const NifsArgs &a, u32 row, const fe *d, const fe &u1) {
     if constexpr (MODE == NIFS_MODE_T) {
         const fe m = fe_mul2_add<F>(d[0], d[3], d[1], d[2]);                  // AZ1 BZ2 + AZ2 BZ1, < 2M
         const fe s = fe_add<F>(fe_mul<F>(u1, d[5]), d[4]);                      // u1 CZ2 + CZ1, < 3M
         store_fe256(a.T + row, sc_to_integer<F>(fe_sub<F, 4>(m, s)));
-    } else {
+    } else if constexpr (MODE == NIFS_MODE_CHECK) {
         const fe lhs = fe_mul<F>(d[0], d[1]);
         const fe rhs = fe_add<F>(fe_mul<F>(u1, d[2]), fe_from_table(load_fe256(a.E + row)));
         const fe diff = fe_canon<F>(fe_sub<F, 4>(lhs, rhs));
@@ -172,7 +178,19 @@ __device__ __forceinline__ void nifs_epilogue(const NifsArgs &a, u32 row, const 
             atomicAdd(a.viol, 1u);
             atomicMin(a.first_bad, row);
         }
+    } else if constexpr (MODE == NIFS_MODE_SPARTAN) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) store_fe256(a.out[k] + row, fe_pack(d[k]));
+        const fe D = fe_add<F>(fe_mul<F>(u1, d[2]), fe_from_table(load_fe256(a.E + row)));
+        store_fe256(a.out[3] + row, fe_to_table<F>(D));
+    } else {                                 // MODE_ABC: `row` is a column, d = its dot products with eq(r_x) in A, B, C
+        const fe v = fe_add<F>(d[0], fe_mul2_add<F>(fe_from_table(a.r1), d[1], fe_from_table(a.r2), d[2]));
+        store_fe256(a.out[0] + row + (row >= a.num_vars ? a.shift : 0u), fe_to_table<F>(v));
     }
+}
+// u of the running instance (MODE_ABC has no z: its `z1` is eq(r_x), and the epilogue takes no u)
+template <int MODE> __device__ __forceinline__ fe nifs_u1(const NifsArgs &a) {
+    return MODE == NIFS_MODE_ABC ? fe_zero() : fe_from_table(load_fe256(a.z1 + a.num_vars));
 }
 
 // One thread per row; rows with more than NIFS_LONG_ROW entries are left to k_nifs_rows_long.  The products of A and B are
@@ -199,7 +217,7 @@ __global__ void __launch_bounds__(256) k_nifs_rows_short(NifsArgs a) {
         fe d[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) nifs_dot<F, 0>(a.m[k], b[k], e[k], 1, a.z1, a.z2, k254, d + k);
-        nifs_epilogue<F, MODE>(a, row, d, fe_from_table(load_fe256(a.z1 + a.num_vars)));
+        nifs_epilogue<F, MODE>(a, row, d, nifs_u1<MODE>(a));
     }
 }
 
@@ -257,7 +275,7 @@ __global__ void __launch_bounds__(64) k_nifs_rows_finish(NifsArgs a, const u32 *
         for (u32 s = s0 + threadIdx.x; s < s1; s += WAVE) d[j] = fe_canon<F>(fe_add<F>(d[j], fe_from_limbs(part[(size_t)s * ND + j], 1.0)));
         nifs_wave_sum<F>(d[j]);
     }
-    if (threadIdx.x == 0) nifs_epilogue<F, MODE>(a, row, d, fe_from_table(load_fe256(a.z1 + a.num_vars)));
+    if (threadIdx.x == 0) nifs_epilogue<F, MODE>(a, row, d, nifs_u1<MODE>(a));
 }
 
 }  // namespace reef

@@ -1,0 +1,357 @@
+// Host side of row N5 (the sum-checks of RelaxedR1CSSNARK::prove: spartan_kernels.inc) on a NIFS ctx; included after nifs_engine.inc.
+// A prover-side state machine: begin -> outer_round x (ell_x - 1) -> outer_claims -> inner_begin -> inner_round x (ell_y - 1) ->
+// inner_claims, with ell_x = log2(num_cons_pad), ell_y = log2(2 num_vars_pad).  The running instance is read, never written.
+namespace reef {
+
+enum { SP_NONE = 0, SP_OUTER, SP_OUTER_DONE, SP_INNER, SP_DONE };
+
+template <int C> struct SpartanState {
+    int phase = SP_NONE;
+    u64 gen = 0;                         // the ctx's gen at begin: any later change of the matrices or the running instance voids the prove
+    size_t ncp = 0, nvp = 0;             // padded sizes
+    u32 ell_x = 0, ell_y = 0, rounds = 0;   // rounds: challenges taken in the current sum-check
+    std::vector<fe> rx, ry;              // the challenges (internal form)
+    DevBuf eq, az, bz, cz, d;            // outer tables (ncp entries); cz and E are never bound
+    DevBuf abc, z;                       // inner tables (2 nvp entries)
+    DevBuf pts, partial, out;            // eq factors, block sums, results
+};
+template <int C> static void spartan_release(SpartanState<C> *s) {
+    if (!s) return;
+    for (DevBuf *b : {&s->eq, &s->az, &s->bz, &s->cz, &s->d, &s->abc, &s->z, &s->pts, &s->partial, &s->out}) b->release();
+    delete s;
+}
+
+static const char *sp_expected(int phase, u32 rounds, u32 ell_x, u32 ell_y) {
+    switch (phase) {
+    case SP_OUTER: return rounds + 1 < ell_x ? "reef_spartan_outer_round" : "reef_spartan_outer_claims";
+    case SP_OUTER_DONE: return "reef_spartan_inner_begin";
+    case SP_INNER: return rounds + 1 < ell_y ? "reef_spartan_inner_round" : "reef_spartan_inner_claims";
+    default: return "reef_spartan_begin";
+    }
+}
+// The call `name` is the one the state machine expects (REEF_ERR_ARG naming the expected call otherwise)
+template <int C> static reef_status sp_expect(NifsCtx<C> *c, const char *name) {
+    SpartanState<C> *s = c->sp;
+    if (s && s->phase != SP_NONE && s->gen != c->gen) {
+        s->phase = SP_NONE;
+        set_error("%s: the matrices or the running instance changed (set_matrix, set_running, commit_T or fold) since reef_spartan_begin: "
+                  "the next call is reef_spartan_begin", name);
+        return REEF_ERR_ARG;
+    }
+    const char *want = s ? sp_expected(s->phase, s->rounds, s->ell_x, s->ell_y) : "reef_spartan_begin";
+    if (strcmp(want, name) != 0) { set_error("%s: out of order, the next call is %s", name, want); return REEF_ERR_ARG; }
+    return REEF_OK;
+}
+
+template <int C> static fe sp_import(const reef_fe *x, bool is_mont) {
+    constexpr int F = NifsCtx<C>::F;
+    fe256 p;
+    memcpy(&p, x, sizeof p);
+    return fe_canon<F>(is_mont ? fe_from_abi<F>(p) : fe_from_integer<F>(p));
+}
+static u32 sp_log2(size_t n) {
+    u32 l = 0;
+    while ((size_t)1 << l < n) ++l;
+    return l;
+}
+static bool sp_valid_fe(const reef_fe *x, int field) {          // canonical: below the modulus
+    fe256 p;
+    memcpy(&p, x, sizeof p);
+    const u32 *m = field == 0 ? FC<0>::MOD : FC<1>::MOD;
+    fe v = fe_unpack(p);
+    for (int i = 8; i >= 0; --i)
+        if (v.l[i] != m[i]) return v.l[i] < m[i];
+    return false;
+}
+
+// eq(p) over 2^ell entries into dst (internal form)
+template <int C> static reef_status sp_eq_table(NifsCtx<C> *c, const fe *p, u32 ell, fe256 *dst) {
+    constexpr int F = NifsCtx<C>::F;
+    SpartanState<C> *s = c->sp;
+    std::vector<fe256> f(2 * std::max<u32>(ell, 1));
+    for (u32 j = 0; j < ell; ++j) {
+        f[2 * j] = fe_to_table<F>(fe_sub<F, 2>(fe_one<F>(), p[j]));
+        f[2 * j + 1] = fe_to_table<F>(p[j]);
+    }
+    REEF_TRY(s->pts.ensure(f.size() * sizeof(fe256)));
+    REEF_HIP_TRY(hipMemcpyAsync(s->pts.p, f.data(), f.size() * sizeof(fe256), hipMemcpyHostToDevice, c->stream));
+    const size_t n = (size_t)1 << ell;
+    hipLaunchKernelGGL(k_sp_eq<F>, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, (const fe256 *)s->pts.p, ell, (u32)n, dst);
+    REEF_HIP_TRY(hipGetLastError());
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));             // f goes out of scope
+    return REEF_OK;
+}
+static u32 sp_grid(size_t n) { return (u32)std::max<size_t>(1, std::min<size_t>(SP_BLOCKS, ceil_div(n, SP_THREADS))); }
+
+// one round (bind with r when bind, then the sums of the next round: nv values) -> evals (HOST) in the caller's form
+template <int C, int CUBIC>
+static reef_status sp_round(NifsCtx<C> *c, fe256 *const *tabs, u32 h, bool bind, const fe &r, bool is_mont, reef_fe *evals) {
+    constexpr int F = NifsCtx<C>::F;
+    constexpr u32 NV = CUBIC ? 3 : 2;
+    SpartanState<C> *s = c->sp;
+    SpRound a;
+    memset(&a, 0, sizeof a);
+    for (int k = 0; k < (CUBIC ? 4 : 2); ++k) a.t[k] = tabs[k];
+    a.h = h;
+    a.bind = bind;
+    a.r = fe_to_table<F>(r);
+    a.partial = s->partial.template as<unsigned long long>();
+    const u32 grid = sp_grid(h);
+    hipLaunchKernelGGL((k_sp_round<F, CUBIC>), dim3(grid), dim3(SP_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(k_sp_finish<F>, dim3(1), dim3(SP_THREADS), 0, c->stream, (const unsigned long long *)a.partial, grid, NV,
+                       is_mont ? (int)SP_FORM_MONT : (int)SP_FORM_INTEGER, s->out.template as<fe256>());
+    REEF_HIP_TRY(hipGetLastError());
+    REEF_HIP_TRY(hipMemcpyAsync(evals, s->out.p, NV * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    return REEF_OK;
+}
+// dot products x . y0 (and x . y1) over n entries -> s->out + slot (nv values, `form`); no wait
+template <int C> static reef_status sp_dots(NifsCtx<C> *c, const fe256 *x, const fe256 *y0, const fe256 *y1, size_t n, int form, u32 slot) {
+    constexpr int F = NifsCtx<C>::F;
+    SpartanState<C> *s = c->sp;
+    unsigned long long *partial = s->partial.template as<unsigned long long>();
+    const u32 grid = sp_grid(n);
+    hipLaunchKernelGGL(k_sp_dot<F>, dim3(grid), dim3(SP_THREADS), 0, c->stream, x, y0, y1, (u32)n, partial);
+    hipLaunchKernelGGL(k_sp_finish<F>, dim3(1), dim3(SP_THREADS), 0, c->stream, (const unsigned long long *)partial, grid, y1 ? 2u : 1u, form,
+                       s->out.template as<fe256>() + slot);
+    REEF_HIP_TRY(hipGetLastError());
+    return REEF_OK;
+}
+
+template <int C>
+static reef_status v_spartan_begin(void *impl, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *tau, bool is_mont, reef_fe *evals) {
+    constexpr int F = NifsCtx<C>::F;
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    if (!tau || !evals) { set_error("null argument"); return REEF_ERR_ARG; }
+    auto pow2 = [](size_t n) { return n >= 2 && n <= ((size_t)1 << 24) && (n & (n - 1)) == 0; };
+    if (!pow2(num_cons_pad) || !pow2(num_vars_pad) || num_cons_pad < c->num_cons || num_vars_pad < c->num_vars || c->num_io >= num_vars_pad) {
+        set_error("reef_spartan_begin: need powers of two 2 <= num_cons_pad, num_vars_pad <= 2^24 with num_cons_pad >= num_cons (%zu), "
+                  "num_vars_pad >= num_vars (%zu) and num_vars_pad > num_io (%zu); got %zu, %zu", c->num_cons, c->num_vars, c->num_io, num_cons_pad,
+                  num_vars_pad);
+        return REEF_ERR_ARG;
+    }
+    const u32 ell_x = sp_log2(num_cons_pad);
+    for (u32 j = 0; j < ell_x; ++j)
+        if (!sp_valid_fe(tau + j, F)) { set_error("reef_spartan_begin: tau[%u] is not below the modulus", j); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->running || !c->has[0] || !c->has[1] || !c->has[2]) {
+        set_error("reef_spartan_begin: set the matrices A, B, C and the running instance first (reef_nifs_set_matrix, reef_nifs_set_running)");
+        return REEF_ERR_ARG;
+    }
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    if (!c->sp) c->sp = new SpartanState<C>();
+    SpartanState<C> *s = c->sp;
+    s->phase = SP_NONE;
+    REEF_TRY(nifs_prepare(c));
+    for (DevBuf *b : {&s->eq, &s->az, &s->bz, &s->cz, &s->d}) REEF_TRY(b->ensure(num_cons_pad * sizeof(fe256)));
+    REEF_TRY(s->partial.ensure(SP_BLOCKS * 27 * sizeof(unsigned long long)));
+    REEF_TRY(s->out.ensure(4 * sizeof(fe256)));
+    // AZ, BZ, CZ, D by row; the padding rows stay zero
+    fe256 *tabs[5] = {s->eq.template as<fe256>(), s->az.template as<fe256>(), s->bz.template as<fe256>(), s->d.template as<fe256>(),
+                      s->cz.template as<fe256>()};
+    for (int k = 1; k < 5; ++k) REEF_HIP_TRY(hipMemsetAsync(tabs[k], 0, num_cons_pad * sizeof(fe256), c->stream));
+    NifsArgs a = nifs_args(c);
+    a.out[0] = tabs[1];
+    a.out[1] = tabs[2];
+    a.out[2] = tabs[4];
+    a.out[3] = tabs[3];
+    REEF_TRY((nifs_line_pass<C, NIFS_MODE_SPARTAN>(a, c->rows, c->stream)));
+    std::vector<fe> t(ell_x);
+    for (u32 j = 0; j < ell_x; ++j) t[j] = sp_import<C>(tau + j, is_mont);
+    REEF_TRY(sp_eq_table(c, t.data(), ell_x, tabs[0]));
+    s->ncp = num_cons_pad;
+    s->nvp = num_vars_pad;
+    s->ell_x = ell_x;
+    s->ell_y = sp_log2(2 * num_vars_pad);
+    s->rounds = 0;
+    s->rx.clear();
+    s->ry.clear();
+    s->gen = c->gen;
+    REEF_TRY((sp_round<C, 1>(c, tabs, (u32)(num_cons_pad / 2), false, fe_zero(), is_mont, evals)));
+    s->phase = SP_OUTER;
+    return REEF_OK;
+}
+
+template <int C> static fe256 *const *sp_outer_tabs(SpartanState<C> *s, fe256 *(&t)[4]) {
+    t[0] = s->eq.template as<fe256>();
+    t[1] = s->az.template as<fe256>();
+    t[2] = s->bz.template as<fe256>();
+    t[3] = s->d.template as<fe256>();
+    return t;
+}
+template <int C> static fe256 *const *sp_inner_tabs(SpartanState<C> *s, fe256 *(&t)[4]) {
+    t[0] = s->abc.template as<fe256>();
+    t[1] = s->z.template as<fe256>();
+    t[2] = t[3] = nullptr;
+    return t;
+}
+// the challenge of a call: canonical when given as an integer
+template <int C> static reef_status sp_challenge(const reef_fe *r, bool is_mont, const char *name, fe &out) {
+    if (!r) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (!sp_valid_fe(r, NifsCtx<C>::F)) { set_error("%s: r is not below the modulus", name); return REEF_ERR_ARG; }
+    out = sp_import<C>(r, is_mont);
+    return REEF_OK;
+}
+
+template <int C> static reef_status v_spartan_outer_round(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals) {
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    fe ri;
+    REEF_TRY(sp_challenge<C>(r, is_mont, "reef_spartan_outer_round", ri));
+    if (!evals) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    REEF_TRY(sp_expect(c, "reef_spartan_outer_round"));
+    SpartanState<C> *s = c->sp;
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    fe256 *t[4];
+    const u32 h = (u32)(s->ncp >> (s->rounds + 2));          // pairs of the next round
+    s->phase = SP_NONE;                                       // a failure half way leaves nothing to continue
+    REEF_TRY((sp_round<C, 1>(c, sp_outer_tabs(s, t), h, true, ri, is_mont, evals)));
+    s->rx.push_back(ri);
+    ++s->rounds;
+    s->phase = SP_OUTER;
+    return REEF_OK;
+}
+
+template <int C> static reef_status v_spartan_outer_claims(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *claims) {
+    constexpr int F = NifsCtx<C>::F;
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    fe ri;
+    REEF_TRY(sp_challenge<C>(r_last, is_mont, "reef_spartan_outer_claims", ri));
+    if (!claims) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    REEF_TRY(sp_expect(c, "reef_spartan_outer_claims"));
+    SpartanState<C> *s = c->sp;
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    s->phase = SP_NONE;
+    const int form = is_mont ? SP_FORM_MONT : SP_FORM_INTEGER;
+    fe256 *t[4];
+    SpRound a;
+    memset(&a, 0, sizeof a);
+    a.t[0] = sp_outer_tabs(s, t)[1];                          // AZ, BZ
+    a.t[1] = t[2];
+    a.r = fe_to_table<F>(ri);
+    hipLaunchKernelGGL(k_sp_bind_last<F>, dim3(1), dim3(64), 0, c->stream, a, 2u, form, s->out.template as<fe256>());
+    REEF_HIP_TRY(hipGetLastError());
+    s->rx.push_back(ri);
+    REEF_TRY(sp_eq_table(c, s->rx.data(), s->ell_x, s->eq.template as<fe256>()));   // eq(r_x) over the bound eq(tau): not needed any more
+    REEF_TRY(sp_dots(c, s->eq.template as<fe256>(), s->cz.template as<fe256>(), c->E.template as<fe256>(), c->num_cons, form, 2));
+    REEF_HIP_TRY(hipMemcpyAsync(claims, s->out.p, 4 * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    s->rounds = 0;
+    s->phase = SP_OUTER_DONE;
+    return REEF_OK;
+}
+
+template <int C> static reef_status v_spartan_inner_begin(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals) {
+    constexpr int F = NifsCtx<C>::F;
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    fe ri;
+    REEF_TRY(sp_challenge<C>(r, is_mont, "reef_spartan_inner_begin", ri));
+    if (!evals) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    REEF_TRY(sp_expect(c, "reef_spartan_inner_begin"));
+    SpartanState<C> *s = c->sp;
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    s->phase = SP_NONE;
+    REEF_TRY(nifs_segments(c, c->h_colptr, c->nz, c->cols));
+    const size_t n2 = 2 * s->nvp;
+    REEF_TRY(s->abc.ensure(n2 * sizeof(fe256)));
+    REEF_TRY(s->z.ensure(n2 * sizeof(fe256)));
+    fe256 *abc = s->abc.template as<fe256>(), *z = s->z.template as<fe256>();
+    const fe256 *z1 = c->z1.template as<fe256>();
+    // z = W || 0 || u || X || 0 (R1CSShape::pad [R]: column c >= num_vars moves to c + num_vars_pad - num_vars)
+    REEF_HIP_TRY(hipMemsetAsync(abc, 0, n2 * sizeof(fe256), c->stream));
+    REEF_HIP_TRY(hipMemsetAsync(z, 0, n2 * sizeof(fe256), c->stream));
+    if (c->num_vars) REEF_HIP_TRY(hipMemcpyAsync(z, z1, c->num_vars * sizeof(fe256), hipMemcpyDeviceToDevice, c->stream));
+    REEF_HIP_TRY(hipMemcpyAsync(z + s->nvp, z1 + c->num_vars, (1 + c->num_io) * sizeof(fe256), hipMemcpyDeviceToDevice, c->stream));
+    // ABC by column over the CSC copy: the lines are the nz columns, "z" is eq(r_x)
+    NifsArgs a;
+    memset(&a, 0, sizeof a);
+    for (int k = 0; k < 3; ++k) a.m[k] = NifsMat{c->colptr[k].template as<u32>(), c->cent[k].template as<uint2>(), c->cside[k].template as<fe256>()};
+    a.z1 = a.z2 = s->eq.template as<fe256>();
+    a.num_cons = (u32)c->nz;
+    a.num_vars = (u32)c->num_vars;
+    a.k254 = c->k254;
+    a.long_rows = c->cols.long_rows.template as<u32>();
+    a.nlong = c->cols.nlong;
+    a.out[0] = abc;
+    a.r1 = fe_to_table<F>(ri);
+    a.r2 = fe_to_table<F>(fe_mul<F>(ri, ri));
+    a.shift = (u32)(s->nvp - c->num_vars);
+    REEF_TRY((nifs_line_pass<C, NIFS_MODE_ABC>(a, c->cols, c->stream)));
+    fe256 *t[4];
+    REEF_TRY((sp_round<C, 0>(c, sp_inner_tabs(s, t), (u32)s->nvp, false, fe_zero(), is_mont, evals)));
+    s->rounds = 0;
+    s->phase = SP_INNER;
+    return REEF_OK;
+}
+
+template <int C> static reef_status v_spartan_inner_round(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals) {
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    fe ri;
+    REEF_TRY(sp_challenge<C>(r, is_mont, "reef_spartan_inner_round", ri));
+    if (!evals) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    REEF_TRY(sp_expect(c, "reef_spartan_inner_round"));
+    SpartanState<C> *s = c->sp;
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    s->phase = SP_NONE;
+    fe256 *t[4];
+    const u32 h = (u32)((2 * s->nvp) >> (s->rounds + 2));
+    REEF_TRY((sp_round<C, 0>(c, sp_inner_tabs(s, t), h, true, ri, is_mont, evals)));
+    s->ry.push_back(ri);
+    ++s->rounds;
+    s->phase = SP_INNER;
+    return REEF_OK;
+}
+
+template <int C> static reef_status v_spartan_inner_claims(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *claims) {
+    constexpr int F = NifsCtx<C>::F;
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    fe ri;
+    REEF_TRY(sp_challenge<C>(r_last, is_mont, "reef_spartan_inner_claims", ri));
+    if (!claims) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    REEF_TRY(sp_expect(c, "reef_spartan_inner_claims"));
+    SpartanState<C> *s = c->sp;
+    REEF_ON_DEVICE(c->device);
+    NifsScope<C> scope(c);
+    REEF_TRY(scope.enter());
+    s->phase = SP_NONE;
+    const int form = is_mont ? SP_FORM_MONT : SP_FORM_INTEGER;
+    fe256 *t[4];
+    SpRound a;
+    memset(&a, 0, sizeof a);
+    a.t[0] = sp_inner_tabs(s, t)[0];                          // ABC, z
+    a.t[1] = t[1];
+    a.r = fe_to_table<F>(ri);
+    hipLaunchKernelGGL(k_sp_bind_last<F>, dim3(1), dim3(64), 0, c->stream, a, 2u, form, s->out.template as<fe256>());
+    REEF_HIP_TRY(hipGetLastError());
+    s->ry.push_back(ri);
+    // eval_W = W~(r_y[1..]) over num_vars_pad entries: eq(r_y[1..]) in the eq table (ncp >= 2 entries, grown to nvp if need be)
+    REEF_TRY(s->eq.ensure(s->nvp * sizeof(fe256)));
+    REEF_TRY(sp_eq_table(c, s->ry.data() + 1, s->ell_y - 1, s->eq.template as<fe256>()));
+    if (c->num_vars) REEF_TRY(sp_dots(c, s->eq.template as<fe256>(), c->z1.template as<fe256>(), nullptr, c->num_vars, form, 2));
+    else REEF_HIP_TRY(hipMemsetAsync(s->out.template as<fe256>() + 2, 0, sizeof(fe256), c->stream));
+    REEF_HIP_TRY(hipMemcpyAsync(claims, s->out.p, 3 * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    s->phase = SP_DONE;
+    return REEF_OK;
+}
+
+template <int C> SpartanVTable make_spartan_vtable() {
+    return SpartanVTable{v_spartan_begin<C>, v_spartan_outer_round<C>, v_spartan_outer_claims<C>, v_spartan_inner_begin<C>, v_spartan_inner_round<C>,
+                         v_spartan_inner_claims<C>};
+}
+
+}  // namespace reef

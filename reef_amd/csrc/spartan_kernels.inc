@@ -1,0 +1,179 @@
+// Row N5: the two sum-checks of the final SNARK, nova-snark's RelaxedR1CSSNARK::prove [R] (Reef: S1 / S2,
+// src/backend/framework.rs:7-8, CompressedSNARK::prove :695-698), over the scalar field of curve C, on the running relaxed
+// instance a NIFS ctx holds (nifs_engine.inc).  spartan_engine.inc drives them, one device call per round:
+//
+//   begin        AZ, BZ, CZ, D = u CZ + E     (the NIFS row pass, MODE_SPARTAN) and eq(tau)      (k_sp_eq)
+//   outer rounds sum eq (AZ BZ - D) at 0, 2, 3 over the low / high halves, fused with the bind of the round before (k_sp_round<F, 1>)
+//   outer claims AZ(r_x), BZ(r_x): the last bind; CZ(r_x), E(r_x): dot products with eq(r_x)   (k_sp_bind_last, k_sp_dot)
+//   ABC          sum_row eq(r_x)[row] (A + r B + r^2 C)[row][col] per column (the NIFS row pass over the CSC copy, MODE_ABC)
+//   inner rounds sum ABC z at 0 and 2                                                              (k_sp_round<F, 0>)
+//   inner claims ABC(r_y), z(r_y): the last bind; eval_W = W . eq(r_y[1..])
+//
+// Tables hold the resident internal form, canonical and packed (fe_to_table), like the NIFS vectors.  Round sums are lazy: each
+// term is one product (< 2M, exact 29-bit limbs) whose limbs go into 64-bit column sums per thread, then per wave (DPP), per block
+// (LDS) into partial[block][27]; k_sp_finish adds the blocks' sums and reduces them once (fe_from_limb_sums) -- a second launch,
+// no grid hand-over inside the round kernel.
+
+namespace reef {
+
+static constexpr u32 SP_BLOCKS = 1024;   // round and dot kernels: at most this many blocks, so a thread adds <= 2^23 / 2^18 terms
+static constexpr u32 SP_THREADS = 256;
+
+// eq(p)[i] = prod_j (bit_{ell-1-j}(i) ? p_j : 1 - p_j) (p_0 pairs with the most significant bit, as EqPolynomial::evals [R]).
+// f[2 j] = 1 - p_j, f[2 j + 1] = p_j (internal form); one thread per entry, ell - 1 products.
+template <int F>
+__global__ void __launch_bounds__(256) k_sp_eq(const fe256 *__restrict__ f, u32 ell, u32 n, fe256 *__restrict__ out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fe acc = fe_from_table(load_fe256(f + ((i >> (ell - 1)) & 1u)));
+    for (u32 j = 1; j < ell; ++j) acc = fe_mul<F>(acc, fe_from_table(load_fe256(f + 2 * j + ((i >> (ell - 1 - j)) & 1u))));
+    store_fe256(out + i, fe_to_table<F>(acc));
+}
+
+// the value at t of the line through lo (t = 0) and hi (t = 1), canonical: lo + t (hi - lo) for t = 2, 3
+template <int F> __device__ __forceinline__ void sp_line(const fe &lo, const fe &hi, fe &v2, fe &v3) {
+    const fe d = fe_sub<F, 2>(hi, lo);                         // < 3M
+    v2 = fe_canon<F>(fe_add<F>(hi, d));
+    v3 = fe_canon<F>(fe_add<F>(v2, d));
+}
+// X[b] + r (X[b + off] - X[b]), canonical
+template <int F> __device__ __forceinline__ fe sp_bind(const fe256 *X, u32 b, u32 off, const fe &r) {
+    const fe a0 = fe_from_table(load_fe256(X + b)), a1 = fe_from_table(load_fe256(X + b + off));
+    return fe_canon<F>(fe_add<F>(a0, fe_mul<F>(r, fe_sub<F, 2>(a1, a0))));
+}
+__device__ __forceinline__ void sp_acc(u64 (&acc)[9], const fe &x) {   // x: exact 29-bit limbs
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] += x.l[i];
+}
+
+// The limb sums of NV values per thread -> partial[blockIdx.x][27] (slots 9 k .. 9 k + 8 for value k).  Every thread of the block
+// calls it (the DPP sums need whole waves); a thread's column sums stay below 2^46.
+template <int NV> __device__ __forceinline__ void sp_block_sums(u64 (&acc)[NV][9], unsigned long long *__restrict__ partial) {
+    __shared__ unsigned long long bs[27];
+    if (threadIdx.x < 27) bs[threadIdx.x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            const unsigned long long s = wave_sum63(acc[k][i]);
+            if ((threadIdx.x & 63) == 63) atomicAdd(&bs[9 * k + i], s);
+        }
+    __syncthreads();
+    if (threadIdx.x < 27) partial[(size_t)blockIdx.x * 27 + threadIdx.x] = bs[threadIdx.x];
+}
+
+struct SpRound {
+    fe256 *t[4];             // cubic: eq, AZ, BZ, D.  quadratic: ABC, z
+    u32 h;                   // pairs (b, b + h) summed this round: the tables hold 2h entries after the bind
+    int bind;                // bind with r first: the tables hold 4h entries before it, (b, b + 2h) -> b
+    fe256 r;                 // internal form
+    unsigned long long *partial;
+};
+// One round: the bind of the round before (if any) fused with this round's sums, one pass over the tables.  Thread b < h binds the
+// entries b and b + h of every table (their partners at + 2h), writes them, and uses them as the pair (lo, hi) of this round:
+//   cubic      e0 = sum eq AZ BZ - eq D at lo,   e2, e3: the same at lo + t (hi - lo) for t = 2, 3   (prove_cubic_with_additive_term)
+//   quadratic  e0 = sum ABC z at lo,             e2: at t = 2                                        (prove_quad)
+// A thread reads b, b + h, b + 2h, b + 3h and writes b, b + h only: binding in place is safe.
+template <int F, int CUBIC>
+__global__ void __launch_bounds__(SP_THREADS) k_sp_round(SpRound a) {
+    constexpr int NT = CUBIC ? 4 : 2, NV = CUBIC ? 3 : 2;
+    const fe r = fe_from_table(a.r);
+    u64 acc[NV][9];
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+#pragma unroll
+        for (int i = 0; i < 9; ++i) acc[k][i] = 0;
+    for (u32 b = blockIdx.x * blockDim.x + threadIdx.x; b < a.h; b += gridDim.x * blockDim.x) {
+        fe lo[NT], hi[NT];
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+            if (a.bind) {
+                lo[k] = sp_bind<F>(a.t[k], b, 2 * a.h, r);
+                hi[k] = sp_bind<F>(a.t[k], b + a.h, 2 * a.h, r);
+                store_fe256(a.t[k] + b, fe_pack(lo[k]));
+                store_fe256(a.t[k] + b + a.h, fe_pack(hi[k]));
+            } else {
+                lo[k] = fe_from_table(load_fe256(a.t[k] + b));
+                hi[k] = fe_from_table(load_fe256(a.t[k] + b + a.h));
+            }
+        }
+        if constexpr (CUBIC) {
+            fe v2[4], v3[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sp_line<F>(lo[k], hi[k], v2[k], v3[k]);
+            // eq (AZ BZ + 2M - D): fe_mul_sub < 4M, times eq < M
+            sp_acc(acc[0], fe_mul<F>(lo[0], fe_mul_sub<F, 2>(lo[1], lo[2], lo[3])));
+            sp_acc(acc[1], fe_mul<F>(v2[0], fe_mul_sub<F, 2>(v2[1], v2[2], v2[3])));
+            sp_acc(acc[2], fe_mul<F>(v3[0], fe_mul_sub<F, 2>(v3[1], v3[2], v3[3])));
+        } else {
+            fe a2, a3, z2, z3;
+            sp_line<F>(lo[0], hi[0], a2, a3);
+            sp_line<F>(lo[1], hi[1], z2, z3);
+            sp_acc(acc[0], fe_mul<F>(lo[0], lo[1]));
+            sp_acc(acc[1], fe_mul<F>(a2, z2));
+        }
+    }
+    sp_block_sums<NV>(acc, a.partial);
+}
+
+// Dot products x . y0 (and x . y1) over n entries -> partial[block][27]
+template <int F>
+__global__ void __launch_bounds__(SP_THREADS) k_sp_dot(const fe256 *__restrict__ x, const fe256 *__restrict__ y0, const fe256 *__restrict__ y1,
+                                                       u32 n, unsigned long long *__restrict__ partial) {
+    u64 acc[2][9];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int i = 0; i < 9; ++i) acc[k][i] = 0;
+    for (u32 b = blockIdx.x * blockDim.x + threadIdx.x; b < n; b += gridDim.x * blockDim.x) {
+        const fe xv = fe_from_table(load_fe256(x + b));
+        sp_acc(acc[0], fe_mul<F>(xv, fe_from_table(load_fe256(y0 + b))));
+        if (y1) sp_acc(acc[1], fe_mul<F>(xv, fe_from_table(load_fe256(y1 + b))));
+    }
+    sp_block_sums<2>(acc, partial);
+}
+
+// a canonical internal value in the caller's form: 0 the internal table form, 1 canonical integer, 2 pasta Montgomery form
+enum { SP_FORM_TABLE = 0, SP_FORM_INTEGER = 1, SP_FORM_MONT = 2 };
+template <int F> __device__ __forceinline__ fe256 sp_out(const fe &x, int form) {
+    return form == SP_FORM_MONT ? fe_to_abi<F>(x) : form == SP_FORM_INTEGER ? sc_to_integer<F>(x) : fe_to_table<F>(x);
+}
+
+// out[k] = the sum over nblocks blocks of value k (k < nv), in `form`.  One block: every thread adds its blocks' 9 nv slots, LDS
+// atomics add the threads; value k's limb sums (< 2^24 terms of < 2^29 each) are reduced once.
+template <int F>
+__global__ void __launch_bounds__(SP_THREADS) k_sp_finish(const unsigned long long *__restrict__ partial, u32 nblocks, u32 nv, int form,
+                                                          fe256 *__restrict__ out) {
+    __shared__ unsigned long long tot[27];
+    if (threadIdx.x < 27) tot[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned long long s[27];
+#pragma unroll
+    for (int i = 0; i < 27; ++i) s[i] = 0;
+    for (u32 b = threadIdx.x; b < nblocks; b += blockDim.x)
+#pragma unroll
+        for (int i = 0; i < 27; ++i)
+            if (i < (int)(9 * nv)) s[i] += partial[(size_t)b * 27 + i];
+#pragma unroll
+    for (int i = 0; i < 27; ++i)
+        if (s[i]) atomicAdd(&tot[i], s[i]);
+    __syncthreads();
+    if (threadIdx.x >= nv) return;
+    fe_wide w;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) w.l[i] = tot[9 * threadIdx.x + i];
+    store_fe256(out + threadIdx.x, sp_out<F>(fe_from_limb_sums<F>(w), form));
+}
+
+// The last bind (two entries left): t[k][0] = t[k][0] + r (t[k][1] - t[k][0]) for k < nt, and out[k] = that value in `form`
+template <int F>
+__global__ void __launch_bounds__(64) k_sp_bind_last(SpRound a, u32 nt, int form, fe256 *__restrict__ out) {
+    const u32 k = threadIdx.x;
+    if (k >= nt) return;
+    const fe v = sp_bind<F>(a.t[k], 0, 1, fe_from_table(a.r));
+    store_fe256(a.t[k], fe_pack(v));
+    store_fe256(out + k, sp_out<F>(v, form));
+}
+
+}  // namespace reef
