@@ -25,6 +25,8 @@
  *      and the relaxed-R1CS check.  Nothing else changed.
  *      Later, still 7 (symbols added, none changed): the sum-checks of the final SNARK on a NIFS ctx's running instance
  *      (reef_spartan_*, section 3g).  A caller that needs them checks for the symbol, not the version.
+ *      Later, still 7 (symbols added, none changed): the batched IPA opening of the final SNARK on the same ctx
+ *      (reef_spartan_open_*, section 3h).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -472,6 +474,47 @@ reef_status reef_spartan_outer_claims(reef_nifs_ctx *ctx, const reef_fe *r_last,
 reef_status reef_spartan_inner_begin(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe evals[2]);
 reef_status reef_spartan_inner_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe evals[2]);
 reef_status reef_spartan_inner_claims(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe claims[3]);
+
+/* ---------------------------------------------------------------------------------------------
+ * (3h) The batched IPA opening of the final SNARK: what RelaxedR1CSSNARK::prove [R] does after the sum-checks of 3g,
+ * EE::prove_batch(&[comm_E, comm_W], &[E, W], &[r_x, r_y[1..]], &[eval_E, eval_W]) in ipa_pc -- NIFSForInnerProduct's fold of
+ * the two instances, then InnerProductArgument::prove -- on the vectors of the same reef_nifs_ctx, after reef_spartan_inner_claims.
+ * The Keccak transcript and every point operation on commitments (comm_a = comm_E + r comm_W, q = gens_c.scale(r)) stay
+ * with the caller; only challenges go in, and only points and single scalars come out.  Same field as 3f and 3g.
+ *
+ * Recalled facts [R], in one place (provider/ipa_pc.rs; correct them here if they are wrong):
+ *   batch      the order is [E, W]: instance 1 is a1 = E with b1 = eq(r_x), instance 2 is a2 = W with b2 = eq(r_y[1..]);
+ *              both are zero-padded to n = max(num_cons_pad, num_vars_pad) (InnerProductInstance / Witness ::pad).
+ *   fold       cross = <a1, b2> + <a2, b1>; a = a1 + r a2, b = b1 + r b2, c = c1 + r^2 c2 + r cross (= <a, b>).
+ *   labels     the NIFS challenge r (after absorbing cross), then the IPA's r (q = gens_s.scale(r)), then one challenge_r
+ *              per round (after absorbing L and R).  b_vec is not absorbed by the IPA; if it is, open_read(.., 1, ..) serves.
+ *   rounds     L = <a_lo, G_hi> + c_L q, R = <a_hi, G_lo> + c_R q with c_L = <a_lo, b_hi>, c_R = <a_hi, b_lo>; then
+ *              a' = a_lo r + a_hi r^-1, b' = b_lo r^-1 + b_hi r, G' = r^-1 G_lo + r G_hi (gens.fold(r^-1, r)); a_hat = a[0]
+ *              after log2(n) folds.
+ *   gens_v     holds exactly n generators: the key of these calls.
+ *
+ * reef_spartan_open_begin     key: gens_v, a reef_msm_ctx of the same curve and device holding exactly n points, used until
+ *                             finish.  Builds eq(r_x) and eq(r_y[1..]); *cross_term = cross.  May restart an opening.
+ * reef_spartan_open_fold      the NIFS challenge r: a and b on the device; *c = <a, b>.
+ * reef_spartan_open_ipa_begin q = gens_c.scale(r_ipa), affine, pasta Montgomery coordinates; round 0's L and R.
+ * reef_spartan_open_ipa_round folds a and b with the round's challenge r; the next round's L and R; exactly log2(n) - 1 calls.
+ * reef_spartan_open_finish    the last fold with r_last; *a_hat = a[0].
+ * reef_spartan_open_read      which: 0 a, 1 b, as they stand now (n, n/2, ... entries); the first `count` to the host.
+ * L and R are computed over the ORIGINAL resident key (the fold challenges go into the scalars, as reef_ipa_cross_terms does),
+ * on the key ctx's stream, with c_L q and c_R q added on the device; one host wait per round, no vector crosses PCIe.
+ * Every challenge must be below the modulus, the IPA's non-zero (REEF_ERR_ARG); r^-1 is computed in the library.  is_mont:
+ * scalar inputs and outputs in pasta Montgomery form, else canonical integers.  Outputs are HOST memory.  A call out of order --
+ * an opening call before reef_spartan_inner_claims, a round before ipa_begin, one round too many, any call after
+ * reef_nifs_set_matrix / set_running / commit_T / fold changed the ctx -- is REEF_ERR_ARG naming the call expected, and changes
+ * nothing; so is a key of another curve, device or length (the message names both lengths).  The calls never modify W, E, u, X,
+ * T or the NIFS state: commit_T, fold and a new reef_spartan_begin stay valid.  The workspace (two eq tables, a and b) grows
+ * with the first open_begin and is freed with the ctx. */
+reef_status reef_spartan_open_begin(reef_nifs_ctx *ctx, reef_msm_ctx *key, bool is_mont, reef_fe *cross_term);
+reef_status reef_spartan_open_fold(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe *c);
+reef_status reef_spartan_open_ipa_begin(reef_nifs_ctx *ctx, const reef_affine *q, reef_jacobian *L, reef_jacobian *R);
+reef_status reef_spartan_open_ipa_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_jacobian *L, reef_jacobian *R);
+reef_status reef_spartan_open_finish(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe *a_hat);
+reef_status reef_spartan_open_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont);
 
 /* ---------------------------------------------------------------------------------------------
  * (4) Runtime plumbing.

@@ -171,6 +171,12 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_spartan_inner_begin": (c_int, [vp, vp, c_bool, vp]),
         "reef_spartan_inner_round": (c_int, [vp, vp, c_bool, vp]),
         "reef_spartan_inner_claims": (c_int, [vp, vp, c_bool, vp]),
+        "reef_spartan_open_begin": (c_int, [vp, vp, c_bool, vp]),
+        "reef_spartan_open_fold": (c_int, [vp, vp, c_bool, vp]),
+        "reef_spartan_open_ipa_begin": (c_int, [vp, vp, vp, vp]),
+        "reef_spartan_open_ipa_round": (c_int, [vp, vp, c_bool, vp, vp]),
+        "reef_spartan_open_finish": (c_int, [vp, vp, c_bool, vp]),
+        "reef_spartan_open_read": (c_int, [vp, c_int, c_size_t, vp, c_bool]),
         "reef_merkle_nodes": (c_uint64, [c_uint64]),
         "reef_merkle_commit": (c_int, [c_int, vp, vp, c_size_t, c_int, c_bool, vp, c_int, vp]),
         "reef_merkle_commit_devices": (c_int, [c_int, vp, vp, c_size_t, c_bool, vp, c_size_t, vp, vp, vp]),

@@ -552,6 +552,38 @@ reef_status reef_spartan_inner_claims(reef_nifs_ctx *ctx, const reef_fe *r_last,
     return guarded([&] { return svt(ctx->curve)->inner_claims(ctx->impl, r_last, is_mont, claims); });
 }
 
+// ---- the batched IPA opening of the final SNARK on a NIFS ctx
+static const OpenVTable *ovt(int curve) { return curve == REEF_PALLAS ? pallas_open_vtable() : vesta_open_vtable(); }
+reef_status reef_spartan_open_begin(reef_nifs_ctx *ctx, reef_msm_ctx *key, bool is_mont, reef_fe *cross_term) {
+    SC_CHECK(ctx);
+    if (!key) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (key->curve != ctx->curve) {
+        set_error("reef_spartan_open_begin: the key is of curve %d, the NIFS ctx of curve %d", key->curve, ctx->curve);
+        return REEF_ERR_ARG;
+    }
+    return guarded([&] { return ovt(ctx->curve)->begin(ctx->impl, key->impl, is_mont, cross_term); });
+}
+reef_status reef_spartan_open_fold(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe *c) {
+    SC_CHECK(ctx);
+    return ovt(ctx->curve)->fold(ctx->impl, r, is_mont, c);
+}
+reef_status reef_spartan_open_ipa_begin(reef_nifs_ctx *ctx, const reef_affine *q, reef_jacobian *L, reef_jacobian *R) {
+    SC_CHECK(ctx);
+    return guarded([&] { return ovt(ctx->curve)->ipa_begin(ctx->impl, q, L, R); });
+}
+reef_status reef_spartan_open_ipa_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_jacobian *L, reef_jacobian *R) {
+    SC_CHECK(ctx);
+    return guarded([&] { return ovt(ctx->curve)->ipa_round(ctx->impl, r, is_mont, L, R); });
+}
+reef_status reef_spartan_open_finish(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe *a_hat) {
+    SC_CHECK(ctx);
+    return ovt(ctx->curve)->finish(ctx->impl, r_last, is_mont, a_hat);
+}
+reef_status reef_spartan_open_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont) {
+    SC_CHECK(ctx);
+    return ovt(ctx->curve)->read(ctx->impl, which, count, out, to_mont);
+}
+
 uint64_t reef_merkle_nodes(uint64_t n) {
     uint64_t total = 0, m = (n + 1) / 2;
     for (;;) {

@@ -424,4 +424,16 @@ struct SpartanVTable {
 const SpartanVTable *pallas_spartan_vtable();
 const SpartanVTable *vesta_spartan_vtable();
 
+// The batched IPA opening of the final SNARK on the same NIFS ctx (open_engine.inc; include/reef_msm.h 3h).  key_impl: a Ctx impl.
+struct OpenVTable {
+    reef_status (*begin)(void *impl, void *key_impl, bool is_mont, reef_fe *cross_term);
+    reef_status (*fold)(void *impl, const reef_fe *r, bool is_mont, reef_fe *c);
+    reef_status (*ipa_begin)(void *impl, const reef_affine *q, reef_jacobian *L, reef_jacobian *R);
+    reef_status (*ipa_round)(void *impl, const reef_fe *r, bool is_mont, reef_jacobian *L, reef_jacobian *R);
+    reef_status (*finish)(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *a_hat);
+    reef_status (*read)(void *impl, int which, size_t count, reef_fe *out, bool to_mont);
+};
+const OpenVTable *pallas_open_vtable();
+const OpenVTable *vesta_open_vtable();
+
 }  // namespace reef

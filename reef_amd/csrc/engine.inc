@@ -1432,29 +1432,23 @@ static reef_status v_msm_rows_symbols(void *impl, const uint8_t *symbols, size_t
     return finish_output<C>(ctx, d_res, rows, out, out_loc);
 }
 
-// Cross terms of IPA round k over the ORIGINAL generators (see k_ipa_expand).  a = a_lo || a_hi
-// (n_k scalars), w1s/w2s = the k fold challenges so far (canonical, host).  L and R go to the host.
+// The three routes of the cross terms (pre-shifted key, byte tables, plain key) on a ctx already entered, a on the device.  With
+// d_blinds (two canonical integers on the device) L += d_blinds[0] h and R += d_blinds[1] h through h's nibble table (h: affine,
+// host); without them nothing is added and the launches are those of reef_ipa_cross_terms.
 template <int C>
-static reef_status v_ipa_cross(void *impl, const reef_fe *a, size_t n_k, int loc, bool is_mont, const reef_fe *w1s,
-                               const reef_fe *w2s, size_t k, reef_jacobian *out_l, reef_jacobian *out_r) {
-    Ctx<C> *ctx = (Ctx<C> *)impl;
-    if (!ctx || !a || !out_l || !out_r || (k && (!w1s || !w2s))) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(ctx->mu);
+static reef_status ipa_cross_run(Ctx<C> *ctx, const fe256 *d_a, size_t n_k, bool is_mont, const reef_fe *w1s, const reef_fe *w2s, size_t k,
+                                 const fe256 *d_blinds, const reef_affine *h, reef_jacobian *out_l, reef_jacobian *out_r) {
     Key<C> *key = ctx->key;
-    REEF_ON_DEVICE(key->device);
-    CtxScope<C> scope(ctx);
-    REEF_TRY(scope.enter());
     const size_t n = key->n;
-    if (k > 31) { set_error("too many IPA rounds"); return REEF_ERR_ARG; }
-    if (n_k < 2 || (n_k & (n_k - 1)) || (n_k << k) != n) { set_error("n_k * 2^k must equal the key length (powers of two)"); return REEF_ERR_ARG; }
     hipStream_t st = ctx->stream;
-    const fe256 *d_a = (const fe256 *)a;
     REEF_TRY(ctx->scalars.ensure((2 * n + n_k) * sizeof(fe256)));
-    fe256 *s_l = ctx->scalars.template as<fe256>(), *s_r = s_l + n, *stage_a = s_r + n;
-    if (loc != REEF_DEVICE) {
-        REEF_HIP_TRY(hipMemcpyAsync(stage_a, a, n_k * sizeof(fe256), hipMemcpyHostToDevice, st));
-        d_a = stage_a;
-    }
+    fe256 *s_l = ctx->scalars.template as<fe256>(), *s_r = s_l + n;
+    struct HostH {                                     // launch_blind takes h's nibble table from ctx->h_host (rebuilt only when h changes)
+        Ctx<C> *c;
+        const reef_affine *saved;
+        ~HostH() { c->h_host = saved; }
+    } host_h{ctx, ctx->h_host};
+    if (d_blinds) ctx->h_host = h;
     const size_t ncoef = (size_t)1 << k;
     REEF_TRY(ctx->blinds.ensure(ncoef * sizeof(fe256)));
     fe256 *coef = ctx->blinds.template as<fe256>();
@@ -1491,6 +1485,7 @@ static reef_status v_ipa_cross(void *impl, const reef_fe *a, size_t n_k, int loc
                            (const short *)ctx->wide_dig.template as<short>(), (u32)n, per, (u32)n_k, p1);
         if (ctx->timing) REEF_HIP_TRY(hipEventRecord(ctx->ev[2], st));
         hipLaunchKernelGGL(k_small_final<C>, dim3(2), dim3(256), 0, st, (const xyzz_mem *)p1, wgs, land);
+        if (d_blinds) REEF_TRY(launch_blind<C>(ctx, land, d_blinds, nullptr, false, 2));
         if (ctx->timing) {
             REEF_HIP_TRY(hipEventRecord(ctx->ev[3], st));
             ctx->ev_pending[ctx->ev_last] = true;
@@ -1507,7 +1502,7 @@ static reef_status v_ipa_cross(void *impl, const reef_fe *a, size_t n_k, int loc
         CorePlan two = pl;
         two.rows = 2;
         two.slice_sort = true;
-        REEF_TRY(run_core<C>(ctx, s_l, two, false, nullptr, nullptr, land));   // the final kernel stores L and R where the host reads them
+        REEF_TRY(run_core<C>(ctx, s_l, two, false, d_blinds, nullptr, land));   // the final kernel stores L and R where the host reads them
         REEF_HIP_TRY(hipStreamSynchronize(st));
         memcpy(out_l, &land[0], sizeof(jacobian256));
         memcpy(out_r, &land[1], sizeof(jacobian256));
@@ -1515,15 +1510,60 @@ static reef_status v_ipa_cross(void *impl, const reef_fe *a, size_t n_k, int loc
     }
     reef_jacobian *outs[2] = {out_l, out_r};
     const fe256 *vecs[2] = {s_l, s_r};
+    // blind terms: d_blinds[v] h into the landing zone's last two slots (past the group sums), ahead of the MSMs whose group-sum
+    // waits cover it; each is added to its window combine on the host
+    jacobian256 *bt = (d_blinds && (size_t)pl.G * sizeof(xyzz_mem) <= 62 * sizeof(jacobian256)) ? land + 62 : nullptr;
+    if (bt) {
+        memset(bt, 0, 2 * sizeof(jacobian256));
+        REEF_TRY(launch_blind<C>(ctx, bt, d_blinds, nullptr, false, 2));
+    }
     for (int v = 0; v < 2; ++v) {   // plain key: finish each window combine on the host (as in v_msm)
         const xyzz_mem *gs = nullptr;
         REEF_TRY(run_core<C>(ctx, vecs[v], pl, false, nullptr, nullptr, d_res + v, &gs));
         std::vector<xyzz_mem> hs;
         REEF_TRY(fetch_group_sums<C>(ctx, gs, pl.G, hs));
-        const jacobian256 j = host_window_combine<C>(hs.data(), pl.G, pl.c);
+        jacobian256 j = host_window_combine<C>(hs.data(), pl.G, pl.c);
+        if (bt) j = host_jacobian_add<C>(j, bt[v]);
         memcpy(outs[v], &j, sizeof j);
     }
+    if (d_blinds && !bt) {   // many groups: the blind term on the device, the combined sums there and back
+        jacobian256 both[2];
+        memcpy(&both[0], out_l, sizeof(jacobian256));
+        memcpy(&both[1], out_r, sizeof(jacobian256));
+        REEF_HIP_TRY(hipMemcpyAsync(d_res, both, sizeof both, hipMemcpyHostToDevice, st));
+        REEF_TRY(launch_blind<C>(ctx, d_res, d_blinds, nullptr, false, 2));
+        REEF_HIP_TRY(hipGetLastError());
+        REEF_HIP_TRY(hipMemcpyAsync(both, d_res, sizeof both, hipMemcpyDeviceToHost, st));
+        REEF_HIP_TRY(hipStreamSynchronize(st));
+        memcpy(out_l, &both[0], sizeof(jacobian256));
+        memcpy(out_r, &both[1], sizeof(jacobian256));
+    }
     return REEF_OK;
+}
+
+// Cross terms of IPA round k over the ORIGINAL generators (see k_ipa_expand).  a = a_lo || a_hi
+// (n_k scalars), w1s/w2s = the k fold challenges so far (canonical, host).  L and R go to the host.
+template <int C>
+static reef_status v_ipa_cross(void *impl, const reef_fe *a, size_t n_k, int loc, bool is_mont, const reef_fe *w1s,
+                               const reef_fe *w2s, size_t k, reef_jacobian *out_l, reef_jacobian *out_r) {
+    Ctx<C> *ctx = (Ctx<C> *)impl;
+    if (!ctx || !a || !out_l || !out_r || (k && (!w1s || !w2s))) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    Key<C> *key = ctx->key;
+    REEF_ON_DEVICE(key->device);
+    CtxScope<C> scope(ctx);
+    REEF_TRY(scope.enter());
+    const size_t n = key->n;
+    if (k > 31) { set_error("too many IPA rounds"); return REEF_ERR_ARG; }
+    if (n_k < 2 || (n_k & (n_k - 1)) || (n_k << k) != n) { set_error("n_k * 2^k must equal the key length (powers of two)"); return REEF_ERR_ARG; }
+    const fe256 *d_a = (const fe256 *)a;
+    if (loc != REEF_DEVICE) {
+        REEF_TRY(ctx->scalars.ensure((2 * n + n_k) * sizeof(fe256)));
+        fe256 *stage_a = ctx->scalars.template as<fe256>() + 2 * n;
+        REEF_HIP_TRY(hipMemcpyAsync(stage_a, a, n_k * sizeof(fe256), hipMemcpyHostToDevice, ctx->stream));
+        d_a = stage_a;
+    }
+    return ipa_cross_run<C>(ctx, d_a, n_k, is_mont, w1s, w2s, k, nullptr, nullptr, out_l, out_r);
 }
 
 // Commitment over the generators k folds away from the resident key, without the folds: the generators after k rounds of

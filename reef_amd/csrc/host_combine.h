@@ -201,4 +201,32 @@ template <int C> static inline jacobian256 host_window_combine(const xyzz_mem *g
     return r;
 }
 
+// a + b for two ABI Jacobian points (x = X / Z^2, y = Y / Z^3; the identity has Z = 0), as host_window_combine returns them
+template <int C> static inline jacobian256 host_jacobian_add(const jacobian256 &a, const jacobian256 &b) {
+    using namespace hostcombine;
+    const Field<C> &fd = field<C>();
+    auto from_abi = [&](const fe256 &w) {
+        f4 r;
+        for (int i = 0; i < 4; ++i) r.l[i] = (u64)w.w[2 * i] | (u64)w.w[2 * i + 1] << 32;
+        return r;
+    };
+    auto to_pt = [&](const jacobian256 &j) {
+        pt p;
+        p.x = from_abi(j.x);
+        p.y = from_abi(j.y);
+        const f4 z = from_abi(j.z);
+        p.zz = fsqr(fd, z);
+        p.zzz = fmul(fd, p.zz, z);
+        return p;
+    };
+    const pt s = pt_add(fd, to_pt(a), to_pt(b));
+    jacobian256 r;
+    memset(&r, 0, sizeof r);
+    if (is_zero(s.zz)) return r;
+    r.x = to_abi_words(fmul(fd, s.x, s.zz));
+    r.y = to_abi_words(fmul(fd, s.y, s.zzz));
+    r.z = to_abi_words(s.zz);
+    return r;
+}
+
 }  // namespace reef

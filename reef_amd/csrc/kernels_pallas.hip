@@ -7,9 +7,11 @@
 #include "keygen_kernels.inc"
 #include "nifs_kernels.inc"
 #include "spartan_kernels.inc"
+#include "open_kernels.inc"
 #include "engine.inc"
 #include "nifs_engine.inc"
 #include "spartan_engine.inc"
+#include "open_engine.inc"
 namespace reef {
 const CurveVTable *pallas_vtable() {
     static const CurveVTable vt = make_vtable<0>();
@@ -21,6 +23,10 @@ const NifsVTable *pallas_nifs_vtable() {
 }
 const SpartanVTable *pallas_spartan_vtable() {
     static const SpartanVTable vt = make_spartan_vtable<0>();
+    return &vt;
+}
+const OpenVTable *pallas_open_vtable() {
+    static const OpenVTable vt = make_open_vtable<0>();
     return &vt;
 }
 }

@@ -7,9 +7,11 @@
 #include "keygen_kernels.inc"
 #include "nifs_kernels.inc"
 #include "spartan_kernels.inc"
+#include "open_kernels.inc"
 #include "engine.inc"
 #include "nifs_engine.inc"
 #include "spartan_engine.inc"
+#include "open_engine.inc"
 namespace reef {
 const CurveVTable *vesta_vtable() {
     static const CurveVTable vt = make_vtable<1>();
@@ -21,6 +23,10 @@ const NifsVTable *vesta_nifs_vtable() {
 }
 const SpartanVTable *vesta_spartan_vtable() {
     static const SpartanVTable vt = make_spartan_vtable<1>();
+    return &vt;
+}
+const OpenVTable *vesta_open_vtable() {
+    static const OpenVTable vt = make_open_vtable<1>();
     return &vt;
 }
 }

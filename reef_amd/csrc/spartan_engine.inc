@@ -3,7 +3,7 @@
 // inner_claims, with ell_x = log2(num_cons_pad), ell_y = log2(2 num_vars_pad).  The running instance is read, never written.
 namespace reef {
 
-enum { SP_NONE = 0, SP_OUTER, SP_OUTER_DONE, SP_INNER, SP_DONE };
+enum { SP_NONE = 0, SP_OUTER, SP_OUTER_DONE, SP_INNER, SP_DONE, SP_OPEN_BEGUN, SP_OPEN_FOLDED, SP_OPEN_IPA, SP_OPEN_DONE };   // SP_OPEN_*: open_engine.inc
 
 template <int C> struct SpartanState {
     int phase = SP_NONE;
@@ -14,15 +14,29 @@ template <int C> struct SpartanState {
     DevBuf eq, az, bz, cz, d;            // outer tables (ncp entries); cz and E are never bound
     DevBuf abc, z;                       // inner tables (2 nvp entries)
     DevBuf pts, partial, out;            // eq factors, block sums, results
+    // the batched IPA opening (open_engine.inc)
+    DevBuf e1, e2, oa, ob;               // eq(r_x), eq(r_y[1..]); a (canonical integers) and b (internal form), n entries each
+    void *key = nullptr;                 // the gens_v key ctx (Ctx<C>) of the opening, from open_begin to finish
+    size_t on = 0, olen = 0;             // n; the length of a and b as they stand
+    reef_affine q = {};                  // gens_c.scale(r): the point of the cross terms' blind term
+    std::vector<fe256> w1s, w2s;         // the IPA challenges so far: r^-1 and r, canonical integers (reef_fold's convention)
 };
 template <int C> static void spartan_release(SpartanState<C> *s) {
     if (!s) return;
-    for (DevBuf *b : {&s->eq, &s->az, &s->bz, &s->cz, &s->d, &s->abc, &s->z, &s->pts, &s->partial, &s->out}) b->release();
+    for (DevBuf *b : {&s->eq, &s->az, &s->bz, &s->cz, &s->d, &s->abc, &s->z, &s->pts, &s->partial, &s->out, &s->e1, &s->e2, &s->oa, &s->ob}) b->release();
     delete s;
 }
 
-static const char *sp_expected(int phase, u32 rounds, u32 ell_x, u32 ell_y) {
+static u32 sp_log2(size_t n) {
+    u32 l = 0;
+    while ((size_t)1 << l < n) ++l;
+    return l;
+}
+static const char *sp_expected(int phase, u32 rounds, u32 ell_x, u32 ell_y, u32 ell_n = 0) {
     switch (phase) {
+    case SP_OPEN_BEGUN: return "reef_spartan_open_fold";
+    case SP_OPEN_FOLDED: return "reef_spartan_open_ipa_begin";
+    case SP_OPEN_IPA: return rounds + 1 < ell_n ? "reef_spartan_open_ipa_round" : "reef_spartan_open_finish";
     case SP_OUTER: return rounds + 1 < ell_x ? "reef_spartan_outer_round" : "reef_spartan_outer_claims";
     case SP_OUTER_DONE: return "reef_spartan_inner_begin";
     case SP_INNER: return rounds + 1 < ell_y ? "reef_spartan_inner_round" : "reef_spartan_inner_claims";
@@ -38,7 +52,7 @@ template <int C> static reef_status sp_expect(NifsCtx<C> *c, const char *name) {
                   "the next call is reef_spartan_begin", name);
         return REEF_ERR_ARG;
     }
-    const char *want = s ? sp_expected(s->phase, s->rounds, s->ell_x, s->ell_y) : "reef_spartan_begin";
+    const char *want = s ? sp_expected(s->phase, s->rounds, s->ell_x, s->ell_y, sp_log2(s->on)) : "reef_spartan_begin";
     if (strcmp(want, name) != 0) { set_error("%s: out of order, the next call is %s", name, want); return REEF_ERR_ARG; }
     return REEF_OK;
 }
@@ -48,11 +62,6 @@ template <int C> static fe sp_import(const reef_fe *x, bool is_mont) {
     fe256 p;
     memcpy(&p, x, sizeof p);
     return fe_canon<F>(is_mont ? fe_from_abi<F>(p) : fe_from_integer<F>(p));
-}
-static u32 sp_log2(size_t n) {
-    u32 l = 0;
-    while ((size_t)1 << l < n) ++l;
-    return l;
 }
 static bool sp_valid_fe(const reef_fe *x, int field) {          // canonical: below the modulus
     fe256 p;

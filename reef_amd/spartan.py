@@ -4,14 +4,18 @@ nova-snark's RelaxedR1CSSNARK::prove (Reef: S1 / S2, src/backend/framework.rs:7-
 sum-check over the running relaxed instance a `reef_amd.nifs.Nifs` holds on the device.  The transcript stays with the caller:
 `prove` drives a whole prove with a caller-supplied `challenge(label, absorbed) -> int` in place of nova's Keccak transcript.
 Field elements cross as Python ints: canonical, or pasta Montgomery form with is_mont=True on the `Spartan` methods.
+
+`Opening` is the batched IPA opening that follows on the same ctx (include/reef_msm.h 3h), and `prove_with_opening` runs both.
+Points cross as numpy uint64 arrays in the C-ABI layouts: affine (8 limbs) in, Jacobian (12 limbs) out.
 """
 from __future__ import annotations
 
-from typing import Callable, List, Sequence
+from typing import Any, Callable, List, Sequence, Tuple
 
 import numpy as np
 
-from ._ffi import check
+from ._ffi import REEF_HOST, check
+from .msm import MsmContext
 from .nifs import Nifs
 
 
@@ -96,3 +100,91 @@ def prove(nifs: Nifs, num_cons_pad: int, num_vars_pad: int, challenge: Callable[
     claims_inner = run(sp.inner_claims, to(r_y[-1]))
     return {"tau": tau, "outer": outer, "r_x": r_x, "claims_outer": claims_outer, "r": r, "inner": inner, "r_y": r_y,
             "claims_inner": claims_inner}
+
+
+class Opening:
+    """The batched IPA opening on one NIFS ctx after `Spartan.inner_claims`: begin, fold, ipa_begin, ipa_round x (log2(n) - 1),
+    finish, with n = max(num_cons_pad, num_vars_pad) and a gens_v key of exactly n points.  Scalars are ints in the caller's form."""
+
+    def __init__(self, nifs: Nifs):
+        self.nifs = nifs
+        self._lib = nifs._lib
+
+    def _scalar(self, fn, *args) -> int:
+        out = np.zeros((1, 4), dtype=np.uint64)
+        check(fn(self.nifs._h, *args, out.ctypes.data))
+        return _ints(out)[0]
+
+    def _points(self, fn, *args) -> Tuple[np.ndarray, np.ndarray]:
+        L, R = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
+        check(fn(self.nifs._h, *args, L.ctypes.data, R.ctypes.data))
+        return L, R
+
+    def begin(self, key: MsmContext, *, is_mont: bool = False) -> int:
+        """The cross term <E, eq(r_y[1..])> + <W, eq(r_x)>."""
+        return self._scalar(self._lib.reef_spartan_open_begin, key._h, is_mont)
+
+    def fold(self, r: int, *, is_mont: bool = False) -> int:
+        """c = <a, b> after a = E + r W, b = eq(r_x) + r eq(r_y[1..])."""
+        ra = _arr([r])
+        return self._scalar(self._lib.reef_spartan_open_fold, ra.ctypes.data, is_mont)
+
+    def ipa_begin(self, q: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """Round 0's L and R; q: gens_c.scale(r), affine (8 uint64 limbs, pasta Montgomery coordinates)."""
+        qa = np.ascontiguousarray(q, dtype=np.uint64).reshape(8)
+        return self._points(self._lib.reef_spartan_open_ipa_begin, qa.ctypes.data)
+
+    def ipa_round(self, r: int, *, is_mont: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        ra = _arr([r])
+        return self._points(self._lib.reef_spartan_open_ipa_round, ra.ctypes.data, is_mont)
+
+    def finish(self, r_last: int, *, is_mont: bool = False) -> int:
+        """a_hat"""
+        ra = _arr([r_last])
+        return self._scalar(self._lib.reef_spartan_open_finish, ra.ctypes.data, is_mont)
+
+    def read(self, which: int, count: int, *, to_mont: bool = False) -> List[int]:
+        """which: 0 a, 1 b, as they stand now."""
+        out = np.zeros((max(count, 1), 4), dtype=np.uint64)
+        check(self._lib.reef_spartan_open_read(self.nifs._h, which, count, out.ctypes.data, to_mont))
+        return _ints(out[:count])
+
+
+def compress(key: MsmContext, jac: np.ndarray) -> bytes:
+    """A point's 32-byte compressed encoding (what the transcript absorbs), on the device of the library."""
+    j = np.ascontiguousarray(jac, dtype=np.uint64).reshape(12)
+    out = np.zeros(32, dtype=np.uint8)
+    check(key._lib.reef_normalize(key.curve, j.ctypes.data, 1, REEF_HOST, None, out.ctypes.data))
+    return out.tobytes()
+
+
+def prove_with_opening(nifs: Nifs, key: MsmContext, num_cons_pad: int, num_vars_pad: int, challenge: Callable[[str, List[Any]], int],
+                       p: int, comm_a: Callable[[int], Any], q_of: Callable[[int], np.ndarray], *, is_mont: bool = False) -> dict:
+    """`prove`, then the batched IPA opening of [E, W] with the same `challenge(label, absorbed)`, in nova's order: "r" (the NIFS
+    challenge, after the cross term), "r" again (the IPA's, after comm_a and c), then "challenge_r" per round (after L and R,
+    compressed).  The caller's point operations: comm_a(r) = comm_E + r comm_W as the transcript absorbs it, and
+    q_of(r) = gens_s.scale(r), affine.  key: gens_v, exactly max(num_cons_pad, num_vars_pad) points.  Canonical ints in and out."""
+    out = prove(nifs, num_cons_pad, num_vars_pad, challenge, p, is_mont=is_mont)
+    op = Opening(nifs)
+    R = (1 << 256) % p
+    Rinv = pow(R, -1, p)
+    to = (lambda v: v * R % p) if is_mont else (lambda v: v)
+    frm = (lambda v: v * Rinv % p) if is_mont else (lambda v: v)
+    cross = frm(op.begin(key, is_mont=is_mont))
+    r_fold = challenge("r", [cross])
+    c = frm(op.fold(to(r_fold), is_mont=is_mont))
+    ca = comm_a(r_fold)
+    r_ipa = challenge("r", [ca, c])
+    L, Rp = op.ipa_begin(q_of(r_ipa))
+    Ls, Rs, rs = [L], [Rp], []
+    n = max(num_cons_pad, num_vars_pad)
+    for _ in range(n.bit_length() - 2):
+        rs.append(challenge("challenge_r", [compress(key, Ls[-1]), compress(key, Rs[-1])]))
+        L, Rp = op.ipa_round(to(rs[-1]), is_mont=is_mont)
+        Ls.append(L)
+        Rs.append(Rp)
+    rs.append(challenge("challenge_r", [compress(key, Ls[-1]), compress(key, Rs[-1])]))
+    a_hat = frm(op.finish(to(rs[-1]), is_mont=is_mont))
+    out.update({"cross_term": cross, "r_fold": r_fold, "c": c, "comm_a": ca, "r_ipa": r_ipa, "L": Ls, "R": Rs, "r_ipa_rounds": rs,
+                "a_hat": a_hat})
+    return out
