@@ -536,6 +536,17 @@ template <int F> REEF_HD fe fe_from_integer(const fe256 &p) {
     REEF_SET_BOUND(x, 1.0);
     return fe_mul<F>(x, fe_const<F>(FC<F>::C_R2, 1.0));
 }
+// internal form -> canonical integer, packed: mont(x, 1) = x / R'
+template <int F> REEF_HD fe256 fe_to_integer(const fe &x) {
+    fe one = fe_zero();
+    one.l[0] = 1;
+    REEF_SET_BOUND(one, 1.0);
+    return fe_pack(fe_canon<F>(fe_mul<F>(x, one)));
+}
+// The caller's form of a field element (a canonical integer, or pasta Montgomery form when is_mont) <-> internal form.
+// fe_from_caller does not canonicalise.
+template <int F> REEF_HD fe fe_from_caller(const fe256 &p, bool is_mont) { return is_mont ? fe_from_abi<F>(p) : fe_from_integer<F>(p); }
+template <int F> REEF_HD fe256 fe_to_caller(const fe &x, bool to_mont) { return to_mont ? fe_to_abi<F>(x) : fe_to_integer<F>(x); }
 
 // a^(M-2); inv(0) = 0.  M - 2 = 2^254 + delta - 2.
 template <int F> REEF_HD fe fe_inv(const fe &a) {

@@ -1,6 +1,7 @@
 // Vesta instantiation of the MSM engine (coordinates in Fq, scalars in Fp).
 #define REEF_CURVE 1
 #include "msm_kernels.inc"
+#include "fe_vec.h"
 #include "sumcheck_kernels.inc"
 #include "mle_kernels.inc"
 #include "merkle_kernels.inc"

@@ -13,7 +13,7 @@
 // Everything pasta_curves fixes and this repository cannot confirm -- a, b, Z, the 13 isogeny coefficients, the domain
 // separation string, the byte order of hash_to_field -- is DATA of the call (reef_keygen_params).
 //
-// Included by kernels_<curve>.hip after sumcheck_kernels.inc (sc_to_integer); C = curve, coordinates in field C.
+// Included by kernels_<curve>.hip after fe_vec.h; C = curve, coordinates in field C.
 namespace reef {
 
 // ---- BLAKE2b-512, unkeyed (RFC 7693) ----
@@ -76,7 +76,7 @@ __device__ void blake2b_512(const unsigned char *in, u32 len, unsigned char *out
 
 // ---- field helpers of the maps ----
 template <int F> __device__ __forceinline__ bool fe_equal(const fe &a, const fe &b) { return fe_is_zero<F>(fe_sub<F, 4>(a, b)); }   // a, b < 4
-template <int F> __device__ __forceinline__ u32 fe_sgn0(const fe &x) { return sc_to_integer<F>(x).w[0] & 1u; }                      // parity of the canonical integer
+template <int F> __device__ __forceinline__ u32 fe_sgn0(const fe &x) { return fe_to_integer<F>(x).w[0] & 1u; }                      // parity of the canonical integer
 // 64 bytes (OS2IP big-endian, or little-endian) mod M -> internal form
 template <int F> __device__ fe fe_from_64_bytes(const unsigned char *s, bool little_endian) {
     fe acc = fe_zero();

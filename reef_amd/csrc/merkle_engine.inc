@@ -52,7 +52,7 @@ template <int F> static void pos_derive_sparse(const reef_poseidon_params *pp, b
     auto in = [&](const reef_fe &v) {
         fe256 raw;
         memcpy(&raw, &v, sizeof raw);
-        return pos_canon<F>(is_mont ? fe_from_abi<F>(raw) : fe_from_integer<F>(raw));
+        return pos_canon<F>(fe_from_caller<F>(raw, is_mont));
     };
     fe M[POS_T][POS_T];
     for (int i = 0; i < POS_T; ++i)
@@ -238,7 +238,7 @@ static reef_status v_merkle_commit(const reef_poseidon_params *pp, const uint32_
     // export: the whole tree (level by level, leaves' parents first) and / or the root, in the form the caller's field elements have
     void *exp = nullptr;
     REEF_TRY(ss.alloc(&exp, total * sizeof(fe256)));
-    hipLaunchKernelGGL(k_fe_export<F>, dim3((u32)ceil_div(total, 256)), dim3(256), 0, ss.s, (const fe256 *)tree, total, (int)is_mont, (fe256 *)exp);
+    hipLaunchKernelGGL(k_fe_export<F>, dim3((u32)ceil_div(total, 256)), dim3(256), 0, ss.s, (const fe256 *)tree, total, 0, (int)is_mont, (fe256 *)exp);
     if (tree_out) {
         REEF_HIP_TRY(hipMemcpyAsync(tree_out, exp, total * sizeof(fe256), out_loc == REEF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ss.s));
     }

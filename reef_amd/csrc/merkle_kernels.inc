@@ -9,44 +9,13 @@
 // SAFE API derives from the IO patterns live in a crate that is not in the reference tree): the Rust binding passes
 // them, so the tree is the reference's tree by construction; the oracle and the tests use stand-in constants.
 //
-// Included by kernels_<curve>.hip after sumcheck_kernels.inc; F = scalar field of the curve.
+// Included by kernels_<curve>.hip after fe_vec.h; F = scalar field of the curve.
 namespace reef {
 
 static constexpr int POS_T = 5;    // width: arity 4 + the capacity element
 
-// ABI field elements (canonical integers, or Montgomery form when is_mont) -> internal table form
-template <int F>
-__global__ void __launch_bounds__(256) k_fe_import(const fe256 *__restrict__ in, u32 n, int is_mont, fe256 *__restrict__ out) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const fe256 v = load_fe256(in + i);
-    store_fe256(out + i, fe_to_table<F>(is_mont ? fe_from_abi<F>(v) : fe_from_integer<F>(v)));
-}
-template <int F>
-__global__ void __launch_bounds__(256) k_fe_export(const fe256 *__restrict__ in, u64 n, int to_mont, fe256 *__restrict__ out) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const fe x = fe_from_table(load_fe256(in + i));
-    store_fe256(out + i, to_mont ? fe_to_abi<F>(x) : sc_to_integer<F>(x));
-}
-
-// sum of up to five products with ONE Montgomery reduction (lazy 18-column accumulation); operands normalised with
-// sum (A/M)(B/M) < 128; result exact limbs, value < 2 M.
-template <int F> __device__ __forceinline__ fe wide18_reduce_small(fe_wide18 &w) {
-    wide18_carry(w);
-    u64 t[10];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) t[i] = w.c[i] + MONT_BIAS;
-    t[9] = 0;
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-        mont_round<F>(t);
-        t[8] += w.c[9 + r];
-    }
-    fe x = mont_finish<F>(t);
-    REEF_SET_BOUND(x, 2.0);
-    return x;
-}
+// A sum of up to five products takes ONE Montgomery reduction (lazy 18-column accumulation, fe_vec.h: wide18_mont); operands
+// normalised with sum (A/M)(B/M) < 128; result exact limbs, value < 2 M.
 
 struct PoseidonDev {
     const fe256 *rc;      // dense form: POS_T * (rf + rp) round constants, round-major.  Sparse form: the rf full rounds only, the
@@ -75,7 +44,7 @@ template <int F> __device__ __forceinline__ void pos_mds(fe (&s)[POS_T], const f
             wide18_mac(w, s[i].l, e.l);
             if (i == 3) wide18_carry(w);                                     // four products fit between carries
         }
-        n[j] = wide18_reduce_small<F>(w);
+        n[j] = wide18_mont<F>(w, 2.0);
     }
 #pragma unroll
     for (int j = 0; j < POS_T; ++j) s[j] = n[j];
@@ -126,7 +95,7 @@ template <int F> __device__ __forceinline__ void poseidon_permute_sparse(fe (&s)
         }
 #pragma unroll
         for (int j = 1; j < POS_T; ++j) s[j] = fe_add<F>(fe_mul<F>(fe_from_table(load_fe256(c + 1 + j)), s0), s[j]);   // grows by < 2 per round
-        s[0] = wide18_reduce_small<F>(w);
+        s[0] = wide18_mont<F>(w, 2.0);
         if ((k & 7u) == 7u) {
 #pragma unroll
             for (int j = 1; j < POS_T; ++j) s[j] = fe_mul<F>(s[j], one);                    // back below 2
@@ -226,7 +195,7 @@ __device__ __forceinline__ fe pos_spread_mds(const fe &s, int elem, int base, in
         wide18_mac(w, si.l, e.l);
         if (i == 3) wide18_carry(w);
     }
-    return wide18_reduce_small<F>(w);
+    return wide18_mont<F>(w, 2.0);
 }
 template <int F>
 __device__ __forceinline__ fe poseidon_permute_spread(fe s, int elem, int base, int lane, const PoseidonDev &p, PosSpreadLds &L) {

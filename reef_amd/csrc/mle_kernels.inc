@@ -32,7 +32,7 @@ __global__ void __launch_bounds__(256) k_mle_eq(MlePoint pt, u32 first, u32 vars
     if (t >= (1u << vars)) return;
     fe acc = fe_one<F>();
     for (u32 k = 0; k < vars; ++k) {
-        const fe r = is_mont ? fe_from_abi<F>(pt.r[first + k]) : fe_from_integer<F>(pt.r[first + k]);
+        const fe r = fe_from_caller<F>(pt.r[first + k], is_mont);
         const fe one_minus = fe_sub<F, 2>(fe_one<F>(), r);
         const bool bit = (t >> (vars - 1 - k)) & 1u;
         acc = fe_mul<F>(acc, bit ? r : one_minus);
@@ -134,7 +134,7 @@ __global__ void __launch_bounds__(256) k_mle_finish(const fe256 *__restrict__ pa
             s = fe_from_wide<F>(w);
         }
         fe256 out;
-        if (COMPACT) out = is_mont ? fe_to_abi<F>(s) : sc_to_integer<F>(s);
+        if (COMPACT) out = fe_to_caller<F>(s, is_mont);
         else out = fe_pack(fe_canon<F>(s));
         if (lz) store_fe256(lz + j, out);
         const fe p = fe_mul<F>(s, fe_from_limbs(Req[j], 1.0));
@@ -160,7 +160,7 @@ __global__ void k_mle_eval_final(unsigned long long *__restrict__ dot, int is_mo
     for (int k = 0; k < 9; ++k) w.l[k] = dot[k];
     const fe s = fe_from_wide<F>(w);
     fe256 o;
-    if (COMPACT) o = is_mont ? fe_to_abi<F>(s) : sc_to_integer<F>(s);
+    if (COMPACT) o = fe_to_caller<F>(s, is_mont);
     else o = fe_pack(fe_canon<F>(s));
     store_fe256(out, o);
 }

@@ -237,7 +237,7 @@ template <int C, int MODE> static reef_status nifs_line_pass(const NifsArgs &a, 
 }
 template <int C, int MODE> static reef_status nifs_row_pass(NifsCtx<C> *c, hipStream_t s) { return nifs_line_pass<C, MODE>(nifs_args(c), c->rows, s); }
 
-// n elements of the caller's (host or device) buffer into dst, in the caller's form: dst holds them raw until k_nifs_import
+// n elements of the caller's (host or device) buffer into dst, in the caller's form: dst holds them raw until k_fe_import
 template <int C> static reef_status nifs_copy_in(NifsCtx<C> *c, fe256 *dst, const reef_fe *src, size_t n, int loc) {
     if (!n) return REEF_OK;
     REEF_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(fe256), loc == REEF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
@@ -260,7 +260,7 @@ static reef_status nifs_load_z(NifsCtx<C> *c, fe256 *z, const reef_fe *w, const 
         REEF_HIP_TRY(hipMemcpyAsync(z + c->num_vars, &one_raw[is_mont ? 1 : 0], sizeof(fe256), hipMemcpyHostToDevice, c->stream));
     }
     REEF_TRY(nifs_copy_in(c, z + c->num_vars + 1, x, c->num_io, loc));
-    hipLaunchKernelGGL(k_nifs_import<F>, dim3(ceil_div(c->nz, 256)), dim3(256), 0, c->stream, z, (u32)c->nz, (int)is_mont, z);
+    hipLaunchKernelGGL(k_fe_import<F>, dim3(ceil_div(c->nz, 256)), dim3(256), 0, c->stream, z, (u64)c->nz, (int)is_mont, z);
     REEF_HIP_TRY(hipGetLastError());
     return REEF_OK;
 }
@@ -279,7 +279,7 @@ static reef_status v_nifs_set_running(void *impl, const reef_fe *W, const reef_f
     REEF_TRY(nifs_load_z(c, c->z1.template as<fe256>(), W, u, X, loc, is_mont));
     if (E) {
         REEF_TRY(nifs_copy_in(c, dE, E, c->num_cons, loc));
-        hipLaunchKernelGGL(k_nifs_import<NifsCtx<C>::F>, dim3(ceil_div(c->num_cons, 256)), dim3(256), 0, c->stream, dE, (u32)c->num_cons, (int)is_mont, dE);
+        hipLaunchKernelGGL(k_fe_import<NifsCtx<C>::F>, dim3(ceil_div(c->num_cons, 256)), dim3(256), 0, c->stream, dE, (u64)c->num_cons, (int)is_mont, dE);
         REEF_HIP_TRY(hipGetLastError());
     } else {
         REEF_HIP_TRY(hipMemsetAsync(dE, 0, c->num_cons * sizeof(fe256), c->stream));     // zero is zero in every form
@@ -334,7 +334,7 @@ template <int C> static reef_status v_nifs_fold(void *impl, const reef_fe *r, bo
     if (!c->committed) { set_error("reef_nifs_fold: no cross term of this step (reef_nifs_commit_T first)"); return REEF_ERR_ARG; }
     fe256 rp;
     memcpy(&rp, r, sizeof rp);
-    const fe ri = is_mont ? fe_from_abi<F>(rp) : fe_from_integer<F>(rp);                 // r R'
+    const fe ri = fe_from_caller<F>(rp, is_mont);                                         // r R'
     const fe256 r_int = fe_to_table<F>(ri);
     const fe256 r_sq = fe_to_table<F>(fe_mul<F>(ri, fe_const<F>(FC<F>::C_R2, 1.0)));    // r R'^2: times an integer T gives r T R'
     REEF_ON_DEVICE(c->device);
@@ -372,7 +372,7 @@ template <int C> static reef_status v_nifs_read(void *impl, int which, size_t co
     NifsScope<C> scope(c);
     REEF_TRY(scope.enter());
     REEF_TRY(c->stage.ensure(count * sizeof(fe256)));
-    hipLaunchKernelGGL(k_nifs_export<NifsCtx<C>::F>, dim3(ceil_div(count, 256)), dim3(256), 0, c->stream, src, (u32)count, (int)(which == 2), (int)to_mont,
+    hipLaunchKernelGGL(k_fe_export<NifsCtx<C>::F>, dim3(ceil_div(count, 256)), dim3(256), 0, c->stream, src, (u64)count, (int)(which == 2), (int)to_mont,
                        c->stage.template as<fe256>());
     REEF_HIP_TRY(hipGetLastError());
     REEF_HIP_TRY(hipMemcpyAsync(out, c->stage.p, count * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));

@@ -69,26 +69,6 @@ __global__ void __launch_bounds__(256) k_nifs_classify(const u32 *__restrict__ c
     ent[e] = make_uint2(cols[e], cls);
 }
 
-// canonical integers or ABI Montgomery form -> resident internal form (in place allowed)
-template <int F>
-__global__ void __launch_bounds__(256) k_nifs_import(const fe256 *__restrict__ in, u32 n, int is_mont, fe256 *__restrict__ out) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const fe256 v = load_fe256(in + i);
-    store_fe256(out + i, fe_to_table<F>(is_mont ? fe_from_abi<F>(v) : fe_from_integer<F>(v)));
-}
-// resident -> the caller's form.  in_integer: the source holds canonical integers (T)
-template <int F>
-__global__ void __launch_bounds__(256) k_nifs_export(const fe256 *__restrict__ in, u32 n, int in_integer, int to_mont, fe256 *__restrict__ out) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const fe256 v = load_fe256(in + i);
-    fe256 o;
-    if (in_integer) o = to_mont ? fe_to_abi<F>(fe_from_integer<F>(v)) : v;
-    else o = to_mont ? fe_to_abi<F>(fe_from_table(v)) : sc_to_integer<F>(fe_from_table(v));
-    store_fe256(out + i, o);
-}
-
 // dst[i] = dst[i] + r * src[i], r pre-scaled so that the product lands in internal form (r R' against an internal src,
 // r R'^2 against an integer src)
 template <int F>
@@ -166,7 +146,7 @@ __device__ __forceinline__ void nifs_epilogue(const NifsArgs &a, u32 row, const 
     if constexpr (MODE == NIFS_MODE_T) {
         const fe m = fe_mul2_add<F>(d[0], d[3], d[1], d[2]);                  // AZ1 BZ2 + AZ2 BZ1, < 2M
         const fe s = fe_add<F>(fe_mul<F>(u1, d[5]), d[4]);                      // u1 CZ2 + CZ1, < 3M
-        store_fe256(a.T + row, sc_to_integer<F>(fe_sub<F, 4>(m, s)));
+        store_fe256(a.T + row, fe_to_integer<F>(fe_sub<F, 4>(m, s)));
     } else if constexpr (MODE == NIFS_MODE_CHECK) {
         const fe lhs = fe_mul<F>(d[0], d[1]);
         const fe rhs = fe_add<F>(fe_mul<F>(u1, d[2]), fe_from_table(load_fe256(a.E + row)));
@@ -212,7 +192,7 @@ __global__ void __launch_bounds__(256) k_nifs_rows_short(NifsArgs a) {
         nifs_dot<F, 1>(a.m[2], b[2], e[2], 1, a.z1, a.z2, k254, cz);
         const fe u1 = fe_from_table(load_fe256(a.z1 + a.num_vars));
         const fe s = fe_add<F>(fe_mul<F>(u1, cz[1]), cz[0]);                   // u1 CZ2 + CZ1, < 3M
-        store_fe256(a.T + row, sc_to_integer<F>(fe_sub<F, 4>(m, s)));
+        store_fe256(a.T + row, fe_to_integer<F>(fe_sub<F, 4>(m, s)));
     } else {
         fe d[3];
 #pragma unroll

@@ -14,12 +14,6 @@ template <int C> static reef_status op_expect(NifsCtx<C> *c, const char *name) {
     }
     return sp_expect(c, name);
 }
-template <int C> static fe256 op_to_integer(const fe &x) {      // canonical integer (sc_to_integer on the host)
-    fe one = fe_zero();
-    one.l[0] = 1;
-    REEF_SET_BOUND(one, 1.0);
-    return fe_pack(fe_canon<NifsCtx<C>::F>(fe_mul<NifsCtx<C>::F>(x, one)));
-}
 // a non-zero challenge below the modulus (the IPA folds with r^-1)
 template <int C> static reef_status op_challenge(const reef_fe *r, bool is_mont, const char *name, fe &out) {
     REEF_TRY(sp_challenge<C>(r, is_mont, name, out));
@@ -55,8 +49,8 @@ template <int C> static reef_status op_fetch(NifsCtx<C> *c, bool is_mont, reef_f
     fe256 v;
     REEF_HIP_TRY(hipMemcpyAsync(&v, c->sp->out.p, sizeof v, hipMemcpyDeviceToHost, c->stream));
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (is_mont) v = fe_to_abi<F>(fe_from_integer<F>(v));
-    memcpy(dst, &v, sizeof v);
+    const fe256 o = fe_to_caller<F>(fe_from_integer<F>(v), is_mont);
+    memcpy(dst, &o, sizeof o);
     return REEF_OK;
 }
 
@@ -192,8 +186,8 @@ template <int C> static reef_status v_open_ipa_round(void *impl, const reef_fe *
     op_finish(c, grid, 2, 1);                                 // the next round's c_L, c_R
     REEF_HIP_TRY(hipGetLastError());
     s->olen /= 2;
-    s->w1s.push_back(op_to_integer<C>(rinv));
-    s->w2s.push_back(op_to_integer<C>(ri));
+    s->w1s.push_back(fe_to_integer<F>(rinv));
+    s->w2s.push_back(fe_to_integer<F>(ri));
     REEF_TRY(op_cross(c, L, R));
     ++s->rounds;
     s->phase = SP_OPEN_IPA;
@@ -246,7 +240,7 @@ template <int C> static reef_status v_open_read(void *impl, int which, size_t co
     REEF_TRY(scope.enter());
     REEF_TRY(c->stage.ensure(count * sizeof(fe256)));
     const fe256 *src = (which == 0 ? s->oa : s->ob).template as<fe256>();
-    hipLaunchKernelGGL(k_nifs_export<NifsCtx<C>::F>, dim3(ceil_div(count, 256)), dim3(256), 0, c->stream, src, (u32)count, (int)(which == 0), (int)to_mont,
+    hipLaunchKernelGGL(k_fe_export<NifsCtx<C>::F>, dim3(ceil_div(count, 256)), dim3(256), 0, c->stream, src, (u64)count, (int)(which == 0), (int)to_mont,
                        c->stage.template as<fe256>());
     REEF_HIP_TRY(hipGetLastError());
     REEF_HIP_TRY(hipMemcpyAsync(out, c->stage.p, count * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));

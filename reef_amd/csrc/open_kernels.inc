@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(SP_THREADS) k_op_fold(OpFold p) {
             const u32 j = i + s * p.h;
             a[s] = fe_canon<F>(fe_add<F>(op_load(p.E, j, p.nE), fe_mul<F>(r, op_load(p.W, j, p.nW))));
             b[s] = fe_canon<F>(fe_add<F>(op_load(p.e1, j, p.n1), fe_mul<F>(r, op_load(p.e2, j, p.n2))));
-            store_fe256(p.a + j, sc_to_integer<F>(a[s]));
+            store_fe256(p.a + j, fe_to_integer<F>(a[s]));
             store_fe256(p.b + j, fe_pack(b[s]));
         }
         sp_acc(acc[0], fe_mul<F>(a[0], b[0]));
@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(SP_THREADS) k_op_round(OpRound p) {
         }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            store_fe256(p.a + i + s * p.q, sc_to_integer<F>(a[s]));
+            store_fe256(p.a + i + s * p.q, fe_to_integer<F>(a[s]));
             store_fe256(p.b + i + s * p.q, fe_pack(b[s]));
         }
         sp_acc(acc[0], fe_mul<F>(a[0], b[1]));
@@ -111,7 +111,7 @@ __global__ void __launch_bounds__(64) k_op_last(fe256 *__restrict__ a, fe256 *__
     const fe r = fe_from_table(r_), ri = fe_from_table(rinv_);
     const fe av = op_fold2<F>(fe_from_integer<F>(load_fe256(a)), r, fe_from_integer<F>(load_fe256(a + 1)), ri);
     const fe bv = op_fold2<F>(fe_from_table(load_fe256(b)), ri, fe_from_table(load_fe256(b + 1)), r);
-    store_fe256(a, sc_to_integer<F>(av));
+    store_fe256(a, fe_to_integer<F>(av));
     store_fe256(b, fe_pack(bv));
     store_fe256(out, sp_out<F>(av, form));
 }

@@ -61,7 +61,7 @@ template <int C> static fe sp_import(const reef_fe *x, bool is_mont) {
     constexpr int F = NifsCtx<C>::F;
     fe256 p;
     memcpy(&p, x, sizeof p);
-    return fe_canon<F>(is_mont ? fe_from_abi<F>(p) : fe_from_integer<F>(p));
+    return fe_canon<F>(fe_from_caller<F>(p, is_mont));
 }
 static bool sp_valid_fe(const reef_fe *x, int field) {          // canonical: below the modulus
     fe256 p;

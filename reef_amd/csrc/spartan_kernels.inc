@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(SP_THREADS) k_sp_dot(const fe256 *__restrict__
 // a canonical internal value in the caller's form: 0 the internal table form, 1 canonical integer, 2 pasta Montgomery form
 enum { SP_FORM_TABLE = 0, SP_FORM_INTEGER = 1, SP_FORM_MONT = 2 };
 template <int F> __device__ __forceinline__ fe256 sp_out(const fe &x, int form) {
-    return form == SP_FORM_MONT ? fe_to_abi<F>(x) : form == SP_FORM_INTEGER ? sc_to_integer<F>(x) : fe_to_table<F>(x);
+    return form == SP_FORM_TABLE ? fe_to_table<F>(x) : fe_to_caller<F>(x, form == SP_FORM_MONT);
 }
 
 // out[k] = the sum over nblocks blocks of value k (k < nv), in `form`.  One block: every thread adds its blocks' 9 nv slots, LDS

@@ -444,7 +444,7 @@ template <int C> static reef_status v_sc_set(void *impl, int which, const reef_f
         REEF_HIP_TRY(hipMemcpyAsync(c->stage.p, vals, n * sizeof(fe256), hipMemcpyHostToDevice, c->stream));
         src = c->stage.template as<fe256>();
     }
-    if (n) hipLaunchKernelGGL(k_sc_import<ScCtx<C>::F>, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, src, (u32)n, dst);
+    if (n) hipLaunchKernelGGL(k_fe_import<ScCtx<C>::F>, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, src, (u64)n, 0, dst);
     if (n < c->len) REEF_HIP_TRY(hipMemsetAsync(dst + n, 0, (c->len - n) * sizeof(fe256), c->stream));
     if (which == 0) c->fresh = true;
     else c->r1 = false;                  // a table given by the caller is a dense table
@@ -471,7 +471,7 @@ template <int C> static reef_status v_sc_read(void *impl, int which, size_t coun
     REEF_TRY(c->stage.ensure(count * sizeof(fe256)));
     if (which == 1 && c->r1) REEF_TRY(sc_r1_materialize<C>(c, true));   // a look at EQ: written out for the reader, the rounds go on without it
     const fe256 *src = (which == 0 ? (c->fresh ? c->T0 : c->T) : c->E).template as<fe256>();
-    hipLaunchKernelGGL(k_sc_export<ScCtx<C>::F>, dim3(ceil_div(count, 256)), dim3(256), 0, c->stream, src, (u32)count,
+    hipLaunchKernelGGL(k_fe_export<ScCtx<C>::F>, dim3(ceil_div(count, 256)), dim3(256), 0, c->stream, src, (u64)count, 0, 0,
                        c->stage.template as<fe256>());
     REEF_HIP_TRY(hipGetLastError());
     REEF_HIP_TRY(hipMemcpyAsync(out_host, c->stage.p, count * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));

@@ -16,7 +16,7 @@ static fe load(const uint32_t *l, double bound) {
     return x;
 }
 
-// The reduction as the sum-check and Merkle kernels run it (wide18_reduce_small): 18 product columns of a*b,
+// The reduction as the sum-check and Merkle kernels run it (fe_vec.h: wide18_mont): 18 product columns of a*b,
 // carried to 29 bits, biased with mont_bias, nine rounds with the upper columns fed in one per round.
 template <int F> static fe wide_reduce(const fe &a, const fe &b) {
     u64 w[18] = {0};
