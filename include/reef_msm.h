@@ -27,6 +27,7 @@
  *      (reef_spartan_*, section 3g).  A caller that needs them checks for the symbol, not the version.
  *      Later, still 7 (symbols added, none changed): the batched IPA opening of the final SNARK on the same ctx
  *      (reef_spartan_open_*, section 3h).
+ *      Later, still 7 (symbols added, none changed): the Hyrax consistency argument on a resident document (reef_hyrax_*, section 3i).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -515,6 +516,64 @@ reef_status reef_spartan_open_ipa_begin(reef_nifs_ctx *ctx, const reef_affine *q
 reef_status reef_spartan_open_ipa_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_jacobian *L, reef_jacobian *R);
 reef_status reef_spartan_open_finish(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe *a_hat);
 reef_status reef_spartan_open_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont);
+
+/* ---------------------------------------------------------------------------------------------
+ * (3i) The Hyrax consistency argument: NLDocCommitment::proof_dot_prod_prover -> HyraxPC::prove_eval [R]
+ * (src/backend/commitment.rs:287-405, :371-391) over a document kept resident on the device, the IPA rounds run as 3h's (same
+ * kernels, same cross-term MSMs over the original key).  Replaces the 3c calls of that argument (LZ back to the host, a second
+ * reef_mle_bound_rows for the blinds, a third pass for doc_poly.evaluate in hybrid mode, :357) and the per-round host fold and
+ * upload of a for reef_ipa_cross_terms.  The transcript and every point operation on commitments stay with the caller; only
+ * challenges and blinds go in, only points and single scalars come out.  Over the SCALAR field of `curve`, as 3c.
+ *
+ * Recalled facts [R], in one place (HyraxPC::prove_eval, nova-snark's ipa_pc / dot-product proofs; correct them here if wrong):
+ *   factoring  compute_factored_lens(num_vars) = (left, right) = (num_vars / 2, num_vars - num_vars / 2) (commitment.rs:173-174):
+ *              Z is the row-major 2^left x 2^right matrix of the zero-padded document; row i was committed as C_i = <Z_i, gens_v>
+ *              (+ blind_i h, HyraxPC::commit's row blinds).
+ *   L and R    point[0] pairs with the most significant index bit; L = eq(point[..left]) weighs the ROWS, R = eq(point[left..])
+ *              the columns.  The argument proves <LZ, R> = eval with LZ = L^T Z (2^right entries): a = LZ, b = R.
+ *   comm_LZ    the prover forms comm_LZ = sum_i L_i C_i itself (the verifier can too) and its blind sum_i L_i blind_i;
+ *              reef_hyrax_eval_comm / lz_blind serve it when the fork does, and cost nothing when it does not.
+ *   rounds     as 3h: L = <a_lo, G_hi> + c_L q, R = <a_hi, G_lo> + c_R q, c_L = <a_lo, b_hi>, c_R = <a_hi, b_lo>; a' = a_lo r +
+ *              a_hi r^-1, b' = b_lo r^-1 + b_hi r; a_hat = a[0] after right folds.  q = gens_1.scale(challenge) is the caller's.
+ *   blinding   plain ipa_pc rounds have no blinding term (h NULL).  A bullet-style reading (Reef's verifier takes a hiding
+ *              v_commit, commitment.rs:477-492) adds bl h to L and br h to R with fresh blinds per round: pass h and the blinds.
+ *
+ * reef_hyrax_create     z: n <= 2^num_vars entries (the rest is zero padding), elem_bytes 1 / 2 / 4 (unsigned document symbols) or
+ *                       32 (field elements in the form is_mont names), on the host or the device (z_loc); copied, kept resident
+ *                       for the life of the ctx.  1 <= left_vars < num_vars <= 28, and the matrix must fit one pass of 3c's
+ *                       bound-rows kernel (at most 65535 row chunks: every left_vars <= 15 does; REEF_ERR_ARG otherwise).
+ *                       row_blinds: 2^left_vars entries (is_mont form; then left_vars <= 25), or NULL (zeros).  device: the
+ *                       ordinal of everything on this ctx.
+ * reef_hyrax_eval_begin point: num_vars entries.  key: gens_v, a reef_msm_ctx of the same curve and device holding exactly
+ *                       2^(num_vars - left_vars) points, used until finish.  a = LZ and b = R on the device; *eval = <LZ, R>
+ *                       (= doc_poly.evaluate(point)), *lz_blind = sum_i L_i blind_i (either may be NULL).  May be called at any
+ *                       time: it starts the argument over (a second eval_begin mid-argument is a restart, not an error).
+ * reef_hyrax_eval_comm  optional, any time after eval_begin: *comm_lz = sum_i L_i row_comms[i] over the 2^left_vars row commitments
+ *                       (affine, host or device per loc), one MSM on the device on a plain key of this ctx's device.  The
+ *                       key is rebuilt from row_comms (one upload of 2^left_vars points) unless they are the host bytes of the
+ *                       previous call; device row_comms are uploaded every time.
+ * reef_hyrax_ipa_begin  q: affine, pasta Montgomery coordinates; h: the optional blinding point, blinds[2]: its blinds for round 0
+ *                       (the term is on when both are given, for the whole argument); round 0's L and R.
+ * reef_hyrax_ipa_round  folds a and b with r; the next round's L and R; blinds: that round's two blinds (NULL = zeros; an error
+ *                       when ipa_begin took no h); exactly right - 1 calls.
+ * reef_hyrax_finish     the last fold with r_last; *a_hat = a[0], *b_hat = b[0] (b_hat may be NULL).
+ * reef_hyrax_read       which: 0 a, 1 b, as they stand now (2^right, 2^(right-1), ... entries); the first `count` to the host.
+ * Every challenge, blind and point entry must be below the modulus, the IPA's challenges non-zero (REEF_ERR_ARG).  is_mont: scalar
+ * inputs and outputs in pasta Montgomery form, else canonical integers.  Outputs are HOST memory.  A call out of order -- a round
+ * before ipa_begin, one round too many, finish too early, anything but eval_begin before the first eval_begin -- is REEF_ERR_ARG
+ * naming the call expected, and changes nothing; so is a key of another curve, device or length (the message names both lengths).
+ * L and R are computed on the key ctx's stream with c_L q, c_R q (and bl h, br h) added on the device: one host wait per round. */
+typedef struct reef_hyrax_ctx reef_hyrax_ctx;
+reef_status reef_hyrax_create(reef_hyrax_ctx **out, int curve, const void *z, size_t n, int elem_bytes, int z_loc, bool is_mont, size_t num_vars,
+                              size_t left_vars, const reef_fe *row_blinds, int device);
+void reef_hyrax_destroy(reef_hyrax_ctx *ctx);
+reef_status reef_hyrax_eval_begin(reef_hyrax_ctx *ctx, reef_msm_ctx *key, const reef_fe *point, bool is_mont, reef_fe *eval, reef_fe *lz_blind);
+reef_status reef_hyrax_eval_comm(reef_hyrax_ctx *ctx, const reef_affine *row_comms, int loc, reef_jacobian *comm_lz);
+reef_status reef_hyrax_ipa_begin(reef_hyrax_ctx *ctx, const reef_affine *q, const reef_affine *h, const reef_fe *blinds, bool is_mont,
+                                 reef_jacobian *L, reef_jacobian *R);
+reef_status reef_hyrax_ipa_round(reef_hyrax_ctx *ctx, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R);
+reef_status reef_hyrax_finish(reef_hyrax_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat);
+reef_status reef_hyrax_read(reef_hyrax_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont);
 
 /* ---------------------------------------------------------------------------------------------
  * (4) Runtime plumbing.

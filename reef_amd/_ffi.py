@@ -177,6 +177,14 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_spartan_open_ipa_round": (c_int, [vp, vp, c_bool, vp, vp]),
         "reef_spartan_open_finish": (c_int, [vp, vp, c_bool, vp]),
         "reef_spartan_open_read": (c_int, [vp, c_int, c_size_t, vp, c_bool]),
+        "reef_hyrax_create": (c_int, [POINTER(vp), c_int, vp, c_size_t, c_int, c_int, c_bool, c_size_t, c_size_t, vp, c_int]),
+        "reef_hyrax_destroy": (None, [vp]),
+        "reef_hyrax_eval_begin": (c_int, [vp, vp, vp, c_bool, vp, vp]),
+        "reef_hyrax_eval_comm": (c_int, [vp, vp, c_int, vp]),
+        "reef_hyrax_ipa_begin": (c_int, [vp, vp, vp, vp, c_bool, vp, vp]),
+        "reef_hyrax_ipa_round": (c_int, [vp, vp, vp, c_bool, vp, vp]),
+        "reef_hyrax_finish": (c_int, [vp, vp, c_bool, vp, vp]),
+        "reef_hyrax_read": (c_int, [vp, c_int, c_size_t, vp, c_bool]),
         "reef_merkle_nodes": (c_uint64, [c_uint64]),
         "reef_merkle_commit": (c_int, [c_int, vp, vp, c_size_t, c_int, c_bool, vp, c_int, vp]),
         "reef_merkle_commit_devices": (c_int, [c_int, vp, vp, c_size_t, c_bool, vp, c_size_t, vp, vp, vp]),

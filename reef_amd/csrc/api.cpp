@@ -584,6 +584,58 @@ reef_status reef_spartan_open_read(reef_nifs_ctx *ctx, int which, size_t count, 
     return ovt(ctx->curve)->read(ctx->impl, which, count, out, to_mont);
 }
 
+// ---- the Hyrax consistency argument on a resident document
+struct reef_hyrax_ctx {
+    int curve;
+    void *impl;
+};
+static const HyraxVTable *hvt(int curve) { return curve == REEF_PALLAS ? pallas_hyrax_vtable() : vesta_hyrax_vtable(); }
+reef_status reef_hyrax_create(reef_hyrax_ctx **out, int curve, const void *z, size_t n, int elem_bytes, int z_loc, bool is_mont, size_t num_vars,
+                              size_t left_vars, const reef_fe *row_blinds, int device) {
+    if (!out) { set_error("null argument"); return REEF_ERR_ARG; }
+    STATELESS_PROLOGUE(curve);
+    (void)v;
+    void *impl = nullptr;
+    REEF_TRY(guarded([&] { return hvt(curve)->create(&impl, z, n, elem_bytes, z_loc, is_mont, num_vars, left_vars, row_blinds, device); }));
+    *out = new reef_hyrax_ctx{curve, impl};
+    return REEF_OK;
+}
+void reef_hyrax_destroy(reef_hyrax_ctx *ctx) {
+    if (!ctx) return;
+    hvt(ctx->curve)->destroy(ctx->impl);
+    delete ctx;
+}
+reef_status reef_hyrax_eval_begin(reef_hyrax_ctx *ctx, reef_msm_ctx *key, const reef_fe *point, bool is_mont, reef_fe *eval, reef_fe *lz_blind) {
+    SC_CHECK(ctx);
+    if (!key) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (key->curve != ctx->curve) {
+        set_error("reef_hyrax_eval_begin: the key is of curve %d, the Hyrax ctx of curve %d", key->curve, ctx->curve);
+        return REEF_ERR_ARG;
+    }
+    return guarded([&] { return hvt(ctx->curve)->eval_begin(ctx->impl, key->impl, point, is_mont, eval, lz_blind); });
+}
+reef_status reef_hyrax_eval_comm(reef_hyrax_ctx *ctx, const reef_affine *row_comms, int loc, reef_jacobian *comm_lz) {
+    SC_CHECK(ctx);
+    return guarded([&] { return hvt(ctx->curve)->eval_comm(ctx->impl, row_comms, loc, comm_lz); });
+}
+reef_status reef_hyrax_ipa_begin(reef_hyrax_ctx *ctx, const reef_affine *q, const reef_affine *h, const reef_fe *blinds, bool is_mont,
+                                 reef_jacobian *L, reef_jacobian *R) {
+    SC_CHECK(ctx);
+    return guarded([&] { return hvt(ctx->curve)->ipa_begin(ctx->impl, q, h, blinds, is_mont, L, R); });
+}
+reef_status reef_hyrax_ipa_round(reef_hyrax_ctx *ctx, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R) {
+    SC_CHECK(ctx);
+    return guarded([&] { return hvt(ctx->curve)->ipa_round(ctx->impl, r, blinds, is_mont, L, R); });
+}
+reef_status reef_hyrax_finish(reef_hyrax_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat) {
+    SC_CHECK(ctx);
+    return hvt(ctx->curve)->finish(ctx->impl, r_last, is_mont, a_hat, b_hat);
+}
+reef_status reef_hyrax_read(reef_hyrax_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont) {
+    SC_CHECK(ctx);
+    return hvt(ctx->curve)->read(ctx->impl, which, count, out, to_mont);
+}
+
 uint64_t reef_merkle_nodes(uint64_t n) {
     uint64_t total = 0, m = (n + 1) / 2;
     for (;;) {

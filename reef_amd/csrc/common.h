@@ -436,4 +436,20 @@ struct OpenVTable {
 const OpenVTable *pallas_open_vtable();
 const OpenVTable *vesta_open_vtable();
 
+// The Hyrax consistency argument on a resident document (hyrax_engine.inc; include/reef_msm.h 3i).  key_impl: a Ctx impl.
+struct HyraxVTable {
+    reef_status (*create)(void **impl, const void *z, size_t n, int elem_bytes, int z_loc, bool is_mont, size_t num_vars, size_t left_vars,
+                          const reef_fe *row_blinds, int device);
+    void (*destroy)(void *impl);
+    reef_status (*eval_begin)(void *impl, void *key_impl, const reef_fe *point, bool is_mont, reef_fe *eval, reef_fe *lz_blind);
+    reef_status (*eval_comm)(void *impl, const reef_affine *row_comms, int loc, reef_jacobian *comm_lz);
+    reef_status (*ipa_begin)(void *impl, const reef_affine *q, const reef_affine *h, const reef_fe *blinds, bool is_mont, reef_jacobian *L,
+                             reef_jacobian *R);
+    reef_status (*ipa_round)(void *impl, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R);
+    reef_status (*finish)(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat);
+    reef_status (*read)(void *impl, int which, size_t count, reef_fe *out, bool to_mont);
+};
+const HyraxVTable *pallas_hyrax_vtable();
+const HyraxVTable *vesta_hyrax_vtable();
+
 }  // namespace reef

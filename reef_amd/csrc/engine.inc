@@ -1432,12 +1432,32 @@ static reef_status v_msm_rows_symbols(void *impl, const uint8_t *symbols, size_t
     return finish_output<C>(ctx, d_res, rows, out, out_loc);
 }
 
+// The nibble table of one point h (ABI affine, host) into buf: small_table_points(1) points, then two staging points.  Built on
+// ctx's stream (its scratch), waited for.  For a second blind term beside the one ctx->h_tab caches (ipa_cross_run's tab2).
+template <int C> static reef_status point_table_build(Ctx<C> *ctx, const reef_affine *h, DevBuf &buf) {
+    REEF_TRY(buf.ensure((small_table_points(1) + 2) * sizeof(affine256)));
+    affine256 *tab = buf.template as<affine256>(), *raw = tab + small_table_points(1), *imp = raw + 1;
+    REEF_HIP_TRY(hipMemcpyAsync(raw, h, sizeof(reef_affine), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_import_key<C>, dim3(1), dim3(256), 0, ctx->stream, (const affine256 *)raw, 1u, imp);
+    REEF_TRY(small_build<C>(ctx, imp, 1, tab));
+    REEF_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return REEF_OK;
+}
+// out += blinds[r] * P for `rows` results on the device, P's nibble table given (blinds: canonical integers)
+template <int C> static reef_status launch_blind_tab(Ctx<C> *ctx, jacobian256 *d_out, const fe256 *d_blinds, const affine256 *tab, size_t rows) {
+    hipLaunchKernelGGL(k_add_blind_tab<C>, dim3(ceil_div(rows * BLIND_LANES, 64)), dim3(64), 0, ctx->stream, d_out, d_blinds, tab, 0, (u32)rows);
+    return REEF_OK;
+}
+
 // The three routes of the cross terms (pre-shifted key, byte tables, plain key) on a ctx already entered, a on the device.  With
 // d_blinds (two canonical integers on the device) L += d_blinds[0] h and R += d_blinds[1] h through h's nibble table (h: affine,
-// host); without them nothing is added and the launches are those of reef_ipa_cross_terms.
+// host); with d_blinds2 also L += d_blinds2[0] P, R += d_blinds2[1] P through P's nibble table tab2 (point_table_build; only with
+// d_blinds); without them nothing is added and the launches are those of reef_ipa_cross_terms.
 template <int C>
 static reef_status ipa_cross_run(Ctx<C> *ctx, const fe256 *d_a, size_t n_k, bool is_mont, const reef_fe *w1s, const reef_fe *w2s, size_t k,
-                                 const fe256 *d_blinds, const reef_affine *h, reef_jacobian *out_l, reef_jacobian *out_r) {
+                                 const fe256 *d_blinds, const reef_affine *h, const fe256 *d_blinds2, const affine256 *tab2,
+                                 reef_jacobian *out_l, reef_jacobian *out_r) {
+    if (!d_blinds) d_blinds2 = nullptr;
     Key<C> *key = ctx->key;
     const size_t n = key->n;
     hipStream_t st = ctx->stream;
@@ -1486,6 +1506,7 @@ static reef_status ipa_cross_run(Ctx<C> *ctx, const fe256 *d_a, size_t n_k, bool
         if (ctx->timing) REEF_HIP_TRY(hipEventRecord(ctx->ev[2], st));
         hipLaunchKernelGGL(k_small_final<C>, dim3(2), dim3(256), 0, st, (const xyzz_mem *)p1, wgs, land);
         if (d_blinds) REEF_TRY(launch_blind<C>(ctx, land, d_blinds, nullptr, false, 2));
+        if (d_blinds2) REEF_TRY(launch_blind_tab<C>(ctx, land, d_blinds2, tab2, 2));
         if (ctx->timing) {
             REEF_HIP_TRY(hipEventRecord(ctx->ev[3], st));
             ctx->ev_pending[ctx->ev_last] = true;
@@ -1503,6 +1524,7 @@ static reef_status ipa_cross_run(Ctx<C> *ctx, const fe256 *d_a, size_t n_k, bool
         two.rows = 2;
         two.slice_sort = true;
         REEF_TRY(run_core<C>(ctx, s_l, two, false, d_blinds, nullptr, land));   // the final kernel stores L and R where the host reads them
+        if (d_blinds2) REEF_TRY(launch_blind_tab<C>(ctx, land, d_blinds2, tab2, 2));
         REEF_HIP_TRY(hipStreamSynchronize(st));
         memcpy(out_l, &land[0], sizeof(jacobian256));
         memcpy(out_r, &land[1], sizeof(jacobian256));
@@ -1516,6 +1538,7 @@ static reef_status ipa_cross_run(Ctx<C> *ctx, const fe256 *d_a, size_t n_k, bool
     if (bt) {
         memset(bt, 0, 2 * sizeof(jacobian256));
         REEF_TRY(launch_blind<C>(ctx, bt, d_blinds, nullptr, false, 2));
+        if (d_blinds2) REEF_TRY(launch_blind_tab<C>(ctx, bt, d_blinds2, tab2, 2));
     }
     for (int v = 0; v < 2; ++v) {   // plain key: finish each window combine on the host (as in v_msm)
         const xyzz_mem *gs = nullptr;
@@ -1532,6 +1555,7 @@ static reef_status ipa_cross_run(Ctx<C> *ctx, const fe256 *d_a, size_t n_k, bool
         memcpy(&both[1], out_r, sizeof(jacobian256));
         REEF_HIP_TRY(hipMemcpyAsync(d_res, both, sizeof both, hipMemcpyHostToDevice, st));
         REEF_TRY(launch_blind<C>(ctx, d_res, d_blinds, nullptr, false, 2));
+        if (d_blinds2) REEF_TRY(launch_blind_tab<C>(ctx, d_res, d_blinds2, tab2, 2));
         REEF_HIP_TRY(hipGetLastError());
         REEF_HIP_TRY(hipMemcpyAsync(both, d_res, sizeof both, hipMemcpyDeviceToHost, st));
         REEF_HIP_TRY(hipStreamSynchronize(st));
@@ -1563,7 +1587,7 @@ static reef_status v_ipa_cross(void *impl, const reef_fe *a, size_t n_k, int loc
         REEF_HIP_TRY(hipMemcpyAsync(stage_a, a, n_k * sizeof(fe256), hipMemcpyHostToDevice, ctx->stream));
         d_a = stage_a;
     }
-    return ipa_cross_run<C>(ctx, d_a, n_k, is_mont, w1s, w2s, k, nullptr, nullptr, out_l, out_r);
+    return ipa_cross_run<C>(ctx, d_a, n_k, is_mont, w1s, w2s, k, nullptr, nullptr, nullptr, nullptr, out_l, out_r);
 }
 
 // Commitment over the generators k folds away from the resident key, without the folds: the generators after k rounds of

@@ -1,0 +1,30 @@
+// The Hyrax consistency argument (include/reef_msm.h 3i): HyraxPC::prove_eval [R] over the resident document.  hyrax_engine.inc
+// drives it with the kernels of 3c and 3h; the one kernel here is the first round's sums, which 3h takes from its fold:
+//
+//   eval_begin  L = eq(point[..left]), a = LZ = L^T Z (k_mle_eq, k_mle_bound, k_mle_finish), eval = <a, b>;
+//               b = eq(point[left..]) (k_sp_eq); the blinds as a one-column table give sum_i L_i blind_i
+//   ipa_begin   round 0's c_L = <a_lo, b_hi>, c_R = <a_hi, b_lo>                                        (k_hy_sums)
+//   rounds      3h's IpaRun: k_op_round, the cross-term MSMs, k_op_last
+//
+// a holds canonical integers, b the internal form, as in 3h.  The sums go through sp_block_sums / k_sp_finish.
+
+namespace reef {
+
+// c_L = sum_{i < h} a[i] b[i + h], c_R = sum_{i < h} a[i + h] b[i] -> partial[block][27], values 0 and 1
+template <int F>
+__global__ void __launch_bounds__(SP_THREADS) k_hy_sums(const fe256 *__restrict__ a, const fe256 *__restrict__ b, u32 h,
+                                                        unsigned long long *__restrict__ partial) {
+    u64 acc[2][9];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int i = 0; i < 9; ++i) acc[k][i] = 0;
+    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < h; i += gridDim.x * blockDim.x) {
+        const fe a0 = fe_from_integer<F>(load_fe256(a + i)), a1 = fe_from_integer<F>(load_fe256(a + i + h));
+        sp_acc(acc[0], fe_mul<F>(a0, fe_from_table(load_fe256(b + i + h))));
+        sp_acc(acc[1], fe_mul<F>(a1, fe_from_table(load_fe256(b + i))));
+    }
+    sp_block_sums<2>(acc, partial);
+}
+
+}  // namespace reef

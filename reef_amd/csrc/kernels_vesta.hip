@@ -9,10 +9,12 @@
 #include "nifs_kernels.inc"
 #include "spartan_kernels.inc"
 #include "open_kernels.inc"
+#include "hyrax_kernels.inc"
 #include "engine.inc"
 #include "nifs_engine.inc"
 #include "spartan_engine.inc"
 #include "open_engine.inc"
+#include "hyrax_engine.inc"
 namespace reef {
 const CurveVTable *vesta_vtable() {
     static const CurveVTable vt = make_vtable<1>();
@@ -28,6 +30,10 @@ const SpartanVTable *vesta_spartan_vtable() {
 }
 const OpenVTable *vesta_open_vtable() {
     static const OpenVTable vt = make_open_vtable<1>();
+    return &vt;
+}
+const HyraxVTable *vesta_hyrax_vtable() {
+    static const HyraxVTable vt = make_hyrax_vtable<1>();
     return &vt;
 }
 }

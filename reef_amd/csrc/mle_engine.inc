@@ -8,6 +8,30 @@ static void mle_launch_bound(hipStream_t st, const void *d_z, u64 n, u32 rows, u
                        part);
 }
 
+// The row chunks of k_mle_bound: enough (column, row-chunk) threads to fill the chip; 32-bit symbols: short chunks (limb sums stay
+// below 2^64).  REEF_ERR_ARG when the matrix is too tall for one pass.
+static reef_status mle_plan(u32 rows, u32 cols, int elem_bytes, u32 *chunks_out, u32 *rows_per_chunk_out) {
+    u32 chunks = (u32)std::min<u64>(rows, std::max<u64>(1, 262144 / cols));
+    u32 rows_per_chunk = ceil_div(rows, chunks);
+    if (elem_bytes == 4) rows_per_chunk = std::min<u32>(rows_per_chunk, 128);
+    if (elem_bytes == 32) rows_per_chunk = std::min<u32>(rows_per_chunk, 1024);   // bound of the lazy 18-column reduction
+    chunks = ceil_div(rows, rows_per_chunk);
+    if (chunks > 65535) { set_error("matrix too tall for one pass (%u row chunks)", chunks); return REEF_ERR_ARG; }
+    *chunks_out = chunks;
+    *rows_per_chunk_out = rows_per_chunk;
+    return REEF_OK;
+}
+template <int C>
+static void mle_launch_bound_any(hipStream_t st, int elem_bytes, const void *d_z, u64 n, u32 rows, u32 cols, u32 rows_per_chunk, u32 chunks,
+                                 const fe_limbs *Leq, fe256 *part) {
+    switch (elem_bytes) {
+    case 1: mle_launch_bound<C, 1>(st, d_z, n, rows, cols, rows_per_chunk, chunks, Leq, part); break;
+    case 2: mle_launch_bound<C, 2>(st, d_z, n, rows, cols, rows_per_chunk, chunks, Leq, part); break;
+    case 4: mle_launch_bound<C, 4>(st, d_z, n, rows, cols, rows_per_chunk, chunks, Leq, part); break;
+    default: mle_launch_bound<C, 32>(st, d_z, n, rows, cols, rows_per_chunk, chunks, Leq, part); break;
+    }
+}
+
 // lz_out[j] = sum_i eq(point[..left], i) * Z[i*2^(m-left) + j]   (2^(m-left) values; may be null)
 // eval_out  = sum_j lz[j] * eq(point[left..], j)                  (host; may be null)
 template <int C>
@@ -31,25 +55,15 @@ static reef_status v_mle_bound(const void *z, size_t n, int elem_bytes, int z_lo
     fe_limbs *Leq = (fe_limbs *)p_eq, *Req = Leq + rows;
     hipLaunchKernelGGL(k_mle_eq<F>, dim3(ceil_div(rows, 256)), dim3(256), 0, ss.s, pt, 0u, (u32)left_vars, (int)is_mont, Leq);
     hipLaunchKernelGGL(k_mle_eq<F>, dim3(ceil_div(cols, 256)), dim3(256), 0, ss.s, pt, (u32)left_vars, (u32)(num_vars - left_vars), (int)is_mont, Req);
-    // enough (column, row-chunk) threads to fill the chip; 32-bit symbols: short chunks (limb sums stay below 2^64)
-    u32 chunks = (u32)std::min<u64>(rows, std::max<u64>(1, 262144 / cols));
-    u32 rows_per_chunk = ceil_div(rows, chunks);
-    if (elem_bytes == 4) rows_per_chunk = std::min<u32>(rows_per_chunk, 128);
-    if (elem_bytes == 32) rows_per_chunk = std::min<u32>(rows_per_chunk, 1024);   // bound of the lazy 18-column reduction
-    chunks = ceil_div(rows, rows_per_chunk);
-    if (chunks > 65535) { set_error("matrix too tall for one pass (%u row chunks)", chunks); return REEF_ERR_ARG; }
+    u32 chunks = 0, rows_per_chunk = 0;
+    REEF_TRY(mle_plan(rows, cols, elem_bytes, &chunks, &rows_per_chunk));
     REEF_TRY(ss.alloc(&p_part, (size_t)chunks * cols * sizeof(fe256)));
     REEF_TRY(ss.alloc(&p_dot, 9 * sizeof(u64) + sizeof(fe256)));
     fe256 *part = (fe256 *)p_part;
     unsigned long long *dot = (unsigned long long *)p_dot;
     fe256 *d_eval = (fe256 *)(dot + 9);
     REEF_HIP_TRY(hipMemsetAsync(dot, 0, 9 * sizeof(u64), ss.s));
-    switch (elem_bytes) {
-    case 1: mle_launch_bound<C, 1>(ss.s, d_z, n, rows, cols, rows_per_chunk, chunks, Leq, part); break;
-    case 2: mle_launch_bound<C, 2>(ss.s, d_z, n, rows, cols, rows_per_chunk, chunks, Leq, part); break;
-    case 4: mle_launch_bound<C, 4>(ss.s, d_z, n, rows, cols, rows_per_chunk, chunks, Leq, part); break;
-    default: mle_launch_bound<C, 32>(ss.s, d_z, n, rows, cols, rows_per_chunk, chunks, Leq, part); break;
-    }
+    mle_launch_bound_any<C>(ss.s, elem_bytes, d_z, n, rows, cols, rows_per_chunk, chunks, Leq, part);
     fe256 *d_lz = nullptr;
     if (lz_out) REEF_TRY(stage_out<fe256>(ss, &d_lz, lz_out, cols, out_loc));
     if (elem_bytes == 32) {

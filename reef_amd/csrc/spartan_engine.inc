@@ -5,6 +5,9 @@ namespace reef {
 
 enum { SP_NONE = 0, SP_OUTER, SP_OUTER_DONE, SP_INNER, SP_DONE, SP_OPEN_BEGUN, SP_OPEN_FOLDED, SP_OPEN_IPA, SP_OPEN_DONE };   // SP_OPEN_*: open_engine.inc
 
+template <int C> struct IpaRun;                            // the IPA rounds of 3h and 3i (open_engine.inc)
+template <int C> static void ipa_run_release(IpaRun<C> *ip);
+
 template <int C> struct SpartanState {
     int phase = SP_NONE;
     u64 gen = 0;                         // the ctx's gen at begin: any later change of the matrices or the running instance voids the prove
@@ -15,15 +18,14 @@ template <int C> struct SpartanState {
     DevBuf abc, z;                       // inner tables (2 nvp entries)
     DevBuf pts, partial, out;            // eq factors, block sums, results
     // the batched IPA opening (open_engine.inc)
-    DevBuf e1, e2, oa, ob;               // eq(r_x), eq(r_y[1..]); a (canonical integers) and b (internal form), n entries each
-    void *key = nullptr;                 // the gens_v key ctx (Ctx<C>) of the opening, from open_begin to finish
-    size_t on = 0, olen = 0;             // n; the length of a and b as they stand
-    reef_affine q = {};                  // gens_c.scale(r): the point of the cross terms' blind term
-    std::vector<fe256> w1s, w2s;         // the IPA challenges so far: r^-1 and r, canonical integers (reef_fold's convention)
+    DevBuf e1, e2;                       // eq(r_x), eq(r_y[1..])
+    size_t on = 0;                       // n
+    IpaRun<C> *ip = nullptr;             // a, b and the rounds, made by the first open_begin
 };
 template <int C> static void spartan_release(SpartanState<C> *s) {
     if (!s) return;
-    for (DevBuf *b : {&s->eq, &s->az, &s->bz, &s->cz, &s->d, &s->abc, &s->z, &s->pts, &s->partial, &s->out, &s->e1, &s->e2, &s->oa, &s->ob}) b->release();
+    for (DevBuf *b : {&s->eq, &s->az, &s->bz, &s->cz, &s->d, &s->abc, &s->z, &s->pts, &s->partial, &s->out, &s->e1, &s->e2}) b->release();
+    ipa_run_release<C>(s->ip);
     delete s;
 }
 

@@ -1,0 +1,170 @@
+"""Python front-end of the Hyrax consistency argument on a resident document (include/reef_msm.h 3i).
+
+NLDocCommitment::proof_dot_prod_prover -> HyraxPC::prove_eval (Reef: src/backend/commitment.rs:287-405): the bound rows LZ = L^T Z,
+the evaluation <LZ, R>, the blind combination sum_i L_i blind_i, optionally comm_LZ = sum_i L_i C_i, then the IPA rounds of 3h over
+gens_v with an optional blinding term on a second point h.  The document stays on the device from `HyraxEval(...)` on; only
+challenges and blinds go in, only points and single scalars come out.  `prove_eval` drives a whole argument with a caller-supplied
+`challenge(label, absorbed) -> int` in place of the transcript.  Scalars cross as Python ints (canonical, or pasta Montgomery form
+with is_mont=True); points as numpy uint64 arrays in the C-ABI layouts: affine (8 limbs) in, Jacobian (12 limbs) out.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Any, Callable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _ffi
+from ._ffi import REEF_DEVICE, REEF_HOST, check
+from .msm import DeviceBuffer, MsmContext, curve_id
+from .spartan import _arr, _ints, compress
+
+_ELEM = {np.dtype(np.uint8): 1, np.dtype(np.uint16): 2, np.dtype(np.int16): 2, np.dtype(np.uint32): 4, np.dtype(np.int32): 4}
+
+
+def _table(z, n: Optional[int] = None, elem_bytes: Optional[int] = None) -> Tuple[int, int, int, int]:
+    """(loc, ptr, n, elem_bytes) of a document: symbols of 1 / 2 / 4 bytes (uint8, uint16 / int16, uint32 / int32: read as unsigned),
+    or field elements as an (n, 4) array of 64-bit limbs (uint64 / int64), C-contiguous, in host memory; or a reef_amd.msm.DeviceBuffer
+    on the ctx's device with n and elem_bytes given (it must hold n * elem_bytes bytes).  Anything else is refused."""
+    if isinstance(z, DeviceBuffer):
+        if n is None or elem_bytes not in (1, 2, 4, 32):
+            raise ValueError("a device document needs n and elem_bytes (1, 2, 4 or 32)")
+        if z.nbytes < n * elem_bytes:
+            raise ValueError(f"the device buffer holds {z.nbytes} bytes, {n} entries of {elem_bytes} need {n * elem_bytes}")
+        return REEF_DEVICE, z.ptr, n, elem_bytes
+    if not isinstance(z, np.ndarray):
+        raise TypeError("the document is a numpy array or a reef_amd.msm.DeviceBuffer")
+    if not z.flags["C_CONTIGUOUS"]:
+        raise ValueError("the document array must be C-contiguous")
+    if z.dtype in _ELEM:
+        return REEF_HOST, z.ctypes.data, z.size, _ELEM[z.dtype]
+    if z.dtype in (np.dtype(np.uint64), np.dtype(np.int64)) and z.ndim == 2 and z.shape[1] == 4:
+        return REEF_HOST, z.ctypes.data, z.shape[0], 32
+    raise TypeError(f"a document array holds uint8/uint16/int16/uint32/int32 symbols or (n, 4) 64-bit limbs, not {z.dtype} {z.shape}")
+
+
+def factored_lens(num_vars: int) -> Tuple[int, int]:
+    """compute_factored_lens (commitment.rs:173-174): (left, right) = (num_vars / 2, num_vars - num_vars / 2)"""
+    return num_vars // 2, num_vars - num_vars // 2
+
+
+class HyraxEval:
+    """The committed matrix Z (2^left x 2^right, row-major, the document zero-padded to 2^num_vars) resident on one device, with
+    its row blinds.  z: symbols of 1 / 2 / 4 bytes or an (n, 4) array of field elements (is_mont form), as a numpy array, or a
+    DeviceBuffer with n and elem_bytes (device memory, copied); see _table for what is accepted."""
+
+    def __init__(self, curve, z, num_vars: int, left_vars: Optional[int] = None, *, row_blinds: Optional[Sequence[int]] = None,
+                 is_mont: bool = False, device: int = 0, n: Optional[int] = None, elem_bytes: Optional[int] = None):
+        self._lib = _ffi.load()
+        self.curve = curve_id(curve)
+        self.num_vars = num_vars
+        self.left = factored_lens(num_vars)[0] if left_vars is None else left_vars
+        self.right = num_vars - self.left
+        loc, ptr, n, eb = _table(z, n, elem_bytes)
+        self._keep = z
+        self.n, self.elem_bytes = n, eb
+        rb = None
+        if row_blinds is not None:
+            rb = _arr(row_blinds)
+            if rb.shape[0] != 1 << self.left:
+                raise ValueError(f"expected {1 << self.left} row blinds, got {rb.shape[0]}")
+        h = ctypes.c_void_p()
+        check(self._lib.reef_hyrax_create(ctypes.byref(h), self.curve, ptr, n, eb, loc, is_mont, num_vars, self.left,
+                                          None if rb is None else rb.ctypes.data, device))
+        self._h = h
+        self._keep = None
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.reef_hyrax_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _points(self, fn, *args) -> Tuple[np.ndarray, np.ndarray]:
+        L, R = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
+        check(fn(self._h, *args, L.ctypes.data, R.ctypes.data))
+        return L, R
+
+    def eval_begin(self, key: MsmContext, point: Sequence[int], *, is_mont: bool = False) -> Tuple[int, int]:
+        """a = LZ, b = eq(point[left..]) on the device; returns (eval, lz_blind).  key: gens_v, exactly 2^right points."""
+        if len(point) != self.num_vars:
+            raise ValueError(f"expected {self.num_vars} point entries, got {len(point)}")
+        pa = _arr(point)
+        out = np.zeros((2, 4), dtype=np.uint64)
+        check(self._lib.reef_hyrax_eval_begin(self._h, key._h, pa.ctypes.data, is_mont, out[0].ctypes.data, out[1].ctypes.data))
+        ev, lb = _ints(out)
+        return ev, lb
+
+    def eval_comm(self, row_comms: np.ndarray) -> np.ndarray:
+        """comm_LZ = sum_i L_i row_comms[i] (affine (2^left, 8) uint64), Jacobian out"""
+        rc = np.ascontiguousarray(row_comms, dtype=np.uint64).reshape(-1, 8)
+        if rc.shape[0] != 1 << self.left:
+            raise ValueError(f"expected {1 << self.left} row commitments, got {rc.shape[0]}")
+        out = np.zeros(12, dtype=np.uint64)
+        check(self._lib.reef_hyrax_eval_comm(self._h, rc.ctypes.data, REEF_HOST, out.ctypes.data))
+        return out
+
+    def ipa_begin(self, q: np.ndarray, h: Optional[np.ndarray] = None, blinds: Optional[Sequence[int]] = None, *,
+                  is_mont: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """Round 0's L and R.  q (and h): affine, 8 uint64 limbs in pasta Montgomery coordinates; blinds: round 0's (bl, br)."""
+        qa = np.ascontiguousarray(q, dtype=np.uint64).reshape(8)
+        ha = None if h is None else np.ascontiguousarray(h, dtype=np.uint64).reshape(8)
+        ba = None if blinds is None else _arr(blinds)
+        return self._points(self._lib.reef_hyrax_ipa_begin, qa.ctypes.data, None if ha is None else ha.ctypes.data,
+                            None if ba is None else ba.ctypes.data, is_mont)
+
+    def ipa_round(self, r: int, blinds: Optional[Sequence[int]] = None, *, is_mont: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        ra = _arr([r])
+        ba = None if blinds is None else _arr(blinds)
+        return self._points(self._lib.reef_hyrax_ipa_round, ra.ctypes.data, None if ba is None else ba.ctypes.data, is_mont)
+
+    def finish(self, r_last: int, *, is_mont: bool = False) -> Tuple[int, int]:
+        """(a_hat, b_hat)"""
+        ra = _arr([r_last])
+        out = np.zeros((2, 4), dtype=np.uint64)
+        check(self._lib.reef_hyrax_finish(self._h, ra.ctypes.data, is_mont, out[0].ctypes.data, out[1].ctypes.data))
+        a, b = _ints(out)
+        return a, b
+
+    def read(self, which: int, count: int, *, to_mont: bool = False) -> List[int]:
+        """which: 0 a, 1 b, as they stand now."""
+        out = np.zeros((max(count, 1), 4), dtype=np.uint64)
+        check(self._lib.reef_hyrax_read(self._h, which, count, out.ctypes.data, to_mont))
+        return _ints(out[:count])
+
+
+def prove_eval(hx: HyraxEval, key: MsmContext, point: Sequence[int], challenge: Callable[[str, List[Any]], int], p: int,
+               q_of: Callable[[int], np.ndarray], *, row_comms: Optional[np.ndarray] = None, h: Optional[np.ndarray] = None,
+               blinds_of: Optional[Callable[[int], Tuple[int, int]]] = None, is_mont: bool = False) -> dict:
+    """The whole argument with `challenge(label, absorbed)`: eval_begin, comm_LZ when row_comms are given, "r" after (comm_LZ, eval)
+    for q = q_of(r), then "challenge_r" per round after L and R (compressed).  With h, blinds_of(round) gives that round's (bl, br).
+    key: gens_v, exactly 2^right points.  Canonical ints in and out (is_mont: the library calls take Montgomery form)."""
+    R = (1 << 256) % p
+    Rinv = pow(R, -1, p)
+    to = (lambda v: v * R % p) if is_mont else (lambda v: v)
+    frm = (lambda v: v * Rinv % p) if is_mont else (lambda v: v)
+    ev, lb = (frm(v) for v in hx.eval_begin(key, [to(x) for x in point], is_mont=is_mont))
+    comm_lz = hx.eval_comm(row_comms) if row_comms is not None else None
+    r_ipa = challenge("r", ([compress(key, comm_lz)] if comm_lz is not None else []) + [ev])
+    bl = (lambda k: [to(x) for x in blinds_of(k)]) if (h is not None and blinds_of is not None) else (lambda k: None)
+    L, Rp = hx.ipa_begin(q_of(r_ipa), h if h is not None and blinds_of is not None else None, bl(0), is_mont=is_mont)
+    Ls, Rs, rs = [L], [Rp], []
+    for k in range(hx.right - 1):
+        rs.append(challenge("challenge_r", [compress(key, Ls[-1]), compress(key, Rs[-1])]))
+        L, Rp = hx.ipa_round(to(rs[-1]), bl(k + 1), is_mont=is_mont)
+        Ls.append(L)
+        Rs.append(Rp)
+    rs.append(challenge("challenge_r", [compress(key, Ls[-1]), compress(key, Rs[-1])]))
+    a_hat, b_hat = (frm(v) for v in hx.finish(to(rs[-1]), is_mont=is_mont))
+    return {"eval": ev, "lz_blind": lb, "comm_lz": comm_lz, "r_ipa": r_ipa, "L": Ls, "R": Rs, "rs": rs, "a_hat": a_hat, "b_hat": b_hat}
