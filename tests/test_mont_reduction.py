@@ -1,10 +1,15 @@
 """The Montgomery reduction of field.h (biased columns, five-MAD rounds, serial final carry) against Python integers.
 
-The host build of the same templates (REEF_BOUNDS, reef_amd/csrc/tools/mont_check.cpp) runs on raw 29-bit limbs, so the
+The host build of the same templates (REEF_BOUNDS, reef_amd/csrc/tools/mont_check.cpp, g++) runs on raw 29-bit limbs, so the
 operands can sit at the limb and value bounds each function states: limbs 1..7 at 2^29 + 7, limb 0 at 2^29 - 1, the top
 limb as large as the value bound allows.  Every result must be the exact integer (T + Q*M) / 2^261 (plus K*M - c for the
 fused subtractions), where Q < 2^261 is the one quotient with T + Q*M = 0 mod 2^261 -- the value the digit-by-digit
-reduction defines, whatever the carry scheme -- with exact 29-bit limbs and the stated value bound."""
+reduction defines, whatever the carry scheme -- with exact 29-bit limbs and the stated value bound.
+
+What this covers: the carry scheme and the bound bookkeeping (REEF_BOUNDS aborts on a violated precondition).  What it does not:
+the host build runs the plain C++ forms of mad_row_*, mad_reduce and sqr_row<I>, not the v_mad_u64_u32 rows of
+field_mad_gfx950.h that gfx950 runs, and fe_vec.h's accumulators do not exist on the host.  tests/test_gpu_field_bounds.py
+runs the same grid, and those accumulators, on the device through the release-flag build of tools/field_check.hip."""
 import ctypes
 import os
 import subprocess
