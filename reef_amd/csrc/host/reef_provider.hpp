@@ -14,11 +14,18 @@
 //   compress()                                    Commitment::compress                   src/backend/commitment.rs:195,351,365
 //   CommitmentGens<CURVE>(label, n, params [, h]) CommitmentGens::new(label, n) / new_with_blinding_gen      src/backend/framework.rs:297-303, commitment.rs:146-149,176-180
 //   MerkleCommitment<CURVE>(doc, pc)              MerkleCommitment::new(&doc, &pc), path_wits, make_wits     src/backend/merkle_tree.rs:25-190
+//   Nifs<CURVE>                                   NIFS::prove's vector work (row N6)     RecursiveSNARK::prove_step, framework.rs:668-675
+//   RelaxedR1CSSnark<CURVE>                       RelaxedR1CSSNARK::prove: sum-checks + EE::prove_batch      CompressedSNARK::prove, framework.rs:695-698
+//   HyraxEval<CURVE>                              HyraxPC::prove_eval on a resident document                 src/backend/commitment.rs:287-405
+// The last three keep the call order of INTEGRATION.md 2f-2i; the transcript is the caller's (a callback), as are the point
+// operations on commitments (comm_a, q = gens_s.scale(r)).
 //
 // Error behaviour: Reef treats every failure as a panic (framework.rs:683,702); here every failed
 // call throws reef_provider::Error carrying reef_last_error().
 #pragma once
 #include <array>
+#include <cstring>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -361,6 +368,196 @@ template <int CURVE> class MerkleCommitment {
     reef_fe commitment = {};
     std::vector<std::vector<reef_fe>> tree;
     std::vector<uint32_t> doc;
+};
+
+// nova's transcript as the rows below see it [R]: absorb `len` bytes under `label`, squeeze the next challenge (below the
+// modulus; the form the caller's is_mont names).  The Keccak sponge itself stays with the caller.
+using Transcript = std::function<reef_fe(const char *label, const void *bytes, size_t len)>;
+
+inline size_t log2_exact(size_t n) {
+    size_t k = 0;
+    while (((size_t)1 << k) < n) ++k;
+    if (((size_t)1 << k) != n) throw std::invalid_argument("not a power of two");
+    return k;
+}
+
+// nova-snark NIFS [R] over one resident context per curve and R1CS shape (reef_msm.h 3f).  The running
+// instance and T stay on the device; the points comm_W, comm_E of the folded instance stay with the caller.
+template <int CURVE> class Nifs {
+  public:
+    Nifs(size_t num_cons, size_t num_vars, size_t num_io, int device = 0) : num_cons_(num_cons), num_vars_(num_vars), num_io_(num_io) {
+        check(reef_nifs_create(&ctx_, CURVE, num_cons, num_vars, num_io, device), "reef_nifs_create");
+    }
+    ~Nifs() { reef_nifs_destroy(ctx_); }
+    Nifs(const Nifs &) = delete;
+    Nifs &operator=(const Nifs &) = delete;
+    size_t num_cons() const { return num_cons_; }
+    size_t num_vars() const { return num_vars_; }
+    size_t num_io() const { return num_io_; }
+    reef_nifs_ctx *handle() const { return ctx_; }
+
+    // PublicParams::setup: which 0 A, 1 B, 2 C as (row, col, value) triples; duplicates are summed
+    void set_matrix(int which, const uint32_t *row, const uint32_t *col, const reef_fe *val, size_t nnz, bool is_mont = true) {
+        check(reef_nifs_set_matrix(ctx_, which, row, col, val, nnz, is_mont), "reef_nifs_set_matrix");
+    }
+    // the running instance; nova's first step passes the first fresh instance with E = NULL (zeros) and u = 1
+    void set_running(const reef_fe *W, const reef_fe *E, const reef_fe &u, const reef_fe *X, int loc = REEF_HOST, bool is_mont = true) {
+        check(reef_nifs_set_running(ctx_, W, E, &u, X, loc, is_mont), "reef_nifs_set_running");
+    }
+    // NIFS::prove's commit_T: T of the running and the fresh instance (W2, u = 1, X2) stays on the device; comm_T = MSM(T) over
+    // `key` (same curve and device, at least num_cons points), returned to the host for the transcript
+    reef_jacobian commit_T(reef_msm_ctx *key, const reef_fe *W2, const reef_fe *X2, int loc = REEF_HOST, bool is_mont = true) {
+        reef_jacobian comm_T;
+        check(reef_nifs_commit_T(ctx_, key, W2, X2, loc, is_mont, &comm_T), "reef_nifs_commit_T");
+        return comm_T;
+    }
+    // W += r W2, E += r T, u += r, X += r X2
+    void fold(const reef_fe &r, bool is_mont = true) { check(reef_nifs_fold(ctx_, &r, is_mont), "reef_nifs_fold"); }
+    // which: 0 W, 1 E, 2 T, 3 u, 4 X; the first `count` entries
+    std::vector<reef_fe> read(int which, size_t count, bool to_mont = true) const {
+        std::vector<reef_fe> out(count);
+        check(reef_nifs_read(ctx_, which, count, out.data(), to_mont), "reef_nifs_read");
+        return out;
+    }
+    // is_sat_relaxed without the commitment check: the number of rows with AZ o BZ != u CZ + E
+    uint64_t check_relaxed(uint64_t *first_bad_row = nullptr) const {
+        uint64_t bad = 0, first = 0;
+        check(reef_nifs_check_relaxed(ctx_, &bad, &first), "reef_nifs_check_relaxed");
+        if (first_bad_row) *first_bad_row = first;
+        return bad;
+    }
+
+  private:
+    reef_nifs_ctx *ctx_ = nullptr;
+    size_t num_cons_, num_vars_, num_io_;
+};
+
+// nova-snark RelaxedR1CSSNARK::prove [R] on the running instance a Nifs context holds after its last fold: the outer and inner
+// sum-checks (reef_msm.h 3g), then EE::prove_batch over [E, W] (3h, 2h).  Scalars in pasta Montgomery form.
+template <int CURVE> class RelaxedR1CSSnark {
+  public:
+    struct Proof {
+        std::vector<reef_fe> tau, r_x, r_y;                  // challenges in call order (r_x[0], r_y[0]: the most significant bit)
+        std::vector<std::array<reef_fe, 3>> outer;          // per outer round {e0, e2, e3}
+        std::array<reef_fe, 4> claims_outer = {};           // AZ(r_x), BZ(r_x), CZ(r_x), E(r_x)
+        reef_fe r_joint = {};                               // the joint-claim challenge
+        std::vector<std::array<reef_fe, 2>> inner;          // per inner round {e0, e2}
+        std::array<reef_fe, 3> claims_inner = {};           // ABC(r_y), z(r_y), eval_W
+        reef_fe cross_term = {}, r_fold = {}, c = {}, r_ipa = {}, a_hat = {};
+        std::vector<reef_jacobian> L, R;                    // per IPA round
+        std::vector<reef_fe> r_rounds;                      // challenge_r per IPA round
+    };
+    // num_cons_pad, num_vars_pad: pk.S's padded sizes (powers of two)
+    RelaxedR1CSSnark(Nifs<CURVE> &nifs, size_t num_cons_pad, size_t num_vars_pad) : nifs_(nifs), ncp_(num_cons_pad), nvp_(num_vars_pad) {
+        log2_exact(ncp_);
+        log2_exact(nvp_);
+    }
+    size_t opening_len() const { return ncp_ > nvp_ ? ncp_ : nvp_; }
+    size_t outer_rounds() const { return log2_exact(ncp_); }
+    size_t inner_rounds() const { return log2_exact(nvp_) + 1; }   // over z's 2 num_vars_pad entries
+    size_t ipa_rounds() const { return log2_exact(opening_len()); }
+
+    // 3g: tau, log2(num_cons_pad) cubic rounds, claims_outer, the joint claim's r, log2(2 num_vars_pad) quadratic rounds, claims_inner
+    void prove_sumchecks(const Transcript &transcript, Proof &pf) const {
+        reef_nifs_ctx *h = nifs_.handle();
+        const size_t ell_x = outer_rounds(), ell_y = inner_rounds();
+        pf.tau.clear(); pf.r_x.clear(); pf.r_y.clear(); pf.outer.clear(); pf.inner.clear();
+        for (size_t j = 0; j < ell_x; ++j) pf.tau.push_back(transcript("t", nullptr, 0));
+        std::array<reef_fe, 3> ev;
+        check(reef_spartan_begin(h, ncp_, nvp_, pf.tau.data(), true, ev.data()), "reef_spartan_begin");
+        for (size_t i = 0; i < ell_x; ++i) {
+            pf.outer.push_back(ev);
+            pf.r_x.push_back(transcript("outer", ev.data(), sizeof ev));
+            if (i + 1 < ell_x) check(reef_spartan_outer_round(h, &pf.r_x.back(), true, ev.data()), "reef_spartan_outer_round");
+            else check(reef_spartan_outer_claims(h, &pf.r_x.back(), true, pf.claims_outer.data()), "reef_spartan_outer_claims");
+        }
+        pf.r_joint = transcript("claims_outer", pf.claims_outer.data(), sizeof pf.claims_outer);
+        std::array<reef_fe, 2> ev2;
+        check(reef_spartan_inner_begin(h, &pf.r_joint, true, ev2.data()), "reef_spartan_inner_begin");
+        for (size_t j = 0; j < ell_y; ++j) {
+            pf.inner.push_back(ev2);
+            pf.r_y.push_back(transcript("inner", ev2.data(), sizeof ev2));
+            if (j + 1 < ell_y) check(reef_spartan_inner_round(h, &pf.r_y.back(), true, ev2.data()), "reef_spartan_inner_round");
+            else check(reef_spartan_inner_claims(h, &pf.r_y.back(), true, pf.claims_inner.data()), "reef_spartan_inner_claims");
+        }
+    }
+    // 3h, after prove_sumchecks.  gens_v: a key of exactly opening_len() points.  comm_a(r): the caller's comm_E + r comm_W, as the
+    // bytes it absorbs; q_of(r_ipa): the caller's gens_s.scale(r_ipa), affine.
+    void prove_opening(reef_msm_ctx *gens_v, const Transcript &transcript, const std::function<std::vector<uint8_t>(const reef_fe &)> &comm_a,
+                       const std::function<reef_affine(const reef_fe &)> &q_of, Proof &pf) const {
+        reef_nifs_ctx *h = nifs_.handle();
+        pf.L.clear(); pf.R.clear(); pf.r_rounds.clear();
+        check(reef_spartan_open_begin(h, gens_v, true, &pf.cross_term), "reef_spartan_open_begin");
+        pf.r_fold = transcript("r", &pf.cross_term, sizeof pf.cross_term);
+        check(reef_spartan_open_fold(h, &pf.r_fold, true, &pf.c), "reef_spartan_open_fold");
+        std::vector<uint8_t> u = comm_a(pf.r_fold);
+        u.insert(u.end(), (const uint8_t *)&pf.c, (const uint8_t *)&pf.c + sizeof pf.c);
+        pf.r_ipa = transcript("r", u.data(), u.size());
+        const reef_affine q = q_of(pf.r_ipa);
+        reef_jacobian lr[2];
+        check(reef_spartan_open_ipa_begin(h, &q, &lr[0], &lr[1]), "reef_spartan_open_ipa_begin");
+        const size_t rounds = ipa_rounds();
+        for (size_t k = 0; k < rounds; ++k) {
+            pf.L.push_back(lr[0]);
+            pf.R.push_back(lr[1]);
+            pf.r_rounds.push_back(transcript("challenge_r", lr, sizeof lr));
+            if (k + 1 < rounds) check(reef_spartan_open_ipa_round(h, &pf.r_rounds.back(), true, &lr[0], &lr[1]), "reef_spartan_open_ipa_round");
+            else check(reef_spartan_open_finish(h, &pf.r_rounds.back(), true, &pf.a_hat), "reef_spartan_open_finish");
+        }
+    }
+
+  private:
+    Nifs<CURVE> &nifs_;
+    size_t ncp_, nvp_;
+};
+
+// HyraxPC::prove_eval [R] over a document kept resident from NLDocCommitment::new on (reef_msm.h 3i): plain
+// ipa_pc rounds (no blinding term).  Scalars in pasta Montgomery form.
+template <int CURVE> class HyraxEval {
+  public:
+    struct Proof {
+        reef_fe eval = {}, lz_blind = {}, r_q = {}, a_hat = {}, b_hat = {};
+        reef_jacobian comm_lz = {};
+        std::vector<reef_jacobian> L, R;
+        std::vector<reef_fe> r_rounds;
+    };
+    // NLDocCommitment::new: z (n <= 2^num_vars entries of elem_bytes each, host or device) and the 2^left_vars row blinds
+    HyraxEval(const void *z, size_t n, int elem_bytes, int z_loc, size_t num_vars, size_t left_vars, const reef_fe *row_blinds, int device = 0)
+        : num_vars_(num_vars), left_(left_vars) {
+        check(reef_hyrax_create(&ctx_, CURVE, z, n, elem_bytes, z_loc, true, num_vars, left_vars, row_blinds, device), "reef_hyrax_create");
+    }
+    ~HyraxEval() { reef_hyrax_destroy(ctx_); }
+    HyraxEval(const HyraxEval &) = delete;
+    HyraxEval &operator=(const HyraxEval &) = delete;
+    size_t rounds() const { return num_vars_ - left_; }
+
+    // proof_dot_prod_prover -> prove_eval at `point` (num_vars entries).  gens_v: a key of exactly 2^rounds() points; row_comms:
+    // the 2^left_vars affine row commitments (row_comms_loc memory); q_of(r): the caller's gens_1.scale(r), affine.
+    void prove(reef_msm_ctx *gens_v, const reef_fe *point, const reef_affine *row_comms, int row_comms_loc, const Transcript &transcript,
+               const std::function<reef_affine(const reef_fe &)> &q_of, Proof &pf) const {
+        pf.L.clear(); pf.R.clear(); pf.r_rounds.clear();
+        check(reef_hyrax_eval_begin(ctx_, gens_v, point, true, &pf.eval, &pf.lz_blind), "reef_hyrax_eval_begin");
+        check(reef_hyrax_eval_comm(ctx_, row_comms, row_comms_loc, &pf.comm_lz), "reef_hyrax_eval_comm");
+        uint8_t u[sizeof(reef_jacobian) + sizeof(reef_fe)];
+        memcpy(u, &pf.comm_lz, sizeof(reef_jacobian));
+        memcpy(u + sizeof(reef_jacobian), &pf.eval, sizeof(reef_fe));
+        pf.r_q = transcript("r", u, sizeof u);
+        const reef_affine q = q_of(pf.r_q);
+        reef_jacobian lr[2];
+        check(reef_hyrax_ipa_begin(ctx_, &q, nullptr, nullptr, true, &lr[0], &lr[1]), "reef_hyrax_ipa_begin");
+        const size_t k_end = rounds();
+        for (size_t k = 0; k < k_end; ++k) {
+            pf.L.push_back(lr[0]);
+            pf.R.push_back(lr[1]);
+            pf.r_rounds.push_back(transcript("challenge_r", lr, sizeof lr));
+            if (k + 1 < k_end) check(reef_hyrax_ipa_round(ctx_, &pf.r_rounds.back(), nullptr, true, &lr[0], &lr[1]), "reef_hyrax_ipa_round");
+            else check(reef_hyrax_finish(ctx_, &pf.r_rounds.back(), true, &pf.a_hat, &pf.b_hat), "reef_hyrax_finish");
+        }
+    }
+
+  private:
+    reef_hyrax_ctx *ctx_ = nullptr;
+    size_t num_vars_, left_;
 };
 
 }  // namespace reef_provider

@@ -4,6 +4,7 @@ src/backend/framework.rs:642-754) issued through the C ABI by the C++ harness re
 The harness is host code of the product side (it links libreef_msm.so only); its MSM lengths come from
 tests/golden/replay_shapes.json, which oracle/gen_replay_shapes.py derives from Reef's cost model.  Every per-step
 commitment is checked inside the harness against its discrete-logarithm closed form; a mismatch is an error here.
+run_prove() is the harness's prove leg: every device row of one proof on synthetic R1CS, checked with the verifier's equations.
 """
 from __future__ import annotations
 
@@ -29,6 +30,10 @@ def _load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
         lib.reef_replay_run.restype = ctypes.c_int
         lib.reef_replay_run.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
+        lib.reef_replay_run_prove.restype = ctypes.c_int
+        lib.reef_replay_run_prove.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+        lib.reef_replay_check_selftest.restype = ctypes.c_int
+        lib.reef_replay_check_selftest.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
         lib.reef_replay_run_devices.restype = ctypes.c_int
         lib.reef_replay_run_devices.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_size_t,
                                                 ctypes.c_char_p, ctypes.c_size_t]
@@ -53,3 +58,53 @@ def run(config: str = "cfg3", nofold: bool = True, tables: bool = False, shapes_
 def shapes(shapes_path: str | None = None) -> dict:
     with open(shapes_path or SHAPES_PATH) as f:
         return {s["name"]: s for s in json.load(f)["shapes"]}
+
+
+PROVE_PHASES = ("nifs", "spartan", "open", "hyrax")
+
+
+class ProofRejected(RuntimeError):
+    """A check of the prove leg failed; .phase names it (nifs | spartan | open | hyrax)."""
+
+    def __init__(self, message: str, phase: str | None):
+        super().__init__(message)
+        self.phase = phase
+
+
+def _phase_of(text: str):
+    for p in PROVE_PHASES:
+        if text.startswith(f"proof check failed [{p}]"):
+            return p
+    return None
+
+
+def run_prove(config: str = "cfg3", tamper: str | None = None, tables: bool = False, shapes_path: str | None = None) -> dict:
+    """The prove leg: every device row of one proof (NIFS steps, the last fold, Spartan sum-checks and the batched opening on both
+    curves, the Hyrax consistency argument) through the C ABI, then checked with the verifier's equations on the host.  Returns the
+    JSON line as a dict.  A rejected proof raises ProofRejected naming the phase; tamper=<phase> alters one recorded value before
+    the checks, so that it must."""
+    if tamper is not None and tamper not in PROVE_PHASES:
+        raise ValueError(f"tamper must be one of {PROVE_PHASES}")
+    flags = " ".join(([f"tamper={tamper}"] if tamper else []) + (["tables"] if tables else []))
+    buf = ctypes.create_string_buffer(32768)
+    rc = _load().reef_replay_run_prove((shapes_path or SHAPES_PATH).encode(), config.encode(), flags.encode(), buf, len(buf))
+    text = buf.value.decode(errors="replace")
+    if rc != 0:
+        phase = _phase_of(text)
+        if phase:
+            raise ProofRejected(f"reef_replay_run_prove({config}): {text}", phase)
+        raise RuntimeError(f"reef_replay_run_prove({config}) failed with {rc}: {text}")
+    return json.loads(text)
+
+
+def check_selftest(tamper: str | None = None) -> dict:
+    """The prove leg's checks on a tiny honest transcript made on the host (no GPU needed).  Returns the summary dict when every check
+    accepts; raises ProofRejected naming the phase when one rejects (as it must with tamper=<phase>)."""
+    buf = ctypes.create_string_buffer(4096)
+    rc = _load().reef_replay_check_selftest(tamper.encode() if tamper else None, buf, len(buf))
+    text = buf.value.decode(errors="replace")
+    if rc == 1:
+        raise ProofRejected(text, _phase_of(text))
+    if rc != 0:
+        raise RuntimeError(f"reef_replay_check_selftest failed with {rc}: {text}")
+    return json.loads(text)
