@@ -16,6 +16,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 
 #include "common.h"
 #include "keccak.h"
@@ -78,13 +79,6 @@ static void hook_process_exit() {
     });
 }
 
-static const CurveVTable *vt(int curve) {
-    if (curve == REEF_PALLAS) return pallas_vtable();
-    if (curve == REEF_VESTA) return vesta_vtable();
-    set_error("unknown curve %d", curve);
-    return nullptr;
-}
-
 static reef_status require_gpu() {
     static std::once_flag once;
     static reef_status st = REEF_OK;
@@ -122,7 +116,7 @@ static void warm_body() {
     a[0].l[0] = 5; a[1].l[0] = 7; b[0].l[0] = 3; b[1].l[0] = 11;
     bool ok = true;
     for (int curve = 0; curve < 2; ++curve)      // stage_in (pageable host -> device), a kernel of this curve's code object, device -> pageable host
-        ok = ok && vt(curve)->test_field_op(0, a, b, out, 2) == REEF_OK;
+        ok = ok && reef_test_field_op(curve, 0, a, b, out, 2) == REEF_OK;
     // every kernel of the bucket pipeline once per curve (a kernel's first launch resolves it in its code object), the engine's one-off attributes, the first
     // pinned allocation: a 2048-point MSM over identity points on a plain key, host scalars in, host result out -- and gone again
     {
@@ -166,12 +160,30 @@ struct WarmAtLoad {                                  // the zero-patch route has
 
 using namespace reef;
 
-struct reef_msm_ctx {
+// Every handle of the ABI is a curve and the engine's context of that curve; the opaque types of include/reef_msm.h stay distinct.
+struct reef_handle {
     int curve;
     void *impl;
 };
+struct reef_msm_ctx : reef_handle {};
+struct reef_sc_ctx : reef_handle {};
+struct reef_nifs_ctx : reef_handle {};     // rows N6 and N5 and the opening (3f-3h) share it
+struct reef_hyrax_ctx : reef_handle {};
 
-// No C++ exception crosses the C ABI: host allocations sized by the caller (key-derivation stream, staging vectors) can fail.
+// The table of a curve's entry points, one per row (common.h); NULL with the error set for a curve that does not exist.
+template <class VT> static const VT *table(int curve) {
+    if (curve != REEF_PALLAS && curve != REEF_VESTA) { set_error("unknown curve %d", curve); return nullptr; }
+    const bool p = curve == REEF_PALLAS;
+    if constexpr (std::is_same<VT, CurveVTable>::value) return p ? pallas_vtable() : vesta_vtable();
+    else if constexpr (std::is_same<VT, NifsVTable>::value) return p ? pallas_nifs_vtable() : vesta_nifs_vtable();
+    else if constexpr (std::is_same<VT, SpartanVTable>::value) return p ? pallas_spartan_vtable() : vesta_spartan_vtable();
+    else if constexpr (std::is_same<VT, OpenVTable>::value) return p ? pallas_open_vtable() : vesta_open_vtable();
+    else return p ? pallas_hyrax_vtable() : vesta_hyrax_vtable();
+}
+
+// No C++ exception crosses the C ABI: host allocations sized by the caller (key-derivation stream, staging vectors, the sum-check's
+// table analysis) can fail.  Wrappers do not call this themselves: they reach the engines through the four helpers below, which do
+// (tests/test_abi.py holds them to it).
 template <class F> static reef_status guarded(F &&f) {
     try {
         return f();
@@ -182,6 +194,39 @@ template <class F> static reef_status guarded(F &&f) {
         set_error("internal error: %s", e.what());
         return REEF_ERR_HIP;
     }
+}
+// An entry point on a handle: f(the row's table of the handle's curve, the engine's context).
+template <class VT, class F> static reef_status dispatch(const reef_handle *ctx, F &&f) {
+    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
+    return guarded([&] { return f(table<VT>(ctx->curve), ctx->impl); });
+}
+// An entry point without a handle: f(the curve's table); needs_gpu = false for what is pure host arithmetic.
+template <class F> static reef_status stateless(int curve, F &&f, bool needs_gpu = true) {
+    const CurveVTable *v = table<CurveVTable>(curve);
+    if (!v) return REEF_ERR_ARG;
+    if (needs_gpu) REEF_TRY(require_gpu());
+    return guarded([&] { return f(v); });
+}
+// A handle H around the context make(v, &impl) creates / the end of one through the row's destroy entry.
+template <class H, class F> static reef_status create_handle(H **out, int curve, F &&make) {
+    if (!out) { set_error("null argument"); return REEF_ERR_ARG; }
+    return stateless(curve, [&](const CurveVTable *v) -> reef_status {
+        void *impl = nullptr;
+        REEF_TRY(make(v, &impl));
+        *out = new H{{curve, impl}};
+        return REEF_OK;
+    });
+}
+template <class VT, class H> static void destroy_handle(H *ctx, void (*VT::*destroy)(void *)) {
+    if (!ctx) return;
+    (table<VT>(ctx->curve)->*destroy)(ctx->impl);
+    delete ctx;
+}
+// the key an entry point borrows is of the ctx's curve (`what`: the kind of ctx, for the message)
+static reef_status require_same_curve(const reef_handle *ctx, const reef_msm_ctx *key, const char *name, const char *what) {
+    if (!ctx || !key) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (key->curve != ctx->curve) { set_error("%s: the key is of curve %d, the %s ctx of curve %d", name, key->curve, what, ctx->curve); return REEF_ERR_ARG; }
+    return REEF_OK;
 }
 
 extern "C" {
@@ -254,74 +299,56 @@ reef_status reef_memcpy(void *dst, const void *src, size_t bytes, int dst_loc, i
 
 reef_status reef_msm_ctx_create(reef_msm_ctx **out, int curve, const reef_affine *bases, size_t n, int bases_loc,
                                 const reef_msm_opts *opts) {
-    if (!out) { set_error("null argument"); return REEF_ERR_ARG; }
-    const CurveVTable *v = vt(curve);
-    if (!v) return REEF_ERR_ARG;
-    REEF_TRY(require_gpu());
-    void *impl = nullptr;
-    REEF_TRY(v->ctx_create(&impl, bases, n, bases_loc, opts));
-    *out = new reef_msm_ctx{curve, impl};
-    return REEF_OK;
+    return create_handle(out, curve, [&](const CurveVTable *v, void **impl) { return v->ctx_create(impl, bases, n, bases_loc, opts); });
 }
 reef_status reef_msm_ctx_set_bases(reef_msm_ctx *ctx, const reef_affine *bases, size_t n, int bases_loc) {
-    if (!ctx || (n && !bases)) { set_error("null argument"); return REEF_ERR_ARG; }
-    return vt(ctx->curve)->ctx_rekey(ctx->impl, bases, n, bases_loc);
+    if (n && !bases) { set_error("null argument"); return REEF_ERR_ARG; }
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_rekey(impl, bases, n, bases_loc); });
 }
 reef_status reef_msm_ctx_attach(reef_msm_ctx *ctx, reef_msm_ctx *src) {
     if (!ctx || !src || ctx->curve != src->curve) { set_error("attach: two contexts of the same curve"); return REEF_ERR_ARG; }
-    return vt(ctx->curve)->ctx_attach(ctx->impl, src->impl);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_attach(impl, src->impl); });
 }
 reef_status reef_msm_ctx_clone(reef_msm_ctx **out, reef_msm_ctx *src) {
-    if (!out || !src) { set_error("null argument"); return REEF_ERR_ARG; }
-    void *impl = nullptr;
-    REEF_TRY(vt(src->curve)->ctx_clone(&impl, src->impl));
-    *out = new reef_msm_ctx{src->curve, impl};
-    return REEF_OK;
+    if (!out) { set_error("null argument"); return REEF_ERR_ARG; }
+    return dispatch<CurveVTable>(src, [&](auto *v, void *src_impl) -> reef_status {
+        void *impl = nullptr;
+        REEF_TRY(v->ctx_clone(&impl, src_impl));
+        *out = new reef_msm_ctx{{src->curve, impl}};
+        return REEF_OK;
+    });
 }
-void reef_msm_ctx_destroy(reef_msm_ctx *ctx) {
-    if (!ctx) return;
-    vt(ctx->curve)->ctx_destroy(ctx->impl);
-    delete ctx;
-}
+void reef_msm_ctx_destroy(reef_msm_ctx *ctx) { destroy_handle(ctx, &CurveVTable::ctx_destroy); }
 reef_status reef_msm_ctx_sync(reef_msm_ctx *ctx) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return vt(ctx->curve)->ctx_sync(ctx->impl);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_sync(impl); });
 }
-void *reef_msm_ctx_stream(reef_msm_ctx *ctx) { return ctx ? vt(ctx->curve)->ctx_stream(ctx->impl) : nullptr; }
+void *reef_msm_ctx_stream(reef_msm_ctx *ctx) { return ctx ? table<CurveVTable>(ctx->curve)->ctx_stream(ctx->impl) : nullptr; }
 reef_status reef_msm_ctx_last_timing(reef_msm_ctx *ctx, float *total_ms, float *accumulate_ms) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return vt(ctx->curve)->ctx_timing(ctx->impl, total_ms, accumulate_ms);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_timing(impl, total_ms, accumulate_ms); });
 }
 reef_status reef_msm_ctx_set_window_split(reef_msm_ctx *ctx, uint32_t rank, uint32_t world) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return vt(ctx->curve)->ctx_window_split(ctx->impl, rank, world);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_window_split(impl, rank, world); });
 }
 reef_status reef_msm_ctx_enable_timing(reef_msm_ctx *ctx, int on) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return vt(ctx->curve)->ctx_enable_timing(ctx->impl, on);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_enable_timing(impl, on); });
 }
 reef_status reef_msm_ctx_timing_stats(reef_msm_ctx *ctx, int reset, uint64_t *calls, double *total_ms, double *accumulate_ms) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return vt(ctx->curve)->ctx_timing_stats(ctx->impl, reset, calls, total_ms, accumulate_ms);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_timing_stats(impl, reset, calls, total_ms, accumulate_ms); });
 }
 reef_status reef_msm_ctx_sum_points(reef_msm_ctx *ctx, const reef_jacobian *in, size_t n, reef_jacobian *out) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return vt(ctx->curve)->ctx_sum_points(ctx->impl, in, n, out);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_sum_points(impl, in, n, out); });
 }
 reef_status reef_msm_ctx_plan(reef_msm_ctx *ctx, uint32_t *c, uint32_t *windows, uint32_t *groups, uint32_t *tables) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return vt(ctx->curve)->ctx_plan(ctx->impl, c, windows, groups, tables);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_plan(impl, c, windows, groups, tables); });
 }
 
 reef_status reef_msm(reef_msm_ctx *ctx, const reef_fe *scalars, size_t n, int scalars_loc, bool is_mont, reef_jacobian *out,
                      int out_loc) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return guarded([&] { return vt(ctx->curve)->msm(ctx->impl, scalars, n, scalars_loc, is_mont, out, out_loc); });
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->msm(impl, scalars, n, scalars_loc, is_mont, out, out_loc); });
 }
 reef_status reef_msm_rows(reef_msm_ctx *ctx, const reef_fe *scalars, size_t rows, size_t row_len, int scalars_loc, bool is_mont,
                           uint32_t max_scalar_bits, const reef_fe *blinds, const reef_affine *h, reef_jacobian *out, int out_loc) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return guarded([&] { return vt(ctx->curve)->msm_rows(ctx->impl, scalars, rows, row_len, scalars_loc, is_mont, max_scalar_bits, blinds, h, out, out_loc); });
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->msm_rows(impl, scalars, rows, row_len, scalars_loc, is_mont, max_scalar_bits, blinds, h, out, out_loc); });
 }
 
 // Several MSMs at once, each on its own context: everything is enqueued first (a context with work in flight keeps its stream,
@@ -342,298 +369,196 @@ reef_status reef_msm_multi(size_t count, reef_msm_ctx *const *ctxs, const reef_f
     } land;
     hook_process_exit();
     if (!land.p) REEF_HIP_TRY(hipHostMalloc((void **)&land.p, 64 * sizeof(reef_jacobian), hipHostMallocDefault));
-    return guarded([&] {
-        reef_status st = REEF_OK;
-        size_t issued = 0;
-        for (; issued < count && st == REEF_OK; ++issued)
-            st = vt(ctxs[issued]->curve)->msm(ctxs[issued]->impl, scalars[issued], n[issued], scalars_loc, is_mont, land.p + issued, REEF_DEVICE);
-        for (size_t i = 0; i < issued; ++i) {           // wait for whatever was enqueued, also after a failure
-            const reef_status w = vt(ctxs[i]->curve)->ctx_sync(ctxs[i]->impl);
-            if (st == REEF_OK) st = w;
-        }
-        if (st == REEF_OK) memcpy(out, land.p, count * sizeof(reef_jacobian));
-        return st;
-    });
+    reef_status st = REEF_OK;
+    size_t issued = 0;
+    for (; issued < count && st == REEF_OK; ++issued)
+        st = reef_msm(ctxs[issued], scalars[issued], n[issued], scalars_loc, is_mont, land.p + issued, REEF_DEVICE);
+    for (size_t i = 0; i < issued; ++i) {               // wait for whatever was enqueued, also after a failure
+        const reef_status w = reef_msm_ctx_sync(ctxs[i]);
+        if (st == REEF_OK) st = w;
+    }
+    if (st == REEF_OK) memcpy(out, land.p, count * sizeof(reef_jacobian));
+    return st;
 }
 
-int reef_msm_ctx_byte_tables(reef_msm_ctx *ctx) { return ctx ? vt(ctx->curve)->ctx_byte_tables(ctx->impl) : 0; }
+int reef_msm_ctx_byte_tables(reef_msm_ctx *ctx) { return ctx ? table<CurveVTable>(ctx->curve)->ctx_byte_tables(ctx->impl) : 0; }
 reef_status reef_msm_plan_for(size_t n, uint32_t window_bits, uint32_t bucket_groups, uint32_t *c, uint32_t *windows,
                               uint32_t *groups, uint32_t *tables) {
-    return pallas_vtable()->plan_for(n, window_bits, bucket_groups, c, windows, groups, tables);
+    return stateless(REEF_PALLAS, [&](const CurveVTable *v) { return v->plan_for(n, window_bits, bucket_groups, c, windows, groups, tables); }, false);   // the same plan for both curves
 }
 
 reef_status reef_msm_rows_symbols(reef_msm_ctx *ctx, const uint8_t *symbols, size_t rows, size_t row_len, int loc, uint32_t symbol_bits,
                                   const reef_fe *blinds, const reef_affine *h, bool blinds_are_mont, reef_jacobian *out, int out_loc) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return guarded([&] { return vt(ctx->curve)->msm_rows_symbols(ctx->impl, symbols, rows, row_len, loc, symbol_bits, blinds, h, blinds_are_mont, out, out_loc); });
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->msm_rows_symbols(impl, symbols, rows, row_len, loc, symbol_bits, blinds, h, blinds_are_mont, out, out_loc); });
 }
 reef_status reef_ipa_cross_terms(reef_msm_ctx *ctx, const reef_fe *a, size_t n_k, int a_loc, bool is_mont, const reef_fe *w1s,
                                  const reef_fe *w2s, size_t k, reef_jacobian *out_l, reef_jacobian *out_r) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return guarded([&] { return vt(ctx->curve)->ipa_cross(ctx->impl, a, n_k, a_loc, is_mont, w1s, w2s, k, out_l, out_r); });
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ipa_cross(impl, a, n_k, a_loc, is_mont, w1s, w2s, k, out_l, out_r); });
 }
 
 reef_status reef_msm_folded(reef_msm_ctx *ctx, const reef_fe *v, size_t len, size_t off, int v_loc, bool is_mont, const reef_fe *w1s,
                             const reef_fe *w2s, size_t k, reef_jacobian *out, int out_loc) {
-    if (!ctx) { set_error("null argument"); return REEF_ERR_ARG; }
-    return guarded([&] { return vt(ctx->curve)->msm_folded(ctx->impl, v, len, off, v_loc, is_mont, w1s, w2s, k, out, out_loc); });
+    return dispatch<CurveVTable>(ctx, [&](auto *t, void *impl) { return t->msm_folded(impl, v, len, off, v_loc, is_mont, w1s, w2s, k, out, out_loc); });
 }
-
-#define STATELESS_PROLOGUE(curve)          \
-    const CurveVTable *v = vt(curve);      \
-    if (!v) return REEF_ERR_ARG;           \
-    REEF_TRY(require_gpu())
 
 reef_status reef_fold(int curve, const reef_affine *gens, size_t half, int loc, const reef_fe *w1, const reef_fe *w2,
                       reef_affine *out) {
-    STATELESS_PROLOGUE(curve);
-    return v->fold(gens, half, loc, w1, w2, out);
+    return stateless(curve, [&](const CurveVTable *v) { return v->fold(gens, half, loc, w1, w2, out); });
 }
 reef_status reef_mle_bound_rows(int curve, const void *z, size_t n, int elem_bytes, int z_loc, bool is_mont, const reef_fe *point,
                                 size_t num_vars, size_t left_vars, reef_fe *lz_out, int out_loc, reef_fe *eval_out) {
-    STATELESS_PROLOGUE(curve);
-    return v->mle_bound(z, n, elem_bytes, z_loc, is_mont, point, num_vars, left_vars, lz_out, out_loc, eval_out);
+    return stateless(curve, [&](const CurveVTable *v) { return v->mle_bound(z, n, elem_bytes, z_loc, is_mont, point, num_vars, left_vars, lz_out, out_loc, eval_out); });
 }
 reef_status reef_normalize(int curve, const reef_jacobian *in, size_t n, int loc, reef_affine *out_affine, uint8_t *out_compressed) {
-    STATELESS_PROLOGUE(curve);
-    return v->normalize(in, n, loc, out_affine, out_compressed);
+    return stateless(curve, [&](const CurveVTable *v) { return v->normalize(in, n, loc, out_affine, out_compressed); });
 }
 reef_status reef_sum_points(int curve, const reef_jacobian *in, size_t n, int loc, reef_jacobian *out) {
-    STATELESS_PROLOGUE(curve);
-    return v->sum_points(in, n, loc, out);
+    return stateless(curve, [&](const CurveVTable *v) { return v->sum_points(in, n, loc, out); });
 }
 reef_status reef_gen_bases(int curve, uint64_t k0, uint64_t d, size_t n, reef_affine *out, int loc) {
-    STATELESS_PROLOGUE(curve);
-    return v->gen_bases(k0, d, n, out, loc);
+    return stateless(curve, [&](const CurveVTable *v) { return v->gen_bases(k0, d, n, out, loc); });
 }
 reef_status reef_gen_scalars(int curve, uint64_t seed, int kind, uint64_t small_bound, size_t n, bool to_mont, reef_fe *out,
                              int loc) {
-    STATELESS_PROLOGUE(curve);
-    return v->gen_scalars(seed, kind, small_bound, n, to_mont, out, loc);
+    return stateless(curve, [&](const CurveVTable *v) { return v->gen_scalars(seed, kind, small_bound, n, to_mont, out, loc); });
 }
 reef_status reef_test_field_op(int field, int op, const reef_fe *a, const reef_fe *b, reef_fe *out, size_t n) {
-    STATELESS_PROLOGUE(field);  // coordinate field of curve `field`
-    return v->test_field_op(op, a, b, out, n);
+    return stateless(field, [&](const CurveVTable *v) { return v->test_field_op(op, a, b, out, n); });
 }
 reef_status reef_test_ec_op(int curve, int op, const reef_affine *p, const reef_affine *q, const reef_fe *k, reef_jacobian *out,
                             size_t n) {
-    STATELESS_PROLOGUE(curve);
-    return v->test_ec_op(op, p, q, k, out, n);
+    return stateless(curve, [&](const CurveVTable *v) { return v->test_ec_op(op, p, q, k, out, n); });
 }
 reef_status reef_bench_fmul(int field, uint32_t iters, double *products_per_s) {
-    STATELESS_PROLOGUE(field);
-    if (!products_per_s) { set_error("null argument"); return REEF_ERR_ARG; }
-    return v->bench_fmul(iters, products_per_s);
+    return stateless(field, [&](const CurveVTable *v) -> reef_status {
+        if (!products_per_s) { set_error("null argument"); return REEF_ERR_ARG; }
+        return v->bench_fmul(iters, products_per_s);
+    });
 }
 
 // ---- row N2: sum-check vector kernels
-struct reef_sc_ctx {
-    int curve;
-    void *impl;
-};
 reef_status reef_sc_create(reef_sc_ctx **out, int curve, size_t table_len) {
-    if (!out) { set_error("null argument"); return REEF_ERR_ARG; }
-    STATELESS_PROLOGUE(curve);
-    void *impl = nullptr;
-    REEF_TRY(v->sc_create(&impl, table_len));
-    *out = new reef_sc_ctx{curve, impl};
-    return REEF_OK;
+    return create_handle(out, curve, [&](const CurveVTable *v, void **impl) { return v->sc_create(impl, table_len); });
 }
-void reef_sc_destroy(reef_sc_ctx *ctx) {
-    if (!ctx) return;
-    vt(ctx->curve)->sc_destroy(ctx->impl);
-    delete ctx;
-}
-#define SC_CHECK(ctx) if (!(ctx)) { set_error("null argument"); return REEF_ERR_ARG; }
+void reef_sc_destroy(reef_sc_ctx *ctx) { destroy_handle(ctx, &CurveVTable::sc_destroy); }
 reef_status reef_sc_set_table(reef_sc_ctx *ctx, int which, const reef_fe *values, size_t n, int loc) {
-    SC_CHECK(ctx);
-    return vt(ctx->curve)->sc_set(ctx->impl, which, values, n, loc);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_set(impl, which, values, n, loc); });
 }
 reef_status reef_sc_gen_eq_table(reef_sc_ctx *ctx, const reef_fe *rs, const uint32_t *qs, size_t nq, const reef_fe *last_q, size_t ell) {
-    SC_CHECK(ctx);
-    return vt(ctx->curve)->sc_gen_eq(ctx->impl, rs, qs, nq, last_q, ell);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_gen_eq(impl, rs, qs, nq, last_q, ell); });
 }
 reef_status reef_sc_round_coeffs(reef_sc_ctx *ctx, size_t pow, reef_fe out[3]) {
-    SC_CHECK(ctx);
-    return vt(ctx->curve)->sc_coeffs(ctx->impl, pow, out);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_coeffs(impl, pow, out); });
 }
 reef_status reef_sc_fold(reef_sc_ctx *ctx, size_t pow, const reef_fe *r) {
-    SC_CHECK(ctx);
-    return vt(ctx->curve)->sc_fold(ctx->impl, pow, r);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_fold(impl, pow, r); });
 }
 reef_status reef_sc_fold_and_next_coeffs(reef_sc_ctx *ctx, size_t pow, const reef_fe *r, reef_fe out[3]) {
-    SC_CHECK(ctx);
-    return vt(ctx->curve)->sc_fold_coeffs(ctx->impl, pow, r, out);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_fold_coeffs(impl, pow, r, out); });
 }
 reef_status reef_sc_read(reef_sc_ctx *ctx, int which, size_t count, reef_fe *out) {
-    SC_CHECK(ctx);
-    return vt(ctx->curve)->sc_read(ctx->impl, which, count, out);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_read(impl, which, count, out); });
 }
 reef_status reef_sc_reset_table(reef_sc_ctx *ctx) {
-    SC_CHECK(ctx);
-    return vt(ctx->curve)->sc_reset(ctx->impl);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_reset(impl); });
 }
 reef_status reef_sc_sync(reef_sc_ctx *ctx) {
-    SC_CHECK(ctx);
-    return vt(ctx->curve)->sc_sync(ctx->impl);
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_sync(impl); });
 }
 
 // ---- row N6: the NIFS fold of one step
-struct reef_nifs_ctx {
-    int curve;
-    void *impl;
-};
-static const NifsVTable *nvt(int curve) { return curve == REEF_PALLAS ? pallas_nifs_vtable() : vesta_nifs_vtable(); }
 reef_status reef_nifs_create(reef_nifs_ctx **out, int curve, size_t num_cons, size_t num_vars, size_t num_io, int device) {
-    if (!out) { set_error("null argument"); return REEF_ERR_ARG; }
-    STATELESS_PROLOGUE(curve);
-    (void)v;
-    void *impl = nullptr;
-    REEF_TRY(guarded([&] { return nvt(curve)->create(&impl, num_cons, num_vars, num_io, device); }));
-    *out = new reef_nifs_ctx{curve, impl};
-    return REEF_OK;
+    return create_handle(out, curve, [&](const CurveVTable *, void **impl) { return table<NifsVTable>(curve)->create(impl, num_cons, num_vars, num_io, device); });
 }
-void reef_nifs_destroy(reef_nifs_ctx *ctx) {
-    if (!ctx) return;
-    nvt(ctx->curve)->destroy(ctx->impl);
-    delete ctx;
-}
+void reef_nifs_destroy(reef_nifs_ctx *ctx) { destroy_handle(ctx, &NifsVTable::destroy); }
 reef_status reef_nifs_set_matrix(reef_nifs_ctx *ctx, int which, const uint32_t *row, const uint32_t *col, const reef_fe *val, size_t nnz, bool is_mont) {
-    SC_CHECK(ctx);
-    return guarded([&] { return nvt(ctx->curve)->set_matrix(ctx->impl, which, row, col, val, nnz, is_mont); });
+    return dispatch<NifsVTable>(ctx, [&](auto *v, void *impl) { return v->set_matrix(impl, which, row, col, val, nnz, is_mont); });
 }
 reef_status reef_nifs_set_running(reef_nifs_ctx *ctx, const reef_fe *W, const reef_fe *E, const reef_fe *u, const reef_fe *X, int loc, bool is_mont) {
-    SC_CHECK(ctx);
-    return nvt(ctx->curve)->set_running(ctx->impl, W, E, u, X, loc, is_mont);
+    return dispatch<NifsVTable>(ctx, [&](auto *v, void *impl) { return v->set_running(impl, W, E, u, X, loc, is_mont); });
 }
 reef_status reef_nifs_commit_T(reef_nifs_ctx *ctx, reef_msm_ctx *key, const reef_fe *W2, const reef_fe *X2, int loc, bool is_mont, reef_jacobian *comm_T) {
-    SC_CHECK(ctx);
-    if (!key) { set_error("null argument"); return REEF_ERR_ARG; }
-    if (key->curve != ctx->curve) { set_error("reef_nifs_commit_T: the key is of curve %d, the NIFS ctx of curve %d", key->curve, ctx->curve); return REEF_ERR_ARG; }
-    return guarded([&] { return nvt(ctx->curve)->commit_t(ctx->impl, key->impl, W2, X2, loc, is_mont, comm_T); });
+    REEF_TRY(require_same_curve(ctx, key, "reef_nifs_commit_T", "NIFS"));
+    return dispatch<NifsVTable>(ctx, [&](auto *v, void *impl) { return v->commit_t(impl, key->impl, W2, X2, loc, is_mont, comm_T); });
 }
 reef_status reef_nifs_fold(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont) {
-    SC_CHECK(ctx);
-    return nvt(ctx->curve)->fold(ctx->impl, r, is_mont);
+    return dispatch<NifsVTable>(ctx, [&](auto *v, void *impl) { return v->fold(impl, r, is_mont); });
 }
 reef_status reef_nifs_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont) {
-    SC_CHECK(ctx);
-    return nvt(ctx->curve)->read(ctx->impl, which, count, out, to_mont);
+    return dispatch<NifsVTable>(ctx, [&](auto *v, void *impl) { return v->read(impl, which, count, out, to_mont); });
 }
 reef_status reef_nifs_check_relaxed(reef_nifs_ctx *ctx, uint64_t *violations, uint64_t *first_bad_row) {
-    SC_CHECK(ctx);
-    return nvt(ctx->curve)->check(ctx->impl, violations, first_bad_row);
+    return dispatch<NifsVTable>(ctx, [&](auto *v, void *impl) { return v->check(impl, violations, first_bad_row); });
 }
 
 // ---- row N5: the sum-checks of the final SNARK on a NIFS ctx
-static const SpartanVTable *svt(int curve) { return curve == REEF_PALLAS ? pallas_spartan_vtable() : vesta_spartan_vtable(); }
 reef_status reef_spartan_begin(reef_nifs_ctx *ctx, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *tau, bool is_mont, reef_fe evals[3]) {
-    SC_CHECK(ctx);
-    return guarded([&] { return svt(ctx->curve)->begin(ctx->impl, num_cons_pad, num_vars_pad, tau, is_mont, evals); });
+    return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) { return v->begin(impl, num_cons_pad, num_vars_pad, tau, is_mont, evals); });
 }
 reef_status reef_spartan_outer_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe evals[3]) {
-    SC_CHECK(ctx);
-    return svt(ctx->curve)->outer_round(ctx->impl, r, is_mont, evals);
+    return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) { return v->outer_round(impl, r, is_mont, evals); });
 }
 reef_status reef_spartan_outer_claims(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe claims[4]) {
-    SC_CHECK(ctx);
-    return guarded([&] { return svt(ctx->curve)->outer_claims(ctx->impl, r_last, is_mont, claims); });
+    return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) { return v->outer_claims(impl, r_last, is_mont, claims); });
 }
 reef_status reef_spartan_inner_begin(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe evals[2]) {
-    SC_CHECK(ctx);
-    return guarded([&] { return svt(ctx->curve)->inner_begin(ctx->impl, r, is_mont, evals); });
+    return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) { return v->inner_begin(impl, r, is_mont, evals); });
 }
 reef_status reef_spartan_inner_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe evals[2]) {
-    SC_CHECK(ctx);
-    return svt(ctx->curve)->inner_round(ctx->impl, r, is_mont, evals);
+    return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) { return v->inner_round(impl, r, is_mont, evals); });
 }
 reef_status reef_spartan_inner_claims(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe claims[3]) {
-    SC_CHECK(ctx);
-    return guarded([&] { return svt(ctx->curve)->inner_claims(ctx->impl, r_last, is_mont, claims); });
+    return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) { return v->inner_claims(impl, r_last, is_mont, claims); });
 }
 
 // ---- the batched IPA opening of the final SNARK on a NIFS ctx
-static const OpenVTable *ovt(int curve) { return curve == REEF_PALLAS ? pallas_open_vtable() : vesta_open_vtable(); }
 reef_status reef_spartan_open_begin(reef_nifs_ctx *ctx, reef_msm_ctx *key, bool is_mont, reef_fe *cross_term) {
-    SC_CHECK(ctx);
-    if (!key) { set_error("null argument"); return REEF_ERR_ARG; }
-    if (key->curve != ctx->curve) {
-        set_error("reef_spartan_open_begin: the key is of curve %d, the NIFS ctx of curve %d", key->curve, ctx->curve);
-        return REEF_ERR_ARG;
-    }
-    return guarded([&] { return ovt(ctx->curve)->begin(ctx->impl, key->impl, is_mont, cross_term); });
+    REEF_TRY(require_same_curve(ctx, key, "reef_spartan_open_begin", "NIFS"));
+    return dispatch<OpenVTable>(ctx, [&](auto *v, void *impl) { return v->begin(impl, key->impl, is_mont, cross_term); });
 }
 reef_status reef_spartan_open_fold(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_fe *c) {
-    SC_CHECK(ctx);
-    return ovt(ctx->curve)->fold(ctx->impl, r, is_mont, c);
+    return dispatch<OpenVTable>(ctx, [&](auto *v, void *impl) { return v->fold(impl, r, is_mont, c); });
 }
 reef_status reef_spartan_open_ipa_begin(reef_nifs_ctx *ctx, const reef_affine *q, reef_jacobian *L, reef_jacobian *R) {
-    SC_CHECK(ctx);
-    return guarded([&] { return ovt(ctx->curve)->ipa_begin(ctx->impl, q, L, R); });
+    return dispatch<OpenVTable>(ctx, [&](auto *v, void *impl) { return v->ipa_begin(impl, q, L, R); });
 }
 reef_status reef_spartan_open_ipa_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_jacobian *L, reef_jacobian *R) {
-    SC_CHECK(ctx);
-    return guarded([&] { return ovt(ctx->curve)->ipa_round(ctx->impl, r, is_mont, L, R); });
+    return dispatch<OpenVTable>(ctx, [&](auto *v, void *impl) { return v->ipa_round(impl, r, is_mont, L, R); });
 }
 reef_status reef_spartan_open_finish(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe *a_hat) {
-    SC_CHECK(ctx);
-    return ovt(ctx->curve)->finish(ctx->impl, r_last, is_mont, a_hat);
+    return dispatch<OpenVTable>(ctx, [&](auto *v, void *impl) { return v->finish(impl, r_last, is_mont, a_hat); });
 }
 reef_status reef_spartan_open_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont) {
-    SC_CHECK(ctx);
-    return ovt(ctx->curve)->read(ctx->impl, which, count, out, to_mont);
+    return dispatch<OpenVTable>(ctx, [&](auto *v, void *impl) { return v->read(impl, which, count, out, to_mont); });
 }
 
 // ---- the Hyrax consistency argument on a resident document
-struct reef_hyrax_ctx {
-    int curve;
-    void *impl;
-};
-static const HyraxVTable *hvt(int curve) { return curve == REEF_PALLAS ? pallas_hyrax_vtable() : vesta_hyrax_vtable(); }
 reef_status reef_hyrax_create(reef_hyrax_ctx **out, int curve, const void *z, size_t n, int elem_bytes, int z_loc, bool is_mont, size_t num_vars,
                               size_t left_vars, const reef_fe *row_blinds, int device) {
-    if (!out) { set_error("null argument"); return REEF_ERR_ARG; }
-    STATELESS_PROLOGUE(curve);
-    (void)v;
-    void *impl = nullptr;
-    REEF_TRY(guarded([&] { return hvt(curve)->create(&impl, z, n, elem_bytes, z_loc, is_mont, num_vars, left_vars, row_blinds, device); }));
-    *out = new reef_hyrax_ctx{curve, impl};
-    return REEF_OK;
+    return create_handle(out, curve, [&](const CurveVTable *, void **impl) {
+        return table<HyraxVTable>(curve)->create(impl, z, n, elem_bytes, z_loc, is_mont, num_vars, left_vars, row_blinds, device);
+    });
 }
-void reef_hyrax_destroy(reef_hyrax_ctx *ctx) {
-    if (!ctx) return;
-    hvt(ctx->curve)->destroy(ctx->impl);
-    delete ctx;
-}
+void reef_hyrax_destroy(reef_hyrax_ctx *ctx) { destroy_handle(ctx, &HyraxVTable::destroy); }
 reef_status reef_hyrax_eval_begin(reef_hyrax_ctx *ctx, reef_msm_ctx *key, const reef_fe *point, bool is_mont, reef_fe *eval, reef_fe *lz_blind) {
-    SC_CHECK(ctx);
-    if (!key) { set_error("null argument"); return REEF_ERR_ARG; }
-    if (key->curve != ctx->curve) {
-        set_error("reef_hyrax_eval_begin: the key is of curve %d, the Hyrax ctx of curve %d", key->curve, ctx->curve);
-        return REEF_ERR_ARG;
-    }
-    return guarded([&] { return hvt(ctx->curve)->eval_begin(ctx->impl, key->impl, point, is_mont, eval, lz_blind); });
+    REEF_TRY(require_same_curve(ctx, key, "reef_hyrax_eval_begin", "Hyrax"));
+    return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->eval_begin(impl, key->impl, point, is_mont, eval, lz_blind); });
 }
 reef_status reef_hyrax_eval_comm(reef_hyrax_ctx *ctx, const reef_affine *row_comms, int loc, reef_jacobian *comm_lz) {
-    SC_CHECK(ctx);
-    return guarded([&] { return hvt(ctx->curve)->eval_comm(ctx->impl, row_comms, loc, comm_lz); });
+    return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->eval_comm(impl, row_comms, loc, comm_lz); });
 }
 reef_status reef_hyrax_ipa_begin(reef_hyrax_ctx *ctx, const reef_affine *q, const reef_affine *h, const reef_fe *blinds, bool is_mont,
                                  reef_jacobian *L, reef_jacobian *R) {
-    SC_CHECK(ctx);
-    return guarded([&] { return hvt(ctx->curve)->ipa_begin(ctx->impl, q, h, blinds, is_mont, L, R); });
+    return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->ipa_begin(impl, q, h, blinds, is_mont, L, R); });
 }
 reef_status reef_hyrax_ipa_round(reef_hyrax_ctx *ctx, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R) {
-    SC_CHECK(ctx);
-    return guarded([&] { return hvt(ctx->curve)->ipa_round(ctx->impl, r, blinds, is_mont, L, R); });
+    return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->ipa_round(impl, r, blinds, is_mont, L, R); });
 }
 reef_status reef_hyrax_finish(reef_hyrax_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat) {
-    SC_CHECK(ctx);
-    return hvt(ctx->curve)->finish(ctx->impl, r_last, is_mont, a_hat, b_hat);
+    return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->finish(impl, r_last, is_mont, a_hat, b_hat); });
 }
 reef_status reef_hyrax_read(reef_hyrax_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont) {
-    SC_CHECK(ctx);
-    return hvt(ctx->curve)->read(ctx->impl, which, count, out, to_mont);
+    return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->read(impl, which, count, out, to_mont); });
 }
 
 uint64_t reef_merkle_nodes(uint64_t n) {
@@ -647,10 +572,7 @@ uint64_t reef_merkle_nodes(uint64_t n) {
 }
 reef_status reef_merkle_commit(int curve, const reef_poseidon_params *params, const uint32_t *doc, size_t n, int doc_loc, bool is_mont,
                                reef_fe *tree_out, int tree_loc, reef_fe *root_out) {
-    const CurveVTable *v = vt(curve);
-    if (!v) return REEF_ERR_ARG;
-    REEF_TRY(require_gpu());
-    return guarded([&] { return v->merkle_commit(params, doc, n, doc_loc, is_mont, tree_out, tree_loc, root_out, nullptr); });
+    return stateless(curve, [&](const CurveVTable *v) { return v->merkle_commit(params, doc, n, doc_loc, is_mont, tree_out, tree_loc, root_out, nullptr); });
 }
 
 // The same tree built by several devices of this process (include/reef_msm.h 3d).  The bottom level is cut into blocks of S = 2^L nodes, one
@@ -658,16 +580,15 @@ reef_status reef_merkle_commit(int curve, const reef_poseidon_params *params, co
 // host), and the levels above L are hashed from those roots on devices[0].
 reef_status reef_merkle_commit_devices(int curve, const reef_poseidon_params *params, const uint32_t *doc, size_t n, bool is_mont, const int *devices,
                                        size_t ndev, reef_fe *tree_out, reef_fe *root_out, uint32_t *blocks_out) {
-    const CurveVTable *v = vt(curve);
-    if (!v) return REEF_ERR_ARG;
+    if (!table<CurveVTable>(curve)) return REEF_ERR_ARG;
     if (!devices || ndev == 0 || ndev > 64) { set_error("reef_merkle_commit_devices: devices"); return REEF_ERR_ARG; }
     if (!params || (n && !doc) || (!tree_out && !root_out)) { set_error("null argument"); return REEF_ERR_ARG; }
     if (n == 0 || n >= (1ull << 33)) { set_error("document length out of range"); return REEF_ERR_ARG; }
-    REEF_TRY(require_gpu());
+    REEF_TRY(require_gpu());                           // before the devices are counted (stateless() asks again: answered once per process)
     const int visible = reef_device_count();
     for (size_t i = 0; i < ndev; ++i)
         if (devices[i] < 0 || devices[i] >= visible) { set_error("reef_merkle_commit_devices: devices[%zu] = %d, %d visible", i, devices[i], visible); return REEF_ERR_ARG; }
-    return guarded([&]() -> reef_status {
+    return stateless(curve, [&](const CurveVTable *v) -> reef_status {
         // global shape of the tree: sizes and offsets of its levels (merkle_tree.rs:25-80)
         std::vector<uint64_t> size, off;
         {
@@ -736,10 +657,7 @@ reef_status reef_merkle_commit_devices(int curve, const reef_poseidon_params *pa
 
 reef_status reef_derive_generators(int curve, const uint8_t *label, size_t label_len, size_t n, const reef_keygen_params *params, bool is_mont,
                                    reef_affine *out, int out_loc) {
-    const CurveVTable *v = vt(curve);
-    if (!v) return REEF_ERR_ARG;
-    REEF_TRY(require_gpu());
-    return guarded([&] { return v->derive_generators(label, label_len, n, params, is_mont, out, out_loc); });
+    return stateless(curve, [&](const CurveVTable *v) { return v->derive_generators(label, label_len, n, params, is_mont, out, out_loc); });
 }
 void reef_shake256(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_len) { reef::shake256(in, in_len, out, out_len); }
 
@@ -1197,7 +1115,7 @@ static reef_status pippenger_plain(int curve, reef_jacobian *out, const reef_aff
         REEF_TRY(reef_msm_ctx_create(&c, curve, points, npoints, REEF_HOST, nullptr));
         g_tls.ctx_dev[curve] = dev;
     } else {
-        REEF_TRY(vt(curve)->ctx_rekey(c->impl, points, npoints, REEF_HOST));
+        REEF_TRY(reef_msm_ctx_set_bases(c, points, npoints, REEF_HOST));
     }
     return reef_msm(c, scalars, npoints, REEF_HOST, is_mont, out, REEF_HOST);
 }

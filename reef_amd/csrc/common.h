@@ -324,6 +324,62 @@ struct StreamLease {
     }
 };
 
+// ---- what every resident context next to the MSM (sum-check, NIFS with the rows on it, Hyrax) holds of the device -----------------
+// Its entry points run under mu with `device` current (REEF_ON_DEVICE) and inside a DeviceScope.
+struct DeviceCtx {
+    std::mutex mu;
+    int device = 0;
+    hipStream_t stream = nullptr;        // the pool stream of the call in progress, or the one the ctx stayed on (StreamLease)
+    StreamLease lease;
+    hipEvent_t ev = nullptr;             // orders a key ctx's stream after this one, where the row borrows a key (create_device_ctx: with_event)
+};
+// How a call leaves the stream it entered on.  WAIT_AND_IDLE: every call waits for its work before it returns, the ctx holds no stream
+// between calls (NIFS, Hyrax).  RELEASE_IF_IDLE: the ctx lets the stream go if it has nothing left on it, and stays where its work is
+// otherwise (the sum-check calls that end with a wait).  STAY: the rounds of a sum-check step keep their stream (they hand their results
+// over through polled memory, not through a wait for the stream).
+enum class OnExit { WAIT_AND_IDLE, RELEASE_IF_IDLE, STAY };
+struct DeviceScope {
+    DeviceCtx *c;
+    OnExit policy;
+    DeviceScope(DeviceCtx *ctx, OnExit on_exit) : c(ctx), policy(on_exit) {}
+    reef_status enter() { return c->lease.enter(c->device, &c->stream); }
+    ~DeviceScope() {
+        if (policy == OnExit::STAY || !c->lease.counted) return;
+        if (policy == OnExit::WAIT_AND_IDLE) {
+            (void)hipStreamSynchronize(c->stream);
+            c->lease.idle();
+        } else if (hipStreamQuery(c->stream) == hipSuccess) c->lease.idle();
+        else (void)hipGetLastError();                  // hipErrorNotReady is not an error
+    }
+    DeviceScope(const DeviceScope &) = delete;
+    DeviceScope &operator=(const DeviceScope &) = delete;
+};
+// The end of a resident context: its work is waited for, the stream, the event and its place in the pool's count are given back.
+inline void retire_device_ctx(DeviceCtx *c) {
+    if (c->lease.counted) (void)hipStreamSynchronize(c->stream);
+    c->lease.idle();
+    if (c->ev) (void)hipEventDestroy(c->ev);
+    c->ev = nullptr;
+    stream_pool().context_destroyed();
+}
+// The start of one, T a DeviceCtx: `device` is checked and made current, the pool is told, the event is made, then fill(c) allocates and
+// uploads what the row holds.  ONE way out of a failure at any step: free_fn(c), which ends in retire_device_ctx and delete.
+template <class T, class Fill>
+reef_status create_device_ctx(void **impl, int device, const char *name, bool with_event, void (*free_fn)(T *), Fill &&fill) {
+    int ndev = 0;
+    REEF_HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) { set_error("%s: no device %d", name, device); return REEF_ERR_ARG; }
+    REEF_ON_DEVICE(device);
+    T *c = new T();
+    c->device = device;
+    reef_status st = stream_pool().context_created(device);   // counted even when it fails: retire_device_ctx takes it back
+    if (st == REEF_OK && with_event && hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); st = REEF_ERR_HIP; }
+    if (st == REEF_OK) st = fill(c);
+    if (st != REEF_OK) { free_fn(c); return st; }
+    *impl = c;
+    return REEF_OK;
+}
+
 // Per-curve entry points, implemented once per curve in kernels_<curve>.hip via engine.inc.
 // One block of a Merkle tree built by several devices: the subtree over the document symbols [index_base, index_base + n) carried up exactly
 // `levels` levels above its bottom level (a ragged last block keeps hashing (node, 0) where the whole tree would: merkle_tree.rs:82-114), or --

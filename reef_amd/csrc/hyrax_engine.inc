@@ -5,13 +5,8 @@ namespace reef {
 
 enum { HY_NONE = 0, HY_EVAL, HY_IPA, HY_DONE };
 
-template <int C> struct HyraxCtx {
+template <int C> struct HyraxCtx : DeviceCtx {   // ev: orders the key ctx's stream after this one (IpaRun::ipa_cross)
     static constexpr int F = 1 - C;      // scalar field of curve C
-    std::mutex mu;
-    int device = 0;
-    hipStream_t stream = nullptr;        // the pool stream of the call in progress (common.h: StreamLease)
-    StreamLease lease;
-    hipEvent_t ev = nullptr;             // orders the key ctx's stream after this one (IpaRun::ipa_cross)
     DevBuf z, rb;                        // Z (n entries of eb bytes; 32-byte entries as canonical integers); the row blinds (integers)
     DevBuf eqs, part, dot, pts, lint, stage;   // eq(point[..left]) || eq(point[left..]) || 1 (fe_limbs); bound-row partial sums;
                                                // limb sums then eval, lz_blind; eq factors; L as integers (eval_comm); read staging
@@ -27,28 +22,14 @@ template <int C> struct HyraxCtx {
     u32 rounds = 0;
 };
 
-// Every call enqueues on a pool stream and waits for it before it returns (as NifsScope)
-template <int C> struct HyScope {
-    HyraxCtx<C> *c;
-    explicit HyScope(HyraxCtx<C> *ctx) : c(ctx) {}
-    reef_status enter() { return c->lease.enter(c->device, &c->stream); }
-    ~HyScope() {
-        if (!c->lease.counted) return;
-        (void)hipStreamSynchronize(c->stream);
-        c->lease.idle();
-    }
-};
-
+// Every call enqueues on a pool stream and waits for it before it returns (common.h: OnExit::WAIT_AND_IDLE)
 template <int C> static void hyrax_free(HyraxCtx<C> *c) {
     if (!c) return;
-    if (c->lease.counted) (void)hipStreamSynchronize(c->stream);
-    c->lease.idle();
+    retire_device_ctx(c);
     for (DevBuf *b : {&c->z, &c->rb, &c->eqs, &c->part, &c->dot, &c->pts, &c->lint, &c->stage, &c->ip.a, &c->ip.b, &c->ip.partial, &c->ip.out,
                       &c->ip.blinds, &c->ip.htab})
         b->release();
     if (c->comms) v_ctx_destroy<C>(c->comms);
-    if (c->ev) (void)hipEventDestroy(c->ev);
-    stream_pool().context_destroyed();
     delete c;
 }
 
@@ -64,31 +45,6 @@ template <int C> static reef_status hy_expect(HyraxCtx<C> *c, const char *name) 
     if (strcmp(want, name) != 0) { set_error("%s: out of order, the next call is %s", name, want); return REEF_ERR_ARG; }
     return REEF_OK;
 }
-// `count` field elements below the modulus, in the caller's form -> canonical integers
-template <int C> static reef_status hy_import(const reef_fe *x, size_t count, bool is_mont, const char *name, const char *what, fe256 *out) {
-    constexpr int F = HyraxCtx<C>::F;
-    for (size_t i = 0; i < count; ++i) {
-        if (!sp_valid_fe(x + i, F)) { set_error("%s: %s[%zu] is not below the modulus", name, what, i); return REEF_ERR_ARG; }
-        out[i] = fe_to_integer<F>(sp_import<C>(x + i, is_mont));
-    }
-    return REEF_OK;
-}
-// eq over the `ell` coordinates of the point from `first` into dst (internal form, 2^ell entries)
-template <int C> static reef_status hy_eq_table(HyraxCtx<C> *c, u32 first, u32 ell, fe256 *dst) {
-    constexpr int F = HyraxCtx<C>::F;
-    std::vector<fe256> f(2 * ell);
-    for (u32 j = 0; j < ell; ++j) {
-        f[2 * j] = fe_to_table<F>(fe_sub<F, 2>(fe_one<F>(), c->pt[first + j]));
-        f[2 * j + 1] = fe_to_table<F>(c->pt[first + j]);
-    }
-    REEF_HIP_TRY(hipMemcpyAsync(c->pts.p, f.data(), f.size() * sizeof(fe256), hipMemcpyHostToDevice, c->stream));
-    const size_t n = (size_t)1 << ell;
-    hipLaunchKernelGGL(k_sp_eq<F>, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, (const fe256 *)c->pts.p, ell, (u32)n, dst);
-    REEF_HIP_TRY(hipGetLastError());
-    REEF_HIP_TRY(hipStreamSynchronize(c->stream));             // f goes out of scope
-    return REEF_OK;
-}
-
 template <int C>
 static reef_status v_hyrax_create(void **impl, const void *z, size_t n, int elem_bytes, int z_loc, bool is_mont, size_t num_vars, size_t left_vars,
                                   const reef_fe *row_blinds, int device) {
@@ -100,9 +56,6 @@ static reef_status v_hyrax_create(void **impl, const void *z, size_t n, int elem
         return REEF_ERR_ARG;
     }
     if (n > ((size_t)1 << num_vars)) { set_error("reef_hyrax_create: n = %zu exceeds 2^num_vars", n); return REEF_ERR_ARG; }
-    int ndev = 0;
-    REEF_HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) { set_error("reef_hyrax_create: no device %d", device); return REEF_ERR_ARG; }
     const u32 rows = 1u << left_vars, cols = 1u << (num_vars - left_vars);
     u32 chunks = 0, rpc = 0, bchunks = 0, brpc = 0;
     REEF_TRY(mle_plan(rows, cols, elem_bytes, &chunks, &rpc));
@@ -112,57 +65,47 @@ static reef_status v_hyrax_create(void **impl, const void *z, size_t n, int elem
         if (bchunks > 65535) { set_error("reef_hyrax_create: row blinds need left_vars <= 25 (%u row chunks)", bchunks); return REEF_ERR_ARG; }
     }
     std::vector<fe256> blinds(row_blinds ? rows : 0);
-    if (row_blinds) REEF_TRY(hy_import<C>(row_blinds, rows, is_mont, "reef_hyrax_create", "row_blinds", blinds.data()));
-    REEF_ON_DEVICE(device);
-    HyraxCtx<C> *c = new HyraxCtx<C>();
-    c->device = device;
-    c->n = n;
-    c->eb = elem_bytes;
-    c->left = (u32)left_vars;
-    c->right = (u32)(num_vars - left_vars);
-    c->rows = rows;
-    c->cols = cols;
-    c->chunks = chunks;
-    c->rpc = rpc;
-    c->bchunks = bchunks;
-    c->brpc = brpc;
-    c->has_blinds = row_blinds != nullptr;
-    reef_status st = stream_pool().context_created(device);
-    if (st != REEF_OK) { delete c; return st; }
-    const size_t bytes = n * (size_t)elem_bytes;
-    if (st == REEF_OK) st = c->z.ensure(std::max<size_t>(bytes, 1));
-    if (st == REEF_OK && c->has_blinds) st = c->rb.ensure(rows * sizeof(fe256));
-    if (st == REEF_OK) st = c->eqs.ensure(((size_t)rows + cols + 1) * sizeof(fe_limbs));
-    if (st == REEF_OK) st = c->part.ensure(std::max<size_t>((size_t)chunks * cols, bchunks) * sizeof(fe256));   // bchunks: 0 without blinds
-    if (st == REEF_OK) st = c->dot.ensure(20 * sizeof(u64) + 2 * sizeof(fe256));
-    if (st == REEF_OK) st = c->pts.ensure(2 * std::max(c->left, c->right) * sizeof(fe256));
-    if (st == REEF_OK) st = c->lint.ensure(rows * sizeof(fe256));
-    if (st == REEF_OK) st = ipa_alloc(&c->ip, cols);
-    if (st == REEF_OK && hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); st = REEF_ERR_HIP; }
-    if (st == REEF_OK) {
-        HyScope<C> scope(c);
-        st = scope.enter();
-        if (st == REEF_OK && bytes &&
-            hipMemcpyAsync(c->z.p, z, bytes, z_loc == REEF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+    if (row_blinds) REEF_TRY(fe_import_all<F>(row_blinds, rows, is_mont, "reef_hyrax_create", "row_blinds", blinds.data()));
+    return create_device_ctx<HyraxCtx<C>>(impl, device, "reef_hyrax_create", true, hyrax_free<C>, [&](HyraxCtx<C> *c) -> reef_status {
+        c->n = n;
+        c->eb = elem_bytes;
+        c->left = (u32)left_vars;
+        c->right = (u32)(num_vars - left_vars);
+        c->rows = rows;
+        c->cols = cols;
+        c->chunks = chunks;
+        c->rpc = rpc;
+        c->bchunks = bchunks;
+        c->brpc = brpc;
+        c->has_blinds = row_blinds != nullptr;
+        const size_t bytes = n * (size_t)elem_bytes;
+        REEF_TRY(c->z.ensure(std::max<size_t>(bytes, 1)));
+        if (c->has_blinds) REEF_TRY(c->rb.ensure(rows * sizeof(fe256)));
+        REEF_TRY(c->eqs.ensure(((size_t)rows + cols + 1) * sizeof(fe_limbs)));
+        REEF_TRY(c->part.ensure(std::max<size_t>((size_t)chunks * cols, bchunks) * sizeof(fe256)));   // bchunks: 0 without blinds
+        REEF_TRY(c->dot.ensure(20 * sizeof(u64) + 2 * sizeof(fe256)));
+        REEF_TRY(c->pts.ensure(2 * std::max(c->left, c->right) * sizeof(fe256)));
+        REEF_TRY(c->lint.ensure(rows * sizeof(fe256)));
+        REEF_TRY(ipa_alloc(&c->ip, cols));
+        DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
+        REEF_TRY(scope.enter());
+        if (bytes && hipMemcpyAsync(c->z.p, z, bytes, z_loc == REEF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream) != hipSuccess) {
             set_error("reef_hyrax_create: the copy of z failed");
-            st = REEF_ERR_HIP;
+            return REEF_ERR_HIP;
         }
-        if (st == REEF_OK && elem_bytes == 32 && is_mont && n) {    // to canonical integers: every sum then comes out as one
+        if (elem_bytes == 32 && is_mont && n) {    // to canonical integers: every sum then comes out as one
             fe256 *zz = c->z.template as<fe256>();
             hipLaunchKernelGGL(k_fe_import<F>, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, (const fe256 *)zz, (u64)n, 1, zz);
             hipLaunchKernelGGL(k_fe_export<F>, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, (const fe256 *)zz, (u64)n, 0, 0, zz);
-            if (hipGetLastError() != hipSuccess) { set_error("reef_hyrax_create: launch failed"); st = REEF_ERR_HIP; }
+            if (hipGetLastError() != hipSuccess) { set_error("reef_hyrax_create: launch failed"); return REEF_ERR_HIP; }
         }
-        if (st == REEF_OK && c->has_blinds &&
-            hipMemcpyAsync(c->rb.p, blinds.data(), rows * sizeof(fe256), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+        if (c->has_blinds && hipMemcpyAsync(c->rb.p, blinds.data(), rows * sizeof(fe256), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
             set_error("reef_hyrax_create: the copy of the row blinds failed");
-            st = REEF_ERR_HIP;
+            return REEF_ERR_HIP;
         }
-        if (st == REEF_OK && hipStreamSynchronize(c->stream) != hipSuccess) { set_error("reef_hyrax_create: %s", hipGetErrorString(hipGetLastError())); st = REEF_ERR_HIP; }
-    }
-    if (st != REEF_OK) { hyrax_free(c); return st; }
-    *impl = c;
-    return REEF_OK;
+        if (hipStreamSynchronize(c->stream) != hipSuccess) { set_error("reef_hyrax_create: %s", hipGetErrorString(hipGetLastError())); return REEF_ERR_HIP; }
+        return REEF_OK;
+    });
 }
 template <int C> static void v_hyrax_destroy(void *impl) { hyrax_free((HyraxCtx<C> *)impl); }
 
@@ -175,24 +118,15 @@ static reef_status v_hyrax_eval_begin(void *impl, void *key_impl, const reef_fe 
     std::lock_guard<std::mutex> lk(c->mu);
     const u32 nv = c->left + c->right;
     std::vector<fe> pt(nv);
-    for (u32 j = 0; j < nv; ++j) {
-        if (!sp_valid_fe(point + j, F)) { set_error("reef_hyrax_eval_begin: point[%u] is not below the modulus", j); return REEF_ERR_ARG; }
-        pt[j] = sp_import<C>(point + j, is_mont);
-    }
-    int key_dev = 0;
+    REEF_TRY(fe_import_all<F>(point, nv, is_mont, "reef_hyrax_eval_begin", "point", pt.data()));
     size_t key_n = 0;
-    {
-        std::lock_guard<std::mutex> kl(key->mu);
-        key_dev = key->key->device;
-        key_n = key->key->n;
-    }
-    if (key_dev != c->device) { set_error("reef_hyrax_eval_begin: the key lives on device %d, the Hyrax ctx on device %d", key_dev, c->device); return REEF_ERR_ARG; }
+    REEF_TRY(key_matches(key, c->device, "reef_hyrax_eval_begin", "Hyrax", &key_n));
     if (key_n != c->cols) {
         set_error("reef_hyrax_eval_begin: the key holds %zu points, the argument needs exactly 2^(num_vars - left_vars) = %u", key_n, c->cols);
         return REEF_ERR_ARG;
     }
     REEF_ON_DEVICE(c->device);
-    HyScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     c->phase = HY_NONE;                                       // a failure half way leaves nothing to continue
     c->pt = pt;
@@ -227,7 +161,7 @@ static reef_status v_hyrax_eval_begin(void *impl, void *key_impl, const reef_fe 
         hipLaunchKernelGGL((k_mle_eval_final<F, true>), dim3(1), dim3(64), 0, st, dot, 0, res);
     }
     REEF_HIP_TRY(hipGetLastError());
-    REEF_TRY(hy_eq_table(c, c->left, c->right, c->ip.b.template as<fe256>()));   // b = eq(point[left..]); waits
+    REEF_TRY(fe_eq_table<F>(st, c->pts, c->pt.data() + c->left, c->right, c->ip.b.template as<fe256>()));   // b = eq(point[left..]); waits
     fe256 h[2];
     REEF_HIP_TRY(hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, st));
     REEF_HIP_TRY(hipStreamSynchronize(st));
@@ -251,10 +185,10 @@ template <int C> static reef_status v_hyrax_eval_comm(void *impl, const reef_aff
     if (c->phase == HY_NONE) { set_error("reef_hyrax_eval_comm: the point is set by reef_hyrax_eval_begin, the next call"); return REEF_ERR_ARG; }
     REEF_ON_DEVICE(c->device);
     {
-        HyScope<C> scope(c);
+        DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
         REEF_TRY(scope.enter());
         fe256 *l = c->lint.template as<fe256>();
-        REEF_TRY(hy_eq_table(c, 0, c->left, l));                 // L = eq(point[..left]), then canonical integers in place
+        REEF_TRY(fe_eq_table<F>(c->stream, c->pts, c->pt.data(), c->left, l));                 // L = eq(point[..left]), then canonical integers in place
         hipLaunchKernelGGL(k_fe_export<F>, dim3(ceil_div(c->rows, 256)), dim3(256), 0, c->stream, (const fe256 *)l, (u64)c->rows, 0, 0, l);
         REEF_HIP_TRY(hipGetLastError());
         REEF_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -289,11 +223,11 @@ static reef_status v_hyrax_ipa_begin(void *impl, const reef_affine *q, const ree
     if (!q || !L || !R) { set_error("null argument"); return REEF_ERR_ARG; }
     const bool with_h = h && blinds;
     fe256 b2[2] = {};
-    if (with_h) REEF_TRY(hy_import<C>(blinds, 2, is_mont, "reef_hyrax_ipa_begin", "blinds", b2));
+    if (with_h) REEF_TRY(fe_import_all<F>(blinds, 2, is_mont, "reef_hyrax_ipa_begin", "blinds", b2));
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_TRY(hy_expect(c, "reef_hyrax_ipa_begin"));
     REEF_ON_DEVICE(c->device);
-    HyScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     c->phase = HY_NONE;
     IpaRun<C> *ip = &c->ip;
@@ -316,17 +250,18 @@ static reef_status v_hyrax_ipa_begin(void *impl, const reef_affine *q, const ree
 
 template <int C>
 static reef_status v_hyrax_ipa_round(void *impl, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R) {
+    constexpr int F = HyraxCtx<C>::F;
     HyraxCtx<C> *c = (HyraxCtx<C> *)impl;
     fe ri;
-    REEF_TRY(op_challenge<C>(r, is_mont, "reef_hyrax_ipa_round", ri));
+    REEF_TRY(fe_challenge<F>(r, is_mont, "reef_hyrax_ipa_round", ri, true));
     if (!L || !R) { set_error("null argument"); return REEF_ERR_ARG; }
     fe256 b2[2] = {};
-    if (blinds) REEF_TRY(hy_import<C>(blinds, 2, is_mont, "reef_hyrax_ipa_round", "blinds", b2));
+    if (blinds) REEF_TRY(fe_import_all<F>(blinds, 2, is_mont, "reef_hyrax_ipa_round", "blinds", b2));
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_TRY(hy_expect(c, "reef_hyrax_ipa_round"));
     if (blinds && !c->ip.with_h) { set_error("reef_hyrax_ipa_round: blinds given, but reef_hyrax_ipa_begin took no h term"); return REEF_ERR_ARG; }
     REEF_ON_DEVICE(c->device);
-    HyScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     c->phase = HY_NONE;
     if (c->ip.with_h) REEF_TRY(ipa_set_blinds(&c->ip, c->stream, b2));   // NULL: zero blinds this round
@@ -339,12 +274,12 @@ static reef_status v_hyrax_ipa_round(void *impl, const reef_fe *r, const reef_fe
 template <int C> static reef_status v_hyrax_finish(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat) {
     HyraxCtx<C> *c = (HyraxCtx<C> *)impl;
     fe ri;
-    REEF_TRY(op_challenge<C>(r_last, is_mont, "reef_hyrax_finish", ri));
+    REEF_TRY(fe_challenge<HyraxCtx<C>::F>(r_last, is_mont, "reef_hyrax_finish", ri, true));
     if (!a_hat) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_TRY(hy_expect(c, "reef_hyrax_finish"));
     REEF_ON_DEVICE(c->device);
-    HyScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     c->phase = HY_NONE;
     REEF_TRY(ipa_last(&c->ip, c->stream, ri, is_mont, a_hat, b_hat));
@@ -362,7 +297,7 @@ template <int C> static reef_status v_hyrax_read(void *impl, int which, size_t c
     if (count > c->ip.len) { set_error("reef_hyrax_read: %zu entries asked, the vector has %zu", count, c->ip.len); return REEF_ERR_ARG; }
     if (!count) return REEF_OK;
     REEF_ON_DEVICE(c->device);
-    HyScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     return ipa_read(&c->ip, c->stream, c->stage, which, count, out, to_mont);
 }

@@ -11,6 +11,7 @@
 #include "open_kernels.inc"
 #include "hyrax_kernels.inc"
 #include "engine.inc"
+#include "fe_host.inc"
 #include "nifs_engine.inc"
 #include "spartan_engine.inc"
 #include "open_engine.inc"

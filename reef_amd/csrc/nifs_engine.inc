@@ -16,12 +16,8 @@ struct NifsSegs {
     }
 };
 
-template <int C> struct NifsCtx {
+template <int C> struct NifsCtx : DeviceCtx {   // ev: orders the key ctx's stream after the upload of z2 (commit_T) and after the IPA rounds
     static constexpr int F = 1 - C;      // scalar field of curve C
-    std::mutex mu;
-    int device = 0;
-    hipStream_t stream = nullptr;        // the pool stream of the call in progress (common.h: StreamLease)
-    StreamLease lease;
     size_t num_cons = 0, num_vars = 0, num_io = 0, nz = 0;   // nz = num_vars + 1 + num_io
     DevBuf rowptr[3], ent[3], side[3];   // CSR of A, B, C: row pointers, {col, class} per entry, general coefficients by entry
     std::vector<u32> h_rowptr[3];        // host copies: the long-row list is made from them
@@ -33,35 +29,21 @@ template <int C> struct NifsCtx {
     SpartanState<C> *sp = nullptr;       // row N5 workspace, made by the first reef_spartan_begin
     u64 gen = 0;                         // bumped by every call that changes the matrices or the running instance (or commits T)
     DevBuf z1, z2, E, T, stage, counters;
-    hipEvent_t ev = nullptr;             // orders the key ctx's stream after the upload of z2 (commit_T)
     bool running = false, committed = false, have_t = false;
     fe256 k254 = {};
 };
 
-// Every call enqueues on a pool stream and waits for it before it returns: the ctx holds no stream between calls.
-template <int C> struct NifsScope {
-    NifsCtx<C> *c;
-    explicit NifsScope(NifsCtx<C> *ctx) : c(ctx) {}
-    reef_status enter() { return c->lease.enter(c->device, &c->stream); }
-    ~NifsScope() {
-        if (!c->lease.counted) return;
-        (void)hipStreamSynchronize(c->stream);
-        c->lease.idle();
-    }
-};
-
+// Every call enqueues on a pool stream and waits for it before it returns: the ctx holds no stream between calls
+// (common.h: OnExit::WAIT_AND_IDLE).
 template <int C> static void nifs_free(NifsCtx<C> *c) {
     if (!c) return;
-    if (c->lease.counted) (void)hipStreamSynchronize(c->stream);
-    c->lease.idle();
+    retire_device_ctx(c);
     for (int k = 0; k < 3; ++k)
         for (DevBuf *b : {&c->rowptr[k], &c->ent[k], &c->side[k], &c->colptr[k], &c->cent[k], &c->cside[k]}) b->release();
     c->rows.release();
     c->cols.release();
     spartan_release<C>(c->sp);
     for (DevBuf *b : {&c->z1, &c->z2, &c->E, &c->T, &c->stage, &c->counters}) b->release();
-    if (c->ev) (void)hipEventDestroy(c->ev);
-    stream_pool().context_destroyed();
     delete c;
 }
 
@@ -70,30 +52,20 @@ template <int C> static reef_status v_nifs_create(void **impl, size_t num_cons, 
         set_error("reef_nifs_create: need 0 < num_cons < 2^31 and num_vars + 1 + num_io < 2^31");
         return REEF_ERR_ARG;
     }
-    int ndev = 0;
-    REEF_HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) { set_error("reef_nifs_create: no device %d", device); return REEF_ERR_ARG; }
-    REEF_ON_DEVICE(device);
-    NifsCtx<C> *c = new NifsCtx<C>();
-    c->device = device;
-    c->num_cons = num_cons;
-    c->num_vars = num_vars;
-    c->num_io = num_io;
-    c->nz = num_vars + 1 + num_io;
-    fe x254 = fe_zero();
-    x254.l[8] = 1u << 22;                // 2^(8 * 29 + 22)
-    REEF_SET_BOUND(x254, 1.0);
-    constexpr int F = NifsCtx<C>::F;
-    c->k254 = fe_to_table<F>(fe_mul<F>(x254, fe_const<F>(FC<F>::C_R2, 1.0)));     // 2^254 R'
-    reef_status st = stream_pool().context_created(device);
-    if (st != REEF_OK) { delete c; return st; }
-    for (DevBuf *b : {&c->z1, &c->z2}) if (st == REEF_OK) st = b->ensure(c->nz * sizeof(fe256));
-    for (DevBuf *b : {&c->E, &c->T}) if (st == REEF_OK) st = b->ensure(num_cons * sizeof(fe256));
-    if (st == REEF_OK) st = c->counters.ensure(2 * sizeof(u32));
-    if (st == REEF_OK && hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); st = REEF_ERR_HIP; }
-    if (st != REEF_OK) { nifs_free(c); return st; }
-    *impl = c;
-    return REEF_OK;
+    return create_device_ctx<NifsCtx<C>>(impl, device, "reef_nifs_create", true, nifs_free<C>, [&](NifsCtx<C> *c) -> reef_status {
+        c->num_cons = num_cons;
+        c->num_vars = num_vars;
+        c->num_io = num_io;
+        c->nz = num_vars + 1 + num_io;
+        fe x254 = fe_zero();
+        x254.l[8] = 1u << 22;                // 2^(8 * 29 + 22)
+        REEF_SET_BOUND(x254, 1.0);
+        constexpr int F = NifsCtx<C>::F;
+        c->k254 = fe_to_table<F>(fe_mul<F>(x254, fe_const<F>(FC<F>::C_R2, 1.0)));     // 2^254 R'
+        for (DevBuf *b : {&c->z1, &c->z2}) REEF_TRY(b->ensure(c->nz * sizeof(fe256)));
+        for (DevBuf *b : {&c->E, &c->T}) REEF_TRY(b->ensure(num_cons * sizeof(fe256)));
+        return c->counters.ensure(2 * sizeof(u32));
+    });
 }
 template <int C> static void v_nifs_destroy(void *impl) { nifs_free((NifsCtx<C> *)impl); }
 
@@ -136,7 +108,7 @@ static reef_status v_nifs_set_matrix(void *impl, int which, const uint32_t *row,
     }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     c->has[which] = false;
     c->rows.prepared = c->cols.prepared = false;
@@ -271,7 +243,7 @@ static reef_status v_nifs_set_running(void *impl, const reef_fe *W, const reef_f
     if ((c->num_vars && !W) || !u || (c->num_io && !X)) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     c->running = c->committed = false;
     ++c->gen;
@@ -298,17 +270,11 @@ static reef_status v_nifs_commit_t(void *impl, void *key_impl, const reef_fe *W2
     if (!key || !comm_t || (c->num_vars && !W2) || (c->num_io && !X2)) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->running) { set_error("reef_nifs_commit_T: no running instance (reef_nifs_set_running first)"); return REEF_ERR_ARG; }
-    int key_dev = 0;
     size_t key_n = 0;
-    {
-        std::lock_guard<std::mutex> kl(key->mu);
-        key_dev = key->key->device;
-        key_n = key->key->n;
-    }
-    if (key_dev != c->device) { set_error("reef_nifs_commit_T: the key lives on device %d, the NIFS ctx on device %d", key_dev, c->device); return REEF_ERR_ARG; }
+    REEF_TRY(key_matches(key, c->device, "reef_nifs_commit_T", "NIFS", &key_n));
     if (key_n < c->num_cons) { set_error("reef_nifs_commit_T: the key holds %zu points, T has %zu entries", key_n, c->num_cons); return REEF_ERR_ARG; }
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     REEF_TRY(nifs_prepare(c));
     c->committed = false;
@@ -338,7 +304,7 @@ template <int C> static reef_status v_nifs_fold(void *impl, const reef_fe *r, bo
     const fe256 r_int = fe_to_table<F>(ri);
     const fe256 r_sq = fe_to_table<F>(fe_mul<F>(ri, fe_const<F>(FC<F>::C_R2, 1.0)));    // r R'^2: times an integer T gives r T R'
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     ++c->gen;
     hipLaunchKernelGGL(k_nifs_axpy<F>, dim3(ceil_div(c->nz, 256)), dim3(256), 0, c->stream, c->z1.template as<fe256>(), (const fe256 *)c->z2.p, (u32)c->nz, r_int);
@@ -369,7 +335,7 @@ template <int C> static reef_status v_nifs_read(void *impl, int which, size_t co
     if (which == 2 ? !c->have_t : !c->running) { set_error("reef_nifs_read: nothing to read yet"); return REEF_ERR_ARG; }
     if (!count) return REEF_OK;
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     REEF_TRY(c->stage.ensure(count * sizeof(fe256)));
     hipLaunchKernelGGL(k_fe_export<NifsCtx<C>::F>, dim3(ceil_div(count, 256)), dim3(256), 0, c->stream, src, (u64)count, (int)(which == 2), (int)to_mont,
@@ -385,7 +351,7 @@ template <int C> static reef_status v_nifs_check(void *impl, uint64_t *violation
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->running) { set_error("reef_nifs_check_relaxed: no running instance (reef_nifs_set_running first)"); return REEF_ERR_ARG; }
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     REEF_TRY(nifs_prepare(c));
     const u32 init[2] = {0u, 0xffffffffu};

@@ -147,12 +147,6 @@ template <int C> static reef_status op_expect(NifsCtx<C> *c, const char *name) {
     }
     return sp_expect(c, name);
 }
-// a non-zero challenge below the modulus (the IPA folds with r^-1)
-template <int C> static reef_status op_challenge(const reef_fe *r, bool is_mont, const char *name, fe &out) {
-    REEF_TRY(sp_challenge<C>(r, is_mont, name, out));
-    if (fe_is_literal_zero(fe_canon<NifsCtx<C>::F>(out))) { set_error("%s: r is zero (it has no inverse)", name); return REEF_ERR_ARG; }
-    return REEF_OK;
-}
 
 template <int C> static reef_status v_open_begin(void *impl, void *key_impl, bool is_mont, reef_fe *cross_term) {
     constexpr int F = NifsCtx<C>::F;
@@ -163,20 +157,14 @@ template <int C> static reef_status v_open_begin(void *impl, void *key_impl, boo
     REEF_TRY(op_expect(c, "reef_spartan_open_begin"));
     SpartanState<C> *s = c->sp;
     const size_t n = std::max(s->ncp, s->nvp);
-    int key_dev = 0;
     size_t key_n = 0;
-    {
-        std::lock_guard<std::mutex> kl(key->mu);
-        key_dev = key->key->device;
-        key_n = key->key->n;
-    }
-    if (key_dev != c->device) { set_error("reef_spartan_open_begin: the key lives on device %d, the NIFS ctx on device %d", key_dev, c->device); return REEF_ERR_ARG; }
+    REEF_TRY(key_matches(key, c->device, "reef_spartan_open_begin", "NIFS", &key_n));
     if (key_n != n) {
         set_error("reef_spartan_open_begin: the key holds %zu points, the opening needs exactly n = max(num_cons_pad, num_vars_pad) = %zu", key_n, n);
         return REEF_ERR_ARG;
     }
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     s->phase = SP_NONE;                                       // a failure half way leaves nothing to continue
     REEF_TRY(s->e1.ensure(s->ncp * sizeof(fe256)));
@@ -185,8 +173,8 @@ template <int C> static reef_status v_open_begin(void *impl, void *key_impl, boo
     IpaRun<C> *ip = s->ip;
     REEF_TRY(ipa_alloc(ip, n));
     const fe256 *e1 = s->e1.template as<fe256>(), *e2 = s->e2.template as<fe256>();
-    REEF_TRY(sp_eq_table(c, s->rx.data(), s->ell_x, s->e1.template as<fe256>()));
-    REEF_TRY(sp_eq_table(c, s->ry.data() + 1, s->ell_y - 1, s->e2.template as<fe256>()));
+    REEF_TRY(fe_eq_table<F>(c->stream, s->pts, s->rx.data(), s->ell_x, s->e1.template as<fe256>()));
+    REEF_TRY(fe_eq_table<F>(c->stream, s->pts, s->ry.data() + 1, s->ell_y - 1, s->e2.template as<fe256>()));
     const u32 nE = (u32)std::min(c->num_cons, s->nvp), nW = (u32)std::min(c->num_vars, s->ncp);
     const u32 grid = sp_grid(std::max(nE, nW));
     hipLaunchKernelGGL(k_op_cross<F>, dim3(grid), dim3(SP_THREADS), 0, c->stream, (const fe256 *)c->E.p, e2, nE, (const fe256 *)c->z1.p, e1, nW,
@@ -205,13 +193,13 @@ template <int C> static reef_status v_open_fold(void *impl, const reef_fe *r, bo
     constexpr int F = NifsCtx<C>::F;
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     fe ri;
-    REEF_TRY(sp_challenge<C>(r, is_mont, "reef_spartan_open_fold", ri));
+    REEF_TRY(fe_challenge<F>(r, is_mont, "reef_spartan_open_fold", ri));
     if (!c_out) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_TRY(op_expect(c, "reef_spartan_open_fold"));
     SpartanState<C> *s = c->sp;
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     s->phase = SP_NONE;
     OpFold p;
@@ -247,7 +235,7 @@ template <int C> static reef_status v_open_ipa_begin(void *impl, const reef_affi
     REEF_TRY(op_expect(c, "reef_spartan_open_ipa_begin"));
     SpartanState<C> *s = c->sp;
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     s->phase = SP_NONE;
     IpaRun<C> *ip = s->ip;
@@ -263,13 +251,13 @@ template <int C> static reef_status v_open_ipa_begin(void *impl, const reef_affi
 template <int C> static reef_status v_open_ipa_round(void *impl, const reef_fe *r, bool is_mont, reef_jacobian *L, reef_jacobian *R) {
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     fe ri;
-    REEF_TRY(op_challenge<C>(r, is_mont, "reef_spartan_open_ipa_round", ri));
+    REEF_TRY(fe_challenge<NifsCtx<C>::F>(r, is_mont, "reef_spartan_open_ipa_round", ri, true));
     if (!L || !R) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_TRY(op_expect(c, "reef_spartan_open_ipa_round"));
     SpartanState<C> *s = c->sp;
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     s->phase = SP_NONE;
     REEF_TRY(ipa_round(s->ip, c->stream, c->ev, ri, L, R));
@@ -281,13 +269,13 @@ template <int C> static reef_status v_open_ipa_round(void *impl, const reef_fe *
 template <int C> static reef_status v_open_finish(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *a_hat) {
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     fe ri;
-    REEF_TRY(op_challenge<C>(r_last, is_mont, "reef_spartan_open_finish", ri));
+    REEF_TRY(fe_challenge<NifsCtx<C>::F>(r_last, is_mont, "reef_spartan_open_finish", ri, true));
     if (!a_hat) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_TRY(op_expect(c, "reef_spartan_open_finish"));
     SpartanState<C> *s = c->sp;
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     s->phase = SP_NONE;
     REEF_TRY(ipa_last(s->ip, c->stream, ri, is_mont, a_hat, nullptr));
@@ -313,7 +301,7 @@ template <int C> static reef_status v_open_read(void *impl, int which, size_t co
     if (count > s->ip->len) { set_error("reef_spartan_open_read: %zu entries asked, the vector has %zu", count, s->ip->len); return REEF_ERR_ARG; }
     if (!count) return REEF_OK;
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     return ipa_read(s->ip, c->stream, c->stage, which, count, out, to_mont);
 }

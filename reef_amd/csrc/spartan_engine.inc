@@ -59,39 +59,6 @@ template <int C> static reef_status sp_expect(NifsCtx<C> *c, const char *name) {
     return REEF_OK;
 }
 
-template <int C> static fe sp_import(const reef_fe *x, bool is_mont) {
-    constexpr int F = NifsCtx<C>::F;
-    fe256 p;
-    memcpy(&p, x, sizeof p);
-    return fe_canon<F>(fe_from_caller<F>(p, is_mont));
-}
-static bool sp_valid_fe(const reef_fe *x, int field) {          // canonical: below the modulus
-    fe256 p;
-    memcpy(&p, x, sizeof p);
-    const u32 *m = field == 0 ? FC<0>::MOD : FC<1>::MOD;
-    fe v = fe_unpack(p);
-    for (int i = 8; i >= 0; --i)
-        if (v.l[i] != m[i]) return v.l[i] < m[i];
-    return false;
-}
-
-// eq(p) over 2^ell entries into dst (internal form)
-template <int C> static reef_status sp_eq_table(NifsCtx<C> *c, const fe *p, u32 ell, fe256 *dst) {
-    constexpr int F = NifsCtx<C>::F;
-    SpartanState<C> *s = c->sp;
-    std::vector<fe256> f(2 * std::max<u32>(ell, 1));
-    for (u32 j = 0; j < ell; ++j) {
-        f[2 * j] = fe_to_table<F>(fe_sub<F, 2>(fe_one<F>(), p[j]));
-        f[2 * j + 1] = fe_to_table<F>(p[j]);
-    }
-    REEF_TRY(s->pts.ensure(f.size() * sizeof(fe256)));
-    REEF_HIP_TRY(hipMemcpyAsync(s->pts.p, f.data(), f.size() * sizeof(fe256), hipMemcpyHostToDevice, c->stream));
-    const size_t n = (size_t)1 << ell;
-    hipLaunchKernelGGL(k_sp_eq<F>, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, (const fe256 *)s->pts.p, ell, (u32)n, dst);
-    REEF_HIP_TRY(hipGetLastError());
-    REEF_HIP_TRY(hipStreamSynchronize(c->stream));             // f goes out of scope
-    return REEF_OK;
-}
 static u32 sp_grid(size_t n) { return (u32)std::max<size_t>(1, std::min<size_t>(SP_BLOCKS, ceil_div(n, SP_THREADS))); }
 
 // one round (bind with r when bind, then the sums of the next round: nv values) -> evals (HOST) in the caller's form
@@ -142,15 +109,15 @@ static reef_status v_spartan_begin(void *impl, size_t num_cons_pad, size_t num_v
         return REEF_ERR_ARG;
     }
     const u32 ell_x = sp_log2(num_cons_pad);
-    for (u32 j = 0; j < ell_x; ++j)
-        if (!sp_valid_fe(tau + j, F)) { set_error("reef_spartan_begin: tau[%u] is not below the modulus", j); return REEF_ERR_ARG; }
+    std::vector<fe> t(ell_x);
+    REEF_TRY(fe_import_all<F>(tau, ell_x, is_mont, "reef_spartan_begin", "tau", t.data()));
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->running || !c->has[0] || !c->has[1] || !c->has[2]) {
         set_error("reef_spartan_begin: set the matrices A, B, C and the running instance first (reef_nifs_set_matrix, reef_nifs_set_running)");
         return REEF_ERR_ARG;
     }
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     if (!c->sp) c->sp = new SpartanState<C>();
     SpartanState<C> *s = c->sp;
@@ -169,9 +136,7 @@ static reef_status v_spartan_begin(void *impl, size_t num_cons_pad, size_t num_v
     a.out[2] = tabs[4];
     a.out[3] = tabs[3];
     REEF_TRY((nifs_line_pass<C, NIFS_MODE_SPARTAN>(a, c->rows, c->stream)));
-    std::vector<fe> t(ell_x);
-    for (u32 j = 0; j < ell_x; ++j) t[j] = sp_import<C>(tau + j, is_mont);
-    REEF_TRY(sp_eq_table(c, t.data(), ell_x, tabs[0]));
+    REEF_TRY(fe_eq_table<F>(c->stream, s->pts, t.data(), ell_x, tabs[0]));
     s->ncp = num_cons_pad;
     s->nvp = num_vars_pad;
     s->ell_x = ell_x;
@@ -198,24 +163,16 @@ template <int C> static fe256 *const *sp_inner_tabs(SpartanState<C> *s, fe256 *(
     t[2] = t[3] = nullptr;
     return t;
 }
-// the challenge of a call: canonical when given as an integer
-template <int C> static reef_status sp_challenge(const reef_fe *r, bool is_mont, const char *name, fe &out) {
-    if (!r) { set_error("null argument"); return REEF_ERR_ARG; }
-    if (!sp_valid_fe(r, NifsCtx<C>::F)) { set_error("%s: r is not below the modulus", name); return REEF_ERR_ARG; }
-    out = sp_import<C>(r, is_mont);
-    return REEF_OK;
-}
-
 template <int C> static reef_status v_spartan_outer_round(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals) {
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     fe ri;
-    REEF_TRY(sp_challenge<C>(r, is_mont, "reef_spartan_outer_round", ri));
+    REEF_TRY(fe_challenge<NifsCtx<C>::F>(r, is_mont, "reef_spartan_outer_round", ri));
     if (!evals) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_TRY(sp_expect(c, "reef_spartan_outer_round"));
     SpartanState<C> *s = c->sp;
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     fe256 *t[4];
     const u32 h = (u32)(s->ncp >> (s->rounds + 2));          // pairs of the next round
@@ -231,13 +188,13 @@ template <int C> static reef_status v_spartan_outer_claims(void *impl, const ree
     constexpr int F = NifsCtx<C>::F;
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     fe ri;
-    REEF_TRY(sp_challenge<C>(r_last, is_mont, "reef_spartan_outer_claims", ri));
+    REEF_TRY(fe_challenge<NifsCtx<C>::F>(r_last, is_mont, "reef_spartan_outer_claims", ri));
     if (!claims) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_TRY(sp_expect(c, "reef_spartan_outer_claims"));
     SpartanState<C> *s = c->sp;
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     s->phase = SP_NONE;
     const int form = is_mont ? SP_FORM_MONT : SP_FORM_INTEGER;
@@ -250,7 +207,7 @@ template <int C> static reef_status v_spartan_outer_claims(void *impl, const ree
     hipLaunchKernelGGL(k_sp_bind_last<F>, dim3(1), dim3(64), 0, c->stream, a, 2u, form, s->out.template as<fe256>());
     REEF_HIP_TRY(hipGetLastError());
     s->rx.push_back(ri);
-    REEF_TRY(sp_eq_table(c, s->rx.data(), s->ell_x, s->eq.template as<fe256>()));   // eq(r_x) over the bound eq(tau): not needed any more
+    REEF_TRY(fe_eq_table<F>(c->stream, s->pts, s->rx.data(), s->ell_x, s->eq.template as<fe256>()));   // eq(r_x) over the bound eq(tau): not needed any more
     REEF_TRY(sp_dots(c, s->eq.template as<fe256>(), s->cz.template as<fe256>(), c->E.template as<fe256>(), c->num_cons, form, 2));
     REEF_HIP_TRY(hipMemcpyAsync(claims, s->out.p, 4 * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -263,13 +220,13 @@ template <int C> static reef_status v_spartan_inner_begin(void *impl, const reef
     constexpr int F = NifsCtx<C>::F;
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     fe ri;
-    REEF_TRY(sp_challenge<C>(r, is_mont, "reef_spartan_inner_begin", ri));
+    REEF_TRY(fe_challenge<NifsCtx<C>::F>(r, is_mont, "reef_spartan_inner_begin", ri));
     if (!evals) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_TRY(sp_expect(c, "reef_spartan_inner_begin"));
     SpartanState<C> *s = c->sp;
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     s->phase = SP_NONE;
     REEF_TRY(nifs_segments(c, c->h_colptr, c->nz, c->cols));
@@ -308,13 +265,13 @@ template <int C> static reef_status v_spartan_inner_begin(void *impl, const reef
 template <int C> static reef_status v_spartan_inner_round(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals) {
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     fe ri;
-    REEF_TRY(sp_challenge<C>(r, is_mont, "reef_spartan_inner_round", ri));
+    REEF_TRY(fe_challenge<NifsCtx<C>::F>(r, is_mont, "reef_spartan_inner_round", ri));
     if (!evals) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_TRY(sp_expect(c, "reef_spartan_inner_round"));
     SpartanState<C> *s = c->sp;
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     s->phase = SP_NONE;
     fe256 *t[4];
@@ -330,13 +287,13 @@ template <int C> static reef_status v_spartan_inner_claims(void *impl, const ree
     constexpr int F = NifsCtx<C>::F;
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     fe ri;
-    REEF_TRY(sp_challenge<C>(r_last, is_mont, "reef_spartan_inner_claims", ri));
+    REEF_TRY(fe_challenge<NifsCtx<C>::F>(r_last, is_mont, "reef_spartan_inner_claims", ri));
     if (!claims) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_TRY(sp_expect(c, "reef_spartan_inner_claims"));
     SpartanState<C> *s = c->sp;
     REEF_ON_DEVICE(c->device);
-    NifsScope<C> scope(c);
+    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(scope.enter());
     s->phase = SP_NONE;
     const int form = is_mont ? SP_FORM_MONT : SP_FORM_INTEGER;
@@ -351,7 +308,7 @@ template <int C> static reef_status v_spartan_inner_claims(void *impl, const ree
     s->ry.push_back(ri);
     // eval_W = W~(r_y[1..]) over num_vars_pad entries: eq(r_y[1..]) in the eq table (ncp >= 2 entries, grown to nvp if need be)
     REEF_TRY(s->eq.ensure(s->nvp * sizeof(fe256)));
-    REEF_TRY(sp_eq_table(c, s->ry.data() + 1, s->ell_y - 1, s->eq.template as<fe256>()));
+    REEF_TRY(fe_eq_table<F>(c->stream, s->pts, s->ry.data() + 1, s->ell_y - 1, s->eq.template as<fe256>()));
     if (c->num_vars) REEF_TRY(sp_dots(c, s->eq.template as<fe256>(), c->z1.template as<fe256>(), nullptr, c->num_vars, form, 2));
     else REEF_HIP_TRY(hipMemsetAsync(s->out.template as<fe256>() + 2, 0, sizeof(fe256), c->stream));
     REEF_HIP_TRY(hipMemcpyAsync(claims, s->out.p, 3 * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));

@@ -1,14 +1,10 @@
 // Host side of the sum-check vector kernels (row N2); included after engine.inc.
 namespace reef {
 
-template <int C> struct ScCtx {
+template <int C> struct ScCtx : DeviceCtx {   // device: where the tables live; no event
     static constexpr int F = 1 - C;      // scalar field of curve C
-    hipStream_t stream = nullptr;        // the pool stream the ctx is on (common.h: StreamLease)
-    StreamLease lease;
-    std::mutex mu;
     size_t len = 0;                      // 2^ell entries per table
     size_t valid_t = 0, valid_e = 0;     // live entries of T / EQ: len after a set / reset / gen_eq, pow after a fold (a fold writes [0, pow) only)
-    int device = 0;                      // the device the tables live on (every entry point runs under a DeviceGuard)
     DevBuf r1acc;                        // R1_GROUPS x R1_SLOTS accumulators of the rank-one / structured sums kernels: zero between rounds (k_sc_r1_final)
     DevBuf T, T0, E, partial, out3, stage, fac, qs, misc;   // T0: pristine copy of T (a fold consumes T)
     u32 nblocks = 0;
@@ -95,64 +91,46 @@ template <int C> static u32 sc_dense_blocks(const ScCtx<C> *c, size_t work) {
 
 template <int C> static void sc_free(ScCtx<C> *c) {
     if (!c) return;
-    if (c->lease.counted) (void)hipStreamSynchronize(c->stream);
-    c->lease.idle();
+    retire_device_ctx(c);
     for (DevBuf *b : {&c->T, &c->T0, &c->E, &c->partial, &c->out3, &c->stage, &c->fac, &c->qs, &c->misc, &c->r1rows, &c->r1mq, &c->r1mw, &c->gacc, &c->st_s32, &c->st_flags, &c->st_lists, &c->st_k, &c->st_sumfl, &c->r1acc}) b->release();
     if (c->pinned3) (void)hipHostFree(c->pinned3);
     if (c->pin_in) (void)hipHostFree(c->pin_in);
     for (auto &e : c->pin_ev) if (e) (void)hipEventDestroy(e);
-    stream_pool().context_destroyed();
     delete c;
 }
 
 // A sum-check ctx takes a pool stream when a call finds it idle and stays on it through the rounds of a step (they hand their
 // results over through polled memory, not through a wait for the stream); the calls that end with a wait for the stream --
-// set_table, gen_eq_table, read, sync -- let it go again if the stream has nothing left.
-template <int C> struct ScScope {
-    ScCtx<C> *c;
-    bool release;
-    ScScope(ScCtx<C> *ctx, bool release_when_idle) : c(ctx), release(release_when_idle) {}
-    reef_status enter() { return c->lease.enter(c->device, &c->stream); }
-    ~ScScope() {
-        if (!release || !c->lease.counted) return;
-        if (hipStreamQuery(c->stream) == hipSuccess) c->lease.idle();
-        else (void)hipGetLastError();
-    }
-};
+// set_table, gen_eq_table, read, sync -- let it go again if the stream has nothing left (common.h: OnExit::RELEASE_IF_IDLE / STAY).
 
 template <int C> static reef_status v_sc_create(void **impl, size_t len) {
     if (!impl || len == 0 || (len & (len - 1)) || len > (1ull << 28)) { set_error("table length must be a power of two <= 2^28"); return REEF_ERR_ARG; }
-    ScCtx<C> *c = new ScCtx<C>();
-    sc_read_switches<C>(c);
-    c->len = len;
-    c->valid_t = c->valid_e = len;
-    if (hipGetDevice(&c->device) != hipSuccess) { set_error("hipGetDevice failed"); delete c; return REEF_ERR_HIP; }
-    reef_status st = stream_pool().context_created(c->device);
-    if (st == REEF_OK) st = c->lease.enter(c->device, &c->stream);
-    if (st != REEF_OK) { stream_pool().context_destroyed(); delete c; return st; }
-    hipError_t e;
-    size_t cap = 2048;                   // REEF_SC_BLOCKS: the most blocks a round is spread over (A/B runs)
-    if (const char *e = exp_env("REEF_SC_BLOCKS")) if (*e) cap = (size_t)std::min<long long>(8192, std::max<long long>(1, atoll(e)));
-    c->nblocks = (u32)std::min<size_t>(cap, std::max<size_t>(1, len / 2 / 256));
-    if ((st = c->T.ensure(len * sizeof(fe256))) != REEF_OK || (st = c->T0.ensure(len * sizeof(fe256))) != REEF_OK ||
-        (st = c->E.ensure(len * sizeof(fe256))) != REEF_OK ||
-        (st = c->partial.ensure((size_t)c->nblocks * 27 * sizeof(u64))) != REEF_OK || (st = c->out3.ensure(3 * sizeof(fe256))) != REEF_OK) {
-        sc_free(c);
-        return st;
-    }
-    e = hipHostMalloc((void **)&c->pinned3, 4 * sizeof(fe256), hipHostMallocDefault);
-    if (e != hipSuccess) { set_error("hipHostMalloc: %s", hipGetErrorString(e)); sc_free(c); return REEF_ERR_HIP; }
-    memset(c->pinned3, 0, 4 * sizeof(fe256));
-    if ((st = c->gacc.ensure(28 * sizeof(u64))) != REEF_OK || (st = c->r1acc.ensure(R1_GROUPS * R1_SLOTS * sizeof(u64))) != REEF_OK) { sc_free(c); return st; }
-    if (hipMemsetAsync(c->r1acc.p, 0, R1_GROUPS * R1_SLOTS * sizeof(u64), c->stream) != hipSuccess) { set_error("hipMemset failed"); sc_free(c); return REEF_ERR_HIP; }
-    if (hipMemsetAsync(c->gacc.p, 0, 28 * sizeof(u64), c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-        set_error("hipMemset failed");
-        sc_free(c);
-        return REEF_ERR_HIP;
-    }
-    c->lease.idle();                     // waited for above: the ctx takes a stream again when its first call comes
-    *impl = c;
-    return REEF_OK;
+    int device = 0;                      // the tables live on the caller's current device
+    if (hipGetDevice(&device) != hipSuccess) { set_error("hipGetDevice failed"); return REEF_ERR_HIP; }
+    return create_device_ctx<ScCtx<C>>(impl, device, "reef_sc_create", false, sc_free<C>, [&](ScCtx<C> *c) -> reef_status {
+        sc_read_switches<C>(c);
+        c->len = len;
+        c->valid_t = c->valid_e = len;
+        REEF_TRY(c->lease.enter(c->device, &c->stream));
+        size_t cap = 2048;                   // REEF_SC_BLOCKS: the most blocks a round is spread over (A/B runs)
+        if (const char *e = exp_env("REEF_SC_BLOCKS")) if (*e) cap = (size_t)std::min<long long>(8192, std::max<long long>(1, atoll(e)));
+        c->nblocks = (u32)std::min<size_t>(cap, std::max<size_t>(1, len / 2 / 256));
+        for (DevBuf *b : {&c->T, &c->T0, &c->E}) REEF_TRY(b->ensure(len * sizeof(fe256)));
+        REEF_TRY(c->partial.ensure((size_t)c->nblocks * 27 * sizeof(u64)));
+        REEF_TRY(c->out3.ensure(3 * sizeof(fe256)));
+        const hipError_t e = hipHostMalloc((void **)&c->pinned3, 4 * sizeof(fe256), hipHostMallocDefault);
+        if (e != hipSuccess) { set_error("hipHostMalloc: %s", hipGetErrorString(e)); return REEF_ERR_HIP; }
+        memset(c->pinned3, 0, 4 * sizeof(fe256));
+        REEF_TRY(c->gacc.ensure(28 * sizeof(u64)));
+        REEF_TRY(c->r1acc.ensure(R1_GROUPS * R1_SLOTS * sizeof(u64)));
+        if (hipMemsetAsync(c->r1acc.p, 0, R1_GROUPS * R1_SLOTS * sizeof(u64), c->stream) != hipSuccess ||
+            hipMemsetAsync(c->gacc.p, 0, 28 * sizeof(u64), c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+            set_error("hipMemset failed");
+            return REEF_ERR_HIP;
+        }
+        c->lease.idle();                     // waited for above: the ctx takes a stream again when its first call comes
+        return REEF_OK;
+    });
 }
 template <int C> static void v_sc_destroy(void *impl) { sc_free((ScCtx<C> *)impl); }
 
@@ -428,7 +406,7 @@ template <int C> static reef_status v_sc_set(void *impl, int which, const reef_f
     if (!c || (n && !vals) || n > c->len || which < 0 || which > 1) { set_error("bad argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_ON_DEVICE(c->device);
-    ScScope<C> scope(c, true);
+    DeviceScope scope(c, OnExit::RELEASE_IF_IDLE);
     REEF_TRY(scope.enter());
     if (which == 1) REEF_TRY(sc_defer_flush<C>(c));
     else c->defer_on = false;               // T is replaced
@@ -460,7 +438,7 @@ template <int C> static reef_status v_sc_read(void *impl, int which, size_t coun
     if (count == 0) return REEF_OK;
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_ON_DEVICE(c->device);
-    ScScope<C> scope(c, true);
+    DeviceScope scope(c, OnExit::RELEASE_IF_IDLE);
     REEF_TRY(scope.enter());
     REEF_TRY(sc_defer_flush<C>(c));        // rows whose first fold was deferred are written out: this is not their second fold
     const size_t live = which == 0 ? c->valid_t : c->valid_e;
@@ -485,7 +463,7 @@ template <int C> static reef_status v_sc_coeffs(void *impl, size_t pow, reef_fe 
     if (!c || !out3_host || pow == 0 || 2 * pow > c->len) { set_error("bad argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_ON_DEVICE(c->device);
-    ScScope<C> scope(c, false);
+    DeviceScope scope(c, OnExit::STAY);
     REEF_TRY(scope.enter());
     REEF_TRY(sc_defer_flush<C>(c));        // rows whose first fold was deferred are written out: this is not their second fold
     if (2 * pow > std::min(c->valid_t, c->valid_e)) { set_error("round with pow = %zu needs %zu live entries per table; T has %zu, EQ has %zu", pow, 2 * pow, c->valid_t, c->valid_e); return REEF_ERR_ARG; }
@@ -521,7 +499,7 @@ template <int C> static reef_status v_sc_fold(void *impl, size_t pow, const reef
     if (!c || !r || pow == 0 || 2 * pow > c->len) { set_error("bad argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_ON_DEVICE(c->device);
-    ScScope<C> scope(c, false);
+    DeviceScope scope(c, OnExit::STAY);
     REEF_TRY(scope.enter());
     REEF_TRY(sc_defer_flush<C>(c));        // rows whose first fold was deferred are written out: this is not their second fold
     c->r1_prev_pow = 0;                  // the tables change: no coefficients on the device describe them any more
@@ -555,7 +533,7 @@ template <int C> static reef_status v_sc_fold_coeffs(void *impl, size_t pow, con
     if (!c || !r || !out3_host || pow < 2 || 2 * pow > c->len) { set_error("bad argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_ON_DEVICE(c->device);
-    ScScope<C> scope(c, false);
+    DeviceScope scope(c, OnExit::STAY);
     REEF_TRY(scope.enter());
     const size_t prev_pow = c->r1_prev_pow;
     c->r1_prev_pow = 0;
@@ -751,7 +729,7 @@ static reef_status v_sc_gen_eq(void *impl, const reef_fe *rs, const uint32_t *qs
         if (qs[k] >= c->len) { set_error("qs[%zu] out of range", k); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     REEF_ON_DEVICE(c->device);
-    ScScope<C> scope(c, true);
+    DeviceScope scope(c, OnExit::RELEASE_IF_IDLE);
     REEF_TRY(scope.enter());
     REEF_TRY(sc_defer_flush<C>(c));        // rows whose first fold was deferred are written out: this is not their second fold
     c->valid_e = c->len;

@@ -17,7 +17,8 @@ import numpy as np
 from . import _ffi
 from ._ffi import REEF_DEVICE, REEF_HOST, check
 from .msm import DeviceBuffer, MsmContext, curve_id
-from .spartan import _arr, _ints, compress
+from ._fe import _Handle, _arr, _ints, _mont_forms
+from .spartan import _ipa_rounds, compress
 
 _ELEM = {np.dtype(np.uint8): 1, np.dtype(np.uint16): 2, np.dtype(np.int16): 2, np.dtype(np.uint32): 4, np.dtype(np.int32): 4}
 
@@ -48,10 +49,11 @@ def factored_lens(num_vars: int) -> Tuple[int, int]:
     return num_vars // 2, num_vars - num_vars // 2
 
 
-class HyraxEval:
+class HyraxEval(_Handle):
     """The committed matrix Z (2^left x 2^right, row-major, the document zero-padded to 2^num_vars) resident on one device, with
     its row blinds.  z: symbols of 1 / 2 / 4 bytes or an (n, 4) array of field elements (is_mont form), as a numpy array, or a
     DeviceBuffer with n and elem_bytes (device memory, copied); see _table for what is accepted."""
+    _destroy = "reef_hyrax_destroy"
 
     def __init__(self, curve, z, num_vars: int, left_vars: Optional[int] = None, *, row_blinds: Optional[Sequence[int]] = None,
                  is_mont: bool = False, device: int = 0, n: Optional[int] = None, elem_bytes: Optional[int] = None):
@@ -73,23 +75,6 @@ class HyraxEval:
                                           None if rb is None else rb.ctypes.data, device))
         self._h = h
         self._keep = None
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.reef_hyrax_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def _points(self, fn, *args) -> Tuple[np.ndarray, np.ndarray]:
         L, R = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
@@ -150,21 +135,12 @@ def prove_eval(hx: HyraxEval, key: MsmContext, point: Sequence[int], challenge: 
     """The whole argument with `challenge(label, absorbed)`: eval_begin, comm_LZ when row_comms are given, "r" after (comm_LZ, eval)
     for q = q_of(r), then "challenge_r" per round after L and R (compressed).  With h, blinds_of(round) gives that round's (bl, br).
     key: gens_v, exactly 2^right points.  Canonical ints in and out (is_mont: the library calls take Montgomery form)."""
-    R = (1 << 256) % p
-    Rinv = pow(R, -1, p)
-    to = (lambda v: v * R % p) if is_mont else (lambda v: v)
-    frm = (lambda v: v * Rinv % p) if is_mont else (lambda v: v)
+    to, frm = _mont_forms(p, is_mont)
     ev, lb = (frm(v) for v in hx.eval_begin(key, [to(x) for x in point], is_mont=is_mont))
     comm_lz = hx.eval_comm(row_comms) if row_comms is not None else None
     r_ipa = challenge("r", ([compress(key, comm_lz)] if comm_lz is not None else []) + [ev])
     bl = (lambda k: [to(x) for x in blinds_of(k)]) if (h is not None and blinds_of is not None) else (lambda k: None)
-    L, Rp = hx.ipa_begin(q_of(r_ipa), h if h is not None and blinds_of is not None else None, bl(0), is_mont=is_mont)
-    Ls, Rs, rs = [L], [Rp], []
-    for k in range(hx.right - 1):
-        rs.append(challenge("challenge_r", [compress(key, Ls[-1]), compress(key, Rs[-1])]))
-        L, Rp = hx.ipa_round(to(rs[-1]), bl(k + 1), is_mont=is_mont)
-        Ls.append(L)
-        Rs.append(Rp)
-    rs.append(challenge("challenge_r", [compress(key, Ls[-1]), compress(key, Rs[-1])]))
-    a_hat, b_hat = (frm(v) for v in hx.finish(to(rs[-1]), is_mont=is_mont))
+    first = hx.ipa_begin(q_of(r_ipa), h if h is not None and blinds_of is not None else None, bl(0), is_mont=is_mont)
+    Ls, Rs, rs, (a_hat, b_hat) = _ipa_rounds(first, lambda k, r: hx.ipa_round(to(r), bl(k), is_mont=is_mont),
+                                             lambda r: [frm(v) for v in hx.finish(to(r), is_mont=is_mont)], key, challenge, hx.right - 1)
     return {"eval": ev, "lz_blind": lb, "comm_lz": comm_lz, "r_ipa": r_ipa, "L": Ls, "R": Rs, "rs": rs, "a_hat": a_hat, "b_hat": b_hat}

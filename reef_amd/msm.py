@@ -14,6 +14,7 @@ from typing import Optional, Tuple, Union
 import numpy as np
 
 from . import _ffi
+from ._fe import _Handle
 from ._ffi import PALLAS, REEF_DEVICE, REEF_HOST, VESTA, MsmOpts, ReefError, check  # noqa: F401
 
 CURVE_IDS = {"pallas": PALLAS, "vesta": VESTA, PALLAS: PALLAS, VESTA: VESTA}
@@ -89,8 +90,9 @@ def scalar_to_limbs(v: int) -> np.ndarray:
     return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
 
 
-class MsmContext:
+class MsmContext(_Handle):
     """A resident commitment key (nova-snark `CommitmentGens<G>`) on one GPU."""
+    _destroy = "reef_msm_ctx_destroy"
 
     def __init__(self, curve, bases: Buf, n: Optional[int] = None, *, window_bits: int = 0, bucket_groups: int = 0,
                  chunk: int = 0, device: int = -1, byte_tables: int = 0, _handle=None):
@@ -128,23 +130,6 @@ class MsmContext:
         """This handle moves to `other`'s resident key (as a clone of it would be), keeping its stream and workspace."""
         check(self._lib.reef_msm_ctx_attach(self._h, other._h))
         self.n = other.n
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.reef_msm_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def sync(self) -> None:
         check(self._lib.reef_msm_ctx_sync(self._h))
@@ -278,10 +263,11 @@ SCALARS_EACH, SCALARS_FANOUT = 0, 1      # reef_msm_group_opts.scalars: how host
 EXCHANGE_PEER, EXCHANGE_HOST, EXCHANGE_RCCL = 1, 2, 3
 
 
-class MsmGroup:
+class MsmGroup(_Handle):
     """A commitment key resident on several GPUs of THIS process (reef_msm_group_*, include/reef_msm.h section 5): one MSM split by
     Pippenger window (every device holds the key) or by points (every device holds a slice), the 96-byte partial sums exchanged
     inside the library; on a windows group the rows of a Hyrax commitment are dealt out whole.  `devices` may repeat an ordinal."""
+    _destroy = "reef_msm_group_destroy"
 
     def __init__(self, curve, bases: Buf, devices, n: Optional[int] = None, *, split: int = SPLIT_WINDOWS, exchange: int = 0,
                  window_bits: int = 0, bucket_groups: int = 1, chunk: int = 0, byte_tables: int = 0, scalars: int = SCALARS_EACH):
@@ -355,23 +341,6 @@ class MsmGroup:
         out = np.zeros((rows, 12), dtype=np.uint64)
         check(self._lib.reef_msm_group_rows_symbols(self._h, ptr, rows, row_len, loc, symbol_bits, bptr, hptr, bool(blinds_are_mont), out.ctypes.data))
         return out
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.reef_msm_group_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def msm_multi(ctxs, scalars, is_mont: bool = True) -> np.ndarray:

@@ -13,6 +13,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _ffi
+from ._fe import _Handle, _arr
 from ._ffi import REEF_HOST, check
 from .msm import MsmContext, curve_id
 
@@ -27,8 +28,9 @@ def _fe(arr, n: Optional[int] = None) -> np.ndarray:
     return a
 
 
-class Nifs:
+class Nifs(_Handle):
     """The resident running instance, the fresh witness and T of one R1CS shape over the scalar field of `curve`."""
+    _destroy = "reef_nifs_destroy"
 
     def __init__(self, curve, num_cons: int, num_vars: int, num_io: int, device: int = 0):
         self._lib = _ffi.load()
@@ -37,23 +39,6 @@ class Nifs:
         h = ctypes.c_void_p()
         check(self._lib.reef_nifs_create(ctypes.byref(h), self.curve, num_cons, num_vars, num_io, device))
         self._h = h
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.reef_nifs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def set_matrix(self, which: int, rows, cols, vals, *, is_mont: bool = False) -> None:
         """Matrix A, B or C from (row, col, value) triples in any order; duplicates are summed."""
@@ -80,7 +65,7 @@ class Nifs:
 
     def fold(self, r: int, *, is_mont: bool = False) -> None:
         """W, E, u, X of the running instance folded with the last commit_t's fresh instance and T."""
-        ra = np.array([(r >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+        ra = _arr([r])
         check(self._lib.reef_nifs_fold(self._h, ra.ctypes.data, is_mont))
 
     def read(self, which: int, count: Optional[int] = None, *, to_mont: bool = False) -> np.ndarray:

@@ -14,18 +14,10 @@ from typing import Any, Callable, List, Sequence, Tuple
 
 import numpy as np
 
+from ._fe import _arr, _ints, _mont_forms   # _arr and _ints: importable from here as before
 from ._ffi import REEF_HOST, check
 from .msm import MsmContext
 from .nifs import Nifs
-
-
-def _arr(vals: Sequence[int]) -> np.ndarray:
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint64).reshape(-1, 4).copy()
-
-
-def _ints(a: np.ndarray) -> List[int]:
-    b = np.ascontiguousarray(a, dtype=np.uint64).tobytes()
-    return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
 
 
 class Spartan:
@@ -74,10 +66,7 @@ def prove(nifs: Nifs, num_cons_pad: int, num_vars_pad: int, challenge: Callable[
     outer round, nothing absorbed), "outer" (a round's [e0, e2, e3]), "r" (the four outer claims), "inner" (a round's [e0, e2]).
     p: the scalar field's modulus.  Canonical ints in and out; is_mont only chooses the form the library is called with."""
     sp = Spartan(nifs)
-    R = (1 << 256) % p
-    Rinv = pow(R, -1, p)
-    to = (lambda v: v * R % p) if is_mont else (lambda v: v)
-    frm = (lambda v: v * Rinv % p) if is_mont else (lambda v: v)
+    to, frm = _mont_forms(p, is_mont)
 
     def run(fn, *a):
         return [frm(v) for v in fn(*a, is_mont=is_mont)]
@@ -158,6 +147,20 @@ def compress(key: MsmContext, jac: np.ndarray) -> bytes:
     return out.tobytes()
 
 
+def _ipa_rounds(first: Tuple[np.ndarray, np.ndarray], step_fn: Callable[[int, int], Tuple[np.ndarray, np.ndarray]], finish_fn: Callable[[int], Any],
+                key: MsmContext, challenge: Callable[[str, List[Any]], int], rounds: int) -> Tuple[list, list, List[int], Any]:
+    """The IPA rounds of the opening and of the Hyrax argument: "challenge_r" after a round's L and R (compressed), then the next
+    round's step_fn(k, r), k = 1..rounds, after round 0's `first`; finish_fn(r) takes the last challenge.  (Ls, Rs, rs, its result)"""
+    Ls, Rs, rs = [first[0]], [first[1]], []
+    for k in range(rounds):
+        rs.append(challenge("challenge_r", [compress(key, Ls[-1]), compress(key, Rs[-1])]))
+        L, Rp = step_fn(k + 1, rs[-1])
+        Ls.append(L)
+        Rs.append(Rp)
+    rs.append(challenge("challenge_r", [compress(key, Ls[-1]), compress(key, Rs[-1])]))
+    return Ls, Rs, rs, finish_fn(rs[-1])
+
+
 def prove_with_opening(nifs: Nifs, key: MsmContext, num_cons_pad: int, num_vars_pad: int, challenge: Callable[[str, List[Any]], int],
                        p: int, comm_a: Callable[[int], Any], q_of: Callable[[int], np.ndarray], *, is_mont: bool = False) -> dict:
     """`prove`, then the batched IPA opening of [E, W] with the same `challenge(label, absorbed)`, in nova's order: "r" (the NIFS
@@ -166,25 +169,15 @@ def prove_with_opening(nifs: Nifs, key: MsmContext, num_cons_pad: int, num_vars_
     q_of(r) = gens_s.scale(r), affine.  key: gens_v, exactly max(num_cons_pad, num_vars_pad) points.  Canonical ints in and out."""
     out = prove(nifs, num_cons_pad, num_vars_pad, challenge, p, is_mont=is_mont)
     op = Opening(nifs)
-    R = (1 << 256) % p
-    Rinv = pow(R, -1, p)
-    to = (lambda v: v * R % p) if is_mont else (lambda v: v)
-    frm = (lambda v: v * Rinv % p) if is_mont else (lambda v: v)
+    to, frm = _mont_forms(p, is_mont)
     cross = frm(op.begin(key, is_mont=is_mont))
     r_fold = challenge("r", [cross])
     c = frm(op.fold(to(r_fold), is_mont=is_mont))
     ca = comm_a(r_fold)
     r_ipa = challenge("r", [ca, c])
-    L, Rp = op.ipa_begin(q_of(r_ipa))
-    Ls, Rs, rs = [L], [Rp], []
     n = max(num_cons_pad, num_vars_pad)
-    for _ in range(n.bit_length() - 2):
-        rs.append(challenge("challenge_r", [compress(key, Ls[-1]), compress(key, Rs[-1])]))
-        L, Rp = op.ipa_round(to(rs[-1]), is_mont=is_mont)
-        Ls.append(L)
-        Rs.append(Rp)
-    rs.append(challenge("challenge_r", [compress(key, Ls[-1]), compress(key, Rs[-1])]))
-    a_hat = frm(op.finish(to(rs[-1]), is_mont=is_mont))
+    Ls, Rs, rs, a_hat = _ipa_rounds(op.ipa_begin(q_of(r_ipa)), lambda k, r: op.ipa_round(to(r), is_mont=is_mont),
+                                    lambda r: frm(op.finish(to(r), is_mont=is_mont)), key, challenge, n.bit_length() - 2)
     out.update({"cross_term": cross, "r_fold": r_fold, "c": c, "comm_a": ca, "r_ipa": r_ipa, "L": Ls, "R": Rs, "r_ipa_rounds": rs,
                 "a_hat": a_hat})
     return out

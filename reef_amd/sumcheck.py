@@ -13,6 +13,7 @@ from typing import List, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
+from ._fe import _Handle
 from ._ffi import REEF_DEVICE, REEF_HOST, check
 from .msm import curve_id
 
@@ -30,8 +31,9 @@ def array_to_ints(arr: np.ndarray) -> List[int]:
     return [sum(int(arr[i, j]) << (64 * j) for j in range(4)) for i in range(arr.shape[0])]
 
 
-class SumCheck:
+class SumCheck(_Handle):
     """Resident (T, EQ) tables of 2^ell entries over the scalar field of `curve`."""
+    _destroy = "reef_sc_destroy"
 
     def __init__(self, curve, ell: int):
         self._lib = _ffi.load()
@@ -40,23 +42,6 @@ class SumCheck:
         h = ctypes.c_void_p()
         check(self._lib.reef_sc_create(ctypes.byref(h), curve_id(curve), self.len))
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.reef_sc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def set_table(self, which: int, values) -> None:
         """values: list of ints, or an (n, 4) uint64 array of canonical limbs."""

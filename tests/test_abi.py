@@ -195,3 +195,101 @@ def test_warm_up_without_a_gpu_fails_quietly_and_says_so():
     words = out.stdout.split()
     state, devices = int(words[1]), int(words[3])
     assert state == (2 if devices > 0 else 3), out.stdout
+
+
+def _balanced(text: str, start: int, open_ch: str, close_ch: str) -> int:
+    """The index just past the bracket that closes the one at text[start]; string literals are skipped."""
+    depth, i, quote = 0, start, None
+    while i < len(text):
+        ch = text[i]
+        if quote:
+            if ch == "\\":
+                i += 1
+            elif ch == quote:
+                quote = None
+        elif ch in "\"'":
+            quote = ch
+        elif ch == open_ch:
+            depth += 1
+        elif ch == close_ch:
+            depth -= 1
+            if depth == 0:
+                return i + 1
+        i += 1
+    raise AssertionError(f"unbalanced {open_ch} at {start}")
+
+
+def test_every_status_entry_point_reaches_the_engines_through_a_guarded_helper():
+    """api.cpp says "No C++ exception crosses the C ABI".  That holds because no wrapper chooses for itself: every extern "C" function
+    that returns reef_status reaches the per-curve tables (common.h: *VTable) through dispatch / stateless / create_handle, which run the
+    engine call under guarded(), or it is on the short list below with its reason; and nowhere in the file is a table's member called
+    outside the arguments of those helpers (destroy_handle: the destroy entries return nothing and free only)."""
+    import re
+    src = re.sub(r"//[^\n]*", "", open(os.path.join(_ffi.CSRC, "api.cpp")).read())
+    common = open(os.path.join(_ffi.CSRC, "common.h")).read()
+    members = set()
+    for m in re.finditer(r"struct (\w+VTable) \{", common):
+        body = common[m.end():_balanced(common, m.end() - 1, "{", "}")]
+        members |= set(re.findall(r"\(\*(\w+)\)\(", body))
+    assert {"msm", "sc_set", "commit_t", "eval_begin", "merkle_commit", "plan_for"} <= members and len(members) >= 50, sorted(members)
+    member_call = re.compile(r"->\s*(?:%s)\s*\(" % "|".join(sorted(members)))     # the tables are only ever held by pointer
+    helpers = ("dispatch", "stateless", "create_handle")
+    helper_call = re.compile(r"\b(?:%s)\s*(?:<[^<>;(){}]*>)?\s*\(" % "|".join(helpers))
+
+    # the helpers themselves: each ends in guarded(), and guarded() is called from nowhere else
+    defs = {}
+    for name in helpers + ("destroy_handle", "guarded"):
+        m = re.search(r"template <[^>]*>\s*static \w+ %s\([^)]*\)[^{]*\{" % name, src)
+        assert m, name
+        defs[name] = (m.start(), _balanced(src, m.end() - 1, "{", "}"))
+    for name in ("dispatch", "stateless"):
+        assert "return guarded(" in src[defs[name][0]:defs[name][1]], name
+    assert "return stateless(" in src[defs["create_handle"][0]:defs["create_handle"][1]]
+    rest = src
+    for a, b in sorted(defs.values(), reverse=True):
+        rest = rest[:a] + rest[b:]
+    assert "guarded(" not in rest, "guarded() is the helpers' business, not a wrapper's"
+
+    def outside_helpers(text: str) -> str:
+        """text without the argument lists of the helper calls in it"""
+        out, pos = [], 0
+        for m in helper_call.finditer(text):
+            if m.start() < pos:
+                continue
+            out.append(text[pos:m.end() - 1])
+            pos = _balanced(text, m.end() - 1, "(", ")")
+        return "".join(out) + text[pos:]
+
+    # entries that return a status without going through a helper, and why that is sound
+    allowed = {
+        "reef_runtime_init": "environment and a detached warm-up thread: no engine call, nothing that throws",
+        "reef_set_device": "one HIP call", "reef_get_device": "one HIP call", "reef_device_sync": "one HIP call", "reef_memcpy": "one HIP call",
+        "reef_msm_multi": "composes reef_msm and reef_msm_ctx_sync, which dispatch; its own allocation is hipHostMalloc",
+    }
+    # entries without a status to report a failure through, which call a table's member directly
+    direct = {"reef_msm_ctx_stream": "returns the stream or NULL", "reef_msm_ctx_byte_tables": "returns a flag"}
+
+    ext = src[src.index('extern "C" {'):]
+    seen, unguarded = set(), []
+    for m in re.finditer(r"^(reef_status|void \*|void|int|uint32_t|uint64_t|const char \*)\s*(\w+)\(([^{};]*)\)\s*\{", ext, re.M):
+        ret, name = m.group(1), m.group(2)
+        body = ext[m.end() - 1:_balanced(ext, m.end() - 1, "{", "}")]
+        stripped = outside_helpers(body)
+        if member_call.search(stripped):
+            assert name in direct and ret != "reef_status", f"{name} calls a table member outside dispatch/stateless/create_handle"
+        if ret != "reef_status":
+            continue
+        seen.add(name)
+        if not helper_call.search(body):
+            unguarded.append(name)
+    declared = set(_ffi.declared_symbols())
+    assert len(seen) > 60 and {"reef_msm", "reef_sc_set_table", "reef_nifs_read", "reef_hyrax_finish", "reef_merkle_commit_devices"} <= seen
+    assert seen <= declared, seen - declared
+    assert sorted(unguarded) == sorted(allowed), (sorted(unguarded), sorted(allowed))
+    # and the code outside the extern "C" block (the warm-up, the drop-in symbols' machinery) goes through the public entry points
+    internal = src[:src.index('extern "C" {')]
+    for a, b in sorted(defs.values(), reverse=True):
+        internal = internal[:a] + internal[b:]
+    hits = [h.group(0) for h in member_call.finditer(internal)] + [h.group(0) for h in member_call.finditer(outside_helpers(ext)) ]
+    direct_calls = [h for h in hits if not any(h.lstrip("-> ").startswith(k) for k in ("ctx_stream", "ctx_byte_tables"))]
+    assert not direct_calls, direct_calls
