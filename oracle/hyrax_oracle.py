@@ -1,12 +1,19 @@
-"""A big-integer reference of the Hyrax consistency argument (include/reef_msm.h 3i) and its verifier, written from 3i's definitions
-over the oracle's curve operations: the bound rows LZ = L^T Z, eval = <LZ, R>, sum_i L_i blind_i, comm_LZ = sum_i L_i C_i, and the IPA
-rounds of 3h with the optional per-round blinding term bl h (on L) and br h (on R).  Shared by tests/test_hyrax_eval_host.py and
-tests/test_gpu_hyrax_eval.py."""
+"""Big-integer prover and verifier of the Hyrax consistency argument, prove_eval (include/reef_msm.h 3i).
+TEST INFRASTRUCTURE ONLY -- only tests/, tools/ and smoke() may import it.
+
+Restated from 3i's definitions, not from source text, over the curve operations of oracle/pasta_ref: the bound rows LZ = L^T Z,
+eval = <LZ, R>, sum_i L_i blind_i, comm_LZ = sum_i L_i C_i, and the IPA rounds of 3h (oracle/ipa_oracle.py) with the optional
+per-round blinding term bl h (on L) and br h (on R).  Field elements are Python integers; points are what oracle.pasta_ref takes
+and returns.
+
+PARITY WITH THE RUST CRATES IS UNPINNED: nothing here was run against Reef's or nova-snark's Hyrax code.  The
+reference is checked by algebra and against oracle/mle_oracle.py for LZ and eval (tests/test_hyrax_eval_host.py): honest
+transcripts with and without the per-round h blinds pass verify_hyrax, a changed L, R, a_hat or challenge fails it."""
 import numpy as np
 
 from oracle import pasta_ref
-from test_spartan_host import eq_evals
-from test_spartan_open_host import compress, dot, msm, s_vector
+from oracle.ipa_oracle import compress, dot, msm, s_vector
+from oracle.spartan_oracle import eq_evals
 
 
 def bound_ref(z, num_vars: int, left: int, point, p: int):

@@ -1017,7 +1017,7 @@ struct StandinTranscript {
     }
 };
 
-// ---- the synthetic R1CS: the layered scheme of tests/test_nifs_host.py::layered_shape, restated --------------------------------
+// ---- the synthetic R1CS: the layered scheme of oracle/r1cs_oracle.py::layered_shape, restated ----------------------------------
 // Variables: num_inputs free inputs, then one output per non-empty constraint; z = W || u || X (num_io = 2).  Constraint i:
 // (2-4 terms) * (2-4 terms) = c_i out_i + (0-1 term) over u, X, the inputs and the outputs of earlier constraints, coefficients from
 // a pool of small, negative, power-of-two and full-width values.  num_vars = num_cons is met by leaving the last rows empty.

@@ -13,22 +13,12 @@ from typing import List, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
-from ._fe import _Handle
+from ._fe import _Handle, _arr, _ints
 from ._ffi import REEF_DEVICE, REEF_HOST, check
 from .msm import curve_id
 
-
-def ints_to_array(values: Sequence[int]) -> np.ndarray:
-    out = np.zeros((len(values), 4), dtype=np.uint64)
-    for i, v in enumerate(values):
-        for j in range(4):
-            out[i, j] = (v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
-    return out
-
-
-def array_to_ints(arr: np.ndarray) -> List[int]:
-    arr = np.asarray(arr, dtype=np.uint64).reshape(-1, 4)
-    return [sum(int(arr[i, j]) << (64 * j) for j in range(4)) for i in range(arr.shape[0])]
+ints_to_array = _arr        # the public names of _fe's pair: Python ints <-> (n, 4) uint64 arrays of little-endian limbs
+array_to_ints = _ints
 
 
 class SumCheck(_Handle):

@@ -132,20 +132,19 @@ def _extreme_coefficients(shape):
 @pytest.mark.parametrize("kind", KINDS)
 def test_spartan_extremes(gpu_lib, curve, name, kind):
     from reef_amd.nifs import Nifs
-    from test_gpu_nifs import _set_running, _upload_shape
-    from test_gpu_spartan import KEYS, _prove_dev, _shape
-    from test_spartan_host import Challenger, prove_ref
-    shape, pads = _shape(curve, name)
+    from gpu_drivers import PROOF_KEYS, prove_dev, set_running, spartan_shape, upload_shape
+    from oracle.spartan_oracle import Challenger, prove_ref
+    shape, pads = spartan_shape(curve, name)
     shape = _extreme_coefficients(shape)
     p = shape["p"]
     inst = _extreme_instance(shape, kind)
     ref = prove_ref(shape, inst, pads[0], pads[1], Challenger(p, curve), strict=False)
     for is_mont in (False, True):
         with Nifs(curve, shape["num_cons"], shape["num_vars"], shape["num_io"]) as nf:
-            _upload_shape(nf, shape, is_mont)
-            _set_running(nf, inst, p, is_mont)
-            got = _prove_dev(nf, shape, pads, is_mont, curve)
-            for k in KEYS:
+            upload_shape(nf, shape, is_mont)
+            set_running(nf, inst, p, is_mont)
+            got = prove_dev(nf, shape, pads, is_mont, curve)
+            for k in PROOF_KEYS:
                 assert got[k] == ref[k], f"{k} ({'Montgomery' if is_mont else 'canonical'} form)"
 
 
@@ -158,7 +157,7 @@ COEFS = [0xFFFF, -0xFFFF, 0x10000, -0x10000, -1, 1]   # the largest small magnit
 def _nifs_shape(curve):
     """Rows of 700 (several long-row segments), 128 (the longest short row), 129 (the shortest long one), 3 and 0 entries;
     coefficients +-0xFFFF, +-0x10000, -1, 1 and table max."""
-    from test_nifs_host import field
+    from oracle.r1cs_oracle import field
     p = field(curve)
     num_vars, num_io = 400, 2
     ncols = num_vars + 1 + num_io
@@ -183,9 +182,10 @@ def test_nifs_extremes(gpu_lib, curve, kind):
     """T = AZ1 o BZ2 + AZ2 o BZ1 - u1 CZ2 - CZ1 and the fold with r = M - 1, both input forms, z at the extremes."""
     from reef_amd.msm import compress
     from reef_amd.nifs import E, T, U, W, X, Nifs
-    from test_gpu_nifs import _arr, _key, _set_running, _upload_shape
-    from test_nifs_host import cross_term, fold, from_arr, to_arr, to_mont
+    from gpu_drivers import ap_key, arr, set_running, upload_shape
     from oracle import pasta_ref as R
+    from oracle.r1cs_oracle import cross_term, fold, to_mont
+    from reef_amd._fe import _arr, _ints
     shape = _nifs_shape(curve)
     p, n = shape["p"], shape["num_cons"]
     other = KINDS[(KINDS.index(kind) + 1) % 3]
@@ -195,19 +195,19 @@ def test_nifs_extremes(gpu_lib, curve, kind):
     t_ref = cross_term(shape, run, fresh, p)
     r = p - 1
     ref = fold(run, fresh, t_ref, r, p)
-    bases, key = _key(curve, n)
+    bases, key = ap_key(curve, n)
     with key:
         for is_mont in (False, True):
             form = "Montgomery" if is_mont else "canonical"
             with Nifs(curve, n, shape["num_vars"], shape["num_io"]) as nf:
-                _upload_shape(nf, shape, is_mont)
-                _set_running(nf, run, p, is_mont)
-                comm = nf.commit_t(key, _arr(fresh["W"], p, is_mont), _arr(fresh["X"], p, is_mont), is_mont=is_mont)
-                assert from_arr(nf.read(T)) == t_ref, f"T ({form})"
+                upload_shape(nf, shape, is_mont)
+                set_running(nf, run, p, is_mont)
+                comm = nf.commit_t(key, arr(fresh["W"], p, is_mont), arr(fresh["X"], p, is_mont), is_mont=is_mont)
+                assert _ints(nf.read(T)) == t_ref, f"T ({form})"
                 if not is_mont:
-                    assert compress(curve, comm) == R.compress(curve, R.msm_pippenger(curve, bases, to_arr(t_ref), mont=False, threads=4))
+                    assert compress(curve, comm) == R.compress(curve, R.msm_pippenger(curve, bases, _arr(t_ref), mont=False, threads=4))
                 nf.fold(to_mont([r], p)[0] if is_mont else r, is_mont=is_mont)
-                got = {"W": from_arr(nf.read(W)), "E": from_arr(nf.read(E)), "u": from_arr(nf.read(U))[0], "X": from_arr(nf.read(X))}
+                got = {"W": _ints(nf.read(W)), "E": _ints(nf.read(E)), "u": _ints(nf.read(U))[0], "X": _ints(nf.read(X))}
                 assert got == ref, f"fold ({form})"
 
 
@@ -220,27 +220,25 @@ def test_opening_extremes(gpu_lib, curve, kind):
     """a = E and W at the extremes (b follows from the reference's challenges), both input forms, every round."""
     from reef_amd.nifs import Nifs
     from reef_amd.spartan import prove
-    from test_gpu_nifs import _set_running, _upload_shape
-    from test_gpu_spartan import _shape
-    from test_gpu_spartan_open import _instances, _key, _run_steps
-    from test_spartan_host import Challenger, prove_ref
-    from test_spartan_open_host import gens_of, open_ref
-    shape, pads = _shape(curve, "dup_empty")
+    from gpu_drivers import key_of_kind, opening_instances, run_opening, set_running, spartan_shape, upload_shape
+    from oracle.ipa_oracle import gens_of, open_ref
+    from oracle.spartan_oracle import Challenger, prove_ref
+    shape, pads = spartan_shape(curve, "dup_empty")
     shape = _extreme_coefficients(shape)
     p, n = shape["p"], max(pads)
     inst = _extreme_instance(shape, kind)
     gens, gens_s = gens_of(curve, n)
     ch = Challenger(p, curve)
     pf = prove_ref(shape, inst, pads[0], pads[1], ch, strict=False)
-    i1, i2 = _instances(curve, shape, inst, pf, gens)
+    i1, i2 = opening_instances(curve, shape, inst, pf, gens)
     ref = open_ref(curve, gens, gens_s, i1, i2, ch)
-    with _key(curve, gens, "pre") as key:
+    with key_of_kind(curve, gens, "pre") as key:
         for is_mont in (False, True):
             with Nifs(curve, shape["num_cons"], shape["num_vars"], shape["num_io"]) as nf:
-                _upload_shape(nf, shape, is_mont)
-                _set_running(nf, inst, p, is_mont)
+                upload_shape(nf, shape, is_mont)
+                set_running(nf, inst, p, is_mont)
                 prove(nf, pads[0], pads[1], Challenger(p, curve), p, is_mont=is_mont)
-                _run_steps(nf, key, ref, curve, p, is_mont)
+                run_opening(nf, key, ref, curve, p, is_mont)
 
 
 # ------------------------------------------------------------------------------------------------------------- Hyrax ----
@@ -251,31 +249,32 @@ def test_opening_extremes(gpu_lib, curve, kind):
 def test_hyrax_extremes(gpu_lib, curve, kind):
     """Field-element documents at the extremes, the point at M - 1 / table max, row blinds and per-round blinds at M - 1: every
     call against hyrax_ref, both input forms."""
-    from hyrax_ref import hyrax_ref
+    from gpu_drivers import hyrax_points, key_of_kind, row_comms, run_hyrax
+    from oracle.hyrax_oracle import hyrax_ref
+    from oracle.ipa_oracle import compress, gens_of
+    from oracle.r1cs_oracle import field
+    from oracle.spartan_oracle import Challenger
+    from reef_amd._fe import _arr
     from reef_amd.hyrax import HyraxEval
-    from test_gpu_hyrax_eval import _key, _points, _row_comms, _run
-    from test_nifs_host import field, to_arr
-    from test_spartan_host import Challenger
-    from test_spartan_open_host import compress, gens_of
     p = field(curve)
     num_vars, left = 7, 3
     right = num_vars - left
     gens, _ = gens_of(curve, 1 << right)
-    q, h = _points(curve)
+    q, h = hyrax_points(curve)
     ints = values(kind, p, (1 << num_vars) - 3)
     point = [p - 1 if i % 2 else table_max(p) for i in range(num_vars)]
     row_blinds = values(kind, p, 1 << left)
     blinds = [(p - 1, table_max(p) if k % 2 else 0) for k in range(right)]
-    rc = _row_comms(curve, gens, ints, num_vars, left, row_blinds, h)
+    rc = row_comms(curve, gens, ints, num_vars, left, row_blinds, h)
     ref = hyrax_ref(curve, gens, ints, num_vars, left, point, q, Challenger(p, num_vars), p, row_blinds=row_blinds, h=h, blinds=blinds,
                     row_comms=rc)
     R = (1 << 256) % p
-    with _key(curve, gens, "pre") as key:
+    with key_of_kind(curve, gens, "pre") as key:
         for is_mont in (False, True):
-            z = to_arr([v * R % p for v in ints] if is_mont else ints)
+            z = _arr([v * R % p for v in ints] if is_mont else ints)
             rb = [v * R % p for v in row_blinds] if is_mont else row_blinds
             with HyraxEval(curve, z, num_vars, left, row_blinds=rb, is_mont=is_mont) as hx:
-                _run(hx, key, ref, curve, point, q, is_mont=is_mont, h=h, blinds=blinds)
+                run_hyrax(hx, key, ref, curve, point, q, is_mont=is_mont, h=h, blinds=blinds)
                 assert compress(curve, hx.eval_comm(rc)) == compress(curve, ref["comm_lz"]), "comm_LZ"
 
 

@@ -12,8 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from mont_grid import KINDS, MASK, PAIRS, RP, check_limbs, mont, operand, value
 from oracle.pasta_oracle import CURVES
-from test_mont_reduction import KINDS, MASK, PAIRS, RP, check_limbs, mont, operand, value
 
 pytestmark = pytest.mark.gpu
 
@@ -82,7 +82,7 @@ def strict(r):
     return all(x <= MASK for x in r[:8])
 
 
-# ---------------------------------------------------------------- products: test_mont_reduction.py's grid, on the device ----
+# ---------------------------------------------------------------- products: the grid of mont_grid.py, on the device ----------
 
 @pytest.mark.parametrize("name", list(FIELDS))
 @pytest.mark.parametrize("ab", PAIRS)

@@ -1,5 +1,5 @@
 """The Hyrax consistency argument on the GPU (reef_amd.hyrax over include/reef_msm.h 3i) against the big-integer reference of
-tests/hyrax_ref.py, bit-exact call by call: eval, lz_blind, comm_LZ, every round's L and R (compressed), a_hat, b_hat and a, b
+oracle/hyrax_oracle.py, bit-exact call by call: eval, lz_blind, comm_LZ, every round's L and R (compressed), a_hat, b_hat and a, b
 between rounds; both curves and input forms, symbols of 1 / 2 / 4 bytes and field elements, the three key kinds, with and without
 row blinds and the per-round h term; a cfg4-sized 2^25 document; a after eval_begin against reef_mle_bound_rows; the device
 transcript through the reference verifier; the order and key errors and the restart; a 3h opening interleaved with an argument."""
@@ -8,11 +8,14 @@ import random
 import numpy as np
 import pytest
 
-from hyrax_ref import blind_total, hyrax_ref, verify_hyrax
+from gpu_drivers import (hyrax_points, key_of_kind, open_shape, opening_instances, row_comms, run_hyrax, set_running,
+                         upload_shape)
 from oracle import pasta_ref
-from test_nifs_host import field, to_arr
-from test_spartan_host import Challenger, eq_evals
-from test_spartan_open_host import compress, gens_of, msm
+from oracle.hyrax_oracle import blind_total, hyrax_ref, verify_hyrax
+from oracle.ipa_oracle import compress, gens_of, msm, open_ref
+from oracle.r1cs_oracle import field, relaxed_instance
+from oracle.spartan_oracle import Challenger, eq_evals, prove_ref
+from reef_amd._fe import _arr
 
 pytestmark = pytest.mark.gpu
 
@@ -29,56 +32,7 @@ def _doc(curve, eb, n, seed, is_mont=False):
         return z, [int(v) for v in z]
     r = random.Random(seed)
     ints = [r.randrange(p) for _ in range(n)]
-    return to_arr([v * (1 << 256) % p for v in ints] if is_mont else ints), ints
-
-
-def _key(curve, gens, kind):
-    from reef_amd.msm import MsmContext
-    kw = {"pre": dict(bucket_groups=1, byte_tables=2), "tables": dict(bucket_groups=1, byte_tables=1), "plain": dict(bucket_groups=4)}[kind]
-    key = MsmContext(curve, gens, **kw)
-    assert key.has_byte_tables() == (kind == "tables")
-    return key
-
-
-def _points(curve):
-    return pasta_ref.gen_bases_ap(curve, 100003, 1, 1)[0], pasta_ref.gen_bases_ap(curve, 5003, 1, 1)[0]
-
-
-def _run(hx, key, ref, curve, point, q, *, is_mont, h=None, blinds=None, trace=True):
-    """The argument call by call with the reference's challenges: every output against the reference"""
-    p = field(curve)
-    R = (1 << 256) % p
-    to = (lambda v: v * R % p) if is_mont else (lambda v: v)
-    frm = (lambda v: v * pow(R, -1, p) % p) if is_mont else (lambda v: v)
-    form = "Montgomery" if is_mont else "canonical"
-    ev, lb = hx.eval_begin(key, [to(x) for x in point], is_mont=is_mont)
-    assert (frm(ev), frm(lb)) == (ref["eval"], ref["lz_blind"]), f"eval, lz_blind ({form})"
-    if trace:
-        assert [frm(v) for v in hx.read(0, len(ref["lz"]), to_mont=is_mont)] == ref["lz"], f"a = LZ ({form})"
-    bl = (lambda k: [to(x) for x in blinds[k]]) if h is not None else (lambda k: None)
-    L, Rp = hx.ipa_begin(q, h, bl(0), is_mont=is_mont)
-    assert (compress(curve, L), compress(curve, Rp)) == (compress(curve, ref["L"][0]), compress(curve, ref["R"][0])), f"L, R round 0 ({form})"
-    for k, r in enumerate(ref["rs"][:-1]):
-        L, Rp = hx.ipa_round(to(r), bl(k + 1), is_mont=is_mont)
-        assert compress(curve, L) == compress(curve, ref["L"][k + 1]), f"L round {k + 1} ({form})"
-        assert compress(curve, Rp) == compress(curve, ref["R"][k + 1]), f"R round {k + 1} ({form})"
-        if trace and (k < 2 or k == len(ref["rs"]) - 2):
-            t = ref["trace"][k]
-            assert [frm(v) for v in hx.read(0, len(t["a"]), to_mont=is_mont)] == t["a"], f"a after round {k} ({form})"
-            assert [frm(v) for v in hx.read(1, len(t["b"]), to_mont=is_mont)] == t["b"], f"b after round {k} ({form})"
-    a_hat, b_hat = hx.finish(to(ref["rs"][-1]), is_mont=is_mont)
-    assert (frm(a_hat), frm(b_hat)) == (ref["a_hat"], ref["b_hat"]), f"a_hat, b_hat ({form})"
-
-
-def _row_comms(curve, gens, z_ints, num_vars, left, row_blinds, h):
-    rows, cols = 1 << left, 1 << (num_vars - left)
-    zz = z_ints + [0] * ((1 << num_vars) - len(z_ints))
-    out = []
-    for i in range(rows):
-        row = zz[i * cols:(i + 1) * cols]
-        c = msm(curve, np.vstack([gens, h[None]]), row + [row_blinds[i]]) if row_blinds else msm(curve, gens, row)
-        out.append(pasta_ref.to_affine(curve, c)[0])
-    return np.stack(out)
+    return _arr([v * (1 << 256) % p for v in ints] if is_mont else ints), ints
 
 
 @pytest.mark.parametrize("curve", [0, 1])
@@ -91,22 +45,22 @@ def test_argument_bit_exact_against_the_reference(gpu_lib, curve, eb, num_vars):
     right = num_vars - left
     n = (1 << num_vars) - (num_vars % 3)
     gens, _ = gens_of(curve, 1 << right)
-    q, h = _points(curve)
+    q, h = hyrax_points(curve)
     rng = random.Random(100 * eb + num_vars + curve)
     point = [rng.randrange(p) for _ in range(num_vars)]
     mode = (eb + num_vars) % 3                           # 0 plain, 1 row blinds, 2 row blinds and the h term
     row_blinds = [rng.randrange(p) for _ in range(1 << left)] if mode else None
     blinds = [(rng.randrange(p), rng.randrange(p) if k % 2 else 0) for k in range(right)] if mode == 2 else None
-    with _key(curve, gens, "pre") as key:
+    with key_of_kind(curve, gens, "pre") as key:
         for is_mont in (False, True):
             z, ints = _doc(curve, eb, n, 7 * num_vars + eb, is_mont)
-            rc = _row_comms(curve, gens, ints, num_vars, left, row_blinds, h)
+            rc = row_comms(curve, gens, ints, num_vars, left, row_blinds, h)
             ref = hyrax_ref(curve, gens, ints, num_vars, left, point, q, Challenger(p, num_vars), p, row_blinds=row_blinds,
                             h=h if mode == 2 else None, blinds=blinds, row_comms=rc)
             R = (1 << 256) % p
             rb = [v * R % p for v in row_blinds] if (row_blinds and is_mont) else row_blinds
             with HyraxEval(curve, z, num_vars, left, row_blinds=rb, is_mont=is_mont) as hx:
-                _run(hx, key, ref, curve, point, q, is_mont=is_mont, h=h if mode == 2 else None, blinds=blinds)
+                run_hyrax(hx, key, ref, curve, point, q, is_mont=is_mont, h=h if mode == 2 else None, blinds=blinds)
                 assert compress(curve, hx.eval_comm(rc)) == compress(curve, ref["comm_lz"]), "comm_LZ"
                 b0 = eq_evals(point[left:], p)
                 total = blind_total(ref["lz_blind"], blinds or [], ref["rs"], p)
@@ -122,7 +76,7 @@ def test_key_kinds_give_the_same_argument(gpu_lib, curve, with_h):
     num_vars, left = 13, 2                               # 2^11 columns: the byte-table range
     right = num_vars - left
     gens, _ = gens_of(curve, 1 << right)
-    q, h = _points(curve)
+    q, h = hyrax_points(curve)
     rng = random.Random(40 + curve)
     point = [rng.randrange(p) for _ in range(num_vars)]
     blinds = [(rng.randrange(p), rng.randrange(p)) for _ in range(right)] if with_h else None
@@ -130,8 +84,8 @@ def test_key_kinds_give_the_same_argument(gpu_lib, curve, with_h):
     ref = hyrax_ref(curve, gens, ints, num_vars, left, point, q, Challenger(p, 9), p, h=h if with_h else None, blinds=blinds)
     with HyraxEval(curve, z, num_vars, left) as hx:
         for kind in ("pre", "tables", "plain"):
-            with _key(curve, gens, kind) as key:
-                _run(hx, key, ref, curve, point, q, is_mont=False, h=h if with_h else None, blinds=blinds, trace=kind == "pre")
+            with key_of_kind(curve, gens, kind) as key:
+                run_hyrax(hx, key, ref, curve, point, q, is_mont=False, h=h if with_h else None, blinds=blinds, trace=kind == "pre")
 
 
 @pytest.mark.parametrize("curve", [0, 1])
@@ -146,7 +100,7 @@ def test_a_after_eval_begin_is_mle_bound_rows(gpu_lib, curve, eb):
     point = [rng.randrange(p) for _ in range(num_vars)]
     lz, ev = mle.bound_rows(curve, z if eb != 32 else ints, point, left)
     gens, _ = gens_of(curve, 1 << (num_vars - left))
-    with _key(curve, gens, "plain") as key, HyraxEval(curve, z, num_vars, left) as hx:
+    with key_of_kind(curve, gens, "plain") as key, HyraxEval(curve, z, num_vars, left) as hx:
         got, _ = hx.eval_begin(key, point)
         assert got == ev
         assert hx.read(0, 1 << (num_vars - left)) == lz
@@ -184,12 +138,12 @@ def test_cfg4_sized_document(gpu_lib):
     ev = sum(x * y for x, y in zip(lz, eq_evals(point[left:], p))) % p
     assert mle.bound_rows(curve, z, point, left) == (lz, ev)
     gens, _ = gens_of(curve, 1 << right)
-    q, h = _points(curve)
+    q, h = hyrax_points(curve)
     blinds = [(rng.randrange(p), rng.randrange(p)) for _ in range(right)]
     ref = hyrax_ref(curve, gens, None, num_vars, left, point, q, Challenger(p, 25), p, h=h, blinds=blinds, lz=lz)
     assert ref["eval"] == ev
-    with _key(curve, gens, "pre") as key, HyraxEval(curve, z, num_vars) as hx:
-        _run(hx, key, ref, curve, point, q, is_mont=False, h=h, blinds=blinds, trace=False)
+    with key_of_kind(curve, gens, "pre") as key, HyraxEval(curve, z, num_vars) as hx:
+        run_hyrax(hx, key, ref, curve, point, q, is_mont=False, h=h, blinds=blinds, trace=False)
         hx.eval_begin(key, point)
         assert hx.read(0, 1 << right) == lz
     comm = msm(curve, gens, lz)
@@ -204,18 +158,18 @@ def test_device_transcript_passes_the_verifier(gpu_lib, curve):
     num_vars, left = 9, 4
     right = num_vars - left
     gens, _ = gens_of(curve, 1 << right)
-    q0, h = _points(curve)
+    q0, h = hyrax_points(curve)
     rng = random.Random(77 + curve)
     point = [rng.randrange(p) for _ in range(num_vars)]
     row_blinds = [rng.randrange(p) for _ in range(1 << left)]
     blinds = [(rng.randrange(p), rng.randrange(p)) for _ in range(right)]
     z, ints = _doc(curve, 32, 1 << num_vars, 77)
-    rc = _row_comms(curve, gens, ints, num_vars, left, row_blinds, h)
+    rc = row_comms(curve, gens, ints, num_vars, left, row_blinds, h)
 
     def q_of(r):
         return pasta_ref.to_affine(curve, pasta_ref.scalar_mul(curve, q0, r))[0]
     for is_mont in (False, True):
-        with _key(curve, gens, "pre") as key, HyraxEval(curve, z, num_vars, left, row_blinds=row_blinds) as hx:
+        with key_of_kind(curve, gens, "pre") as key, HyraxEval(curve, z, num_vars, left, row_blinds=row_blinds) as hx:
             pf = prove_eval(hx, key, point, Challenger(p, 3), p, q_of, row_comms=rc, h=h, blinds_of=lambda k: blinds[k], is_mont=is_mont)
         q = q_of(pf["r_ipa"])
         total = blind_total(pf["lz_blind"], blinds, pf["rs"], p)
@@ -231,21 +185,21 @@ def test_order_key_and_restart_errors(gpu_lib):
     curve, num_vars, left = 0, 8, 4
     p = field(curve)
     gens, _ = gens_of(curve, 16)
-    q, h = _points(curve)
+    q, h = hyrax_points(curve)
     z, ints = _doc(curve, 2, 200, 5)
     rng = random.Random(5)
     point = [rng.randrange(p) for _ in range(num_vars)]
     ref = hyrax_ref(curve, gens, ints, num_vars, left, point, q, Challenger(p, 1), p)
-    with _key(curve, gens, "pre") as key, HyraxEval(curve, z, num_vars, left) as hx:
+    with key_of_kind(curve, gens, "pre") as key, HyraxEval(curve, z, num_vars, left) as hx:
         with pytest.raises(ReefError, match="reef_hyrax_eval_begin"):
             hx.ipa_begin(q)
         with pytest.raises(ReefError, match="reef_hyrax_eval_begin"):
             hx.read(0, 1)
         with pytest.raises(ReefError, match="reef_hyrax_eval_begin"):
             hx.eval_comm(np.zeros((16, 8), np.uint64))
-        with _key(curve, gens[:8], "pre") as short, pytest.raises(ReefError, match="8 points.*exactly 2\\^\\(num_vars - left_vars\\) = 16"):
+        with key_of_kind(curve, gens[:8], "pre") as short, pytest.raises(ReefError, match="8 points.*exactly 2\\^\\(num_vars - left_vars\\) = 16"):
             hx.eval_begin(short, point)
-        with _key(1, gens_of(1, 16)[0], "pre") as other, pytest.raises(ReefError, match="curve 1"):
+        with key_of_kind(1, gens_of(1, 16)[0], "pre") as other, pytest.raises(ReefError, match="curve 1"):
             hx.eval_begin(other, point)
         with pytest.raises(ReefError, match="below the modulus"):
             hx.eval_begin(key, [p] + point[1:])
@@ -260,10 +214,10 @@ def test_order_key_and_restart_errors(gpu_lib):
         with pytest.raises(ReefError, match="zero"):
             hx.ipa_round(0)
         hx.ipa_round(ref["rs"][0])
-        _run(hx, key, ref, curve, point, q, is_mont=False)            # a second eval_begin mid-argument starts over
+        run_hyrax(hx, key, ref, curve, point, q, is_mont=False)            # a second eval_begin mid-argument starts over
         with pytest.raises(ReefError, match="out of order, the next call is reef_hyrax_eval_begin"):
             hx.ipa_round(ref["rs"][0])
-        _run(hx, key, ref, curve, point, q, is_mont=True)
+        run_hyrax(hx, key, ref, curve, point, q, is_mont=True)
 
 
 def test_interleaved_with_a_3h_opening(gpu_lib):
@@ -271,33 +225,29 @@ def test_interleaved_with_a_3h_opening(gpu_lib):
     from reef_amd.hyrax import HyraxEval
     from reef_amd.nifs import Nifs
     from reef_amd.spartan import Opening, prove
-    from test_gpu_nifs import _set_running, _upload_shape
-    from test_gpu_spartan_open import _instances, _open_shape
-    from test_spartan_host import prove_ref, relaxed_instance
-    from test_spartan_open_host import open_ref
     curve = 0
-    shape, pads = _open_shape(curve, "cons_gt_vars")
+    shape, pads = open_shape(curve, "cons_gt_vars")
     p, n = shape["p"], max(pads)
     inst = relaxed_instance(shape, 1, 11)
     gens3, gens_s = gens_of(curve, n)
     ch = Challenger(p, 0)
     pf = prove_ref(shape, inst, pads[0], pads[1], ch)
-    i1, i2 = _instances(curve, shape, inst, pf, gens3)
+    i1, i2 = opening_instances(curve, shape, inst, pf, gens3)
     ref3 = open_ref(curve, gens3, gens_s, i1, i2, ch)
     num_vars = 2 * (n.bit_length() - 1)
     left = num_vars // 2
     gens, _ = gens_of(curve, 1 << (num_vars - left))
-    q, h = _points(curve)
+    q, h = hyrax_points(curve)
     rng = random.Random(8)
     point = [rng.randrange(p) for _ in range(num_vars)]
     blinds = [(rng.randrange(p), rng.randrange(p)) for _ in range(num_vars - left)]
     z, ints = _doc(curve, 1, 1 << num_vars, 8)
     ref = hyrax_ref(curve, gens, ints, num_vars, left, point, q, Challenger(p, 8), p, h=h, blinds=blinds)
     assert len(ref["rs"]) == len(ref3["rs"])
-    with _key(curve, gens3, "pre") as key3, _key(curve, gens, "plain") as key, HyraxEval(curve, z, num_vars, left) as hx, \
+    with key_of_kind(curve, gens3, "pre") as key3, key_of_kind(curve, gens, "plain") as key, HyraxEval(curve, z, num_vars, left) as hx, \
             Nifs(curve, shape["num_cons"], shape["num_vars"], shape["num_io"]) as nf:
-        _upload_shape(nf, shape, False)
-        _set_running(nf, inst, p, False)
+        upload_shape(nf, shape, False)
+        set_running(nf, inst, p, False)
         prove(nf, pads[0], pads[1], Challenger(p, 0), p)
         op = Opening(nf)
         assert op.begin(key3) == ref3["cross"]
@@ -327,11 +277,11 @@ def test_document_from_device_memory(gpu_lib, eb):
     rng = random.Random(eb)
     point = [rng.randrange(p) for _ in range(num_vars)]
     gens, _ = gens_of(curve, 1 << (num_vars - left))
-    q, _ = _points(curve)
+    q, _ = hyrax_points(curve)
     ref = hyrax_ref(curve, gens, ints, num_vars, left, point, q, Challenger(p, eb), p)
-    with _key(curve, gens, "pre") as key, HyraxEval(curve, dz, num_vars, left, n=len(ints), elem_bytes=eb) as hx:
+    with key_of_kind(curve, gens, "pre") as key, HyraxEval(curve, dz, num_vars, left, n=len(ints), elem_bytes=eb) as hx:
         assert hx.elem_bytes == eb and hx.n == len(ints)
-        _run(hx, key, ref, curve, point, q, is_mont=False)
+        run_hyrax(hx, key, ref, curve, point, q, is_mont=False)
     for n, e in ((len(ints) + 1, eb), (len(ints), None), (len(ints), 8)):     # more than the buffer holds, no width, a bad width
         with pytest.raises(ValueError):
             HyraxEval(curve, dz, num_vars, left, n=n, elem_bytes=e)
@@ -347,10 +297,10 @@ def test_tall_matrix_with_row_blinds(gpu_lib):
     point = [rng.randrange(p) for _ in range(num_vars)]
     row_blinds = [rng.randrange(p) for _ in range(1 << left)]
     gens, _ = gens_of(curve, 2)
-    q, _ = _points(curve)
+    q, _ = hyrax_points(curve)
     ref = hyrax_ref(curve, gens, ints, num_vars, left, point, q, Challenger(p, 16), p, row_blinds=row_blinds)
-    with _key(curve, gens, "plain") as key, HyraxEval(curve, z, num_vars, left, row_blinds=row_blinds) as hx:
-        _run(hx, key, ref, curve, point, q, is_mont=False)
+    with key_of_kind(curve, gens, "plain") as key, HyraxEval(curve, z, num_vars, left, row_blinds=row_blinds) as hx:
+        run_hyrax(hx, key, ref, curve, point, q, is_mont=False)
 
 
 def test_eval_comm_reuses_and_replaces_the_row_commitments(gpu_lib):
@@ -359,12 +309,12 @@ def test_eval_comm_reuses_and_replaces_the_row_commitments(gpu_lib):
     p = field(curve)
     gens, _ = gens_of(curve, 16)
     z, ints = _doc(curve, 1, 256, 31)
-    rc = _row_comms(curve, gens, ints, num_vars, left, None, None)
+    rc = row_comms(curve, gens, ints, num_vars, left, None, None)
     other = np.ascontiguousarray(rc[::-1])
     rng = random.Random(31)
     point = [rng.randrange(p) for _ in range(num_vars)]
     L = eq_evals(point[:left], p)
-    with _key(curve, gens, "pre") as key, HyraxEval(curve, z, num_vars, left) as hx:
+    with key_of_kind(curve, gens, "pre") as key, HyraxEval(curve, z, num_vars, left) as hx:
         hx.eval_begin(key, point)
         for comms in (rc, rc, other, rc):
             assert compress(curve, hx.eval_comm(comms)) == compress(curve, msm(curve, comms, L))

@@ -1,5 +1,5 @@
 """Row N6 on the GPU: the NIFS step (reef_amd.nifs over include/reef_msm.h 3f) against the big-integer reference of
-tests/test_nifs_host.py, bit-exact: T for canonical and Montgomery inputs, comm_T against oracle/pasta_ref's MSM of the
+oracle/r1cs_oracle.py, bit-exact: T for canonical and Montgomery inputs, comm_T against oracle/pasta_ref's MSM of the
 reference T, the four folds, a chain of folding steps under the relaxed-R1CS check, a shape of cfg5's size, argument errors."""
 import random
 import time
@@ -7,27 +7,12 @@ import time
 import numpy as np
 import pytest
 
+from gpu_drivers import ap_key, arr, set_running, upload_shape
 from oracle import pasta_ref as R
-from test_nifs_host import (bad_rows, cross_term, field, fold, fresh_instance, from_arr, layered_shape, running_from_fresh, to_arr,
-                            to_mont)
+from oracle.r1cs_oracle import bad_rows, cross_term, fold, fresh_instance, layered_shape, running_from_fresh, to_mont
+from reef_amd._fe import _arr, _ints
 
 pytestmark = pytest.mark.gpu
-
-
-def _upload_shape(nf, shape, is_mont):
-    p = shape["p"]
-    for k, m in enumerate("ABC"):
-        r, c, v = shape[m]
-        nf.set_matrix(k, r, c, to_arr(to_mont(v, p) if is_mont else v), is_mont=is_mont)
-
-
-def _arr(vals, p, is_mont):
-    return to_arr(to_mont(vals, p) if is_mont else vals)
-
-
-def _set_running(nf, run, p, is_mont, zero_e=False):
-    nf.set_running(_arr(run["W"], p, is_mont), None if zero_e else _arr(run["E"], p, is_mont), _arr([run["u"]], p, is_mont),
-                   _arr(run["X"], p, is_mont), is_mont=is_mont)
 
 
 def _relaxed_running(shape, seed):
@@ -36,12 +21,6 @@ def _relaxed_running(shape, seed):
     run = running_from_fresh(fresh_instance(shape, seed), n)
     fresh = fresh_instance(shape, seed + 1000)
     return fold(run, fresh, cross_term(shape, run, fresh, p), random.Random(seed).randrange(p), p)
-
-
-def _key(curve, n):
-    from reef_amd.msm import MsmContext
-    bases = R.gen_bases_ap(curve, 42, 5, n)
-    return bases, MsmContext(curve, bases)
 
 
 SHAPES = {   # name: layered_shape keyword arguments
@@ -65,23 +44,23 @@ def test_cross_term_commitment_and_fold_bit_exact(gpu_lib, curve, name):
     t_ref = cross_term(shape, run, fresh, p)
     r = random.Random(name).randrange(p)
     ref = fold(run, fresh, t_ref, r, p)
-    bases, key = _key(curve, n)
+    bases, key = ap_key(curve, n)
     with key:
         for is_mont in (False, True):
             with Nifs(curve, n, shape["num_vars"], shape["num_io"]) as nf:
-                _upload_shape(nf, shape, is_mont)
-                _set_running(nf, run, p, is_mont)
-                comm = nf.commit_t(key, _arr(fresh["W"], p, is_mont), _arr(fresh["X"], p, is_mont), is_mont=is_mont)
-                assert from_arr(nf.read(T)) == t_ref, f"T ({'Montgomery' if is_mont else 'canonical'} inputs)"
+                upload_shape(nf, shape, is_mont)
+                set_running(nf, run, p, is_mont)
+                comm = nf.commit_t(key, arr(fresh["W"], p, is_mont), arr(fresh["X"], p, is_mont), is_mont=is_mont)
+                assert _ints(nf.read(T)) == t_ref, f"T ({'Montgomery' if is_mont else 'canonical'} inputs)"
                 if not is_mont:
-                    exp = R.compress(curve, R.msm_pippenger(curve, bases, to_arr(t_ref), mont=False, threads=4))
+                    exp = R.compress(curve, R.msm_pippenger(curve, bases, _arr(t_ref), mont=False, threads=4))
                     assert compress(curve, comm) == exp, "comm_T"
                 nf.fold(to_mont([r], p)[0] if is_mont else r, is_mont=is_mont)
-                assert from_arr(nf.read(W)) == ref["W"]
-                assert from_arr(nf.read(E)) == ref["E"]
-                assert from_arr(nf.read(U)) == [ref["u"]]
-                assert from_arr(nf.read(X)) == ref["X"]
-                assert from_arr(nf.read(E, to_mont=True)) == to_mont(ref["E"], p)
+                assert _ints(nf.read(W)) == ref["W"]
+                assert _ints(nf.read(E)) == ref["E"]
+                assert _ints(nf.read(U)) == [ref["u"]]
+                assert _ints(nf.read(X)) == ref["X"]
+                assert _ints(nf.read(E, to_mont=True)) == to_mont(ref["E"], p)
                 assert nf.check_relaxed() == (0, None)
 
 
@@ -92,34 +71,34 @@ def test_chain_of_folding_steps_stays_satisfied_and_tampering_is_reported(gpu_li
     p, n = shape["p"], shape["num_cons"]
     rng = random.Random(curve)
     run = running_from_fresh(fresh_instance(shape, 0), n)
-    _, key = _key(curve, n)
+    _, key = ap_key(curve, n)
     with key, Nifs(curve, n, shape["num_vars"], shape["num_io"]) as nf:
-        _upload_shape(nf, shape, False)
-        _set_running(nf, run, p, False, zero_e=True)                 # nova's first step: E = 0, u = 1
+        upload_shape(nf, shape, False)
+        set_running(nf, run, p, False, zero_e=True)                 # nova's first step: E = 0, u = 1
         assert nf.check_relaxed() == (0, None)
         for step in range(1, 10):
             fresh = fresh_instance(shape, step)
-            nf.commit_t(key, to_arr(fresh["W"]), to_arr(fresh["X"]))
+            nf.commit_t(key, _arr(fresh["W"]), _arr(fresh["X"]))
             t = cross_term(shape, run, fresh, p)
-            assert from_arr(nf.read(T)) == t, f"T of step {step}"
+            assert _ints(nf.read(T)) == t, f"T of step {step}"
             r = rng.randrange(p)
             nf.fold(r)
             run = fold(run, fresh, t, r, p)
             assert nf.check_relaxed() == (0, None), f"step {step}"
-        got = {"W": from_arr(nf.read(W)), "E": from_arr(nf.read(E)), "u": from_arr(nf.read(U))[0], "X": from_arr(nf.read(X))}
+        got = {"W": _ints(nf.read(W)), "E": _ints(nf.read(E)), "u": _ints(nf.read(U))[0], "X": _ints(nf.read(X))}
         assert got == run
         assert bad_rows(shape, got, p) == []                          # the Python check agrees
         rows = [i for i in range(n) if shape["plan"][i] is not None]
         for k in (rows[0], rows[len(rows) // 2], rows[-1]):
             bad = dict(run, E=list(run["E"]))
             bad["E"][k] = (bad["E"][k] + 1) % p
-            _set_running(nf, bad, p, False)
+            set_running(nf, bad, p, False)
             assert nf.check_relaxed() == (1, k)
             assert bad_rows(shape, bad, p) == [k]
         bad = dict(run, E=list(run["E"]))
         for k in rows[5:12]:
             bad["E"][k] = (bad["E"][k] + 3) % p
-        _set_running(nf, bad, p, False)
+        set_running(nf, bad, p, False)
         assert nf.check_relaxed() == (7, rows[5])
 
 
@@ -142,16 +121,16 @@ def test_cfg5_sized_shape_three_folds_and_sampled_rows(gpu_lib, curve):
     sample = sorted(rng.sample(range(n), 255) + [n // 2])             # the long row among them
     run = running_from_fresh(fresh[0], n)
     z1 = run["W"] + [1] + run["X"]
-    _, key = _key(curve, n)
+    _, key = ap_key(curve, n)
     with key, Nifs(curve, n, shape["num_vars"], shape["num_io"]) as nf:
-        _upload_shape(nf, shape, False)
-        _set_running(nf, run, p, False, zero_e=True)
+        upload_shape(nf, shape, False)
+        set_running(nf, run, p, False, zero_e=True)
         e_rows = {i: 0 for i in sample}
         for step in range(3):
             fr = fresh[1 - step % 2] if step < 2 else fresh[1]
             z2 = fr["W"] + [1] + fr["X"]
-            nf.commit_t(key, to_arr(fr["W"]), to_arr(fr["X"]))
-            t = from_arr(nf.read(T))
+            nf.commit_t(key, _arr(fr["W"]), _arr(fr["X"]))
+            t = _ints(nf.read(T))
             u1 = z1[shape["num_vars"]]
             for i in sample:
                 ta, tb, tc, cinv, out = shape["plan"][i]
@@ -177,22 +156,22 @@ def test_argument_errors(gpu_lib, curve):
             with pytest.raises(ReefError) as e:
                 fn(*a, **k)
             assert e.value.status == 1          # REEF_ERR_ARG
-        one = to_arr([1])
+        one = _arr([1])
         arg_error(nf.set_matrix, 0, [0], [nv + 1 + nio], one)           # column out of range
         arg_error(nf.set_matrix, 0, [n], [0], one)                      # row out of range
         arg_error(nf.set_matrix, 3, [0], [0], one)                      # no matrix D
-        _upload_shape(nf, shape, False)
-        _set_running(nf, running_from_fresh(fresh, n), p, False, zero_e=True)
+        upload_shape(nf, shape, False)
+        set_running(nf, running_from_fresh(fresh, n), p, False, zero_e=True)
         arg_error(nf.fold, 5)                                           # fold before commit_T
-        _, wrong = _key(1 - curve, n)
+        _, wrong = ap_key(1 - curve, n)
         with wrong:
-            arg_error(nf.commit_t, wrong, to_arr(fresh["W"]), to_arr(fresh["X"]))
-        _, short = _key(curve, n - 1)
+            arg_error(nf.commit_t, wrong, _arr(fresh["W"]), _arr(fresh["X"]))
+        _, short = ap_key(curve, n - 1)
         with short:
-            arg_error(nf.commit_t, short, to_arr(fresh["W"]), to_arr(fresh["X"]))
-        _, key = _key(curve, n)
+            arg_error(nf.commit_t, short, _arr(fresh["W"]), _arr(fresh["X"]))
+        _, key = ap_key(curve, n)
         with key:
-            nf.commit_t(key, to_arr(fresh["W"]), to_arr(fresh["X"]))
+            nf.commit_t(key, _arr(fresh["W"]), _arr(fresh["X"]))
             nf.fold(5)
             arg_error(nf.fold, 5)                                       # a second fold needs the next commit_T
         arg_error(nf.read, 0, nv + 1)                                   # more than W holds

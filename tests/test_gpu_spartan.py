@@ -1,5 +1,5 @@
 """Row N5 on the GPU: the sum-checks of the final SNARK (reef_amd.spartan over include/reef_msm.h 3g) against the big-integer
-reference of tests/test_spartan_host.py, bit-exact: every round's evaluations, every challenge and every claim, both curves, both
+reference of oracle/spartan_oracle.py, bit-exact: every round's evaluations, every challenge and every claim, both curves, both
 input forms, on shapes that reach each path (renumbered columns, empty rows, duplicates, a long row, a long column, cfg4's size);
 a running instance folded on the device; a 2^20-row shape checked by the verifier's identities; the NIFS state left as it was;
 the order and argument errors."""
@@ -7,73 +7,31 @@ import random
 
 import pytest
 
-from test_gpu_nifs import _key, _set_running, _upload_shape
-from test_nifs_host import cross_term, fold, fresh_instance, from_arr, layered_shape, running_from_fresh, to_arr
-from test_spartan_host import Challenger, next_pow2, prove_ref, relaxed_instance, verify
+from gpu_drivers import PROOF_KEYS, SPARTAN_SHAPES, ap_key, pads_of, prove_dev, set_running, spartan_shape, upload_shape
+from oracle.r1cs_oracle import cross_term, fold, fresh_instance, layered_shape, matvec, relaxed_instance, running_from_fresh
+from oracle.spartan_oracle import Challenger, next_pow2, prove_ref, verify
+from reef_amd._fe import _arr, _ints
 
 pytestmark = pytest.mark.gpu
 
 
-def with_long_column(shape, col: int, seed: int) -> dict:
-    """Adds to B, in every row, the pair (row, col, v), (row, col, -v): a column of 2 num_cons entries that sums to nothing."""
-    p, rng = shape["p"], random.Random(seed)
-    r, c, v = (list(x) for x in shape["B"])
-    for i in range(shape["num_cons"]):
-        x = rng.randrange(p)
-        r += [i, i]
-        c += [col, col]
-        v += [x, (p - x) % p]
-    return dict(shape, B=(r, c, v))
-
-
-def _pads(shape, pads):
-    return pads or (next_pow2(shape["num_cons"]), next_pow2(max(shape["num_vars"], shape["num_io"] + 1)))
-
-
-SHAPES = {   # name: (layered_shape keyword arguments, (num_cons_pad, num_vars_pad) or None: the smallest legal)
-    "smallest": (dict(num_cons=1, num_inputs=1, num_io=1), (2, 2)),
-    "dup_empty": (dict(num_cons=127, dup_every=3, empty_every=5, extra_vars=4), None),
-    "long_row": (dict(num_cons=300, long_row=1500, num_io=2), None),
-    "vars_lt_cons": (dict(num_cons=500, num_inputs=3, empty_every=2, num_io=3), (512, 512)),      # u moves; num_vars_pad > num_vars
-    "io_close": (dict(num_cons=100, num_inputs=4, num_io=120), None),                            # num_io = num_vars_pad - 8
-    "cfg4": (dict(num_cons=39484, long_row=1100, empty_every=101, dup_every=13), (1 << 16, None)),
-}
-
-
-def _shape(curve, name):
-    kw, pads = SHAPES[name]
-    shape = layered_shape(curve, seed=len(name) + curve, **kw)
-    if name == "cfg4":
-        shape = with_long_column(shape, shape["num_vars"], 3)        # the u column: 2 x 39484 entries more
-        pads = (pads[0], next_pow2(shape["num_vars"]))
-    return shape, _pads(shape, pads)
-
-
-def _prove_dev(nf, shape, pads, is_mont, seed):
-    from reef_amd.spartan import prove
-    return prove(nf, pads[0], pads[1], Challenger(shape["p"], seed), shape["p"], is_mont=is_mont)
-
-
-KEYS = ("tau", "outer", "r_x", "claims_outer", "r", "inner", "r_y", "claims_inner")
-
-
 @pytest.mark.parametrize("curve", [0, 1])
-@pytest.mark.parametrize("name", list(SHAPES))
+@pytest.mark.parametrize("name", list(SPARTAN_SHAPES))
 def test_prove_bit_exact_against_the_reference(gpu_lib, curve, name):
     from reef_amd.nifs import E, U, W, X, Nifs
-    shape, pads = _shape(curve, name)
+    shape, pads = spartan_shape(curve, name)
     p = shape["p"]
     inst = relaxed_instance(shape, 1, 11 + curve)                   # u != 1, E != 0 (reference folds)
     ref = prove_ref(shape, inst, pads[0], pads[1], Challenger(p, curve))
     for is_mont in (False, True):
         with Nifs(curve, shape["num_cons"], shape["num_vars"], shape["num_io"]) as nf:
-            _upload_shape(nf, shape, is_mont)
-            _set_running(nf, inst, p, is_mont)
-            got = _prove_dev(nf, shape, pads, is_mont, curve)
-            for k in KEYS:
+            upload_shape(nf, shape, is_mont)
+            set_running(nf, inst, p, is_mont)
+            got = prove_dev(nf, shape, pads, is_mont, curve)
+            for k in PROOF_KEYS:
                 assert got[k] == ref[k], f"{k} ({'Montgomery' if is_mont else 'canonical'} form)"
-            assert from_arr(nf.read(W)) == inst["W"] and from_arr(nf.read(E)) == inst["E"]      # the running instance is untouched
-            assert from_arr(nf.read(U)) == [inst["u"]] and from_arr(nf.read(X)) == inst["X"]
+            assert _ints(nf.read(W)) == inst["W"] and _ints(nf.read(E)) == inst["E"]      # the running instance is untouched
+            assert _ints(nf.read(U)) == [inst["u"]] and _ints(nf.read(X)) == inst["X"]
             assert nf.check_relaxed() == (0, None)
 
 
@@ -84,36 +42,36 @@ def test_device_folded_instance_then_fold_after_the_prove(gpu_lib, curve):
     from reef_amd.nifs import E, T, U, W, X, Nifs
     shape = layered_shape(curve, 3000, num_io=3, extra_vars=17, empty_every=23, dup_every=7, long_row=700, seed=60 + curve)
     p, n = shape["p"], shape["num_cons"]
-    pads = _pads(shape, None)
+    pads = pads_of(shape, None)
     rng = random.Random(curve)
     run = running_from_fresh(fresh_instance(shape, 0), n)
-    _, key = _key(curve, n)
+    _, key = ap_key(curve, n)
     with key, Nifs(curve, n, shape["num_vars"], shape["num_io"]) as nf:
-        _upload_shape(nf, shape, False)
-        _set_running(nf, run, p, False, zero_e=True)
+        upload_shape(nf, shape, False)
+        set_running(nf, run, p, False, zero_e=True)
         for step in range(1, 4):
             fresh = fresh_instance(shape, step)
-            nf.commit_t(key, to_arr(fresh["W"]), to_arr(fresh["X"]))
+            nf.commit_t(key, _arr(fresh["W"]), _arr(fresh["X"]))
             r = rng.randrange(p)
             nf.fold(r)
             run = fold(run, fresh, cross_term(shape, run, fresh, p), r, p)
         assert run["u"] != 1 and any(run["E"])
         ref = prove_ref(shape, run, pads[0], pads[1], Challenger(p, 7))
-        got = _prove_dev(nf, shape, pads, False, 7)
-        for k in KEYS:
+        got = prove_dev(nf, shape, pads, False, 7)
+        for k in PROOF_KEYS:
             assert got[k] == ref[k], k
-        got = {"W": from_arr(nf.read(W)), "E": from_arr(nf.read(E)), "u": from_arr(nf.read(U))[0], "X": from_arr(nf.read(X))}
+        got = {"W": _ints(nf.read(W)), "E": _ints(nf.read(E)), "u": _ints(nf.read(U))[0], "X": _ints(nf.read(X))}
         assert got == run
         fresh = fresh_instance(shape, 9)
-        nf.commit_t(key, to_arr(fresh["W"]), to_arr(fresh["X"]))
+        nf.commit_t(key, _arr(fresh["W"]), _arr(fresh["X"]))
         t = cross_term(shape, run, fresh, p)
-        assert from_arr(nf.read(T)) == t
+        assert _ints(nf.read(T)) == t
         nf.fold(12345)
         run = fold(run, fresh, t, 12345, p)
-        assert from_arr(nf.read(W)) == run["W"] and from_arr(nf.read(E)) == run["E"]
+        assert _ints(nf.read(W)) == run["W"] and _ints(nf.read(E)) == run["E"]
         assert nf.check_relaxed() == (0, None)
         # a second prove on the new running instance (the workspace is reused)
-        assert _prove_dev(nf, shape, pads, False, 8)["claims_inner"] == prove_ref(shape, run, pads[0], pads[1], Challenger(p, 8))["claims_inner"]
+        assert prove_dev(nf, shape, pads, False, 8)["claims_inner"] == prove_ref(shape, run, pads[0], pads[1], Challenger(p, 8))["claims_inner"]
 
 
 def test_2_20_rows_by_the_verifier_identities(gpu_lib):
@@ -125,15 +83,14 @@ def test_2_20_rows_by_the_verifier_identities(gpu_lib):
     p, n = shape["p"], shape["num_cons"]
     inst = running_from_fresh(fresh_instance(shape, 1), n)
     inst["u"] = 5                                                     # relaxed: E makes up the difference row by row
-    from test_nifs_host import matvec
     z = inst["W"] + [5] + inst["X"]
     az, bz, cz = (matvec(shape[m], z, n, p) for m in "ABC")
     inst["E"] = [(a * b - 5 * c) % p for a, b, c in zip(az, bz, cz)]
     pads = (1 << 20, next_pow2(shape["num_vars"]))
     with Nifs(curve, n, shape["num_vars"], shape["num_io"]) as nf:
-        _upload_shape(nf, shape, False)
-        _set_running(nf, inst, p, False)
-        got = _prove_dev(nf, shape, pads, False, 3)
+        upload_shape(nf, shape, False)
+        set_running(nf, inst, p, False)
+        got = prove_dev(nf, shape, pads, False, 3)
     verify(shape, inst, pads[0], pads[1], got, Challenger(p, 3))
 
 
@@ -145,7 +102,7 @@ def test_order_and_argument_errors(gpu_lib, curve):
     shape = layered_shape(curve, 20, num_io=2, seed=5)
     p, n, nv, nio = shape["p"], shape["num_cons"], shape["num_vars"], shape["num_io"]
     inst = running_from_fresh(fresh_instance(shape, 1), n)
-    ncp, nvp = _pads(shape, None)
+    ncp, nvp = pads_of(shape, None)
     ell_x, ell_y = ncp.bit_length() - 1, (2 * nvp).bit_length() - 1
     tau = list(range(3, 3 + ell_x))
 
@@ -158,9 +115,9 @@ def test_order_and_argument_errors(gpu_lib, curve):
 
     with Nifs(curve, n, nv, nio) as nf:
         sp = Spartan(nf)
-        _upload_shape(nf, shape, False)
+        upload_shape(nf, shape, False)
         arg_error(sp.begin, ncp, nvp, tau)                                     # no running instance yet
-        _set_running(nf, inst, p, False)
+        set_running(nf, inst, p, False)
         arg_error(sp.outer_round, 7, expect="reef_spartan_begin")              # a round before begin
         arg_error(sp.begin, ncp // 2, nvp, tau[:-1])                           # num_cons_pad < num_cons
         arg_error(sp.begin, ncp + 2, nvp, tau)                                 # not a power of two
@@ -185,15 +142,15 @@ def test_order_and_argument_errors(gpu_lib, curve):
         arg_error(sp.inner_round, 5, expect="reef_spartan_begin")              # nothing after the claims
         # the NIFS calls void a prove in progress
         sp.begin(ncp, nvp, tau)
-        _set_running(nf, inst, p, False)
+        set_running(nf, inst, p, False)
         arg_error(sp.outer_round, 5, expect="reef_spartan_begin")
         arg_error(sp.outer_round, 5, expect="reef_spartan_begin")
-        _, key = _key(curve, n)
+        _, key = ap_key(curve, n)
         with key:
             for undo in ("commit", "fold"):
                 sp.begin(ncp, nvp, tau)
                 fresh = fresh_instance(shape, 2)
-                nf.commit_t(key, to_arr(fresh["W"]), to_arr(fresh["X"]))
+                nf.commit_t(key, _arr(fresh["W"]), _arr(fresh["X"]))
                 if undo == "fold":
                     sp.begin(ncp, nvp, tau)
                     nf.fold(3)
@@ -207,6 +164,6 @@ def test_order_and_argument_errors(gpu_lib, curve):
         # the ctx is still usable: a whole prove matches the reference
         pads = (ncp, nvp)
         ref = prove_ref(shape, inst, ncp, nvp, Challenger(p, 1))
-        got = _prove_dev(nf, shape, pads, False, 1)
-        for k in KEYS:
+        got = prove_dev(nf, shape, pads, False, 1)
+        for k in PROOF_KEYS:
             assert got[k] == ref[k], k

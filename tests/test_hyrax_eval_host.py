@@ -1,4 +1,4 @@
-"""The Hyrax consistency argument on the host (include/reef_msm.h 3i): the big-integer reference of tests/hyrax_ref.py checked by its
+"""The Hyrax consistency argument on the host (include/reef_msm.h 3i): the big-integer reference of oracle/hyrax_oracle.py checked by its
 verifier -- honest transcripts with and without the per-round h blinds pass, a changed L, R, a_hat or challenge fails -- and against
 oracle/mle_oracle.py for LZ and eval; the library's new symbols agree with their ctypes signatures and INTEGRATION 2i's Rust block."""
 import ctypes
@@ -9,12 +9,12 @@ import re
 import numpy as np
 import pytest
 
-from hyrax_ref import blind_total, bound_ref, hyrax_ref, verify_hyrax
+from abi_text import header_prototypes, rust_kind, split_top, strip_comments
 from oracle import mle_oracle, pasta_ref
-from test_integration_doc import _header_prototypes, _rust_kind, _split_top, _strip_comments
-from test_nifs_host import field
-from test_spartan_host import Challenger, eq_evals
-from test_spartan_open_host import gens_of, msm
+from oracle.hyrax_oracle import blind_total, bound_ref, hyrax_ref, verify_hyrax
+from oracle.ipa_oracle import gens_of, msm
+from oracle.r1cs_oracle import field
+from oracle.spartan_oracle import Challenger, eq_evals
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("reef_hyrax_create", "reef_hyrax_destroy", "reef_hyrax_eval_begin", "reef_hyrax_eval_comm", "reef_hyrax_ipa_begin",
@@ -130,7 +130,7 @@ def _ctypes_kind(t):
 def test_header_ctypes_and_integration_agree_on_the_new_symbols():
     from reef_amd import _ffi
     lib = _ffi.load()
-    protos = _header_prototypes()
+    protos = header_prototypes()
     for name in SYMBOLS:
         assert name in protos and name in _ffi.declared_symbols(), name
         fn = getattr(lib, name)
@@ -143,8 +143,8 @@ def test_header_ctypes_and_integration_agree_on_the_new_symbols():
     block = m.group(0)
     seen = set()
     for f in re.finditer(r"\bfn\s+(reef_hyrax_\w+)\s*\(((?:[^;{}()\[\]]|\[[^\]]*\])*?)\)\s*(?:->\s*([^;{]+?))?\s*;", block, flags=re.S):
-        name, args, ret = f.group(1), _strip_comments(f.group(2)), (f.group(3) or "void").strip()
-        got = (_rust_kind(ret), [_rust_kind(a.split(":", 1)[1]) for a in _split_top(args)])
+        name, args, ret = f.group(1), strip_comments(f.group(2)), (f.group(3) or "void").strip()
+        got = (rust_kind(ret), [rust_kind(a.split(":", 1)[1]) for a in split_top(args)])
         assert got == protos[name], f"{name}: INTEGRATION 2i {got}, header {protos[name]}"
         seen.add(name)
     assert seen == set(SYMBOLS), sorted(set(SYMBOLS) - seen)

@@ -17,13 +17,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from mont_grid import KINDS, PAIRS, check_limbs, mont, operand, value
 from oracle.pasta_oracle import CURVES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "reef_amd", "csrc")
 SO = os.path.join(ROOT, "reef_amd", "_lib", "libreef_montcheck.so")
-MASK = (1 << 29) - 1
-RP = 1 << 261
 FIELDS = {"pallas": 0, "vesta": 1}
 
 
@@ -40,38 +39,6 @@ def lib():
     return h
 
 
-def value(l):
-    return sum(int(x) << (29 * i) for i, x in enumerate(l))
-
-
-def mont(t, m):
-    q = (-t * pow(m, -1, RP)) % RP
-    assert (t + q * m) % RP == 0
-    return (t + q * m) // RP
-
-
-def operand(rng, m, bound, kind):
-    """Nine limbs, normalised (limb 0 < 2^29, limbs 1..7 <= 2^29 + 7), value < bound * M."""
-    lim = int(bound * m) - 1
-    if kind == "zero":
-        return [0] * 9
-    if kind == "max":      # every low limb at its bound, the top limb as large as the value bound allows
-        low = [MASK] + [MASK + 8] * 7
-    elif kind == "top":    # canonical low limbs, value just below the bound
-        v = lim - int(rng.integers(0, 1 << 20))
-        return [(v >> (29 * i)) & MASK for i in range(8)] + [v >> 232]
-    else:
-        low = [int(rng.integers(0, 1 << 29))] + [int(rng.integers(0, MASK + 9)) for _ in range(7)]
-    rest = lim - value(low + [0])
-    assert rest >= 0
-    top_max = rest >> 232
-    top = top_max if kind == "max" else int(rng.integers(0, top_max + 1))
-    return low + [top]
-
-
-KINDS = ["max", "top", "zero"] + ["rand"] * 61
-
-
 def run(lib, f, op, k, ops, bounds):
     n = len(ops[0])
     arrs = [np.array(x, dtype=np.uint32).reshape(n, 9) for x in ops]
@@ -81,17 +48,6 @@ def run(lib, f, op, k, ops, bounds):
     b = np.array(list(bounds) + [0.0] * (4 - len(bounds)), dtype=np.float64)
     lib.mc_op(f, op, k, *[a.ctypes.data for a in arrs], b.ctypes.data, out.ctypes.data, n)
     return out
-
-
-def check_limbs(r, m, vmax, want):
-    assert all(int(x) <= MASK for x in r[:8]), [hex(int(x)) for x in r]
-    v = value(r)
-    assert v == want, (hex(v), hex(want))
-    assert v < vmax * m
-
-
-# (A/M, B/M) pairs with (A/M)(B/M) < 128: balanced, lopsided, and the operands of the group law (ec.h: 9.02 x 5.04)
-PAIRS = [(1.0, 1.0), (2.0, 2.0), (11.3, 11.3), (2.0, 63.9), (1.0, 127.9), (9.02, 5.04), (5.2, 5.2)]
 
 
 @pytest.mark.parametrize("name", list(FIELDS))

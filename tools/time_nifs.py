@@ -16,26 +16,15 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from oracle import pasta_ref as R                     # noqa: E402
 from reef_amd.msm import MsmContext                    # noqa: E402
 from reef_amd.nifs import Nifs                         # noqa: E402
+from _synthetic import synthetic_matrix                # noqa: E402
 
 SHAPES = [("secondary", 11376), ("cfg3", 27790), ("cfg4", 39484), ("cfg5", 1032421)]
 HBM = 8e12
-
-
-def synthetic_matrix(rng, n, nz, long_rows):
-    lens = rng.integers(2, 5, size=n)
-    lens[long_rows] = 10000
-    rows = np.repeat(np.arange(n, dtype=np.uint32), lens)
-    cols = rng.integers(0, nz, size=rows.shape[0], dtype=np.uint32)
-    kind = rng.integers(0, 8, size=rows.shape[0])
-    vals = np.zeros((rows.shape[0], 4), dtype=np.uint64)
-    vals[:, 0] = np.where(kind < 4, 1, rng.integers(2, 1 << 16, size=rows.shape[0]))     # +1, or a small value
-    full = kind == 7                                                                       # one in eight: full width (< 2^250)
-    vals[full] = rng.integers(0, 1 << 62, size=(int(full.sum()), 4), dtype=np.uint64)
-    return rows, cols, vals, int(full.sum())
 
 
 def timed(fn, reps):

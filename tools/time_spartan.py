@@ -3,7 +3,7 @@
     python tools/time_spartan.py [reps] [--quick]
 
 Per curve and padded size (num_cons_pad = num_vars_pad = 2^14, 2^15, 2^16, 2^20): a NIFS ctx with SYNTHETIC matrices (the
-generator of tools/time_nifs.py: 2-4 entries per row and matrix, one coefficient in eight full-width, four long rows of 10^4
+generator of tools/_synthetic.py: 2-4 entries per row and matrix, one coefficient in eight full-width, four long rows of 10^4
 entries; num_cons = num_vars = the padded size minus 3, num_io = 2) and a random running instance.  They say nothing about
 Reef's real matrices.  Reported: begin (the row pass, eq(tau), round 0), the mean outer round, outer_claims, inner_begin (the ABC
 pass and round 0), the mean inner round, inner_claims and the whole prove, each the median over `reps` proves, host to host.
@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from reef_amd.nifs import Nifs                         # noqa: E402
 from reef_amd.spartan import Spartan                   # noqa: E402
-from time_nifs import synthetic_matrix                 # noqa: E402
+from _synthetic import synthetic_matrix                # noqa: E402
 
 SIZES = [14, 15, 16, 20]
 

@@ -5,7 +5,7 @@ reef_ipa_cross_terms with a uploaded from the host as the baseline round.
     python tools/time_spartan_open.py --one          (one prove and ONE opening, Pallas at 2^16, no baseline: for rocprofv3)
 
 Per curve and padded size (num_cons_pad = num_vars_pad = 2^14, 2^15, 2^16, 2^20): a NIFS ctx with SYNTHETIC matrices (the
-generator of tools/time_nifs.py; num_cons = num_vars = the padded size minus 3, num_io = 2), a random running instance, one prove of
+generator of tools/_synthetic.py; num_cons = num_vars = the padded size minus 3, num_io = 2), a random running instance, one prove of
 both sum-checks (3g), then `reps` openings on it, each with random challenges.  The key is gens_v with default options (reported:
 its kind).  Reported: begin (eq tables, cross term), fold, the mean IPA round (fold + next L, R), ipa_begin, finish and the whole
 opening, each the median over the openings, host to host.  Baseline, in the same process on the same key: reef_ipa_cross_terms
@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from reef_amd import msm                               # noqa: E402
 from reef_amd.nifs import Nifs                         # noqa: E402
 from reef_amd.spartan import Opening, Spartan          # noqa: E402
-from time_nifs import synthetic_matrix                 # noqa: E402
+from _synthetic import synthetic_matrix                # noqa: E402
 from time_spartan import one_prove                     # noqa: E402
 
 SIZES = [14, 15, 16, 20]
