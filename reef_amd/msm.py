@@ -240,6 +240,9 @@ class MsmContext(_Handle):
 
     def msm_rows(self, scalars: Buf, rows: int, row_len: int, *, is_mont: bool = True, max_scalar_bits: int = 0,
                  blinds: Optional[Buf] = None, h: Optional[Buf] = None, out: Optional[Buf] = None) -> Buf:
+        """reef_msm_rows: rows commitments over the first row_len bases (+ blinds[r] * h).  max_scalar_bits bounds the canonical scalars; 0 measures
+        the width on the device.  The bound is TRUSTED -- it picks the window size and how many windows are recoded -- so a bound below the bit
+        length of the widest scalar gives undefined results (the high bits are dropped without an error); one that is too large is always safe."""
         if row_len > self.n:
             raise ValueError(f"row_len = {row_len} exceeds the key length {self.n}")
         if (blinds is None) != (h is None):
