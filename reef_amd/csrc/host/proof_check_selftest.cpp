@@ -1,0 +1,18 @@
+// proof_check_selftest [nifs|spartan|open|hyrax] -- the prove leg's checks (proof_check.hpp) on a tiny honest transcript, as a program
+// of its own: no GPU and no libreef_msm.so, so it also runs under host sanitizers.  Prints and exits with what
+// reef_replay_check_selftest() of libreef_replay.so writes and returns: the JSON line and 0, a rejection and 1, a usage error and 2.
+#include "proof_check.hpp"
+
+int main(int argc, char **argv) {
+    int rc = 0;
+    std::string line;
+    try {
+        line = check_selftest(argc > 1 ? argv[1] : "");
+    } catch (const Rejected &e) {
+        line = e.what(), rc = 1;
+    } catch (const std::exception &e) {
+        line = e.what(), rc = 2;
+    }
+    printf("%s\n", line.c_str());
+    return rc;
+}

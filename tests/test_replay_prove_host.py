@@ -1,9 +1,11 @@
 """The prove leg of the replay (reef_amd/csrc/host/reef_replay.cpp, `reef_replay cfgN prove`) on the host: its exports, and its
-checks run on a tiny honest transcript made on the host -- the NIFS bookkeeping, the two sum-check identities, the verifier's sparse
+checks (host/proof_check.hpp) run on a tiny honest transcript made on the host -- the NIFS bookkeeping, the two sum-check identities, the verifier's sparse
 evaluation and the IPA identities of the opening and of the Hyrax argument -- which they must accept, and, with one recorded value
 altered, reject naming the phase.  No GPU: libreef_replay.so loads without one."""
 import ctypes
 import inspect
+import os
+import subprocess
 
 import pytest
 
@@ -37,6 +39,18 @@ def test_an_unknown_tamper_phase_is_a_usage_error():
     buf = ctypes.create_string_buffer(512)
     assert replay._load().reef_replay_check_selftest(b"everything", buf, len(buf)) == 2
     assert b"one of nifs, spartan, open, hyrax" in buf.value
+
+
+def test_the_host_only_checker_program_agrees_with_the_library():
+    """proof_check_selftest is proof_check.hpp linked WITHOUT libreef_msm.so (host/Makefile): the same exit code and the same line as
+    the library's entry point, for an honest transcript, every tampered phase and a usage error."""
+    exe = os.path.join(os.path.dirname(replay.LIB_PATH), "proof_check_selftest")
+    for arg, rc in [("", 0), ("nifs", 1), ("spartan", 1), ("open", 1), ("hyrax", 1), ("bogus", 2)]:
+        run = subprocess.run([exe, arg], capture_output=True, text=True, timeout=60)
+        buf = ctypes.create_string_buffer(4096)
+        assert replay._load().reef_replay_check_selftest(arg.encode(), buf, len(buf)) == rc, arg
+        assert run.returncode == rc, (arg, run.stderr)
+        assert run.stdout == buf.value.decode() + "\n", arg
 
 
 def test_the_msm_replay_defaults_are_unchanged():
