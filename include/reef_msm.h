@@ -28,6 +28,7 @@
  *      Later, still 7 (symbols added, none changed): the batched IPA opening of the final SNARK on the same ctx
  *      (reef_spartan_open_*, section 3h).
  *      Later, still 7 (symbols added, none changed): the Hyrax consistency argument on a resident document (reef_hyrax_*, section 3i).
+ *      Later, still 7 (symbols added, none changed): K4's inverse, reef_decompress, and reef_hyrax_eval_comm_compressed on top of it.
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -246,6 +247,15 @@ reef_status reef_fold(int curve, const reef_affine *gens, size_t half, int loc, 
  * (src/backend/commitment.rs:195,351,365,425,427,431).  Either output may be NULL. */
 reef_status reef_normalize(int curve, const reef_jacobian *in, size_t n, int loc, reef_affine *out_affine,
                            uint8_t *out_compressed);
+
+/* K4 inverse: n 32-byte encodings -> affine (ABI form).  Replaces CompressedCommitment::decompress [R] over PolyCommit.comm
+ * (src/backend/commitment.rs:60,192-197; HyraxPC::prove_eval).  The rule is pasta_curves' from_bytes [R]: 32 zero bytes are the
+ * identity, (0, 0); otherwise bit 255 is the parity of y and the low 255 bits are x, little-endian; x >= p or x^3 + 5 a non-residue
+ * (00..00 80 among them: x = 0) is invalid.  Invalid entries give (0,0); *invalid (host, may be NULL) = how many,
+ * *first_invalid (host, may be NULL) = the lowest such index (n when none).  REEF_OK whenever the batch was decoded.
+ * loc names the memory of both `in` and out_affine; device buffers are 16-byte aligned (as reef_normalize's out_compressed). */
+reef_status reef_decompress(int curve, const uint8_t *in, size_t n, int loc, reef_affine *out_affine,
+                            uint64_t *invalid, uint64_t *first_invalid);
 
 /* Sum of n Jacobian points (multi-GPU: combine the per-rank partial MSMs after an all-gather). */
 reef_status reef_sum_points(int curve, const reef_jacobian *in, size_t n, int loc, reef_jacobian *out);
@@ -552,6 +562,11 @@ reef_status reef_spartan_open_read(reef_nifs_ctx *ctx, int which, size_t count, 
  *                       (affine, host or device per loc), one MSM on the device on a plain key of this ctx's device.  The
  *                       key is rebuilt from row_comms (one upload of 2^left_vars points) unless they are the host bytes of the
  *                       previous call; device row_comms are uploaded every time.
+ * reef_hyrax_eval_comm_compressed  the same from the rows as Reef holds them (PolyCommit.comm, what a .cmt file holds): 2^left_vars x 32
+ *                       bytes, host or device (16-byte aligned).  Decoded on the ctx's device (reef_decompress's kernel) straight into the
+ *                       buffer the key is built from: no affine point visits the host.  The same host bytes as the previous call skip the
+ *                       decode and the re-key.  An invalid row is REEF_ERR_ARG naming the first such row; the ctx stays usable and keeps
+ *                       the row commitments it had.
  * reef_hyrax_ipa_begin  q: affine, pasta Montgomery coordinates; h: the optional blinding point, blinds[2]: its blinds for round 0
  *                       (the term is on when both are given, for the whole argument); round 0's L and R.
  * reef_hyrax_ipa_round  folds a and b with r; the next round's L and R; blinds: that round's two blinds (NULL = zeros; an error
@@ -569,6 +584,8 @@ reef_status reef_hyrax_create(reef_hyrax_ctx **out, int curve, const void *z, si
 void reef_hyrax_destroy(reef_hyrax_ctx *ctx);
 reef_status reef_hyrax_eval_begin(reef_hyrax_ctx *ctx, reef_msm_ctx *key, const reef_fe *point, bool is_mont, reef_fe *eval, reef_fe *lz_blind);
 reef_status reef_hyrax_eval_comm(reef_hyrax_ctx *ctx, const reef_affine *row_comms, int loc, reef_jacobian *comm_lz);
+/* reef_hyrax_eval_comm from the rows as Reef holds them (PolyCommit.comm): 2^left_vars x 32 bytes, host or device. */
+reef_status reef_hyrax_eval_comm_compressed(reef_hyrax_ctx *ctx, const uint8_t *row_comms32, int loc, reef_jacobian *comm_lz);
 reef_status reef_hyrax_ipa_begin(reef_hyrax_ctx *ctx, const reef_affine *q, const reef_affine *h, const reef_fe *blinds, bool is_mont,
                                  reef_jacobian *L, reef_jacobian *R);
 reef_status reef_hyrax_ipa_round(reef_hyrax_ctx *ctx, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R);
@@ -650,7 +667,10 @@ reef_status reef_msm_plan_for(size_t n, uint32_t window_bits, uint32_t bucket_gr
                               uint32_t *windows, uint32_t *groups, uint32_t *tables);
 
 /* Device self-tests used by the parity suite (element-wise kernels over n inputs, HOST buffers).
- * field: 0 Fp, 1 Fq.  op: 0 mul 1 add 2 sub 3 inv 4 to_mont 5 from_mont 6 neg 7 sqr. */
+ * field: 0 Fp, 1 Fq.  op: 0 mul 1 add 2 sub 3 inv 4 to_mont 5 from_mont 6 neg 7 sqr; 8 sqrt: out[i] = the root of a[i] whose canonical
+ * integer is even, in the form the other ops use, or 32 bytes of 0xff when a[i] is a non-residue -- by the root reef_decompress ships
+ * (fixed trip count, 4-bit windows); 9 the same by Tonelli-Shanks, the root of reef_derive_generators (same bytes; for comparison
+ * and timing). */
 reef_status reef_test_field_op(int field, int op, const reef_fe *a, const reef_fe *b, reef_fe *out, size_t n);
 /* op: 0 mixed add P+Q, 1 general add, 2 double P, 3 k*P (k canonical in kbuf); the four-wave forms of the tail
  * kernels: 4 general add, 5 double, 6 the chain 4*(P + Q) + P, 7-10 latency probes, 11-19 every back-to-back order

@@ -110,6 +110,7 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_ipa_cross_terms": (c_int, [vp, vp, c_size_t, c_int, c_bool, vp, vp, c_size_t, vp, vp]),
         "reef_fold": (c_int, [c_int, vp, c_size_t, c_int, vp, vp, vp]),
         "reef_normalize": (c_int, [c_int, vp, c_size_t, c_int, vp, vp]),
+        "reef_decompress": (c_int, [c_int, vp, c_size_t, c_int, vp, POINTER(c_uint64), POINTER(c_uint64)]),
         "reef_mle_bound_rows": (c_int, [c_int, vp, c_size_t, c_int, c_int, c_bool, vp, c_size_t, c_size_t, vp, c_int, vp]),
         "reef_sum_points": (c_int, [c_int, vp, c_size_t, c_int, vp]),
         "reef_gen_bases": (c_int, [c_int, c_uint64, c_uint64, c_size_t, vp, c_int]),
@@ -181,6 +182,7 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_hyrax_destroy": (None, [vp]),
         "reef_hyrax_eval_begin": (c_int, [vp, vp, vp, c_bool, vp, vp]),
         "reef_hyrax_eval_comm": (c_int, [vp, vp, c_int, vp]),
+        "reef_hyrax_eval_comm_compressed": (c_int, [vp, vp, c_int, vp]),
         "reef_hyrax_ipa_begin": (c_int, [vp, vp, vp, vp, c_bool, vp, vp]),
         "reef_hyrax_ipa_round": (c_int, [vp, vp, vp, c_bool, vp, vp]),
         "reef_hyrax_finish": (c_int, [vp, vp, c_bool, vp, vp]),

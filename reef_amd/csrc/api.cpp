@@ -412,6 +412,9 @@ reef_status reef_mle_bound_rows(int curve, const void *z, size_t n, int elem_byt
 reef_status reef_normalize(int curve, const reef_jacobian *in, size_t n, int loc, reef_affine *out_affine, uint8_t *out_compressed) {
     return stateless(curve, [&](const CurveVTable *v) { return v->normalize(in, n, loc, out_affine, out_compressed); });
 }
+reef_status reef_decompress(int curve, const uint8_t *in, size_t n, int loc, reef_affine *out_affine, uint64_t *invalid, uint64_t *first_invalid) {
+    return stateless(curve, [&](const CurveVTable *v) { return v->decompress(in, n, loc, out_affine, invalid, first_invalid); });
+}
 reef_status reef_sum_points(int curve, const reef_jacobian *in, size_t n, int loc, reef_jacobian *out) {
     return stateless(curve, [&](const CurveVTable *v) { return v->sum_points(in, n, loc, out); });
 }
@@ -546,6 +549,9 @@ reef_status reef_hyrax_eval_begin(reef_hyrax_ctx *ctx, reef_msm_ctx *key, const 
 }
 reef_status reef_hyrax_eval_comm(reef_hyrax_ctx *ctx, const reef_affine *row_comms, int loc, reef_jacobian *comm_lz) {
     return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->eval_comm(impl, row_comms, loc, comm_lz); });
+}
+reef_status reef_hyrax_eval_comm_compressed(reef_hyrax_ctx *ctx, const uint8_t *row_comms32, int loc, reef_jacobian *comm_lz) {
+    return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->eval_comm_compressed(impl, row_comms32, loc, comm_lz); });
 }
 reef_status reef_hyrax_ipa_begin(reef_hyrax_ctx *ctx, const reef_affine *q, const reef_affine *h, const reef_fe *blinds, bool is_mont,
                                  reef_jacobian *L, reef_jacobian *R) {

@@ -447,7 +447,8 @@ struct CurveVTable {
     // row N1: commitment-key derivation (hash to the curve; coordinates in the curve's base field)
     reef_status (*derive_generators)(const uint8_t *label, size_t label_len, size_t n, const reef_keygen_params *kp, bool is_mont, reef_affine *out,
                                      int out_loc);
-    reef_status (*plan_for)(size_t n, uint32_t c_opt, uint32_t g_opt, uint32_t *c, uint32_t *w, uint32_t *g, uint32_t *t);
+    reef_status (*plan_for)(size_t n, uint32_t c_opt, uint32_t g_opt, uint32_t *c, uint32_t *w, uint32_t *g, uint32_t *t);    // K4's inverse: 32-byte encodings -> affine points (coordinates in the curve's base field)
+    reef_status (*decompress)(const uint8_t *in, size_t n, int loc, reef_affine *out_aff, uint64_t *invalid, uint64_t *first_invalid);
 };
 
 const CurveVTable *pallas_vtable();
@@ -504,6 +505,7 @@ struct HyraxVTable {
     reef_status (*ipa_round)(void *impl, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R);
     reef_status (*finish)(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat);
     reef_status (*read)(void *impl, int which, size_t count, reef_fe *out, bool to_mont);
+    reef_status (*eval_comm_compressed)(void *impl, const uint8_t *row_comms32, int loc, reef_jacobian *comm_lz);
 };
 const HyraxVTable *pallas_hyrax_vtable();
 const HyraxVTable *vesta_hyrax_vtable();

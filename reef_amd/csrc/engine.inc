@@ -1786,6 +1786,59 @@ static reef_status v_normalize(const reef_jacobian *in, size_t n, int loc, reef_
     return REEF_OK;
 }
 
+// K4's inverse (decompress_kernels.inc).  The decode of n encodings on stream s, device pointers; stats: two 64-bit words on the device
+// (how many were invalid, the lowest such index: all ones when none).  The root is the windowed one; the +experiment build takes
+// REEF_DECOMPRESS_ROOT=0 for Tonelli-Shanks (tools/time_decompress.py compares the two).
+template <int C>
+static void decompress_launch(hipStream_t s, const fe256 *d_in, size_t n, affine256 *d_out, unsigned long long *d_stats, hipEvent_t before_kernel = nullptr) {
+    const char *e = exp_env("REEF_DECOMPRESS_ROOT");
+    (void)hipMemsetAsync(d_stats, 0, sizeof(u64), s);
+    (void)hipMemsetAsync(d_stats + 1, 0xff, sizeof(u64), s);
+    if (before_kernel) (void)hipEventRecord(before_kernel, s);
+    if (e && e[0] == '0') hipLaunchKernelGGL((k_decompress<C, false>), dim3(ceil_div(n, 64)), dim3(64), 0, s, d_in, (u32)n, d_out, d_stats);
+    else hipLaunchKernelGGL((k_decompress<C, true>), dim3(ceil_div(n, 64)), dim3(64), 0, s, d_in, (u32)n, d_out, d_stats);
+}
+template <int C>
+static reef_status v_decompress(const uint8_t *in, size_t n, int loc, reef_affine *out_aff, uint64_t *invalid, uint64_t *first_invalid) {
+    if (n && (!in || !out_aff)) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (n >= (1ull << 32)) { set_error("reef_decompress: %zu encodings, the limit is 2^32 - 1", n); return REEF_ERR_ARG; }
+    if (loc == REEF_DEVICE && (((uintptr_t)in | (uintptr_t)out_aff) & 15)) { set_error("reef_decompress: device buffers must be 16-byte aligned"); return REEF_ERR_ARG; }
+    if (invalid) *invalid = 0;
+    if (first_invalid) *first_invalid = n;
+    if (n == 0) return REEF_OK;
+    ScratchStream ss;
+    REEF_TRY(ss.init());
+    const fe256 *d_in;
+    affine256 *d_out;
+    void *d_stats;
+    REEF_TRY(stage_in<fe256>(ss, &d_in, in, n, loc));
+    REEF_TRY(stage_out<affine256>(ss, &d_out, out_aff, n, loc));
+    REEF_TRY(ss.alloc(&d_stats, 2 * sizeof(u64)));
+    // the +experiment build times the kernel alone on request and leaves the figure where reef_last_error() finds it (the call still returns REEF_OK)
+    const bool timed = exp_env("REEF_DECOMPRESS_EVENTS") != nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (timed) {
+        REEF_HIP_TRY(hipEventCreate(&e0));
+        REEF_HIP_TRY(hipEventCreate(&e1));
+    }
+    decompress_launch<C>(ss.s, d_in, n, d_out, (unsigned long long *)d_stats, e0);
+    if (timed) REEF_HIP_TRY(hipEventRecord(e1, ss.s));
+    REEF_HIP_TRY(hipGetLastError());
+    u64 stats[2] = {0, 0};
+    REEF_HIP_TRY(hipMemcpyAsync(stats, d_stats, sizeof stats, hipMemcpyDeviceToHost, ss.s));
+    REEF_TRY(finish_out<affine256>(ss, d_out, out_aff, n, loc));
+    if (invalid) *invalid = stats[0];
+    if (first_invalid) *first_invalid = stats[0] ? stats[1] : n;
+    if (timed) {
+        float ms = 0;
+        REEF_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        set_error("reef_decompress: kernel %.3f us", ms * 1e3);
+    }
+    return REEF_OK;
+}
+
 template <int C> static reef_status v_sum_points(const reef_jacobian *in, size_t n, int loc, reef_jacobian *out) {
     if (!in || !out || n > 65536) { set_error("bad argument"); return REEF_ERR_ARG; }
     ScratchStream ss;
@@ -1836,7 +1889,9 @@ template <int C> static reef_status v_test_field_op(int op, const reef_fe *a, co
     REEF_TRY(stage_in<fe256>(ss, &da, a, n, REEF_HOST));
     REEF_TRY(stage_in<fe256>(ss, &db, b, n, REEF_HOST));
     REEF_TRY(stage_out<fe256>(ss, &dout, out, n, REEF_HOST));
-    hipLaunchKernelGGL(k_test_field<C>, dim3(ceil_div(n, 64)), dim3(64), 0, ss.s, op, da, db, dout, (u32)n);
+    if (op == 8) hipLaunchKernelGGL((k_test_sqrt<C, true>), dim3(ceil_div(n, 64)), dim3(64), 0, ss.s, da, dout, (u32)n);          // the root that ships
+    else if (op == 9) hipLaunchKernelGGL((k_test_sqrt<C, false>), dim3(ceil_div(n, 64)), dim3(64), 0, ss.s, da, dout, (u32)n);   // Tonelli-Shanks
+    else hipLaunchKernelGGL(k_test_field<C>, dim3(ceil_div(n, 64)), dim3(64), 0, ss.s, op, da, db, dout, (u32)n);
     return finish_out<fe256>(ss, dout, out, n, REEF_HOST);
 }
 
@@ -1929,7 +1984,7 @@ template <int C> static CurveVTable make_vtable() {
     return CurveVTable{v_ctx_create<C>, v_ctx_rekey<C>, v_ctx_clone<C>, v_ctx_attach<C>, v_ctx_destroy<C>, v_ctx_sync<C>, v_ctx_stream<C>,
                        v_ctx_timing<C>, v_ctx_enable_timing<C>, v_ctx_window_split<C>, v_ctx_timing_stats<C>, v_ctx_sum_points<C>, v_ctx_plan<C>, v_ctx_byte_tables<C>, v_msm<C>, v_msm_rows<C>, v_msm_rows_symbols<C>, v_ipa_cross<C>, v_msm_folded<C>, v_fold<C>, v_normalize<C>, v_sum_points<C>,
                        v_gen_bases<C>, v_gen_scalars<C>, v_test_field_op<C>, v_test_ec_op<C>, v_bench_fmul<C>,
-                       v_sc_create<C>, v_sc_destroy<C>, v_sc_set<C>, v_sc_read<C>, v_sc_coeffs<C>, v_sc_fold<C>, v_sc_fold_coeffs<C>, v_sc_gen_eq<C>, v_sc_reset<C>, v_sc_sync<C>, v_mle_bound<C>, v_merkle_commit<C>, v_derive_generators<C>, plan_for};
+                       v_sc_create<C>, v_sc_destroy<C>, v_sc_set<C>, v_sc_read<C>, v_sc_coeffs<C>, v_sc_fold<C>, v_sc_fold_coeffs<C>, v_sc_gen_eq<C>, v_sc_reset<C>, v_sc_sync<C>, v_mle_bound<C>, v_merkle_commit<C>, v_derive_generators<C>, plan_for, v_decompress<C>};
 }
 
 }  // namespace reef

@@ -12,6 +12,7 @@
 //       ::commit / ::commit_rows / ::commit_symbols   CE::commit split by Pippenger window over the devices, HyraxPC::commit rows dealt out whole
 //   SumCheck                                      gen_eq_table / linear_mle_product      src/backend/r1cs_helper.rs:441-544, driven as in r1cs.rs:2318-2385
 //   compress()                                    Commitment::compress                   src/backend/commitment.rs:195,351,365
+//   decompress()                                  CompressedCommitment::decompress [R]   src/backend/commitment.rs:192-197 (a batch per call)
 //   CommitmentGens<CURVE>(label, n, params [, h]) CommitmentGens::new(label, n) / new_with_blinding_gen      src/backend/framework.rs:297-303, commitment.rs:146-149,176-180
 //   MerkleCommitment<CURVE>(doc, pc)              MerkleCommitment::new(&doc, &pc), path_wits, make_wits     src/backend/merkle_tree.rs:25-190
 //   Nifs<CURVE>                                   NIFS::prove's vector work (row N6)     RecursiveSNARK::prove_step, framework.rs:668-675
@@ -49,6 +50,15 @@ template <int CURVE> inline Compressed compress(const reef_jacobian &p) {
     Compressed c;
     check(reef_normalize(CURVE, &p, 1, REEF_HOST, nullptr, c.data()), "reef_normalize");
     return c;
+}
+
+// n encodings (host) -> affine points; throws on the first encoding that is no point, as the reference's unwrap() panics
+template <int CURVE> inline std::vector<reef_affine> decompress(const Compressed *c, size_t n) {
+    std::vector<reef_affine> out(n);
+    uint64_t bad = 0, first = 0;
+    check(reef_decompress(CURVE, n ? c->data() : nullptr, n, REEF_HOST, out.data(), &bad, &first), "reef_decompress");
+    if (bad) throw std::invalid_argument("reef_decompress: encoding " + std::to_string(first) + " is not a point (" + std::to_string(bad) + " invalid)");
+    return out;
 }
 
 // nova-snark CommitmentGens<G>: a vector of generators (+ blinding generator h) resident on the GPU,
@@ -535,9 +545,23 @@ template <int CURVE> class HyraxEval {
     // the 2^left_vars affine row commitments (row_comms_loc memory); q_of(r): the caller's gens_1.scale(r), affine.
     void prove(reef_msm_ctx *gens_v, const reef_fe *point, const reef_affine *row_comms, int row_comms_loc, const Transcript &transcript,
                const std::function<reef_affine(const reef_fe &)> &q_of, Proof &pf) const {
+        prove_with(gens_v, point, transcript, q_of, pf, [&] { check(reef_hyrax_eval_comm(ctx_, row_comms, row_comms_loc, &pf.comm_lz), "reef_hyrax_eval_comm"); });
+    }
+    // the same with the rows as Reef holds them, PolyCommit.comm: 2^left_vars compressed commitments (host), decoded on the device
+    void prove(reef_msm_ctx *gens_v, const reef_fe *point, const Compressed *row_comms, const Transcript &transcript,
+               const std::function<reef_affine(const reef_fe &)> &q_of, Proof &pf) const {
+        prove_with(gens_v, point, transcript, q_of, pf, [&] {
+            check(reef_hyrax_eval_comm_compressed(ctx_, row_comms->data(), REEF_HOST, &pf.comm_lz), "reef_hyrax_eval_comm_compressed");
+        });
+    }
+
+  private:
+    template <class CommLz>
+    void prove_with(reef_msm_ctx *gens_v, const reef_fe *point, const Transcript &transcript, const std::function<reef_affine(const reef_fe &)> &q_of,
+                    Proof &pf, CommLz &&comm_lz) const {
         pf.L.clear(); pf.R.clear(); pf.r_rounds.clear();
         check(reef_hyrax_eval_begin(ctx_, gens_v, point, true, &pf.eval, &pf.lz_blind), "reef_hyrax_eval_begin");
-        check(reef_hyrax_eval_comm(ctx_, row_comms, row_comms_loc, &pf.comm_lz), "reef_hyrax_eval_comm");
+        comm_lz();
         uint8_t u[sizeof(reef_jacobian) + sizeof(reef_fe)];
         memcpy(u, &pf.comm_lz, sizeof(reef_jacobian));
         memcpy(u + sizeof(reef_jacobian), &pf.eval, sizeof(reef_fe));
@@ -554,8 +578,6 @@ template <int CURVE> class HyraxEval {
             else check(reef_hyrax_finish(ctx_, &pf.r_rounds.back(), true, &pf.a_hat, &pf.b_hat), "reef_hyrax_finish");
         }
     }
-
-  private:
     reef_hyrax_ctx *ctx_ = nullptr;
     size_t num_vars_, left_;
 };

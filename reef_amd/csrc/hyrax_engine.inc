@@ -18,6 +18,8 @@ template <int C> struct HyraxCtx : DeviceCtx {   // ev: orders the key ctx's str
     IpaRun<C> ip;                        // a = LZ, b = eq(point[left..]) and the rounds
     Ctx<C> *comms = nullptr;             // a plain key over the row commitments, made by the first eval_comm
     std::vector<reef_affine> comms_host; // the host row commitments that key holds (empty: device bases, compared never)
+    std::vector<uint8_t> comms_bytes;    // or the host rows it was decoded from, 32 bytes each (eval_comm_compressed); at most one of the two is set
+    DevBuf cenc, cdec, cstat;            // eval_comm_compressed: the encodings of host rows, the decoded rows the key is built from, the decode's two counters
     int phase = HY_NONE;
     u32 rounds = 0;
 };
@@ -27,7 +29,7 @@ template <int C> static void hyrax_free(HyraxCtx<C> *c) {
     if (!c) return;
     retire_device_ctx(c);
     for (DevBuf *b : {&c->z, &c->rb, &c->eqs, &c->part, &c->dot, &c->pts, &c->lint, &c->stage, &c->ip.a, &c->ip.b, &c->ip.partial, &c->ip.out,
-                      &c->ip.blinds, &c->ip.htab})
+                      &c->ip.blinds, &c->ip.htab, &c->cenc, &c->cdec, &c->cstat})
         b->release();
     if (c->comms) v_ctx_destroy<C>(c->comms);
     delete c;
@@ -177,8 +179,30 @@ static reef_status v_hyrax_eval_begin(void *impl, void *key_impl, const reef_fe 
     return REEF_OK;
 }
 
-template <int C> static reef_status v_hyrax_eval_comm(void *impl, const reef_affine *row_comms, int loc, reef_jacobian *comm_lz) {
+// the weights of comm_LZ where the MSM reads them: lint = eq(point[..left]) as canonical integers.  Inside the ctx's scope; waits.
+template <int C> static reef_status hy_row_weights(HyraxCtx<C> *c) {
     constexpr int F = HyraxCtx<C>::F;
+    fe256 *l = c->lint.template as<fe256>();
+    REEF_TRY(fe_eq_table<F>(c->stream, c->pts, c->pt.data(), c->left, l));                 // L = eq(point[..left]), then canonical integers in place
+    hipLaunchKernelGGL(k_fe_export<F>, dim3(ceil_div(c->rows, 256)), dim3(256), 0, c->stream, (const fe256 *)l, (u64)c->rows, 0, 0, l);
+    REEF_HIP_TRY(hipGetLastError());
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    return REEF_OK;
+}
+// the plain key over the row commitments, from `rows` affine points in loc memory: made by the first call, re-keyed by the others
+template <int C> static reef_status hy_set_comms(HyraxCtx<C> *c, const reef_affine *row_comms, int loc) {
+    if (c->comms) return v_ctx_rekey<C>(c->comms, row_comms, c->rows, loc);
+    reef_msm_opts o;
+    memset(&o, 0, sizeof o);
+    o.byte_tables = 2;                                           // a plain key: the bases change with every document
+    o.device = c->device;
+    void *k = nullptr;
+    REEF_TRY(v_ctx_create<C>(&k, row_comms, c->rows, loc, &o));
+    c->comms = (Ctx<C> *)k;
+    return REEF_OK;
+}
+
+template <int C> static reef_status v_hyrax_eval_comm(void *impl, const reef_affine *row_comms, int loc, reef_jacobian *comm_lz) {
     HyraxCtx<C> *c = (HyraxCtx<C> *)impl;
     if (!row_comms || !comm_lz) { set_error("null argument"); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
@@ -187,30 +211,65 @@ template <int C> static reef_status v_hyrax_eval_comm(void *impl, const reef_aff
     {
         DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
         REEF_TRY(scope.enter());
-        fe256 *l = c->lint.template as<fe256>();
-        REEF_TRY(fe_eq_table<F>(c->stream, c->pts, c->pt.data(), c->left, l));                 // L = eq(point[..left]), then canonical integers in place
-        hipLaunchKernelGGL(k_fe_export<F>, dim3(ceil_div(c->rows, 256)), dim3(256), 0, c->stream, (const fe256 *)l, (u64)c->rows, 0, 0, l);
-        REEF_HIP_TRY(hipGetLastError());
-        REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+        REEF_TRY(hy_row_weights(c));
     }
     const bool same = loc != REEF_DEVICE && c->comms && c->comms_host.size() == c->rows &&
                       memcmp(c->comms_host.data(), row_comms, c->rows * sizeof(reef_affine)) == 0;
+    if (!same) c->comms_bytes.clear();
     if (same) {
         // the key already holds these row commitments: no upload
-    } else if (!c->comms) {
-        reef_msm_opts o;
-        memset(&o, 0, sizeof o);
-        o.byte_tables = 2;                                       // a plain key: the bases change with every document
-        o.device = c->device;
-        void *k = nullptr;
-        REEF_TRY(v_ctx_create<C>(&k, row_comms, c->rows, loc, &o));
-        c->comms = (Ctx<C> *)k;
     } else {
-        REEF_TRY(v_ctx_rekey<C>(c->comms, row_comms, c->rows, loc));
+        REEF_TRY(hy_set_comms(c, row_comms, loc));
     }
     if (!same) {
         if (loc != REEF_DEVICE) c->comms_host.assign(row_comms, row_comms + c->rows);
         else c->comms_host.clear();
+    }
+    return v_msm<C>(c->comms, (const reef_fe *)c->lint.p, c->rows, REEF_DEVICE, false, comm_lz, REEF_HOST);
+}
+
+// reef_hyrax_eval_comm from the rows as Reef holds them: the 32-byte encodings are decoded on this ctx's device (k_decompress) into cdec and
+// the key is made or re-keyed from there -- no affine point visits the host.  An invalid row changes nothing: the key is touched only
+// after the whole batch has decoded.
+template <int C> static reef_status v_hyrax_eval_comm_compressed(void *impl, const uint8_t *row_comms32, int loc, reef_jacobian *comm_lz) {
+    HyraxCtx<C> *c = (HyraxCtx<C> *)impl;
+    if (!row_comms32 || !comm_lz) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (loc == REEF_DEVICE && ((uintptr_t)row_comms32 & 15)) { set_error("reef_hyrax_eval_comm_compressed: device rows must be 16-byte aligned"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->phase == HY_NONE) { set_error("reef_hyrax_eval_comm_compressed: the point is set by reef_hyrax_eval_begin, the next call"); return REEF_ERR_ARG; }
+    REEF_ON_DEVICE(c->device);
+    const size_t bytes = (size_t)c->rows * 32;
+    const bool same = loc != REEF_DEVICE && c->comms && c->comms_bytes.size() == bytes && memcmp(c->comms_bytes.data(), row_comms32, bytes) == 0;
+    {
+        DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
+        REEF_TRY(scope.enter());
+        REEF_TRY(hy_row_weights(c));
+        if (!same) {
+            REEF_TRY(c->cdec.ensure(c->rows * sizeof(affine256)));
+            REEF_TRY(c->cstat.ensure(2 * sizeof(u64)));
+            const fe256 *enc = (const fe256 *)row_comms32;
+            if (loc != REEF_DEVICE) {
+                REEF_TRY(c->cenc.ensure(bytes));
+                REEF_HIP_TRY(hipMemcpyAsync(c->cenc.p, row_comms32, bytes, hipMemcpyHostToDevice, c->stream));
+                enc = c->cenc.template as<fe256>();
+            }
+            decompress_launch<C>(c->stream, enc, c->rows, c->cdec.template as<affine256>(), c->cstat.template as<unsigned long long>());
+            REEF_HIP_TRY(hipGetLastError());
+            u64 stats[2] = {0, 0};
+            REEF_HIP_TRY(hipMemcpyAsync(stats, c->cstat.p, sizeof stats, hipMemcpyDeviceToHost, c->stream));
+            REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+            if (stats[0]) {
+                set_error("reef_hyrax_eval_comm_compressed: row %llu is not the encoding of a point (%llu such rows); the row commitments of the previous call stay",
+                          (unsigned long long)stats[1], (unsigned long long)stats[0]);
+                return REEF_ERR_ARG;
+            }
+        }
+    }
+    if (!same) {
+        c->comms_host.clear();
+        c->comms_bytes.clear();
+        REEF_TRY(hy_set_comms(c, (const reef_affine *)c->cdec.p, REEF_DEVICE));
+        if (loc != REEF_DEVICE) c->comms_bytes.assign(row_comms32, row_comms32 + bytes);
     }
     return v_msm<C>(c->comms, (const reef_fe *)c->lint.p, c->rows, REEF_DEVICE, false, comm_lz, REEF_HOST);
 }
@@ -304,7 +363,7 @@ template <int C> static reef_status v_hyrax_read(void *impl, int which, size_t c
 
 template <int C> HyraxVTable make_hyrax_vtable() {
     return HyraxVTable{v_hyrax_create<C>, v_hyrax_destroy<C>, v_hyrax_eval_begin<C>, v_hyrax_eval_comm<C>, v_hyrax_ipa_begin<C>,
-                       v_hyrax_ipa_round<C>, v_hyrax_finish<C>, v_hyrax_read<C>};
+                       v_hyrax_ipa_round<C>, v_hyrax_finish<C>, v_hyrax_read<C>, v_hyrax_eval_comm_compressed<C>};
 }
 
 }  // namespace reef

@@ -6,6 +6,7 @@
 #include "mle_kernels.inc"
 #include "merkle_kernels.inc"
 #include "keygen_kernels.inc"
+#include "decompress_kernels.inc"
 #include "nifs_kernels.inc"
 #include "spartan_kernels.inc"
 #include "open_kernels.inc"

@@ -100,6 +100,24 @@ class HyraxEval(_Handle):
         check(self._lib.reef_hyrax_eval_comm(self._h, rc.ctypes.data, REEF_HOST, out.ctypes.data))
         return out
 
+    def eval_comm_compressed(self, row_comms) -> np.ndarray:
+        """comm_LZ from the rows as Reef holds them (PolyCommit.comm): 2^left encodings of 32 bytes -- bytes or a uint8 array (host), or a
+        DeviceBuffer -- decoded on the device; Jacobian out.  An invalid row raises ReefError (REEF_ERR_ARG) naming it."""
+        want = 32 << self.left
+        if isinstance(row_comms, DeviceBuffer):
+            if row_comms.nbytes < want:
+                raise ValueError(f"expected {want} bytes of row commitments, the device buffer holds {row_comms.nbytes}")
+            loc, ptr, keep = REEF_DEVICE, row_comms.ptr, row_comms
+        else:
+            keep = np.frombuffer(bytes(row_comms), dtype=np.uint8) if isinstance(row_comms, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(row_comms, dtype=np.uint8).reshape(-1)
+            if keep.size != want:
+                raise ValueError(f"expected {1 << self.left} row commitments of 32 bytes, got {keep.size} bytes")
+            loc, ptr = REEF_HOST, keep.ctypes.data
+        out = np.zeros(12, dtype=np.uint64)
+        check(self._lib.reef_hyrax_eval_comm_compressed(self._h, ptr, loc, out.ctypes.data))
+        return out
+
     def ipa_begin(self, q: np.ndarray, h: Optional[np.ndarray] = None, blinds: Optional[Sequence[int]] = None, *,
                   is_mont: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """Round 0's L and R.  q (and h): affine, 8 uint64 limbs in pasta Montgomery coordinates; blinds: round 0's (bl, br)."""
@@ -130,17 +148,26 @@ class HyraxEval(_Handle):
 
 
 def prove_eval(hx: HyraxEval, key: MsmContext, point: Sequence[int], challenge: Callable[[str, List[Any]], int], p: int,
-               q_of: Callable[[int], np.ndarray], *, row_comms: Optional[np.ndarray] = None, h: Optional[np.ndarray] = None,
+               q_of: Callable[[int], np.ndarray], *, row_comms: Optional[np.ndarray] = None, row_comms_compressed=None,
+               h: Optional[np.ndarray] = None,
                blinds_of: Optional[Callable[[int], Tuple[int, int]]] = None, is_mont: bool = False) -> dict:
-    """The whole argument with `challenge(label, absorbed)`: eval_begin, comm_LZ when row_comms are given, "r" after (comm_LZ, eval)
+    """The whole argument with `challenge(label, absorbed)`: eval_begin, comm_LZ when row_comms (affine) or row_comms_compressed (the
+    32-byte rows of PolyCommit.comm, see HyraxEval.eval_comm_compressed) are given, "r" after (comm_LZ, eval)
     for q = q_of(r), then "challenge_r" per round after L and R (compressed).  With h, blinds_of(round) gives that round's (bl, br).
     key: gens_v, exactly 2^right points.  Canonical ints in and out (is_mont: the library calls take Montgomery form)."""
     to, frm = _mont_forms(p, is_mont)
     ev, lb = (frm(v) for v in hx.eval_begin(key, [to(x) for x in point], is_mont=is_mont))
+    if row_comms is not None and row_comms_compressed is not None:
+        raise ValueError("row_comms or row_comms_compressed, not both")
     comm_lz = hx.eval_comm(row_comms) if row_comms is not None else None
+    if row_comms_compressed is not None:
+        comm_lz = hx.eval_comm_compressed(row_comms_compressed)
     r_ipa = challenge("r", ([compress(key, comm_lz)] if comm_lz is not None else []) + [ev])
     bl = (lambda k: [to(x) for x in blinds_of(k)]) if (h is not None and blinds_of is not None) else (lambda k: None)
     first = hx.ipa_begin(q_of(r_ipa), h if h is not None and blinds_of is not None else None, bl(0), is_mont=is_mont)
     Ls, Rs, rs, (a_hat, b_hat) = _ipa_rounds(first, lambda k, r: hx.ipa_round(to(r), bl(k), is_mont=is_mont),
                                              lambda r: [frm(v) for v in hx.finish(to(r), is_mont=is_mont)], key, challenge, hx.right - 1)
     return {"eval": ev, "lz_blind": lb, "comm_lz": comm_lz, "r_ipa": r_ipa, "L": Ls, "R": Rs, "rs": rs, "a_hat": a_hat, "b_hat": b_hat}
+
+
+prove = prove_eval   # the argument under the name the other rows use (spartan.prove)

@@ -406,6 +406,33 @@ def compress(curve, jac: np.ndarray) -> bytes:
     return normalize(curve, jac, affine=False, compressed=True)[1].tobytes()
 
 
+def decompress(curve, data: Union[bytes, Buf], n: Optional[int] = None, *, loc: Optional[int] = None, out: Optional[Buf] = None):
+    """32-byte encodings -> (affine, invalid, first_invalid): reef_normalize's compressed output, the other way (reef_decompress).
+    data: bytes or a uint8 array of 32 n bytes (host), or a DeviceBuffer with n given; affine is an (n, 8) uint64 array, or a
+    DeviceBuffer (`out`, or a new one) for device data.  An invalid encoding gives (0, 0) in its slot and is counted; first_invalid
+    is the lowest such index, n when there is none.  loc, when given, must name where `data` lives."""
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        data = np.frombuffer(bytes(data), dtype=np.uint8)
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8 or data.size % 32:
+            raise ValueError("encodings are uint8, 32 bytes each")
+        data = np.ascontiguousarray(data).reshape(-1, 32)
+        n = data.shape[0]
+    elif n is None:
+        raise ValueError("a device buffer of encodings needs n")
+    dloc, ptr = _loc_ptr(data, 32 * n)
+    if loc is not None and loc != dloc:
+        raise ValueError("loc does not name the memory `data` lives in")
+    if out is None:
+        out = np.zeros((n, 8), dtype=np.uint64) if dloc == REEF_HOST else DeviceBuffer(64 * max(n, 1))
+    oloc, optr = _loc_ptr(out, 64 * n)
+    if oloc != dloc:
+        raise ValueError("data and out must live in the same place")
+    bad, first = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(_ffi.load().reef_decompress(curve_id(curve), ptr, n, dloc, optr, ctypes.byref(bad), ctypes.byref(first)))
+    return out, bad.value, first.value
+
+
 def sum_points(curve, jac: Buf, n: Optional[int] = None, out: Optional[Buf] = None) -> Buf:
     if isinstance(jac, np.ndarray):
         jac = np.ascontiguousarray(jac.reshape(-1, 12))

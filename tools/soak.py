@@ -18,7 +18,7 @@ t_end = time.time() + budget
 done = 0
 while time.time() < t_end:
     cid = int(rng.integers(0, 2))
-    shape = rng.integers(0, 13)
+    shape = rng.integers(0, 14)
     if shape == 0:      # single MSM, any size
         n = int(2 ** rng.uniform(0, 21.2 if os.environ.get("SOAK_BIG") else 18.5))
         kind = int(rng.integers(0, 3))
@@ -114,6 +114,23 @@ while time.time() < t_end:
         want = R.compress(cid, R.msm_pippenger(cid, bases, sc, threads=16))
         with msm.MsmContext(cid, bases, bucket_groups=int(rng.choice([0, 1])), window_bits=int(rng.choice([0, 5, 13])), byte_tables=int(rng.choice([1, 2]))) as ctx:
             assert msm.compress(cid, ctx.msm(sc)) == want, ("collide", cid, n)
+    elif shape == 13:   # K4 and its inverse: reef_normalize's encodings decode to the points they came from; an entry set to x = p is counted
+        n = int(2 ** rng.uniform(0, 14))
+        base = msm.PALLAS_BASE_P if cid == 0 else msm.PALLAS_SCALAR_Q
+        aff = R.gen_bases_ap(cid, int(rng.integers(1, 1 << 30)), 3, n)
+        if n > 8:
+            aff[rng.integers(0, n, size=2)] = 0
+        jac = np.zeros((n, 12), dtype=np.uint64)
+        jac[:, :8] = aff
+        jac[aff.any(axis=1), 8:] = msm.scalar_to_limbs((1 << 256) % base)
+        comp = msm.normalize(cid, jac, affine=False, compressed=True)[1]
+        got, bad, first = msm.decompress(cid, comp)
+        assert (bad, first) == (0, n) and (got == aff).all(), ("decompress", cid, n)
+        k = int(rng.integers(0, n))
+        comp[k] = np.frombuffer(base.to_bytes(32, "little"), dtype=np.uint8)
+        got, bad, first = msm.decompress(cid, comp)
+        aff[k] = 0
+        assert (bad, first) == (1, k) and (got == aff).all(), ("decompress-invalid", cid, n, k)
     elif shape == 1:    # stateless drop-in symbol
         n = int(2 ** rng.uniform(0, 16))
         bases = R.gen_bases_ap(cid, int(rng.integers(1, 1 << 30)), 3, n)
