@@ -208,6 +208,18 @@ reef_status reef_msm_rows_symbols(reef_msm_ctx *ctx, const uint8_t *symbols, siz
                                   uint32_t symbol_bits, const reef_fe *blinds, const reef_affine *h, bool blinds_are_mont,
                                   reef_jacobian *out, int out_loc);
 
+/* The same from symbols wider than a byte: elem_bytes = 2 (uint16_t) or 4 (uint32_t), little-endian, symbol_bits in
+ * 1..8*elem_bytes (an alphabet of 254 characters already needs 9 bits: EPSILON and EOF are |ab| + 1 and |ab| + 2,
+ * framework.rs:978-1011).  Only the low symbol_bits bits of a symbol are used.  A symbol is the sum of its bytes times powers of
+ * 256, so a row is the plain sum of P * row_len entries (P = ceil(symbol_bits / 8)) of byte-multiple tables over the plane
+ * generators 256^p * G_j, cached per (ctx, row_len, symbol_bits) like the byte entry's tables (one set at a time: a byte call
+ * after a wide call rebuilds its own, and the reverse).  Everything else is the contract of reef_msm_rows_symbols.
+ * REEF_ERR_ARG before any device work: elem_bytes not 2 or 4, symbol_bits out of range, row_len above the key length, blinds
+ * without h, more than 2^26 table points, rows * row_len * P >= 2^31 entries. */
+reef_status reef_msm_rows_symbols_wide(reef_msm_ctx *ctx, const void *symbols, uint32_t elem_bytes, size_t rows, size_t row_len,
+                                       int symbols_loc, uint32_t symbol_bits, const reef_fe *blinds, const reef_affine *h,
+                                       bool blinds_are_mont, reef_jacobian *out, int out_loc);
+
 /* IPA round WITHOUT generator folding.  After k rounds of G'_i = w1*G_i + w2*G_{i+half} the
  * generators are fixed linear combinations of the original ones, so the cross terms of round k
  *     L = <a_lo, G^(k)_hi>,   R = <a_hi, G^(k)_lo>        (a = a_lo || a_hi, n_k = n / 2^k scalars)

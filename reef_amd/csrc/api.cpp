@@ -391,6 +391,11 @@ reef_status reef_msm_rows_symbols(reef_msm_ctx *ctx, const uint8_t *symbols, siz
                                   const reef_fe *blinds, const reef_affine *h, bool blinds_are_mont, reef_jacobian *out, int out_loc) {
     return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->msm_rows_symbols(impl, symbols, rows, row_len, loc, symbol_bits, blinds, h, blinds_are_mont, out, out_loc); });
 }
+reef_status reef_msm_rows_symbols_wide(reef_msm_ctx *ctx, const void *symbols, uint32_t elem_bytes, size_t rows, size_t row_len, int loc,
+                                       uint32_t symbol_bits, const reef_fe *blinds, const reef_affine *h, bool blinds_are_mont, reef_jacobian *out,
+                                       int out_loc) {
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->msm_rows_symbols_wide(impl, symbols, elem_bytes, rows, row_len, loc, symbol_bits, blinds, h, blinds_are_mont, out, out_loc); });
+}
 reef_status reef_ipa_cross_terms(reef_msm_ctx *ctx, const reef_fe *a, size_t n_k, int a_loc, bool is_mont, const reef_fe *w1s,
                                  const reef_fe *w2s, size_t k, reef_jacobian *out_l, reef_jacobian *out_r) {
     return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ipa_cross(impl, a, n_k, a_loc, is_mont, w1s, w2s, k, out_l, out_r); });

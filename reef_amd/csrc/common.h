@@ -414,6 +414,8 @@ struct CurveVTable {
                             uint32_t max_bits, const reef_fe *blinds, const reef_affine *h, reef_jacobian *out, int out_loc);
     reef_status (*msm_rows_symbols)(void *impl, const uint8_t *symbols, size_t rows, size_t row_len, int loc, uint32_t bits,
                                     const reef_fe *blinds, const reef_affine *h, bool blinds_are_mont, reef_jacobian *out, int out_loc);
+    reef_status (*msm_rows_symbols_wide)(void *impl, const void *symbols, uint32_t elem_bytes, size_t rows, size_t row_len, int loc, uint32_t bits,
+                                         const reef_fe *blinds, const reef_affine *h, bool blinds_are_mont, reef_jacobian *out, int out_loc);
     reef_status (*ipa_cross)(void *impl, const reef_fe *a, size_t n_k, int loc, bool is_mont, const reef_fe *w1s, const reef_fe *w2s, size_t k,
                              reef_jacobian *out_l, reef_jacobian *out_r);
     reef_status (*msm_folded)(void *impl, const reef_fe *v, size_t len, size_t off, int loc, bool is_mont, const reef_fe *w1s, const reef_fe *w2s,

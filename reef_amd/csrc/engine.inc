@@ -100,6 +100,7 @@ template <int C> struct Ctx {
     bool timing = false;
     DevBuf sym_table, sym_tmp, sym_u8;        // block tables of the tiny-scalar row commit (cached per ctx)
     u32 sym_bits = 0, sym_k = 0, sym_row_len = 0;
+    u32 symw_bits = 0, symw_planes = 0, symw_row_len = 0;   // the same buffers holding the plane tables of wide symbols instead (0: they do not)
     int two_level = -1;                       // sort: -1 by size, 0 never, 1 whenever the window allows (REEF_MSM_SORT2 overrides)
     u32 wsplit_rank = 0, wsplit_world = 1;   // window split across GPUs (reef_msm_ctx_set_window_split)
     DevBuf h_tab, small_partial;             // nibble table of the blinding generator last used, partial sums of k_small_msm
@@ -452,7 +453,7 @@ static reef_status key_build(Ctx<C> *ctx, const reef_affine *bases, size_t n, in
         key->cap = need;
     }
     key->n = n; key->c = c; key->W = W; key->G = G; key->T = T;
-    ctx->sym_bits = 0;   // block tables belong to the previous bases
+    ctx->sym_bits = ctx->symw_bits = 0;   // block tables belong to the previous bases
     graphs_clear(ctx);   // captured launches read the previous tables and plan
     if (n == 0) return REEF_OK;
     // ABI points -> key-table form (internal Montgomery radix, canonical): one pass, once per key
@@ -613,7 +614,7 @@ template <int C> static reef_status v_ctx_attach(void *impl, void *src_) {
     ctx->opt_c = src->opt_c; ctx->opt_G = src->opt_G; ctx->opt_tables = src->opt_tables;
     ctx->wsplit_rank = src->wsplit_rank;
     ctx->wsplit_world = src->wsplit_world;
-    ctx->sym_bits = 0;   // block tables and captured launches belong to the previous key
+    ctx->sym_bits = ctx->symw_bits = 0;   // block tables and captured launches belong to the previous key
     graphs_clear(ctx);
     return REEF_OK;
 }
@@ -1199,6 +1200,51 @@ static reef_status v_msm(void *impl, const reef_fe *scalars, size_t n, int loc, 
     return msm_device_scalars<C>(ctx, d_scalars, n, is_mont, out, out_loc, d_res);
 }
 
+// The tail the symbol routes share: M table entries in row order, `blocks` a row, written by launch_entries(entries, bucket_start)
+// as (row, table index) with bucket_start[row] = row*blocks, are summed per row by k_accum0 with the rows as "buckets".
+template <int C, class LaunchEntries>
+static reef_status sym_rows_sum(Ctx<C> *ctx, u64 M, u32 blocks, size_t rows, bool is_mont, const fe256 *d_blinds, const affine256 *d_h,
+                                jacobian256 *d_out, LaunchEntries launch_entries) {
+    hipStream_t st = ctx->stream;
+    // chunk length as in run_core: about one wave per two SIMDs at least, long chunks when the chip stays full
+    u32 L0 = ctx->L0;
+    if (L0 == 0) {
+        L0 = 32;
+        while (L0 < 128 && L0 < blocks && M / (2 * L0) >= 131072) L0 *= 2;
+        while (L0 > 8 && M / L0 < 24576) L0 /= 2;
+    }
+    const u32 nchunks0 = (u32)round_up(ceil_div(M, L0), 64);
+    REEF_TRY(ctx->entries.ensure((u64)nchunks0 * L0 * sizeof(u32x2)));
+    REEF_TRY(ctx->bstart.ensure((rows + 1) * sizeof(u32)));
+    REEF_TRY(ctx->bucket_acc.ensure(rows * sizeof(xyzz_mem)));
+    const u32 len1 = 2 * nchunks0, len2 = 2 * ceil_div(len1, 64);
+    REEF_TRY(ctx->lkeys[0].ensure((u64)len1 * sizeof(u32)));
+    REEF_TRY(ctx->lvals[0].ensure((u64)len1 * sizeof(xyzz_mem)));
+    REEF_TRY(ctx->lkeys[1].ensure((u64)len2 * sizeof(u32)));
+    REEF_TRY(ctx->lvals[1].ensure((u64)len2 * sizeof(xyzz_mem)));
+    u32x2 *entries = ctx->entries.template as<u32x2>();
+    u32 *bstart = ctx->bstart.template as<u32>();
+    xyzz_mem *row_acc = ctx->bucket_acc.template as<xyzz_mem>();
+    if (ctx->timing) {
+        REEF_TRY(ctx_begin_timing<C>(ctx));
+        REEF_HIP_TRY(hipEventRecord(ctx->ev[0], st));
+    }
+    launch_entries(entries, bstart);
+    if (ctx->timing) REEF_HIP_TRY(hipEventRecord(ctx->ev[1], st));
+    hipLaunchKernelGGL((k_accum0<C, false, false>), dim3(ceil_div(nchunks0, 256)), dim3(256), 0, st, ctx->sym_table.template as<affine256>(), (const void *)entries, bstart + rows, L0,
+                       nchunks0, row_acc, ctx->lkeys[0].template as<u32>(), ctx->lvals[0].template as<xyzz_mem>(), 0u);
+    if (ctx->timing) REEF_HIP_TRY(hipEventRecord(ctx->ev[2], st));
+    launch_partial_merge<C>(ctx, nchunks0, row_acc);
+    hipLaunchKernelGGL(k_final<C>, dim3(ceil_div(rows, 64)), dim3(64), 0, st, row_acc, 1u, 0u, (u32)rows, d_out);   // XYZZ row sums -> Jacobian
+    if (d_blinds) REEF_TRY(launch_blind<C>(ctx, d_out, d_blinds, d_h, is_mont, rows));
+    if (ctx->timing) {
+        REEF_HIP_TRY(hipEventRecord(ctx->ev[3], st));
+        ctx->ev_pending[ctx->ev_last] = true;
+    }
+    REEF_HIP_TRY(hipGetLastError());
+    return REEF_OK;
+}
+
 // Row commits of `bits`-bit symbols through block tables (see k_sym_multiples).  d_sym: rows*row_len bytes on the device.
 static inline u32 sym_block_size(u32 bits) { return std::max<u32>(1, 9 / bits); }
 static inline bool sym_path_pays(size_t rows, size_t row_len, u32 bits, bool cached) {
@@ -1235,45 +1281,65 @@ static reef_status run_rows_symbols(Ctx<C> *ctx, const unsigned char *d_sym, siz
         hipLaunchKernelGGL((k_xyzz_normalize<C, false>), dim3((u32)ceil_div(ceil_div(table_points, NORM_PER), 256)), dim3(256), 0, st, src,
                            (u32)table_points, ctx->sym_table.template as<affine256>());
         ctx->sym_bits = bits; ctx->sym_k = k; ctx->sym_row_len = (u32)row_len;
+        ctx->symw_bits = 0;                             // the wide route's tables lived in the same buffers
     }
-    // chunk length as in run_core: about one wave per two SIMDs at least, long chunks when the chip stays full
-    u32 L0 = ctx->L0;
-    if (L0 == 0) {
-        L0 = 32;
-        while (L0 < 128 && L0 < blocks && M / (2 * L0) >= 131072) L0 *= 2;
-        while (L0 > 8 && M / L0 < 24576) L0 /= 2;
+    return sym_rows_sum<C>(ctx, M, blocks, rows, is_mont, d_blinds, d_h, d_out, [&](u32x2 *entries, u32 *bstart) {
+        hipLaunchKernelGGL(k_sym_entries, dim3((u32)ceil_div(std::max<u64>(M, rows + 1), 256)), dim3(256), 0, st, d_sym, (u32)rows, (u32)row_len, bits, k, blocks,
+                           entries, bstart);
+    });
+}
+
+// Row commits of symbols wider than a byte (see k_sym_entries_wide): P = ceil(bits / 8) byte planes over the generators 256^p * G_j.
+// The tables are the byte route's at k = 1, built by its kernels over the plane generators: 256 multiples for each generator of the
+// P - 1 full planes, 2^top_bits for the top plane.  d_sym: rows*row_len symbols of T on the device.
+static inline u64 sym_wide_table_points(size_t row_len, u32 bits) {
+    const u32 P = ceil_div(bits, 8u);
+    return (u64)(P - 1) * row_len * 256 + ((u64)row_len << (bits - 8 * (P - 1)));
+}
+template <int C>
+static void sym_wide_multiples(Ctx<C> *ctx, const affine256 *gens, u64 n, u32 bits, xyzz_mem *scratch, xyzz_mem *table) {
+    const u32 lb = bits <= 4 ? bits : (bits + 1) / 2, hb = bits - lb;   // n*2^bits table entries: v*gens[j] at table[(j << bits) + v]
+    xyzz_mem *lo = hb ? scratch : table, *hi = scratch + (n << lb);      // one level: the multiples are the table
+    hipLaunchKernelGGL(k_sym_multiples<C>, dim3((u32)ceil_div(2 * n, 256)), dim3(256), 0, ctx->stream, gens, (u32)n, lb, hb, lo, hi);
+    if (hb) hipLaunchKernelGGL(k_sym_blocks<C>, dim3((u32)ceil_div(n << bits, 256)), dim3(256), 0, ctx->stream, lo, hi, (u32)n, bits, lb, 1u, (u32)n, table);
+}
+template <int C, typename T>
+static reef_status run_rows_symbols_wide(Ctx<C> *ctx, const T *d_sym, size_t rows, size_t row_len, u32 bits, bool is_mont,
+                                         const fe256 *d_blinds, const affine256 *d_h, jacobian256 *d_out) {
+    hipStream_t st = ctx->stream;
+    if (ctx->wsplit_world > 1 && ctx->wsplit_rank != 0) {   // as run_rows_symbols: rank 0 owns the whole sum
+        REEF_HIP_TRY(hipMemsetAsync(d_out, 0, rows * sizeof(jacobian256), st));
+        return REEF_OK;
     }
-    const u32 nchunks0 = (u32)round_up(ceil_div(M, L0), 64);
-    REEF_TRY(ctx->entries.ensure((u64)nchunks0 * L0 * sizeof(u32x2)));
-    REEF_TRY(ctx->bstart.ensure((rows + 1) * sizeof(u32)));
-    REEF_TRY(ctx->bucket_acc.ensure(rows * sizeof(xyzz_mem)));
-    const u32 len1 = 2 * nchunks0, len2 = 2 * ceil_div(len1, 64);
-    REEF_TRY(ctx->lkeys[0].ensure((u64)len1 * sizeof(u32)));
-    REEF_TRY(ctx->lvals[0].ensure((u64)len1 * sizeof(xyzz_mem)));
-    REEF_TRY(ctx->lkeys[1].ensure((u64)len2 * sizeof(u32)));
-    REEF_TRY(ctx->lvals[1].ensure((u64)len2 * sizeof(xyzz_mem)));
-    u32x2 *entries = ctx->entries.template as<u32x2>();
-    u32 *bstart = ctx->bstart.template as<u32>();
-    xyzz_mem *row_acc = ctx->bucket_acc.template as<xyzz_mem>();
-    if (ctx->timing) {
-        REEF_TRY(ctx_begin_timing<C>(ctx));
-        REEF_HIP_TRY(hipEventRecord(ctx->ev[0], st));
+    const u32 P = ceil_div(bits, 8u), top_bits = bits - 8 * (P - 1);
+    const u64 full_gens = (u64)(P - 1) * row_len, table_points = sym_wide_table_points(row_len, bits);
+    const u64 M = (u64)rows * row_len * P;
+    if (ctx->symw_bits != bits || ctx->symw_planes != P || ctx->symw_row_len != row_len) {
+        ctx->sym_bits = 0; ctx->symw_bits = 0;          // the byte route's tables lived in the same buffers
+        // scratch: plane generators (XYZZ, then affine), the two half-byte multiples of the widest build, the table in XYZZ
+        const u64 mult_cnt = std::max<u64>(full_gens << 5, top_bits > 4 ? (u64)row_len << (1 + (top_bits + 1) / 2) : 0);
+        REEF_TRY(ctx->sym_table.ensure(table_points * sizeof(affine256)));
+        REEF_TRY(ctx->sym_tmp.ensure((u64)P * row_len * (sizeof(xyzz_mem) + sizeof(affine256)) + (mult_cnt + table_points) * sizeof(xyzz_mem)));
+        xyzz_mem *planes = ctx->sym_tmp.template as<xyzz_mem>(), *mult = planes + (u64)P * row_len, *full = mult + mult_cnt;
+        affine256 *gens = (affine256 *)(full + table_points);
+        const affine256 *top_gens = ctx->key->tables;   // table 0 of the key: G_j itself, whatever the key's kind
+        if (P > 1) {
+            // planes[p*row_len + j] = 256^p * G_j, 8 doublings from the plane below, then one batch normalisation
+            hipLaunchKernelGGL(k_shift_chain<C>, dim3((u32)ceil_div(row_len, 64)), dim3(64), 0, st, ctx->key->tables, (u32)row_len, 8u, P, 1, planes);
+            hipLaunchKernelGGL((k_xyzz_normalize<C, false>), dim3((u32)ceil_div(ceil_div((u64)P * row_len, NORM_PER), 256)), dim3(256), 0, st, planes,
+                               (u32)(P * row_len), gens);
+            sym_wide_multiples<C>(ctx, gens, full_gens, 8, mult, full);
+            top_gens = gens + full_gens;
+        }
+        sym_wide_multiples<C>(ctx, top_gens, row_len, top_bits, mult, full + (full_gens << 8));
+        hipLaunchKernelGGL((k_xyzz_normalize<C, false>), dim3((u32)ceil_div(ceil_div(table_points, NORM_PER), 256)), dim3(256), 0, st, full,
+                           (u32)table_points, ctx->sym_table.template as<affine256>());
+        ctx->symw_bits = bits; ctx->symw_planes = P; ctx->symw_row_len = (u32)row_len;
     }
-    hipLaunchKernelGGL(k_sym_entries, dim3((u32)ceil_div(std::max<u64>(M, rows + 1), 256)), dim3(256), 0, st, d_sym, (u32)rows, (u32)row_len, bits, k, blocks,
-                       entries, bstart);
-    if (ctx->timing) REEF_HIP_TRY(hipEventRecord(ctx->ev[1], st));
-    hipLaunchKernelGGL((k_accum0<C, false, false>), dim3(ceil_div(nchunks0, 256)), dim3(256), 0, st, ctx->sym_table.template as<affine256>(), (const void *)entries, bstart + rows, L0,
-                       nchunks0, row_acc, ctx->lkeys[0].template as<u32>(), ctx->lvals[0].template as<xyzz_mem>(), 0u);
-    if (ctx->timing) REEF_HIP_TRY(hipEventRecord(ctx->ev[2], st));
-    launch_partial_merge<C>(ctx, nchunks0, row_acc);
-    hipLaunchKernelGGL(k_final<C>, dim3(ceil_div(rows, 64)), dim3(64), 0, st, row_acc, 1u, 0u, (u32)rows, d_out);   // XYZZ row sums -> Jacobian
-    if (d_blinds) REEF_TRY(launch_blind<C>(ctx, d_out, d_blinds, d_h, is_mont, rows));
-    if (ctx->timing) {
-        REEF_HIP_TRY(hipEventRecord(ctx->ev[3], st));
-        ctx->ev_pending[ctx->ev_last] = true;
-    }
-    REEF_HIP_TRY(hipGetLastError());
-    return REEF_OK;
+    return sym_rows_sum<C>(ctx, M, (u32)(P * row_len), rows, is_mont, d_blinds, d_h, d_out, [&](u32x2 *entries, u32 *bstart) {
+        hipLaunchKernelGGL(k_sym_entries_wide<T>, dim3((u32)ceil_div(std::max<u64>((u64)rows * row_len, rows + 1), 256)), dim3(256), 0, st, d_sym, (u32)rows,
+                           (u32)row_len, bits, P, entries, bstart);
+    });
 }
 
 template <int C>
@@ -1386,13 +1452,15 @@ static reef_status v_msm_rows(void *impl, const reef_fe *scalars, size_t rows, s
     return finish_output<C>(ctx, d_res, rows, out, out_loc);
 }
 
-// HyraxPC::commit on the document's own symbols (one byte each, < 2^bits): no field elements cross the ABI.
+// HyraxPC::commit on the document's own symbols (elem_bytes = 1, 2 or 4 each, < 2^bits): no field elements cross the ABI.
 template <int C>
-static reef_status v_msm_rows_symbols(void *impl, const uint8_t *symbols, size_t rows, size_t row_len, int loc, uint32_t bits,
-                                      const reef_fe *blinds, const reef_affine *h, bool blinds_are_mont, reef_jacobian *out, int out_loc) {
+static reef_status msm_rows_symbols_any(void *impl, const void *symbols, u32 elem_bytes, size_t rows, size_t row_len, int loc, uint32_t bits,
+                                        const reef_fe *blinds, const reef_affine *h, bool blinds_are_mont, reef_jacobian *out, int out_loc) {
     Ctx<C> *ctx = (Ctx<C> *)impl;
+    const bool wide = elem_bytes > 1;
     if (!ctx || !out || ((rows * row_len) && !symbols) || (blinds && !h)) { set_error("null argument"); return REEF_ERR_ARG; }
-    if (bits == 0 || bits > 8) { set_error("symbol width must be 1..8 bits"); return REEF_ERR_ARG; }
+    if (!wide && (bits == 0 || bits > 8)) { set_error("symbol width must be 1..8 bits"); return REEF_ERR_ARG; }
+    if (wide && (bits == 0 || bits > 8 * elem_bytes)) { set_error("symbol_bits = %u: a %u-byte symbol holds 1..%u bits", bits, elem_bytes, 8 * elem_bytes); return REEF_ERR_ARG; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     Key<C> *key = ctx->key;
     REEF_ON_DEVICE(key->device);
@@ -1400,19 +1468,21 @@ static reef_status v_msm_rows_symbols(void *impl, const uint8_t *symbols, size_t
     REEF_TRY(scope.enter());
     if (row_len > key->n) { set_error("row_len = %zu exceeds the key length %zu", row_len, key->n); return REEF_ERR_ARG; }
     if (rows == 0) return REEF_OK;
-    const u64 table_points = (u64)ceil_div(std::max<size_t>(row_len, 1), sym_block_size(bits)) << (bits * sym_block_size(bits));
+    const u64 table_points = wide ? sym_wide_table_points(std::max<size_t>(row_len, 1), bits)
+                                  : (u64)ceil_div(std::max<size_t>(row_len, 1), sym_block_size(bits)) << (bits * sym_block_size(bits));
     if (table_points > (1ull << 26)) { set_error("symbol tables too large for this row length"); return REEF_ERR_ARG; }
+    if (wide && (u64)rows * row_len * ceil_div(bits, 8u) >= (1ull << 31)) { set_error("too many row entries"); return REEF_ERR_ARG; }
     jacobian256 *d_res = nullptr;
     REEF_TRY(result_target<C>(ctx, rows, out, out_loc, &d_res));
     const fe256 *d_blinds = (const fe256 *)blinds;
     const affine256 *d_h = (const affine256 *)h;
     ctx->h_host = (loc != REEF_DEVICE && blinds) ? h : nullptr;
-    const unsigned char *d_sym = symbols;
+    const void *d_sym = symbols;
     if (loc != REEF_DEVICE) {
         if (rows * row_len) {
-            REEF_TRY(ctx->sym_u8.ensure(rows * row_len));
-            REEF_HIP_TRY(hipMemcpyAsync(ctx->sym_u8.p, symbols, rows * row_len, hipMemcpyHostToDevice, ctx->stream));
-            d_sym = ctx->sym_u8.template as<unsigned char>();
+            REEF_TRY(ctx->sym_u8.ensure(rows * row_len * elem_bytes));
+            REEF_HIP_TRY(hipMemcpyAsync(ctx->sym_u8.p, symbols, rows * row_len * elem_bytes, hipMemcpyHostToDevice, ctx->stream));
+            d_sym = ctx->sym_u8.p;
         }
         if (blinds) {
             REEF_TRY(ctx->blinds.ensure(rows * sizeof(fe256)));
@@ -1428,8 +1498,22 @@ static reef_status v_msm_rows_symbols(void *impl, const uint8_t *symbols, size_t
         if (d_blinds && (ctx->wsplit_world <= 1 || ctx->wsplit_rank == 0)) REEF_TRY(launch_blind<C>(ctx, d_res, d_blinds, d_h, blinds_are_mont, rows));
         return finish_output<C>(ctx, d_res, rows, out, out_loc);
     }
-    REEF_TRY(run_rows_symbols<C>(ctx, d_sym, rows, row_len, bits, blinds_are_mont, d_blinds, d_h, d_res));
+    if (elem_bytes == 4) REEF_TRY((run_rows_symbols_wide<C, uint32_t>(ctx, (const uint32_t *)d_sym, rows, row_len, bits, blinds_are_mont, d_blinds, d_h, d_res)));
+    else if (elem_bytes == 2) REEF_TRY((run_rows_symbols_wide<C, uint16_t>(ctx, (const uint16_t *)d_sym, rows, row_len, bits, blinds_are_mont, d_blinds, d_h, d_res)));
+    else REEF_TRY(run_rows_symbols<C>(ctx, (const unsigned char *)d_sym, rows, row_len, bits, blinds_are_mont, d_blinds, d_h, d_res));
     return finish_output<C>(ctx, d_res, rows, out, out_loc);
+}
+template <int C>
+static reef_status v_msm_rows_symbols(void *impl, const uint8_t *symbols, size_t rows, size_t row_len, int loc, uint32_t bits,
+                                      const reef_fe *blinds, const reef_affine *h, bool blinds_are_mont, reef_jacobian *out, int out_loc) {
+    return msm_rows_symbols_any<C>(impl, symbols, 1, rows, row_len, loc, bits, blinds, h, blinds_are_mont, out, out_loc);
+}
+// The same from 16- and 32-bit symbols (reef_msm_rows_symbols_wide).
+template <int C>
+static reef_status v_msm_rows_symbols_wide(void *impl, const void *symbols, uint32_t elem_bytes, size_t rows, size_t row_len, int loc, uint32_t bits,
+                                           const reef_fe *blinds, const reef_affine *h, bool blinds_are_mont, reef_jacobian *out, int out_loc) {
+    if (elem_bytes != 2 && elem_bytes != 4) { set_error("elem_bytes = %u: wide symbols are 2 or 4 bytes each", elem_bytes); return REEF_ERR_ARG; }
+    return msm_rows_symbols_any<C>(impl, symbols, elem_bytes, rows, row_len, loc, bits, blinds, h, blinds_are_mont, out, out_loc);
 }
 
 // The nibble table of one point h (ABI affine, host) into buf: small_table_points(1) points, then two staging points.  Built on
@@ -1982,7 +2066,7 @@ static reef_status plan_for(size_t n, uint32_t c_opt, uint32_t g_opt, uint32_t *
 
 template <int C> static CurveVTable make_vtable() {
     return CurveVTable{v_ctx_create<C>, v_ctx_rekey<C>, v_ctx_clone<C>, v_ctx_attach<C>, v_ctx_destroy<C>, v_ctx_sync<C>, v_ctx_stream<C>,
-                       v_ctx_timing<C>, v_ctx_enable_timing<C>, v_ctx_window_split<C>, v_ctx_timing_stats<C>, v_ctx_sum_points<C>, v_ctx_plan<C>, v_ctx_byte_tables<C>, v_msm<C>, v_msm_rows<C>, v_msm_rows_symbols<C>, v_ipa_cross<C>, v_msm_folded<C>, v_fold<C>, v_normalize<C>, v_sum_points<C>,
+                       v_ctx_timing<C>, v_ctx_enable_timing<C>, v_ctx_window_split<C>, v_ctx_timing_stats<C>, v_ctx_sum_points<C>, v_ctx_plan<C>, v_ctx_byte_tables<C>, v_msm<C>, v_msm_rows<C>, v_msm_rows_symbols<C>, v_msm_rows_symbols_wide<C>, v_ipa_cross<C>, v_msm_folded<C>, v_fold<C>, v_normalize<C>, v_sum_points<C>,
                        v_gen_bases<C>, v_gen_scalars<C>, v_test_field_op<C>, v_test_ec_op<C>, v_bench_fmul<C>,
                        v_sc_create<C>, v_sc_destroy<C>, v_sc_set<C>, v_sc_read<C>, v_sc_coeffs<C>, v_sc_fold<C>, v_sc_fold_coeffs<C>, v_sc_gen_eq<C>, v_sc_reset<C>, v_sc_sync<C>, v_mle_bound<C>, v_merkle_commit<C>, v_derive_generators<C>, plan_for, v_decompress<C>};
 }

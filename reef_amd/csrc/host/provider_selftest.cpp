@@ -51,6 +51,14 @@ int main() {
         for (size_t i = 0; i < sym.size(); ++i) sym[i] = (uint8_t)zc[i].l[0];
         const auto c1 = pc.commit(z.data(), vars, bl.data());
         const auto c2 = pc.commit_symbols(sym.data(), vars, 8, bl.data());
+        // the same symbols two and four bytes wide (reef_msm_rows_symbols_wide; declared 9 bits wide, the 32-bit ones take two planes)
+        std::vector<uint16_t> sym16(sym.begin(), sym.end());
+        std::vector<uint32_t> sym32(sym.begin(), sym.end());
+        const auto c3 = pc.commit_symbols(sym16.data(), vars, 8, bl.data());
+        const auto c4 = pc.commit_symbols(sym32.data(), vars, 9, bl.data());
+        for (size_t i = 0; i < rows; ++i)
+            if (chex<REEF_PALLAS>(c3[i]) != chex<REEF_PALLAS>(c2[i]) || chex<REEF_PALLAS>(c4[i]) != chex<REEF_PALLAS>(c2[i]))
+                throw std::runtime_error("commit_symbols: 16- or 32-bit symbols differ from the same bytes at row " + std::to_string(i));
         out += "\"hyrax\": [";
         for (size_t i = 0; i < rows; ++i) out += std::string(i ? ", " : "") + "\"" + chex<REEF_PALLAS>(c1[i]) + "\"";
         out += "], \"hyrax_symbols\": [";

@@ -241,6 +241,26 @@ template <int CURVE> class HyraxPC {
               "reef_msm_rows_symbols");
         return out;
     }
+    // The same from 16- or 32-bit symbols (an alphabet of 254 characters or more; reef_msm_rows_symbols_wide).
+    std::vector<reef_jacobian> commit_symbols(const uint16_t *symbols, size_t num_vars, uint32_t symbol_bits, const reef_fe *blinds,
+                                              int symbols_loc = REEF_HOST) const {
+        return commit_symbols_wide(symbols, 2, num_vars, symbol_bits, blinds, symbols_loc);
+    }
+    std::vector<reef_jacobian> commit_symbols(const uint32_t *symbols, size_t num_vars, uint32_t symbol_bits, const reef_fe *blinds,
+                                              int symbols_loc = REEF_HOST) const {
+        return commit_symbols_wide(symbols, 4, num_vars, symbol_bits, blinds, symbols_loc);
+    }
+    std::vector<reef_jacobian> commit_symbols_wide(const void *symbols, uint32_t elem_bytes, size_t num_vars, uint32_t symbol_bits,
+                                                   const reef_fe *blinds, int symbols_loc = REEF_HOST) const {
+        const auto lr = compute_factored_lens(num_vars);
+        const size_t rows = (size_t)1 << lr.first, row_len = (size_t)1 << lr.second;
+        if (row_len > gens_.len()) throw std::logic_error("not enough row generators");
+        std::vector<reef_jacobian> out(rows);
+        check(reef_msm_rows_symbols_wide(gens_.handle(), symbols, elem_bytes, rows, row_len, symbols_loc, symbol_bits, blinds,
+                                         blinds ? gens_.h() : nullptr, true, out.data(), REEF_HOST),
+              "reef_msm_rows_symbols_wide");
+        return out;
+    }
     // First step of prove_eval: LZ = L^T Z and eval = <LZ, R> for (L, R) = eq-evaluations of the two halves of `point`.
     struct BoundRows {
         std::vector<reef_fe> lz;

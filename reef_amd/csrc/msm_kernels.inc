@@ -1915,6 +1915,27 @@ static __global__ void __launch_bounds__(256) k_sym_entries(const unsigned char 
     entries[t] = mk_u32x2(row, (block << (bits * k)) + combo);
 }
 
+// Symbols wider than a byte (T = uint16_t, uint32_t; P = ceil(bits / 8) byte planes).  A symbol is sum_p byte_p * 256^p, so its
+// term is the sum of P entries of byte-multiple tables over the plane generators 256^p * G_j.  The table holds the full planes
+// first, 256 multiples per generator, and then the top plane with 2^top_bits (top_bits = bits - 8(P - 1)):
+//   index(p, j, v) = (p*row_len + j)*256 + v               for p < P - 1
+//   index(P-1, j, v) = (P - 1)*row_len*256 + (j << top_bits) + v
+// One symbol per thread; its P entries are consecutive (generator-major), so a thread's store is one 8P-byte run and a wave's
+// stores are contiguous.  entries[(row*row_len + j)*P + p] = (row, index(p, j, byte_p)); bucket_start[row] = row*P*row_len.
+template <typename T>
+static __global__ void __launch_bounds__(256) k_sym_entries_wide(const T *__restrict__ sym, u32 rows, u32 row_len, u32 bits, u32 P,
+                                                                 u32x2 *__restrict__ entries, u32 *__restrict__ bucket_start) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t <= rows) bucket_start[t] = (u32)t * P * row_len;
+    if (t >= (u64)rows * row_len) return;
+    const u32 row = (u32)(t / row_len), j = (u32)(t % row_len);
+    const u32 s = (u32)sym[t] & (bits >= 32 ? ~0u : (1u << bits) - 1u);
+    const u32 top_bits = bits - 8 * (P - 1);
+    u32x2 *e = entries + t * P;
+    for (u32 p = 0; p + 1 < P; ++p) e[p] = mk_u32x2(row, ((p * row_len + j) << 8) + ((s >> (8 * p)) & 0xffu));
+    e[P - 1] = mk_u32x2(row, (((P - 1) * row_len) << 8) + (j << top_bits) + (s >> (8 * (P - 1))));
+}
+
 // Deterministic test key: B_i = (k0 + i*d)*G, G = (-1, 2) (the discrete logs are known, so
 // any MSM over these bases can be checked in O(n) field operations).  Thread t produces
 // `per` consecutive points (XYZZ, normalised afterwards by k_xyzz_normalize).

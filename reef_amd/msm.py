@@ -212,6 +212,41 @@ class MsmContext(_Handle):
         check(self._lib.reef_msm_rows_symbols(self._h, ptr, rows, row_len, loc, symbol_bits, bp, hp, bool(blinds_are_mont), optr, oloc))
         return out
 
+    def msm_rows_symbols_wide(self, symbols: Buf, rows: int, row_len: int, symbol_bits: int, *, elem_bytes: Optional[int] = None,
+                              blinds: Optional[Buf] = None, h: Optional[Buf] = None, blinds_are_mont: bool = True,
+                              out: Optional[Buf] = None) -> Buf:
+        """HyraxPC::commit on 16- or 32-bit document symbols (< 2^symbol_bits): a uint16 / uint32 array, or a device buffer of
+        rows*row_len symbols of `elem_bytes` (2 or 4) each."""
+        if isinstance(symbols, np.ndarray):
+            if symbols.dtype not in (np.uint16, np.uint32):
+                raise TypeError("wide symbols must be uint16 or uint32")
+            if elem_bytes not in (None, symbols.dtype.itemsize):
+                raise ValueError(f"elem_bytes = {elem_bytes} does not match {symbols.dtype}")
+            elem_bytes = symbols.dtype.itemsize
+            if not symbols.flags["C_CONTIGUOUS"]:
+                raise ValueError("host buffers must be C-contiguous")
+            if symbols.nbytes < rows * row_len * elem_bytes:
+                raise ValueError(f"host buffer too small: {symbols.nbytes} < {rows * row_len * elem_bytes} bytes")
+            loc, ptr = REEF_HOST, symbols.ctypes.data
+        else:
+            if elem_bytes is None:
+                raise ValueError("elem_bytes is required for device-resident symbols")
+            loc, ptr = _loc_ptr(symbols, rows * row_len * elem_bytes)
+        bp = hp = None
+        if blinds is not None:
+            if h is None:
+                raise ValueError("blinds need the blinding generator h")
+            bloc, bp = _loc_ptr(blinds, 32 * rows)
+            hloc, hp = _loc_ptr(h, 64)
+            if bloc != loc or hloc != loc:
+                raise ValueError("blinds and h must live where the symbols live")
+        if out is None:
+            out = np.zeros((rows, 12), dtype=np.uint64)
+        oloc, optr = _loc_ptr(out, 96 * rows)
+        check(self._lib.reef_msm_rows_symbols_wide(self._h, ptr, elem_bytes, rows, row_len, loc, symbol_bits, bp, hp, bool(blinds_are_mont),
+                                                   optr, oloc))
+        return out
+
     def ipa_cross_terms(self, a: np.ndarray, w1s, w2s, *, is_mont: bool = True):
         """Cross terms (L, R) of IPA round k = len(w1s) over the original generators, without
         folding them: a = a_lo || a_hi (n / 2^k scalars), w1s/w2s = challenges so far (ints)."""

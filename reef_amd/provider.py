@@ -260,10 +260,25 @@ class HyraxPC:
         comp = msm.normalize(self.gens_v.curve, out, affine=False, compressed=True)[1]
         return out, comp
 
+    @staticmethod
+    def check_symbols(symbols, symbol_bits: int) -> np.ndarray:
+        """The flat uint8 / uint16 / uint32 array `commit_symbols` hands to the device, or ValueError: another dtype, a width the
+        dtype cannot hold, or a value of 2^symbol_bits or more (which would otherwise wrap or be masked: a wrong commitment)."""
+        symbols = np.asarray(symbols)
+        if symbols.dtype not in (np.uint8, np.uint16, np.uint32):
+            raise ValueError(f"symbols must be uint8, uint16 or uint32, not {symbols.dtype}")
+        if not 1 <= symbol_bits <= 8 * symbols.dtype.itemsize:
+            raise ValueError(f"symbol_bits = {symbol_bits} does not fit {symbols.dtype} symbols")
+        symbols = np.ascontiguousarray(symbols).reshape(-1)
+        if symbols.size and int(symbols.max()) >> symbol_bits:
+            raise ValueError(f"symbol {int(symbols.max())} does not fit symbol_bits = {symbol_bits}")
+        return symbols
+
     def commit_symbols(self, symbols: np.ndarray, blinds: np.ndarray, symbol_bits: int, *, blinds_are_mont: bool = True):
-        """HyraxPC::commit from the document symbols themselves (uint8, < 2^symbol_bits; the values Reef turns into
-        the polynomial's evaluations, framework.rs:978-1011): same row commitments as `commit`."""
-        symbols = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1)
+        """HyraxPC::commit from the document symbols themselves (uint8, uint16 or uint32, < 2^symbol_bits; the values Reef turns
+        into the polynomial's evaluations, framework.rs:978-1011): same row commitments as `commit`.  The dtype chooses the
+        entry: bytes go to reef_msm_rows_symbols, wider symbols to reef_msm_rows_symbols_wide."""
+        symbols = self.check_symbols(symbols, symbol_bits)
         n = symbols.shape[0]
         if n & (n - 1):
             raise ValueError("polynomial length must be a power of two")
@@ -272,8 +287,14 @@ class HyraxPC:
         if row_len > len(self.gens_v):
             raise ValueError("not enough row generators")
         blinds = np.ascontiguousarray(blinds, dtype=np.uint64).reshape(rows, 4)
-        target = self.gens_v._on_devices() or self.gens_v._context()
-        out = target.msm_rows_symbols(symbols, rows, row_len, symbol_bits, blinds=blinds, h=self.gens_v.h, blinds_are_mont=blinds_are_mont)
+        if symbols.dtype == np.uint8:
+            target = self.gens_v._on_devices() or self.gens_v._context()
+            out = target.msm_rows_symbols(symbols, rows, row_len, symbol_bits, blinds=blinds, h=self.gens_v.h, blinds_are_mont=blinds_are_mont)
+        else:
+            if self.gens_v._devices is not None:
+                raise ValueError("wide symbols are not split over devices yet")
+            out = self.gens_v._context().msm_rows_symbols_wide(symbols, rows, row_len, symbol_bits, blinds=blinds, h=self.gens_v.h,
+                                                               blinds_are_mont=blinds_are_mont)
         comp = msm.normalize(self.gens_v.curve, out, affine=False, compressed=True)[1]
         return out, comp
 

@@ -217,6 +217,10 @@ while time.time() < t_end:
                 sym = np.ascontiguousarray(R.gen_scalars(cid, seed, rows * row_len, kind=2, small_bound=bound, mont=False)[:, 0].astype(np.uint8))
                 bits = max(1, (bound - 1).bit_length())
                 assert msm.compress(cid, ctx.msm_rows_symbols(sym, rows, row_len, bits, blinds=bl, h=h)) == want, ("sym", cid, rows, row_len, bound)
+            if 0 < bound <= 1 << 16:    # the same values as 16-bit symbols (32-bit on Vesta): plane tables, two planes at bound = 2^16
+                wsym = np.ascontiguousarray(R.gen_scalars(cid, seed, rows * row_len, kind=2, small_bound=bound, mont=False)[:, 0].astype(np.uint32 if cid else np.uint16))
+                bits = max(1, (bound - 1).bit_length())
+                assert msm.compress(cid, ctx.msm_rows_symbols_wide(wsym, rows, row_len, bits, blinds=bl, h=h)) == want, ("sym-wide", cid, rows, row_len, bound)
             if rng.random() < 0.5:      # every buffer on the device, another h (its table is checked and rebuilt on the device)
                 h2 = R.gen_bases_ap(cid, int(rng.integers(1, 1 << 30)), 1, 1)[0].copy() if rng.random() < 0.8 else np.zeros_like(h)
                 want2 = R.compress(cid, R.row_msm(cid, bases, sc, rows, row_len, h=h2, blinds=bl, threads=16))
