@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <optional>
 #include <thread>
 #include <stdio.h>
 #include <stdlib.h>
@@ -325,7 +326,7 @@ struct StreamLease {
 };
 
 // ---- what every resident context next to the MSM (sum-check, NIFS with the rows on it, Hyrax) holds of the device -----------------
-// Its entry points run under mu with `device` current (REEF_ON_DEVICE) and inside a DeviceScope.
+// Its entry points run under mu with `device` current and inside a DeviceScope: all three are one DeviceCall.
 struct DeviceCtx {
     std::mutex mu;
     int device = 0;
@@ -353,6 +354,30 @@ struct DeviceScope {
     }
     DeviceScope(const DeviceScope &) = delete;
     DeviceScope &operator=(const DeviceScope &) = delete;
+};
+// The prologue of an entry point.  The constructor locks mu; the checks that need the lock but no device (the call order, key_matches)
+// come next; enter() makes `device` current and enters the scope.  The destructor leaves in reverse: the scope's wait or idle, the
+// caller's device, the lock.  leave(): the scope ends early (its work is waited for), where a call goes on to a key ctx's own MSM.
+// A state machine's call hands enter() its phase, which is voided once the scope is entered -- a failure half way leaves nothing to
+// continue -- and set only as the call's last step: return call.done(next).
+struct DeviceCall {
+    DeviceCtx *c;
+    OnExit policy;
+    int *phase = nullptr;
+    std::lock_guard<std::mutex> lk;
+    std::optional<DeviceGuard> dev;
+    std::optional<DeviceScope> scope;
+    DeviceCall(DeviceCtx *ctx, OnExit on_exit) : c(ctx), policy(on_exit), lk(ctx->mu) {}
+    reef_status enter(int *void_phase = nullptr) {
+        dev.emplace(c->device);
+        if (!dev->ok) { set_error("cannot make device %d current: %s", c->device, hipGetErrorString(dev->err)); return REEF_ERR_HIP; }
+        scope.emplace(c, policy);
+        REEF_TRY(scope->enter());
+        if ((phase = void_phase)) *phase = 0;
+        return REEF_OK;
+    }
+    reef_status done(int next) { *phase = next; return REEF_OK; }
+    void leave() { scope.reset(); }
 };
 // The end of a resident context: its work is waited for, the stream, the event and its place in the pool's count are given back.
 inline void retire_device_ctx(DeviceCtx *c) {

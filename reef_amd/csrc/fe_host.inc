@@ -1,6 +1,6 @@
 // Host side of the conversion layer (fe_vec.h): scalars in the caller's form on their way into a row's state machine, the eq table
 // over a point, and the check of a borrowed key.  Included after engine.inc and before the rows that sit on a resident context
-// (nifs_engine.inc, spartan_engine.inc, open_engine.inc, hyrax_engine.inc).
+// (nifs_engine.inc, ipa_engine.inc, spartan_engine.inc, open_engine.inc, hyrax_engine.inc).
 namespace reef {
 
 static bool fe_valid(const reef_fe *x, int field) {              // canonical: below the modulus

@@ -1,9 +1,8 @@
 // Host side of the Hyrax consistency argument (hyrax_kernels.inc; include/reef_msm.h 3i) on a resident document; included after
-// open_engine.inc.  create -> eval_begin -> [eval_comm] -> ipa_begin -> ipa_round x (right - 1) -> finish, right = num_vars - left_vars;
-// eval_begin may come at any time and starts the argument over.  The rounds are 3h's (IpaRun), driven from this ctx's stream.
+// proof_order.h (the HY_* phases and the call order) and ipa_engine.inc.  create -> eval_begin -> [eval_comm] -> ipa_begin ->
+// ipa_round x (right - 1) -> finish, right = num_vars - left_vars; eval_begin may come at any time and starts the argument over.  The
+// rounds are IpaRun's, driven from this ctx's stream.
 namespace reef {
-
-enum { HY_NONE = 0, HY_EVAL, HY_IPA, HY_DONE };
 
 template <int C> struct HyraxCtx : DeviceCtx {   // ev: orders the key ctx's stream after this one (IpaRun::ipa_cross)
     static constexpr int F = 1 - C;      // scalar field of curve C
@@ -28,23 +27,16 @@ template <int C> struct HyraxCtx : DeviceCtx {   // ev: orders the key ctx's str
 template <int C> static void hyrax_free(HyraxCtx<C> *c) {
     if (!c) return;
     retire_device_ctx(c);
-    for (DevBuf *b : {&c->z, &c->rb, &c->eqs, &c->part, &c->dot, &c->pts, &c->lint, &c->stage, &c->ip.a, &c->ip.b, &c->ip.partial, &c->ip.out,
-                      &c->ip.blinds, &c->ip.htab, &c->cenc, &c->cdec, &c->cstat})
-        b->release();
+    for (DevBuf *b : {&c->z, &c->rb, &c->eqs, &c->part, &c->dot, &c->pts, &c->lint, &c->stage, &c->cenc, &c->cdec, &c->cstat}) b->release();
+    c->ip.release();
     if (c->comms) v_ctx_destroy<C>(c->comms);
     delete c;
 }
 
-static const char *hy_expected(int phase, u32 rounds, u32 right) {
-    switch (phase) {
-    case HY_EVAL: return "reef_hyrax_ipa_begin";
-    case HY_IPA: return rounds + 1 < right ? "reef_hyrax_ipa_round" : "reef_hyrax_finish";
-    default: return "reef_hyrax_eval_begin";
-    }
-}
+// The call `name` may come now (proof_order.h: REEF_ERR_ARG naming the next call otherwise)
 template <int C> static reef_status hy_expect(HyraxCtx<C> *c, const char *name) {
-    const char *want = hy_expected(c->phase, c->rounds, c->right);
-    if (strcmp(want, name) != 0) { set_error("%s: out of order, the next call is %s", name, want); return REEF_ERR_ARG; }
+    const OrderVerdict v = hy_check(name, c->phase, c->rounds, c->right);
+    if (!v.ok) { set_error("%s", v.text); return REEF_ERR_ARG; }
     return REEF_OK;
 }
 template <int C>
@@ -117,7 +109,7 @@ static reef_status v_hyrax_eval_begin(void *impl, void *key_impl, const reef_fe 
     HyraxCtx<C> *c = (HyraxCtx<C> *)impl;
     Ctx<C> *key = (Ctx<C> *)key_impl;
     if (!key || !point) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     const u32 nv = c->left + c->right;
     std::vector<fe> pt(nv);
     REEF_TRY(fe_import_all<F>(point, nv, is_mont, "reef_hyrax_eval_begin", "point", pt.data()));
@@ -127,10 +119,7 @@ static reef_status v_hyrax_eval_begin(void *impl, void *key_impl, const reef_fe 
         set_error("reef_hyrax_eval_begin: the key holds %zu points, the argument needs exactly 2^(num_vars - left_vars) = %u", key_n, c->cols);
         return REEF_ERR_ARG;
     }
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
-    c->phase = HY_NONE;                                       // a failure half way leaves nothing to continue
+    REEF_TRY(call.enter(&c->phase));
     c->pt = pt;
     REEF_TRY(ipa_alloc(&c->ip, c->cols));
     MlePoint mp;
@@ -175,8 +164,7 @@ static reef_status v_hyrax_eval_begin(void *impl, void *key_impl, const reef_fe 
     }
     c->ip.key = key;
     c->rounds = 0;
-    c->phase = HY_EVAL;
-    return REEF_OK;
+    return call.done(HY_EVAL);
 }
 
 // the weights of comm_LZ where the MSM reads them: lint = eq(point[..left]) as canonical integers.  Inside the ctx's scope; waits.
@@ -205,14 +193,11 @@ template <int C> static reef_status hy_set_comms(HyraxCtx<C> *c, const reef_affi
 template <int C> static reef_status v_hyrax_eval_comm(void *impl, const reef_affine *row_comms, int loc, reef_jacobian *comm_lz) {
     HyraxCtx<C> *c = (HyraxCtx<C> *)impl;
     if (!row_comms || !comm_lz) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (c->phase == HY_NONE) { set_error("reef_hyrax_eval_comm: the point is set by reef_hyrax_eval_begin, the next call"); return REEF_ERR_ARG; }
-    REEF_ON_DEVICE(c->device);
-    {
-        DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-        REEF_TRY(scope.enter());
-        REEF_TRY(hy_row_weights(c));
-    }
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    REEF_TRY(hy_expect(c, "reef_hyrax_eval_comm"));
+    REEF_TRY(call.enter());
+    REEF_TRY(hy_row_weights(c));
+    call.leave();                                             // the rest is the key ctx's own work, on its stream
     const bool same = loc != REEF_DEVICE && c->comms && c->comms_host.size() == c->rows &&
                       memcmp(c->comms_host.data(), row_comms, c->rows * sizeof(reef_affine)) == 0;
     if (!same) c->comms_bytes.clear();
@@ -235,36 +220,33 @@ template <int C> static reef_status v_hyrax_eval_comm_compressed(void *impl, con
     HyraxCtx<C> *c = (HyraxCtx<C> *)impl;
     if (!row_comms32 || !comm_lz) { set_error("null argument"); return REEF_ERR_ARG; }
     if (loc == REEF_DEVICE && ((uintptr_t)row_comms32 & 15)) { set_error("reef_hyrax_eval_comm_compressed: device rows must be 16-byte aligned"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (c->phase == HY_NONE) { set_error("reef_hyrax_eval_comm_compressed: the point is set by reef_hyrax_eval_begin, the next call"); return REEF_ERR_ARG; }
-    REEF_ON_DEVICE(c->device);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    REEF_TRY(hy_expect(c, "reef_hyrax_eval_comm_compressed"));
     const size_t bytes = (size_t)c->rows * 32;
     const bool same = loc != REEF_DEVICE && c->comms && c->comms_bytes.size() == bytes && memcmp(c->comms_bytes.data(), row_comms32, bytes) == 0;
-    {
-        DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-        REEF_TRY(scope.enter());
-        REEF_TRY(hy_row_weights(c));
-        if (!same) {
-            REEF_TRY(c->cdec.ensure(c->rows * sizeof(affine256)));
-            REEF_TRY(c->cstat.ensure(2 * sizeof(u64)));
-            const fe256 *enc = (const fe256 *)row_comms32;
-            if (loc != REEF_DEVICE) {
-                REEF_TRY(c->cenc.ensure(bytes));
-                REEF_HIP_TRY(hipMemcpyAsync(c->cenc.p, row_comms32, bytes, hipMemcpyHostToDevice, c->stream));
-                enc = c->cenc.template as<fe256>();
-            }
-            decompress_launch<C>(c->stream, enc, c->rows, c->cdec.template as<affine256>(), c->cstat.template as<unsigned long long>());
-            REEF_HIP_TRY(hipGetLastError());
-            u64 stats[2] = {0, 0};
-            REEF_HIP_TRY(hipMemcpyAsync(stats, c->cstat.p, sizeof stats, hipMemcpyDeviceToHost, c->stream));
-            REEF_HIP_TRY(hipStreamSynchronize(c->stream));
-            if (stats[0]) {
-                set_error("reef_hyrax_eval_comm_compressed: row %llu is not the encoding of a point (%llu such rows); the row commitments of the previous call stay",
-                          (unsigned long long)stats[1], (unsigned long long)stats[0]);
-                return REEF_ERR_ARG;
-            }
+    REEF_TRY(call.enter());
+    REEF_TRY(hy_row_weights(c));
+    if (!same) {
+        REEF_TRY(c->cdec.ensure(c->rows * sizeof(affine256)));
+        REEF_TRY(c->cstat.ensure(2 * sizeof(u64)));
+        const fe256 *enc = (const fe256 *)row_comms32;
+        if (loc != REEF_DEVICE) {
+            REEF_TRY(c->cenc.ensure(bytes));
+            REEF_HIP_TRY(hipMemcpyAsync(c->cenc.p, row_comms32, bytes, hipMemcpyHostToDevice, c->stream));
+            enc = c->cenc.template as<fe256>();
+        }
+        decompress_launch<C>(c->stream, enc, c->rows, c->cdec.template as<affine256>(), c->cstat.template as<unsigned long long>());
+        REEF_HIP_TRY(hipGetLastError());
+        u64 stats[2] = {0, 0};
+        REEF_HIP_TRY(hipMemcpyAsync(stats, c->cstat.p, sizeof stats, hipMemcpyDeviceToHost, c->stream));
+        REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+        if (stats[0]) {
+            set_error("reef_hyrax_eval_comm_compressed: row %llu is not the encoding of a point (%llu such rows); the row commitments of the previous call stay",
+                      (unsigned long long)stats[1], (unsigned long long)stats[0]);
+            return REEF_ERR_ARG;
         }
     }
+    call.leave();                                             // the rest is the key ctx's own work, on its stream
     if (!same) {
         c->comms_host.clear();
         c->comms_bytes.clear();
@@ -283,12 +265,9 @@ static reef_status v_hyrax_ipa_begin(void *impl, const reef_affine *q, const ree
     const bool with_h = h && blinds;
     fe256 b2[2] = {};
     if (with_h) REEF_TRY(fe_import_all<F>(blinds, 2, is_mont, "reef_hyrax_ipa_begin", "blinds", b2));
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(hy_expect(c, "reef_hyrax_ipa_begin"));
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
-    c->phase = HY_NONE;
+    REEF_TRY(call.enter(&c->phase));
     IpaRun<C> *ip = &c->ip;
     ip->q = *q;
     ip->with_h = false;
@@ -303,8 +282,7 @@ static reef_status v_hyrax_ipa_begin(void *impl, const reef_affine *q, const ree
     REEF_HIP_TRY(hipGetLastError());
     REEF_TRY(ipa_cross(ip, c->stream, c->ev, L, R));
     c->rounds = 0;
-    c->phase = HY_IPA;
-    return REEF_OK;
+    return call.done(HY_IPA);
 }
 
 template <int C>
@@ -316,18 +294,14 @@ static reef_status v_hyrax_ipa_round(void *impl, const reef_fe *r, const reef_fe
     if (!L || !R) { set_error("null argument"); return REEF_ERR_ARG; }
     fe256 b2[2] = {};
     if (blinds) REEF_TRY(fe_import_all<F>(blinds, 2, is_mont, "reef_hyrax_ipa_round", "blinds", b2));
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(hy_expect(c, "reef_hyrax_ipa_round"));
     if (blinds && !c->ip.with_h) { set_error("reef_hyrax_ipa_round: blinds given, but reef_hyrax_ipa_begin took no h term"); return REEF_ERR_ARG; }
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
-    c->phase = HY_NONE;
+    REEF_TRY(call.enter(&c->phase));
     if (c->ip.with_h) REEF_TRY(ipa_set_blinds(&c->ip, c->stream, b2));   // NULL: zero blinds this round
     REEF_TRY(ipa_round(&c->ip, c->stream, c->ev, ri, L, R));
     ++c->rounds;
-    c->phase = HY_IPA;
-    return REEF_OK;
+    return call.done(HY_IPA);
 }
 
 template <int C> static reef_status v_hyrax_finish(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat) {
@@ -335,15 +309,11 @@ template <int C> static reef_status v_hyrax_finish(void *impl, const reef_fe *r_
     fe ri;
     REEF_TRY(fe_challenge<HyraxCtx<C>::F>(r_last, is_mont, "reef_hyrax_finish", ri, true));
     if (!a_hat) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(hy_expect(c, "reef_hyrax_finish"));
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
-    c->phase = HY_NONE;
+    REEF_TRY(call.enter(&c->phase));
     REEF_TRY(ipa_last(&c->ip, c->stream, ri, is_mont, a_hat, b_hat));
-    c->phase = HY_DONE;
-    return REEF_OK;
+    return call.done(HY_DONE);
 }
 
 // which: 0 a, 1 b, the first `count` of their current length
@@ -351,13 +321,11 @@ template <int C> static reef_status v_hyrax_read(void *impl, int which, size_t c
     HyraxCtx<C> *c = (HyraxCtx<C> *)impl;
     if (count && !out) { set_error("null argument"); return REEF_ERR_ARG; }
     if (which != 0 && which != 1) { set_error("reef_hyrax_read: which must be 0 (a) or 1 (b)"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (c->phase == HY_NONE) { set_error("reef_hyrax_read: a and b exist from reef_hyrax_eval_begin on, the next call"); return REEF_ERR_ARG; }
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    REEF_TRY(hy_expect(c, "reef_hyrax_read"));
     if (count > c->ip.len) { set_error("reef_hyrax_read: %zu entries asked, the vector has %zu", count, c->ip.len); return REEF_ERR_ARG; }
     if (!count) return REEF_OK;
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
+    REEF_TRY(call.enter());
     return ipa_read(&c->ip, c->stream, c->stage, which, count, out, to_mont);
 }
 

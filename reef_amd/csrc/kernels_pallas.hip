@@ -14,6 +14,8 @@
 #include "engine.inc"
 #include "fe_host.inc"
 #include "nifs_engine.inc"
+#include "proof_order.h"
+#include "ipa_engine.inc"
 #include "spartan_engine.inc"
 #include "open_engine.inc"
 #include "hyrax_engine.inc"

@@ -106,10 +106,8 @@ static reef_status v_nifs_set_matrix(void *impl, int which, const uint32_t *row,
                 cvals[p] = vals[e];
             }
     }
-    std::lock_guard<std::mutex> lk(c->mu);
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    REEF_TRY(call.enter());
     c->has[which] = false;
     c->rows.prepared = c->cols.prepared = false;
     ++c->gen;
@@ -241,10 +239,8 @@ template <int C>
 static reef_status v_nifs_set_running(void *impl, const reef_fe *W, const reef_fe *E, const reef_fe *u, const reef_fe *X, int loc, bool is_mont) {
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     if ((c->num_vars && !W) || !u || (c->num_io && !X)) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    REEF_TRY(call.enter());
     c->running = c->committed = false;
     ++c->gen;
     fe256 *dE = c->E.template as<fe256>();
@@ -268,14 +264,12 @@ static reef_status v_nifs_commit_t(void *impl, void *key_impl, const reef_fe *W2
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     Ctx<C> *key = (Ctx<C> *)key_impl;
     if (!key || !comm_t || (c->num_vars && !W2) || (c->num_io && !X2)) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     if (!c->running) { set_error("reef_nifs_commit_T: no running instance (reef_nifs_set_running first)"); return REEF_ERR_ARG; }
     size_t key_n = 0;
     REEF_TRY(key_matches(key, c->device, "reef_nifs_commit_T", "NIFS", &key_n));
     if (key_n < c->num_cons) { set_error("reef_nifs_commit_T: the key holds %zu points, T has %zu entries", key_n, c->num_cons); return REEF_ERR_ARG; }
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
+    REEF_TRY(call.enter());
     REEF_TRY(nifs_prepare(c));
     c->committed = false;
     ++c->gen;
@@ -296,16 +290,14 @@ template <int C> static reef_status v_nifs_fold(void *impl, const reef_fe *r, bo
     constexpr int F = NifsCtx<C>::F;
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     if (!r) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     if (!c->committed) { set_error("reef_nifs_fold: no cross term of this step (reef_nifs_commit_T first)"); return REEF_ERR_ARG; }
     fe256 rp;
     memcpy(&rp, r, sizeof rp);
     const fe ri = fe_from_caller<F>(rp, is_mont);                                         // r R'
     const fe256 r_int = fe_to_table<F>(ri);
     const fe256 r_sq = fe_to_table<F>(fe_mul<F>(ri, fe_const<F>(FC<F>::C_R2, 1.0)));    // r R'^2: times an integer T gives r T R'
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
+    REEF_TRY(call.enter());
     ++c->gen;
     hipLaunchKernelGGL(k_nifs_axpy<F>, dim3(ceil_div(c->nz, 256)), dim3(256), 0, c->stream, c->z1.template as<fe256>(), (const fe256 *)c->z2.p, (u32)c->nz, r_int);
     hipLaunchKernelGGL(k_nifs_axpy<F>, dim3(ceil_div(c->num_cons, 256)), dim3(256), 0, c->stream, c->E.template as<fe256>(), (const fe256 *)c->T.p,
@@ -320,7 +312,7 @@ template <int C> static reef_status v_nifs_fold(void *impl, const reef_fe *r, bo
 template <int C> static reef_status v_nifs_read(void *impl, int which, size_t count, reef_fe *out, bool to_mont) {
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     if (count && !out) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     const fe256 *src = nullptr;
     size_t len = 0;
     switch (which) {
@@ -334,9 +326,7 @@ template <int C> static reef_status v_nifs_read(void *impl, int which, size_t co
     if (count > len) { set_error("reef_nifs_read: %zu entries asked, the vector has %zu", count, len); return REEF_ERR_ARG; }
     if (which == 2 ? !c->have_t : !c->running) { set_error("reef_nifs_read: nothing to read yet"); return REEF_ERR_ARG; }
     if (!count) return REEF_OK;
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
+    REEF_TRY(call.enter());
     REEF_TRY(c->stage.ensure(count * sizeof(fe256)));
     hipLaunchKernelGGL(k_fe_export<NifsCtx<C>::F>, dim3(ceil_div(count, 256)), dim3(256), 0, c->stream, src, (u64)count, (int)(which == 2), (int)to_mont,
                        c->stage.template as<fe256>());
@@ -348,11 +338,9 @@ template <int C> static reef_status v_nifs_read(void *impl, int which, size_t co
 
 template <int C> static reef_status v_nifs_check(void *impl, uint64_t *violations, uint64_t *first_bad_row) {
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     if (!c->running) { set_error("reef_nifs_check_relaxed: no running instance (reef_nifs_set_running first)"); return REEF_ERR_ARG; }
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
+    REEF_TRY(call.enter());
     REEF_TRY(nifs_prepare(c));
     const u32 init[2] = {0u, 0xffffffffu};
     REEF_HIP_TRY(hipMemcpyAsync(c->counters.p, init, sizeof init, hipMemcpyHostToDevice, c->stream));

@@ -1,12 +1,8 @@
-// Host side of row N5 (the sum-checks of RelaxedR1CSSNARK::prove: spartan_kernels.inc) on a NIFS ctx; included after nifs_engine.inc.
+// Host side of row N5 (the sum-checks of RelaxedR1CSSNARK::prove: spartan_kernels.inc) on a NIFS ctx; included after nifs_engine.inc,
+// proof_order.h (the SP_* phases and the call order, the opening's included) and ipa_engine.inc.
 // A prover-side state machine: begin -> outer_round x (ell_x - 1) -> outer_claims -> inner_begin -> inner_round x (ell_y - 1) ->
 // inner_claims, with ell_x = log2(num_cons_pad), ell_y = log2(2 num_vars_pad).  The running instance is read, never written.
 namespace reef {
-
-enum { SP_NONE = 0, SP_OUTER, SP_OUTER_DONE, SP_INNER, SP_DONE, SP_OPEN_BEGUN, SP_OPEN_FOLDED, SP_OPEN_IPA, SP_OPEN_DONE };   // SP_OPEN_*: open_engine.inc
-
-template <int C> struct IpaRun;                            // the IPA rounds of 3h and 3i (open_engine.inc)
-template <int C> static void ipa_run_release(IpaRun<C> *ip);
 
 template <int C> struct SpartanState {
     int phase = SP_NONE;
@@ -20,12 +16,12 @@ template <int C> struct SpartanState {
     // the batched IPA opening (open_engine.inc)
     DevBuf e1, e2;                       // eq(r_x), eq(r_y[1..])
     size_t on = 0;                       // n
-    IpaRun<C> *ip = nullptr;             // a, b and the rounds, made by the first open_begin
+    IpaRun<C> ip;                        // a, b and the rounds
 };
 template <int C> static void spartan_release(SpartanState<C> *s) {
     if (!s) return;
     for (DevBuf *b : {&s->eq, &s->az, &s->bz, &s->cz, &s->d, &s->abc, &s->z, &s->pts, &s->partial, &s->out, &s->e1, &s->e2}) b->release();
-    ipa_run_release<C>(s->ip);
+    s->ip.release();
     delete s;
 }
 
@@ -34,32 +30,15 @@ static u32 sp_log2(size_t n) {
     while ((size_t)1 << l < n) ++l;
     return l;
 }
-static const char *sp_expected(int phase, u32 rounds, u32 ell_x, u32 ell_y, u32 ell_n = 0) {
-    switch (phase) {
-    case SP_OPEN_BEGUN: return "reef_spartan_open_fold";
-    case SP_OPEN_FOLDED: return "reef_spartan_open_ipa_begin";
-    case SP_OPEN_IPA: return rounds + 1 < ell_n ? "reef_spartan_open_ipa_round" : "reef_spartan_open_finish";
-    case SP_OUTER: return rounds + 1 < ell_x ? "reef_spartan_outer_round" : "reef_spartan_outer_claims";
-    case SP_OUTER_DONE: return "reef_spartan_inner_begin";
-    case SP_INNER: return rounds + 1 < ell_y ? "reef_spartan_inner_round" : "reef_spartan_inner_claims";
-    default: return "reef_spartan_begin";
-    }
-}
-// The call `name` is the one the state machine expects (REEF_ERR_ARG naming the expected call otherwise)
+// The call `name` (of N5 or of the opening) may come now (proof_order.h: REEF_ERR_ARG naming the next call otherwise)
 template <int C> static reef_status sp_expect(NifsCtx<C> *c, const char *name) {
     SpartanState<C> *s = c->sp;
-    if (s && s->phase != SP_NONE && s->gen != c->gen) {
-        s->phase = SP_NONE;
-        set_error("%s: the matrices or the running instance changed (set_matrix, set_running, commit_T or fold) since reef_spartan_begin: "
-                  "the next call is reef_spartan_begin", name);
-        return REEF_ERR_ARG;
-    }
-    const char *want = s ? sp_expected(s->phase, s->rounds, s->ell_x, s->ell_y, sp_log2(s->on)) : "reef_spartan_begin";
-    if (strcmp(want, name) != 0) { set_error("%s: out of order, the next call is %s", name, want); return REEF_ERR_ARG; }
+    const SpOrder o = s ? SpOrder{s->phase, s->rounds, s->ell_x, s->ell_y, sp_log2(s->on)} : SpOrder{};
+    const OrderVerdict v = sp_check(name, s ? &o : nullptr, s && s->gen != c->gen);
+    if (v.reset) s->phase = SP_NONE;
+    if (!v.ok) { set_error("%s", v.text); return REEF_ERR_ARG; }
     return REEF_OK;
 }
-
-static u32 sp_grid(size_t n) { return (u32)std::max<size_t>(1, std::min<size_t>(SP_BLOCKS, ceil_div(n, SP_THREADS))); }
 
 // one round (bind with r when bind, then the sums of the next round: nv values) -> evals (HOST) in the caller's form
 template <int C, int CUBIC>
@@ -111,17 +90,14 @@ static reef_status v_spartan_begin(void *impl, size_t num_cons_pad, size_t num_v
     const u32 ell_x = sp_log2(num_cons_pad);
     std::vector<fe> t(ell_x);
     REEF_TRY(fe_import_all<F>(tau, ell_x, is_mont, "reef_spartan_begin", "tau", t.data()));
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     if (!c->running || !c->has[0] || !c->has[1] || !c->has[2]) {
         set_error("reef_spartan_begin: set the matrices A, B, C and the running instance first (reef_nifs_set_matrix, reef_nifs_set_running)");
         return REEF_ERR_ARG;
     }
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
     if (!c->sp) c->sp = new SpartanState<C>();
     SpartanState<C> *s = c->sp;
-    s->phase = SP_NONE;
+    REEF_TRY(call.enter(&s->phase));
     REEF_TRY(nifs_prepare(c));
     for (DevBuf *b : {&s->eq, &s->az, &s->bz, &s->cz, &s->d}) REEF_TRY(b->ensure(num_cons_pad * sizeof(fe256)));
     REEF_TRY(s->partial.ensure(SP_BLOCKS * 27 * sizeof(unsigned long long)));
@@ -146,8 +122,7 @@ static reef_status v_spartan_begin(void *impl, size_t num_cons_pad, size_t num_v
     s->ry.clear();
     s->gen = c->gen;
     REEF_TRY((sp_round<C, 1>(c, tabs, (u32)(num_cons_pad / 2), false, fe_zero(), is_mont, evals)));
-    s->phase = SP_OUTER;
-    return REEF_OK;
+    return call.done(SP_OUTER);
 }
 
 template <int C> static fe256 *const *sp_outer_tabs(SpartanState<C> *s, fe256 *(&t)[4]) {
@@ -168,20 +143,16 @@ template <int C> static reef_status v_spartan_outer_round(void *impl, const reef
     fe ri;
     REEF_TRY(fe_challenge<NifsCtx<C>::F>(r, is_mont, "reef_spartan_outer_round", ri));
     if (!evals) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(sp_expect(c, "reef_spartan_outer_round"));
     SpartanState<C> *s = c->sp;
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
+    REEF_TRY(call.enter(&s->phase));
     fe256 *t[4];
     const u32 h = (u32)(s->ncp >> (s->rounds + 2));          // pairs of the next round
-    s->phase = SP_NONE;                                       // a failure half way leaves nothing to continue
     REEF_TRY((sp_round<C, 1>(c, sp_outer_tabs(s, t), h, true, ri, is_mont, evals)));
     s->rx.push_back(ri);
     ++s->rounds;
-    s->phase = SP_OUTER;
-    return REEF_OK;
+    return call.done(SP_OUTER);
 }
 
 template <int C> static reef_status v_spartan_outer_claims(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *claims) {
@@ -190,13 +161,10 @@ template <int C> static reef_status v_spartan_outer_claims(void *impl, const ree
     fe ri;
     REEF_TRY(fe_challenge<NifsCtx<C>::F>(r_last, is_mont, "reef_spartan_outer_claims", ri));
     if (!claims) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(sp_expect(c, "reef_spartan_outer_claims"));
     SpartanState<C> *s = c->sp;
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
-    s->phase = SP_NONE;
+    REEF_TRY(call.enter(&s->phase));
     const int form = is_mont ? SP_FORM_MONT : SP_FORM_INTEGER;
     fe256 *t[4];
     SpRound a;
@@ -212,8 +180,7 @@ template <int C> static reef_status v_spartan_outer_claims(void *impl, const ree
     REEF_HIP_TRY(hipMemcpyAsync(claims, s->out.p, 4 * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));
     s->rounds = 0;
-    s->phase = SP_OUTER_DONE;
-    return REEF_OK;
+    return call.done(SP_OUTER_DONE);
 }
 
 template <int C> static reef_status v_spartan_inner_begin(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals) {
@@ -222,13 +189,10 @@ template <int C> static reef_status v_spartan_inner_begin(void *impl, const reef
     fe ri;
     REEF_TRY(fe_challenge<NifsCtx<C>::F>(r, is_mont, "reef_spartan_inner_begin", ri));
     if (!evals) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(sp_expect(c, "reef_spartan_inner_begin"));
     SpartanState<C> *s = c->sp;
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
-    s->phase = SP_NONE;
+    REEF_TRY(call.enter(&s->phase));
     REEF_TRY(nifs_segments(c, c->h_colptr, c->nz, c->cols));
     const size_t n2 = 2 * s->nvp;
     REEF_TRY(s->abc.ensure(n2 * sizeof(fe256)));
@@ -258,8 +222,7 @@ template <int C> static reef_status v_spartan_inner_begin(void *impl, const reef
     fe256 *t[4];
     REEF_TRY((sp_round<C, 0>(c, sp_inner_tabs(s, t), (u32)s->nvp, false, fe_zero(), is_mont, evals)));
     s->rounds = 0;
-    s->phase = SP_INNER;
-    return REEF_OK;
+    return call.done(SP_INNER);
 }
 
 template <int C> static reef_status v_spartan_inner_round(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals) {
@@ -267,20 +230,16 @@ template <int C> static reef_status v_spartan_inner_round(void *impl, const reef
     fe ri;
     REEF_TRY(fe_challenge<NifsCtx<C>::F>(r, is_mont, "reef_spartan_inner_round", ri));
     if (!evals) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(sp_expect(c, "reef_spartan_inner_round"));
     SpartanState<C> *s = c->sp;
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
-    s->phase = SP_NONE;
+    REEF_TRY(call.enter(&s->phase));
     fe256 *t[4];
     const u32 h = (u32)((2 * s->nvp) >> (s->rounds + 2));
     REEF_TRY((sp_round<C, 0>(c, sp_inner_tabs(s, t), h, true, ri, is_mont, evals)));
     s->ry.push_back(ri);
     ++s->rounds;
-    s->phase = SP_INNER;
-    return REEF_OK;
+    return call.done(SP_INNER);
 }
 
 template <int C> static reef_status v_spartan_inner_claims(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *claims) {
@@ -289,13 +248,10 @@ template <int C> static reef_status v_spartan_inner_claims(void *impl, const ree
     fe ri;
     REEF_TRY(fe_challenge<NifsCtx<C>::F>(r_last, is_mont, "reef_spartan_inner_claims", ri));
     if (!claims) { set_error("null argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
     REEF_TRY(sp_expect(c, "reef_spartan_inner_claims"));
     SpartanState<C> *s = c->sp;
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
-    REEF_TRY(scope.enter());
-    s->phase = SP_NONE;
+    REEF_TRY(call.enter(&s->phase));
     const int form = is_mont ? SP_FORM_MONT : SP_FORM_INTEGER;
     fe256 *t[4];
     SpRound a;
@@ -313,8 +269,7 @@ template <int C> static reef_status v_spartan_inner_claims(void *impl, const ree
     else REEF_HIP_TRY(hipMemsetAsync(s->out.template as<fe256>() + 2, 0, sizeof(fe256), c->stream));
     REEF_HIP_TRY(hipMemcpyAsync(claims, s->out.p, 3 * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));
-    s->phase = SP_DONE;
-    return REEF_OK;
+    return call.done(SP_DONE);
 }
 
 template <int C> SpartanVTable make_spartan_vtable() {

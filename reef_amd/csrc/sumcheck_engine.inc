@@ -404,10 +404,8 @@ template <int C> static reef_status sc_defer_flush(ScCtx<C> *c) {
 template <int C> static reef_status v_sc_set(void *impl, int which, const reef_fe *vals, size_t n, int loc) {
     ScCtx<C> *c = (ScCtx<C> *)impl;
     if (!c || (n && !vals) || n > c->len || which < 0 || which > 1) { set_error("bad argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::RELEASE_IF_IDLE);
-    REEF_TRY(scope.enter());
+    DeviceCall call(c, OnExit::RELEASE_IF_IDLE);
+    REEF_TRY(call.enter());
     if (which == 1) REEF_TRY(sc_defer_flush<C>(c));
     else c->defer_on = false;               // T is replaced
     (which == 0 ? c->valid_t : c->valid_e) = c->len;
@@ -436,10 +434,8 @@ template <int C> static reef_status v_sc_read(void *impl, int which, size_t coun
     ScCtx<C> *c = (ScCtx<C> *)impl;
     if (!c || !out_host || count > c->len || which < 0 || which > 1) { set_error("bad argument"); return REEF_ERR_ARG; }
     if (count == 0) return REEF_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::RELEASE_IF_IDLE);
-    REEF_TRY(scope.enter());
+    DeviceCall call(c, OnExit::RELEASE_IF_IDLE);
+    REEF_TRY(call.enter());
     REEF_TRY(sc_defer_flush<C>(c));        // rows whose first fold was deferred are written out: this is not their second fold
     const size_t live = which == 0 ? c->valid_t : c->valid_e;
     if (count > live) {
@@ -461,10 +457,8 @@ template <int C> static reef_status v_sc_read(void *impl, int which, size_t coun
 template <int C> static reef_status v_sc_coeffs(void *impl, size_t pow, reef_fe *out3_host) {
     ScCtx<C> *c = (ScCtx<C> *)impl;
     if (!c || !out3_host || pow == 0 || 2 * pow > c->len) { set_error("bad argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::STAY);
-    REEF_TRY(scope.enter());
+    DeviceCall call(c, OnExit::STAY);
+    REEF_TRY(call.enter());
     REEF_TRY(sc_defer_flush<C>(c));        // rows whose first fold was deferred are written out: this is not their second fold
     if (2 * pow > std::min(c->valid_t, c->valid_e)) { set_error("round with pow = %zu needs %zu live entries per table; T has %zu, EQ has %zu", pow, 2 * pow, c->valid_t, c->valid_e); return REEF_ERR_ARG; }
     if (sc_r1_round<C>(c, pow) && sc_struct_round<C>(c, pow)) {
@@ -497,10 +491,8 @@ template <int C> static reef_status v_sc_coeffs(void *impl, size_t pow, reef_fe 
 template <int C> static reef_status v_sc_fold(void *impl, size_t pow, const reef_fe *r) {
     ScCtx<C> *c = (ScCtx<C> *)impl;
     if (!c || !r || pow == 0 || 2 * pow > c->len) { set_error("bad argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::STAY);
-    REEF_TRY(scope.enter());
+    DeviceCall call(c, OnExit::STAY);
+    REEF_TRY(call.enter());
     REEF_TRY(sc_defer_flush<C>(c));        // rows whose first fold was deferred are written out: this is not their second fold
     c->r1_prev_pow = 0;                  // the tables change: no coefficients on the device describe them any more
     if (2 * pow > std::min(c->valid_t, c->valid_e)) { set_error("fold with pow = %zu needs %zu live entries per table; T has %zu, EQ has %zu", pow, 2 * pow, c->valid_t, c->valid_e); return REEF_ERR_ARG; }
@@ -531,10 +523,8 @@ template <int C> static reef_status v_sc_fold(void *impl, size_t pow, const reef
 template <int C> static reef_status v_sc_fold_coeffs(void *impl, size_t pow, const reef_fe *r, reef_fe *out3_host) {
     ScCtx<C> *c = (ScCtx<C> *)impl;
     if (!c || !r || !out3_host || pow < 2 || 2 * pow > c->len) { set_error("bad argument"); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::STAY);
-    REEF_TRY(scope.enter());
+    DeviceCall call(c, OnExit::STAY);
+    REEF_TRY(call.enter());
     const size_t prev_pow = c->r1_prev_pow;
     c->r1_prev_pow = 0;
     if (2 * pow > std::min(c->valid_t, c->valid_e)) { set_error("fold with pow = %zu needs %zu live entries per table; T has %zu, EQ has %zu", pow, 2 * pow, c->valid_t, c->valid_e); return REEF_ERR_ARG; }
@@ -727,10 +717,8 @@ static reef_status v_sc_gen_eq(void *impl, const reef_fe *rs, const uint32_t *qs
     if (!c || !rs || (nq && !qs) || !last_q || ((size_t)1 << ell) != c->len) { set_error("bad argument (ell must be log2 of the table length)"); return REEF_ERR_ARG; }
     for (size_t k = 0; k < nq; ++k)
         if (qs[k] >= c->len) { set_error("qs[%zu] out of range", k); return REEF_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(c->mu);
-    REEF_ON_DEVICE(c->device);
-    DeviceScope scope(c, OnExit::RELEASE_IF_IDLE);
-    REEF_TRY(scope.enter());
+    DeviceCall call(c, OnExit::RELEASE_IF_IDLE);
+    REEF_TRY(call.enter());
     REEF_TRY(sc_defer_flush<C>(c));        // rows whose first fold was deferred are written out: this is not their second fold
     c->valid_e = c->len;
     sc_read_switches<C>(c);                  // a step runs under one setting of the switches

@@ -53,6 +53,16 @@ def test_the_host_only_checker_program_agrees_with_the_library():
         assert run.stdout == buf.value.decode() + "\n", arg
 
 
+def test_the_call_order_of_the_resident_proof_contexts():
+    """proof_order_selftest is csrc/proof_order.h alone (host/Makefile: no HIP, no library): every phase of the Spartan sum-checks with
+    the opening and of the Hyrax argument against every call of the family, with a table written out in the program -- accept or
+    refuse, the full error text and the phase reset.  One line, exit 1 on a mismatch."""
+    exe = os.path.join(os.path.dirname(replay.LIB_PATH), "proof_order_selftest")
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert run.stdout.startswith("proof_order_selftest: ok, ") and run.stdout.count("\n") == 1, run.stdout
+
+
 def test_the_msm_replay_defaults_are_unchanged():
     """bench.py calls replay.run(cfg, nofold=True, tables=...): the prove leg is a separate entry point, opt-in."""
     sig = inspect.signature(replay.run)
