@@ -29,6 +29,7 @@
  *      (reef_spartan_open_*, section 3h).
  *      Later, still 7 (symbols added, none changed): the Hyrax consistency argument on a resident document (reef_hyrax_*, section 3i).
  *      Later, still 7 (symbols added, none changed): K4's inverse, reef_decompress, and reef_hyrax_eval_comm_compressed on top of it.
+ *      Later, still 7 (symbols added, none changed): the verifier's IPA check on a key ctx (reef_ipa_check, reef_ipa_check_eq, section 3j).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -603,6 +604,44 @@ reef_status reef_hyrax_ipa_begin(reef_hyrax_ctx *ctx, const reef_affine *q, cons
 reef_status reef_hyrax_ipa_round(reef_hyrax_ctx *ctx, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R);
 reef_status reef_hyrax_finish(reef_hyrax_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat);
 reef_status reef_hyrax_read(reef_hyrax_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont);
+
+/* ---------------------------------------------------------------------------------------------
+ * (3j) The verifier's half of an inner-product argument: the check EE::verify_batch ends CompressedSNARK::verify with [R] and
+ * HyraxPC::verify_eval makes inside verify_consistency (src/backend/commitment.rs:446-492).  Two stateless calls on a reef_msm_ctx
+ * that holds gens_v: no handle of their own, no call order.  The transcript, the sum-check verification and the matrix evaluations
+ * stay with the caller; the proof's points and scalars go in, a verdict comes out, and no n-entry vector crosses PCIe.
+ *
+ * With k = log2(n), round 0 pairing with the MOST significant index bit (3h's folds):
+ *   s_j    = prod_i (bit_{k-1-i}(j) ? rs[i] : rs[i]^-1)
+ *   P_hat  = comm + c q + sum_i rs[i]^2 L[i] + sum_i rs[i]^-2 R[i]
+ *   G_hat  = sum_{j<n} s_j key[j]            (the first n points of the key; n <= key length)
+ *   b_hat  = sum_{j<b_len} s_j b[j]          (b zero-padded to n)
+ *   accept = [ P_hat == a_hat G_hat + (a_hat b_hat) q (+ blind h) ]   as group elements
+ *
+ * reef_ipa_check     b: b_len <= n entries in the form is_mont names, host or device (b_loc).  comm, L, R (k each): Jacobian, pasta
+ *                    Montgomery coordinates, any Z; q, h: affine.  c, rs (k), a_hat, blind: host scalars.  h and blind: both NULL (no
+ *                    blind term) or both given.  *accept: 1 or 0.  p_hat, g_hat, b_hat: the intermediates, each may be NULL.
+ * reef_ipa_check_eq  the same with b built on the device: b = sum_t weights[t] pad(eq(points[t])), npoints 1 or 2, eq(p) of 2^vars[t]
+ *                    <= n entries with p[0] pairing with the most significant bit.  b = eq(r_x) + r eq(r_y[1..]) is 3h's opening,
+ *                    b = eq(point[left..]) 3i's.  points, vars, weights: host.
+ * A proof that does not verify is REEF_OK with *accept = 0, not an error.  REEF_ERR_ARG, with nothing written: a challenge that is
+ * zero or not below the modulus, any HOST scalar not below the modulus, n not a power of two >= 2 or beyond the key length, h without
+ * blind or blind without h, a device b that is not 16-byte aligned, a key ctx with a window split set
+ * (reef_msm_ctx_set_window_split: its MSMs are partial sums).  The calls take no curve: the key's curve is the call's, so scalars of
+ * the other curve's field are caught only where they are not below this one's modulus.  A b in DEVICE memory is not checked: its
+ * entries are reduced modulo the field's modulus as they are read.  Outputs are HOST memory, scalars in the form is_mont names.
+ * The s vector, b_hat and the G_hat MSM (whatever kind of key: plain, pre-shifted, byte tables, small) run on the key ctx's stream.
+ * The 2k + 4 one-off points run beside them on a second stream: made affine on the device, imported into a small plain key the key
+ * ctx keeps for this (made by the first call), one MSM over it -- two when p_hat is asked for.  With g_hat asked for, a_hat G_hat is
+ * a 255-step chain after the MSM (~2 ms more); otherwise a_hat rides in s.  The comparison needs no inversion; one host wait. */
+reef_status reef_ipa_check(reef_msm_ctx *key, size_t n, const reef_jacobian *comm, const reef_fe *c, const reef_affine *q, const reef_jacobian *L,
+                           const reef_jacobian *R, const reef_fe *rs, const reef_fe *a_hat, const reef_fe *b, size_t b_len, int b_loc,
+                           const reef_affine *h, const reef_fe *blind, bool is_mont, uint32_t *accept, reef_jacobian *p_hat, reef_jacobian *g_hat,
+                           reef_fe *b_hat);
+reef_status reef_ipa_check_eq(reef_msm_ctx *key, size_t n, const reef_jacobian *comm, const reef_fe *c, const reef_affine *q, const reef_jacobian *L,
+                              const reef_jacobian *R, const reef_fe *rs, const reef_fe *a_hat, const reef_fe *const *points, const size_t *vars,
+                              const reef_fe *weights, size_t npoints, const reef_affine *h, const reef_fe *blind, bool is_mont, uint32_t *accept,
+                              reef_jacobian *p_hat, reef_jacobian *g_hat, reef_fe *b_hat);
 
 /* ---------------------------------------------------------------------------------------------
  * (4) Runtime plumbing.

@@ -188,6 +188,8 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_hyrax_ipa_round": (c_int, [vp, vp, vp, c_bool, vp, vp]),
         "reef_hyrax_finish": (c_int, [vp, vp, c_bool, vp, vp]),
         "reef_hyrax_read": (c_int, [vp, c_int, c_size_t, vp, c_bool]),
+        "reef_ipa_check": (c_int, [vp, c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, c_size_t, c_int, vp, vp, c_bool, POINTER(c_uint32), vp, vp, vp]),
+        "reef_ipa_check_eq": (c_int, [vp, c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_size_t, vp, vp, c_bool, POINTER(c_uint32), vp, vp, vp]),
         "reef_merkle_nodes": (c_uint64, [c_uint64]),
         "reef_merkle_commit": (c_int, [c_int, vp, vp, c_size_t, c_int, c_bool, vp, c_int, vp]),
         "reef_merkle_commit_devices": (c_int, [c_int, vp, vp, c_size_t, c_bool, vp, c_size_t, vp, vp, vp]),

@@ -178,6 +178,7 @@ template <class VT> static const VT *table(int curve) {
     else if constexpr (std::is_same<VT, NifsVTable>::value) return p ? pallas_nifs_vtable() : vesta_nifs_vtable();
     else if constexpr (std::is_same<VT, SpartanVTable>::value) return p ? pallas_spartan_vtable() : vesta_spartan_vtable();
     else if constexpr (std::is_same<VT, OpenVTable>::value) return p ? pallas_open_vtable() : vesta_open_vtable();
+    else if constexpr (std::is_same<VT, IpaCheckVTable>::value) return p ? pallas_ipa_check_vtable() : vesta_ipa_check_vtable();
     else return p ? pallas_hyrax_vtable() : vesta_hyrax_vtable();
 }
 
@@ -570,6 +571,24 @@ reef_status reef_hyrax_finish(reef_hyrax_ctx *ctx, const reef_fe *r_last, bool i
 }
 reef_status reef_hyrax_read(reef_hyrax_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont) {
     return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->read(impl, which, count, out, to_mont); });
+}
+
+// ---- the verifier's IPA check on a key ctx (the curve is the key's)
+reef_status reef_ipa_check(reef_msm_ctx *key, size_t n, const reef_jacobian *comm, const reef_fe *c, const reef_affine *q, const reef_jacobian *L,
+                           const reef_jacobian *R, const reef_fe *rs, const reef_fe *a_hat, const reef_fe *b, size_t b_len, int b_loc,
+                           const reef_affine *h, const reef_fe *blind, bool is_mont, uint32_t *accept, reef_jacobian *p_hat, reef_jacobian *g_hat,
+                           reef_fe *b_hat) {
+    return dispatch<IpaCheckVTable>(key, [&](auto *v, void *impl) {
+        return v->ipa_check(impl, n, comm, c, q, L, R, rs, a_hat, b, b_len, b_loc, h, blind, is_mont, accept, p_hat, g_hat, b_hat);
+    });
+}
+reef_status reef_ipa_check_eq(reef_msm_ctx *key, size_t n, const reef_jacobian *comm, const reef_fe *c, const reef_affine *q, const reef_jacobian *L,
+                              const reef_jacobian *R, const reef_fe *rs, const reef_fe *a_hat, const reef_fe *const *points, const size_t *vars,
+                              const reef_fe *weights, size_t npoints, const reef_affine *h, const reef_fe *blind, bool is_mont, uint32_t *accept,
+                              reef_jacobian *p_hat, reef_jacobian *g_hat, reef_fe *b_hat) {
+    return dispatch<IpaCheckVTable>(key, [&](auto *v, void *impl) {
+        return v->ipa_check_eq(impl, n, comm, c, q, L, R, rs, a_hat, points, vars, weights, npoints, h, blind, is_mont, accept, p_hat, g_hat, b_hat);
+    });
 }
 
 uint64_t reef_merkle_nodes(uint64_t n) {

@@ -537,4 +537,18 @@ struct HyraxVTable {
 const HyraxVTable *pallas_hyrax_vtable();
 const HyraxVTable *vesta_hyrax_vtable();
 
+// The verifier's IPA check on a key ctx (ipa_check_engine.inc; include/reef_msm.h 3j).  key_impl: a Ctx impl.
+struct IpaCheckVTable {
+    reef_status (*ipa_check)(void *key_impl, size_t n, const reef_jacobian *comm, const reef_fe *c, const reef_affine *q, const reef_jacobian *L,
+                             const reef_jacobian *R, const reef_fe *rs, const reef_fe *a_hat, const reef_fe *b, size_t b_len, int b_loc,
+                             const reef_affine *h, const reef_fe *blind, bool is_mont, uint32_t *accept, reef_jacobian *p_hat, reef_jacobian *g_hat,
+                             reef_fe *b_hat);
+    reef_status (*ipa_check_eq)(void *key_impl, size_t n, const reef_jacobian *comm, const reef_fe *c, const reef_affine *q, const reef_jacobian *L,
+                                const reef_jacobian *R, const reef_fe *rs, const reef_fe *a_hat, const reef_fe *const *points, const size_t *vars,
+                                const reef_fe *weights, size_t npoints, const reef_affine *h, const reef_fe *blind, bool is_mont, uint32_t *accept,
+                                reef_jacobian *p_hat, reef_jacobian *g_hat, reef_fe *b_hat);
+};
+const IpaCheckVTable *pallas_ipa_check_vtable();
+const IpaCheckVTable *vesta_ipa_check_vtable();
+
 }  // namespace reef

@@ -116,6 +116,7 @@ template <int C> struct Ctx {
         hipGraph_t graph; hipGraphExec_t exec;
     };
     std::vector<GraphEntry> graphs;
+    Ctx<C> *side = nullptr;                  // a small plain key of this ctx's own for the one-off points of reef_ipa_check (ipa_check_engine.inc)
 };
 // Every entry point that enqueues work holds one of these (under ctx->mu, with the key's device current): the ctx takes the
 // pool stream with the fewest callers at work unless work of its own is still in flight.  When the call returns -- with its
@@ -501,6 +502,7 @@ static reef_status key_build(Ctx<C> *ctx, const reef_affine *bases, size_t n, in
 
 template <int C> static void ctx_free(Ctx<C> *ctx) {
     if (!ctx) return;
+    ctx_free(ctx->side);
     graphs_clear(ctx);
     for (DevBuf *b : {&ctx->scalars, &ctx->blinds, &ctx->hpoint, &ctx->dig, &ctx->counts, &ctx->bstart, &ctx->bstart1, &ctx->seg_first,
                       &ctx->seg_counts, &ctx->entries1, &ctx->sym_table, &ctx->sym_tmp, &ctx->sym_u8, &ctx->tile_sums,
@@ -1758,14 +1760,19 @@ struct ScratchStream {
         s = ps->s;
         return REEF_OK;
     }
-    // a second stream for the call and two events (created on first use)
-    reef_status side(hipStream_t *s2, hipEvent_t **ev) {
+    // the thread's two events (created on first use), for a call that orders its stream against another
+    reef_status events(hipEvent_t **ev) {
         ScratchPool &p = scratch_pool();
         if (!p.ev[0])
             for (auto &e : p.ev) REEF_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        if (!ps2) REEF_TRY(stream_pool().pick(p.device, &ps2, &bg2));
-        *s2 = ps2->s;
         *ev = p.ev;
+        return REEF_OK;
+    }
+    // a second stream for the call and the two events
+    reef_status side(hipStream_t *s2, hipEvent_t **ev) {
+        REEF_TRY(events(ev));
+        if (!ps2) REEF_TRY(stream_pool().pick(scratch_pool().device, &ps2, &bg2));
+        *s2 = ps2->s;
         return REEF_OK;
     }
     reef_status alloc(void **out, size_t bytes) {

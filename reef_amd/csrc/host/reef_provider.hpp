@@ -602,4 +602,29 @@ template <int CURVE> class HyraxEval {
     size_t num_vars_, left_;
 };
 
+// InnerProductArgument::verify [R]: the check EE::verify_batch and HyraxPC::verify_eval end with (reef_msm.h 3j).
+// The caller has drawn the round challenges from its transcript; b = sum_t weights[t] pad(eq(points[t])) is built on the device.
+// Scalars in pasta Montgomery form.  A proof that does not verify gives false; bad arguments throw.
+template <int CURVE> struct InnerProductArgument {
+    std::vector<reef_jacobian> L, R;     // log2(n) each
+    reef_fe a_hat = {};
+    // gens_v: a key of at least n points; comm, c: the instance's commitment and claimed inner product; q = gens_s.scale(r), affine;
+    // rs: log2(n) round challenges; h, blind: the optional blind term (both or neither)
+    bool verify(reef_msm_ctx *gens_v, size_t n, const reef_jacobian &comm, const reef_fe &c, const reef_affine &q, const std::vector<reef_fe> &rs,
+                const std::vector<std::vector<reef_fe>> &points, const std::vector<reef_fe> &weights, const reef_affine *h = nullptr,
+                const reef_fe *blind = nullptr) const {
+        if (L.size() != rs.size() || R.size() != rs.size() || points.size() != weights.size()) return false;
+        std::vector<const reef_fe *> pts;
+        std::vector<size_t> vars;
+        for (const auto &p : points) {
+            pts.push_back(p.data());
+            vars.push_back(p.size());
+        }
+        uint32_t accept = 0;
+        check(reef_ipa_check_eq(gens_v, n, &comm, &c, &q, L.data(), R.data(), rs.data(), &a_hat, pts.data(), vars.data(), weights.data(), points.size(), h,
+                                blind, true, &accept, nullptr, nullptr, nullptr), "reef_ipa_check_eq");
+        return accept == 1;
+    }
+};
+
 }  // namespace reef_provider

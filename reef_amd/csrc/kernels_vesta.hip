@@ -11,11 +11,13 @@
 #include "spartan_kernels.inc"
 #include "open_kernels.inc"
 #include "hyrax_kernels.inc"
+#include "ipa_check_kernels.inc"
 #include "engine.inc"
 #include "fe_host.inc"
 #include "nifs_engine.inc"
 #include "proof_order.h"
 #include "ipa_engine.inc"
+#include "ipa_check_engine.inc"
 #include "spartan_engine.inc"
 #include "open_engine.inc"
 #include "hyrax_engine.inc"
@@ -38,6 +40,10 @@ const OpenVTable *vesta_open_vtable() {
 }
 const HyraxVTable *vesta_hyrax_vtable() {
     static const HyraxVTable vt = make_hyrax_vtable<1>();
+    return &vt;
+}
+const IpaCheckVTable *vesta_ipa_check_vtable() {
+    static const IpaCheckVTable vt = make_ipa_check_vtable<1>();
     return &vt;
 }
 }

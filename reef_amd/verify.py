@@ -1,0 +1,173 @@
+"""Python front-end of the verifier's IPA check (include/reef_msm.h 3j).
+
+`ipa_check` / `ipa_check_eq` are the two C-ABI calls: P_hat rebuilt from the proof, the challenges expanded into s on the device,
+G_hat = <s, key>, b_hat = <s, b>, and the two sides compared as group elements.  `verify_opening` is the device counterpart of
+EE::verify_batch at the end of CompressedSNARK::verify (3h's opening), `verify_eval` of HyraxPC::verify_eval inside
+verify_consistency (3i's argument); both take a caller-supplied `challenge(label, absorbed) -> int` in place of the transcript and
+draw their challenges in the provers' label order.  A proof that does not verify gives False, never an exception; bad arguments
+raise ReefError (REEF_ERR_ARG).  The C calls take no curve -- the key's curve is the call's -- so "a key of another curve" is a
+check of THIS module, not of the library: pass curve= and a key of another curve raises ReefError(1) before any call is made.
+Scalars cross as Python ints (canonical, or pasta Montgomery form with is_mont=True); points as numpy uint64 arrays in the C-ABI
+layouts: affine (8 limbs) or Jacobian (12 limbs).
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Any, Callable, List, Optional, Sequence
+
+import numpy as np
+
+from ._ffi import REEF_DEVICE, REEF_HOST, ReefError, check
+from ._fe import _arr, _ints
+from .msm import DeviceBuffer, MsmContext, curve_id, decompress, normalize
+from .spartan import compress
+
+
+def _jac(pts, count: Optional[int] = None) -> np.ndarray:
+    a = np.ascontiguousarray(np.stack([np.asarray(x, dtype=np.uint64).reshape(12) for x in pts]) if isinstance(pts, (list, tuple)) else pts,
+                             dtype=np.uint64).reshape(-1, 12)
+    if count is not None and a.shape[0] != count:
+        raise ValueError(f"expected {count} points, got {a.shape[0]}")
+    return a
+
+
+def _aff(pt) -> np.ndarray:
+    return np.ascontiguousarray(pt, dtype=np.uint64).reshape(8)
+
+
+def _rounds(n: int) -> int:
+    return max(n.bit_length() - 1, 0)
+
+
+def _call(key: MsmContext, fn, n, comm, c, q, L, R, rs, a_hat, mid, h, blind, is_mont, intermediates, curve):
+    if curve is not None and curve_id(curve) != key.curve:
+        raise ReefError(1, f"the key is of curve {key.curve}, the check of curve {curve_id(curve)}")
+    k = _rounds(n)
+    ca, qa = _jac([comm], 1), _aff(q)
+    if (len(rs) != k or len(L) != k or len(R) != k) and n >= 2 and n & (n - 1) == 0:
+        raise ValueError(f"n = {n} takes {k} rounds: L, R and rs have {len(L)}, {len(R)}, {len(rs)} entries")
+    if not (len(L) and len(R) and len(rs)):
+        L, R, rs = [np.zeros(12, np.uint64)], [np.zeros(12, np.uint64)], [0]      # n < 2: the library says what is wrong with it
+    La, Ra = _jac(L, len(L)), _jac(R, len(R))
+    cs, rsa, aa = _arr([c]), _arr(rs), _arr([a_hat])
+    ha = None if h is None else _aff(h)
+    ba = None if blind is None else _arr([blind])
+    accept = ctypes.c_uint32(0xFFFFFFFF)
+    ph, gh, bh = (np.zeros(12, np.uint64), np.zeros(12, np.uint64), np.zeros((1, 4), np.uint64)) if intermediates else (None, None, None)
+    check(fn(key._h, n, ca.ctypes.data, cs.ctypes.data, qa.ctypes.data, La.ctypes.data, Ra.ctypes.data, rsa.ctypes.data, aa.ctypes.data,
+             *mid, None if ha is None else ha.ctypes.data, None if ba is None else ba.ctypes.data, bool(is_mont), ctypes.byref(accept),
+             None if ph is None else ph.ctypes.data, None if gh is None else gh.ctypes.data, None if bh is None else bh.ctypes.data))
+    out = {"accept": accept.value == 1}
+    if intermediates:
+        out.update({"p_hat": ph, "g_hat": gh, "b_hat": _ints(bh)[0]})
+    return out
+
+
+def ipa_check(key: MsmContext, n: int, comm, c: int, q, L, R, rs: Sequence[int], a_hat: int, b, *, b_len: Optional[int] = None, h=None,
+              blind: Optional[int] = None, is_mont: bool = False, intermediates: bool = False, curve=None) -> dict:
+    """reef_ipa_check.  b: ints (at most n of them; the rest is zero padding), or a DeviceBuffer of b_len field elements in the form
+    is_mont names.  {"accept": bool} and, with intermediates, "p_hat", "g_hat" (Jacobian) and "b_hat"."""
+    if isinstance(b, DeviceBuffer):
+        if b_len is None or b.nbytes < 32 * b_len:
+            raise ValueError("a device b needs b_len, and 32 bytes per entry")
+        mid, keep = (b.ptr, b_len, REEF_DEVICE), b
+    else:
+        keep = _arr(b) if len(b) else np.zeros((1, 4), np.uint64)
+        mid = (keep.ctypes.data if len(b) else None, len(b), REEF_HOST)
+    return _call(key, key._lib.reef_ipa_check, n, comm, c, q, L, R, rs, a_hat, mid, h, blind, is_mont, intermediates, curve)
+
+
+def ipa_check_eq(key: MsmContext, n: int, comm, c: int, q, L, R, rs: Sequence[int], a_hat: int, points: Sequence[Sequence[int]],
+                 weights: Sequence[int], *, h=None, blind: Optional[int] = None, is_mont: bool = False, intermediates: bool = False,
+                 curve=None) -> dict:
+    """reef_ipa_check_eq: b = sum_t weights[t] pad(eq(points[t])) built on the device, one or two points."""
+    if len(points) != len(weights):
+        raise ValueError("one weight per point")
+    arrs = [_arr(pt) if len(pt) else np.zeros((1, 4), np.uint64) for pt in points]
+    ptrs = (ctypes.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+    nvars = (ctypes.c_size_t * max(len(arrs), 1))(*[len(pt) for pt in points])
+    wa = _arr(weights) if len(weights) else np.zeros((1, 4), np.uint64)
+    mid = (ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(nvars, ctypes.c_void_p), wa.ctypes.data, len(points))
+    return _call(key, key._lib.reef_ipa_check_eq, n, comm, c, q, L, R, rs, a_hat, mid, h, blind, is_mont, intermediates, curve)
+
+
+def _lincomb(curve: int, points, scalars: Sequence[int]) -> np.ndarray:
+    """sum scalars[i] points[i] through calls that exist: reef_normalize, a plain key, reef_msm.  Jacobian (12) or affine (8) in,
+    Jacobian out"""
+    aff = []
+    for pt in points:
+        a = np.ascontiguousarray(pt, dtype=np.uint64).reshape(-1)
+        aff.append(a if a.size == 8 else normalize(curve, a)[0][0])
+    with MsmContext(curve, np.stack(aff), byte_tables=2) as ctx:
+        return ctx.msm(_arr(scalars), is_mont=False)
+
+
+def verify_opening(key: MsmContext, gens_s, comm_e, r_x: Sequence[int], eval_e: int, comm_w, r_y: Sequence[int], eval_w: int, proof: dict,
+                   challenge: Callable[[str, List[Any]], int], p: int, *, check_fn=None) -> bool:
+    """EE::verify_batch [R] over the instances [E, W] of 3h: {comm_E, eq(r_x), eval_E} and {comm_W, eq(r_y[1..]), eval_W}, and the
+    proof {"cross", "L", "R", "a_hat"}.  Challenges: "r" after the cross term, "r" after (comm_a, c), "challenge_r" per round after
+    (L, R) compressed -- prove_with_opening's order.  key: gens_v with at least n = max(2^len(r_x), 2^(len(r_y) - 1)) points; gens_s:
+    one affine point.  Canonical ints.  check_fn: stands in for ipa_check_eq (tests)."""
+    curve = key.curve
+    ry = list(r_y[1:])
+    n = max(1 << len(r_x), 1 << len(ry))
+    r = challenge("r", [proof["cross"]])
+    c = (eval_e + r * r * eval_w + r * proof["cross"]) % p
+    comm_a = _lincomb(curve, [comm_e, comm_w], [1, r])
+    r_ipa = challenge("r", [compress(key, comm_a), c])
+    q = normalize(curve, _lincomb(curve, [gens_s], [r_ipa]))[0][0]
+    if len(proof["L"]) != _rounds(n) or len(proof["R"]) != _rounds(n):
+        return False
+    rs = [challenge("challenge_r", [compress(key, L), compress(key, R)]) for L, R in zip(proof["L"], proof["R"])]
+    fn = check_fn or ipa_check_eq
+    return fn(key, n, comm_a, c, q, proof["L"], proof["R"], rs, proof["a_hat"], [list(r_x), ry], [1, r])["accept"]
+
+
+def comm_lz(curve, row_comms32, point_left: Sequence[int], p: int) -> np.ndarray:
+    """comm_LZ = sum_i eq(point[..left])_i C_i from the 32-byte rows a .cmt file holds, without a document: reef_decompress to device
+    memory, reef_msm_ctx_set_bases on a plain context, reef_msm with the weights built on the host (2^left of them)."""
+    rows = 1 << len(point_left)
+    enc = np.frombuffer(bytes(row_comms32), dtype=np.uint8) if isinstance(row_comms32, (bytes, bytearray, memoryview)) else \
+        np.ascontiguousarray(row_comms32, dtype=np.uint8).reshape(-1)
+    if enc.size != 32 * rows:
+        raise ValueError(f"expected {rows} row commitments of 32 bytes, got {enc.size} bytes")
+    dec, bad, first = decompress(curve, DeviceBuffer.from_host(enc), rows)
+    if bad:
+        raise ReefError(1, f"row {first} is not the encoding of a point ({bad} such rows)")
+    w = [1]
+    for x in point_left:
+        w = [v for e in w for v in (e * (1 - x) % p, e * x % p)]
+    with MsmContext(curve, np.zeros((1, 8), np.uint64), byte_tables=2) as ctx:
+        ctx.set_bases(dec, rows)
+        return ctx.msm(_arr(w), is_mont=False)
+
+
+def verify_eval(key: MsmContext, q, row_comms32, point: Sequence[int], left: int, eval_: int, proof: dict, p: int, *, h=None,
+                blind_total: Optional[int] = None, challenge: Optional[Callable[[str, List[Any]], int]] = None, q_of=None,
+                check_fn=None) -> bool:
+    """HyraxPC::verify_eval [R] for 3i's argument: comm_LZ from the compressed row commitments (comm_lz above), then P_hat = comm_LZ +
+    eval q + sum r_k^2 L_k + sum r_k^-2 R_k against a_hat G_hat + a_hat b_hat q (+ blind_total h), b = eq(point[left..]) built on the
+    device.  proof: {"L", "R", "a_hat"} and either "rs", or a `challenge` to draw them with: "r" after (comm_LZ, eval) -- q is then
+    q_of(r) -- and "challenge_r" per round, prove_eval's order.  key: gens_v with 2^(len(point) - left) points.  Canonical ints."""
+    curve = key.curve
+    right = len(point) - left
+    n = 1 << right
+    if challenge is None and "rs" not in proof:
+        raise ValueError("verify_eval needs the round challenges: proof['rs'], or a challenge callable to draw them")
+    if q is None and (challenge is None or q_of is None):
+        raise ValueError("verify_eval needs q, or a challenge callable and q_of to form it from the drawn r")
+    if (h is None) != (blind_total is None):
+        raise ValueError("h and blind_total come together or not at all")
+    clz = comm_lz(curve, row_comms32, point[:left], p)
+    if challenge is not None:
+        r_ipa = challenge("r", [compress(key, clz), eval_])
+        if q_of is not None:
+            q = q_of(r_ipa)
+        rs = [challenge("challenge_r", [compress(key, L), compress(key, R)]) for L, R in zip(proof["L"], proof["R"])]
+    else:
+        rs = list(proof["rs"])
+    if len(proof["L"]) != right or len(proof["R"]) != right or len(rs) != right:
+        return False
+    fn = check_fn or ipa_check_eq
+    blind = None if blind_total is None else blind_total % p
+    return fn(key, n, clz, eval_ % p, q, proof["L"], proof["R"], rs, proof["a_hat"], [list(point[left:])], [1], h=h, blind=blind)["accept"]
