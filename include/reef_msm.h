@@ -30,6 +30,7 @@
  *      Later, still 7 (symbols added, none changed): the Hyrax consistency argument on a resident document (reef_hyrax_*, section 3i).
  *      Later, still 7 (symbols added, none changed): K4's inverse, reef_decompress, and reef_hyrax_eval_comm_compressed on top of it.
  *      Later, still 7 (symbols added, none changed): the verifier's IPA check on a key ctx (reef_ipa_check, reef_ipa_check_eq, section 3j).
+ *      Later, still 7 (symbols added, none changed): the verifier's matrix evaluations on a NIFS ctx (reef_spartan_eval_matrices, section 3k).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -642,6 +643,26 @@ reef_status reef_ipa_check_eq(reef_msm_ctx *key, size_t n, const reef_jacobian *
                               const reef_jacobian *R, const reef_fe *rs, const reef_fe *a_hat, const reef_fe *const *points, const size_t *vars,
                               const reef_fe *weights, size_t npoints, const reef_affine *h, const reef_fe *blind, bool is_mont, uint32_t *accept,
                               reef_jacobian *p_hat, reef_jacobian *g_hat, reef_fe *b_hat);
+
+/* ---------------------------------------------------------------------------------------------
+ * (3k) The verifier's matrix evaluations: what RelaxedR1CSSNARK::verify [R] ends with, A~(r_x, r_y), B~(r_x, r_y), C~(r_x, r_y), on the
+ * matrices a reef_nifs_ctx holds.  With 3j this is the verifier's device work; the transcript and the O(log n) sum-check verification stay
+ * with the caller.  For M = A, B, C as given to reef_nifs_set_matrix (duplicates summed), ell_x = log2(num_cons_pad), ell_y =
+ * log2(2 num_vars_pad) and col' = col for col < num_vars, col + num_vars_pad - num_vars otherwise (R1CSShape::pad [R], 3g):
+ *
+ *   M~(r_x, r_y) = sum_entries val eq(r_x)[row] eq(r_y)[col']        (eq as 3g: index 0 of a point pairs with the most significant bit)
+ *
+ * r_x: ell_x entries, r_y: ell_y entries, evals = {A~, B~, C~}: HOST memory, in the form is_mont names.  num_cons_pad, num_vars_pad:
+ * reef_spartan_begin's rule.  Every entry must be below the modulus; 0 and 1 are legal.  REEF_ERR_ARG, with nothing written and the ctx
+ * usable: a null pointer, an illegal pad, an entry not below the modulus, a matrix not yet set.
+ * The call needs the three matrices only: no reef_nifs_set_running (a verifier has no witness).  It may come at any time, between any
+ * two calls of a 3g prove or a 3h opening on the same ctx: it reads no table of theirs and changes neither their phase nor the NIFS
+ * state, and is in no call order.  After a reef_nifs_set_matrix the next call sees the new matrix.  Its workspace (num_cons + num_vars
+ * + 1 + num_io field elements and the block sums -- none of 3g's tables) is made by the first call, grows, and is freed with the ctx.
+ * One pass over the entries: a row's three dot products with eq(r_y)[col'] (the row pass of 3f: +-1 coefficients are additions), three
+ * products with eq(r_x)[row], a sum over the rows.  One host wait; three field elements cross PCIe. */
+reef_status reef_spartan_eval_matrices(reef_nifs_ctx *ctx, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *r_x, const reef_fe *r_y,
+                                       bool is_mont, reef_fe evals[3]);
 
 /* ---------------------------------------------------------------------------------------------
  * (4) Runtime plumbing.

@@ -519,6 +519,10 @@ reef_status reef_spartan_inner_round(reef_nifs_ctx *ctx, const reef_fe *r, bool 
 reef_status reef_spartan_inner_claims(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe claims[3]) {
     return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) { return v->inner_claims(impl, r_last, is_mont, claims); });
 }
+reef_status reef_spartan_eval_matrices(reef_nifs_ctx *ctx, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *r_x, const reef_fe *r_y, bool is_mont,
+                                       reef_fe evals[3]) {
+    return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) { return v->eval_matrices(impl, num_cons_pad, num_vars_pad, r_x, r_y, is_mont, evals); });
+}
 
 // ---- the batched IPA opening of the final SNARK on a NIFS ctx
 reef_status reef_spartan_open_begin(reef_nifs_ctx *ctx, reef_msm_ctx *key, bool is_mont, reef_fe *cross_term) {

@@ -504,6 +504,8 @@ struct SpartanVTable {
     reef_status (*inner_begin)(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals);
     reef_status (*inner_round)(void *impl, const reef_fe *r, bool is_mont, reef_fe *evals);
     reef_status (*inner_claims)(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *claims);
+    // the verifier's matrix evaluations (3k): needs the matrices only
+    reef_status (*eval_matrices)(void *impl, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *r_x, const reef_fe *r_y, bool is_mont, reef_fe *evals);
 };
 const SpartanVTable *pallas_spartan_vtable();
 const SpartanVTable *vesta_spartan_vtable();

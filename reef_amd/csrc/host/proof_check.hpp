@@ -376,6 +376,21 @@ static void check_nifs(const Mod &m, const NifsRecord &rec, const Inst &fin, con
         for (const PointRec &p : rec.points) pc(ph, p.pt, p.dlog, c + " " + p.what);
 }
 
+// The verifier's matrix evaluations on one host core: {A~, B~, C~}(r_x, r_y) = sum val eq(r_x)[row] eq(r_y)[col'] per matrix, columns
+// renumbered as R1CSShape::pad; erx = eq(r_x), ery = eq(r_y).  What reef_spartan_eval_matrices (3k) does on the device.
+static std::array<reef_fe, 3> host_matrix_evals(const Mod &m, const R1cs &S, size_t nvp, const std::vector<reef_fe> &erx, const std::vector<reef_fe> &ery) {
+    std::array<reef_fe, 3> out;
+    for (int k = 0; k < 3; ++k) {
+        reef_fe s = {};
+        for (size_t e = 0; e < S.row[k].size(); ++e) {
+            const size_t c = S.col[k][e] < S.num_vars ? S.col[k][e] : S.col[k][e] + nvp - S.num_vars;
+            s = fadd(m, s, fmul(m, fmul(m, S.val[k][e], erx[S.row[k][e]]), ery[c]));
+        }
+        out[k] = s;
+    }
+    return out;
+}
+
 // 3g's verifier: challenges as recorded, every evaluation straight from the unpadded shape and instance
 template <class Pf> static void check_sumchecks(const Mod &m, const R1cs &S, const Inst &I, size_t ncp, size_t nvp, const Pf &pf, const char *curve) {
     const char *ph = "spartan";
@@ -406,18 +421,10 @@ template <class Pf> static void check_sumchecks(const Mod &m, const R1cs &S, con
         const reef_fe y[3] = {pf.inner[j][0], fsub(m, claim, pf.inner[j][0]), pf.inner[j][1]};
         claim = interp2(m, y, pf.r_y[j]);
     }
-    // the verifier's sparse evaluation: sum val eq(r_x)[row] eq(r_y)[col'] over A + r B + r^2 C, columns renumbered as R1CSShape::pad
+    // the verifier's sparse evaluation over A + r B + r^2 C
     const std::vector<reef_fe> ery = eq_evals(m, pf.r_y.data(), ell_y);
-    reef_fe abc = {};
-    const reef_fe coef[3] = {m.one, r, r2};
-    for (int k = 0; k < 3; ++k) {
-        reef_fe s = {};
-        for (size_t e = 0; e < S.row[k].size(); ++e) {
-            const size_t c = S.col[k][e] < S.num_vars ? S.col[k][e] : S.col[k][e] + nvp - S.num_vars;
-            s = fadd(m, s, fmul(m, fmul(m, S.val[k][e], erx[S.row[k][e]]), ery[c]));
-        }
-        abc = fadd(m, abc, fmul(m, coef[k], s));
-    }
+    const std::array<reef_fe, 3> mev = host_matrix_evals(m, S, nvp, erx, ery);
+    const reef_fe abc = fadd(m, fadd(m, mev[0], fmul(m, r, mev[1])), fmul(m, r2, mev[2]));
     // z(r_y) of z = W || 0 || u || X || 0: (1 - r_y[0]) W~(r_y[1..]) + r_y[0] (u, X)~(r_y[1..])
     const std::vector<reef_fe> eq1 = eq_evals(m, pf.r_y.data() + 1, ell_y - 1);
     const reef_fe eval_w = dot(m, eq1.data(), I.W.data(), S.num_vars);

@@ -536,6 +536,19 @@ template <int CURVE> class RelaxedR1CSSnark {
         }
     }
 
+    // 3k: A~, B~, C~ at (r_x, r_y), outer_rounds() and inner_rounds() entries, on the ctx's matrices alone (no running instance).
+    // RelaxedR1CSSNARK::verify [R] is made of three parts.  (1) The host chain: tau, r_x, r, r_y re-drawn from the transcript, the round
+    // sums chained with e1 = claim - e0, claim_outer == eq(tau, r_x) (az bz - u cz - ex) on claims_outer as claimed, eval_X =
+    // sum_j eq(r_y[1..])[j] (u || X)[j] and z(r_y) = (1 - r_y[0]) eval_W + r_y[0] eval_X: O(log n) field operations.  (2) This call, for
+    // claim_inner == (A~ + r B~ + r^2 C~) z(r_y).  (3) InnerProductArgument::verify below over [E, W] at (r_x, r_y[1..]) with eval_E =
+    // claims_outer[3], eval_W = claims_inner[2], c = eval_E + r'^2 eval_W + r' cross.  May be called at any time, mid-prove included.
+    std::array<reef_fe, 3> eval_matrices(const std::vector<reef_fe> &r_x, const std::vector<reef_fe> &r_y) const {
+        if (r_x.size() != outer_rounds() || r_y.size() != inner_rounds()) throw std::invalid_argument("eval_matrices: r_x, r_y lengths");
+        std::array<reef_fe, 3> ev;
+        check(reef_spartan_eval_matrices(nifs_.handle(), ncp_, nvp_, r_x.data(), r_y.data(), true, ev.data()), "reef_spartan_eval_matrices");
+        return ev;
+    }
+
   private:
     Nifs<CURVE> &nifs_;
     size_t ncp_, nvp_;

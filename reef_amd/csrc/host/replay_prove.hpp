@@ -31,6 +31,10 @@ template <int CURVE> struct ProveSide {
     Inst fin;                                       // the running instance, read back after the timed region
     uint64_t violations = 0;
     double init_ms = 0, spartan_ms = 0, open_ms = 0;
+    reef_fe comm_a_dlog = {};                       // the opening's comm_a = comm_E + r comm_W and q, as the callbacks produced them
+    reef_affine q_open = {};
+    double verify_ipa_ms = 0;                       // 3j on the opening, after the host checks
+    double verify_evals_ms = 0, verify_evals_host_ms = 0;   // 3k on the device (warm: the second call) against the host loop of proof_check.hpp alone
     ProveSide(const Mod &mod, const char *nm, size_t cons, size_t vars, uint64_t domain) : m(mod), name(nm), num_cons(cons), num_vars(vars), tr(mod, domain) {}
     Inst fresh(uint64_t seed) const { return fresh_instance(m, S, seed); }
 };
@@ -132,10 +136,47 @@ template <int CURVE> static void final_snark(ProveSide<CURVE> &s) {
         s.c.key, tr,
         [&](const reef_fe &r) {   // comm_a = comm_E + r comm_W, as its discrete logarithm
             const reef_fe d = fadd(s.m, s.rec.dE, fmul(s.m, r, s.rec.dW));
+            s.comm_a_dlog = d;
             return std::vector<uint8_t>((const uint8_t *)&d, (const uint8_t *)&d + sizeof d);
         },
-        [&](const reef_fe &r) { return scaled_G(s, fmul(s.m, s.gs, r)); }, s.pf);
+        [&](const reef_fe &r) { return s.q_open = scaled_G(s, fmul(s.m, s.gs, r)); }, s.pf);
     s.open_ms = ms_since(t0);
+}
+// After the host checks: the verifier's matrix evaluations on the device (3k) at the recorded (r_x, r_y), on the ctx the prove ran on.
+// A~ + r B~ + r^2 C~ must equal the recorded claims_inner[0] and the host's own value.  Both sides build their eq tables on the clock.
+template <int CURVE> static void device_matrix_evals(ProveSide<CURVE> &s) {
+    const typename ProveSide<CURVE>::Snark snark(*s.nifs, s.ncp, s.nvp);
+    snark.eval_matrices(s.pf.r_x, s.pf.r_y);                  // the first call makes the workspace
+    auto t0 = clk::now();
+    const std::array<reef_fe, 3> dev = snark.eval_matrices(s.pf.r_x, s.pf.r_y);
+    s.verify_evals_ms = ms_since(t0);
+    t0 = clk::now();
+    const std::vector<reef_fe> erx = eq_evals(s.m, s.pf.r_x.data(), s.pf.r_x.size()), ery = eq_evals(s.m, s.pf.r_y.data(), s.pf.r_y.size());
+    const std::array<reef_fe, 3> host = host_matrix_evals(s.m, s.S, s.nvp, erx, ery);
+    s.verify_evals_host_ms = ms_since(t0);
+    const reef_fe r = s.pf.r_joint, r2 = fmul(s.m, r, r);
+    const reef_fe abc_dev = fadd(s.m, fadd(s.m, dev[0], fmul(s.m, r, dev[1])), fmul(s.m, r2, dev[2]));
+    const reef_fe abc_host = fadd(s.m, fadd(s.m, host[0], fmul(s.m, r, host[1])), fmul(s.m, r2, host[2]));
+    const std::string cn(s.name);
+    for (int k = 0; k < 3; ++k) EXPECT("spartan", feq(dev[k], host[k]), cn + ": the device's matrix evaluation " + "ABC"[k] + "~(r_x, r_y) differs from the host's");
+    EXPECT("spartan", feq(abc_dev, abc_host), cn + ": the device's A~ + r B~ + r^2 C~ differs from the host's");
+    EXPECT("spartan", feq(abc_dev, s.pf.claims_inner[0]), cn + ": the device's A~ + r B~ + r^2 C~ differs from the recorded claims_inner[0]");
+}
+// and the opening through InnerProductArgument::verify (3j): comm_a as the point of its tracked discrete logarithm, c, q, the recorded
+// L, R, round challenges and a_hat, b = eq(r_x) + r_fold eq(r_y[1..]) built on the device
+template <int CURVE> static void device_ipa_verify(ProveSide<CURVE> &s) {
+    reef_jacobian comm;
+    CK(reef_msm(s.c.one, &s.comm_a_dlog, 1, REEF_HOST, true, &comm, REEF_HOST));
+    reef_provider::InnerProductArgument<CURVE> ipa;
+    ipa.L = s.pf.L;
+    ipa.R = s.pf.R;
+    ipa.a_hat = s.pf.a_hat;
+    const std::vector<std::vector<reef_fe>> points = {s.pf.r_x, std::vector<reef_fe>(s.pf.r_y.begin() + 1, s.pf.r_y.end())};
+    const std::vector<reef_fe> weights = {s.m.one, s.pf.r_fold};
+    const auto t0 = clk::now();
+    const bool ok = ipa.verify(s.c.key, s.n, comm, s.pf.c, s.q_open, s.pf.r_rounds, points, weights);
+    s.verify_ipa_ms = ms_since(t0);
+    EXPECT("open", ok, std::string(s.name) + ": the device's IPA check rejects the recorded opening");
 }
 template <int CURVE> static void read_back(ProveSide<CURVE> &s) {
     s.fin.W = s.nifs->read(0, s.num_vars, true);
@@ -274,6 +315,10 @@ static std::string prove_body(const Shape &shape, const std::string &tamper, boo
         check_hyrax(mp, doc, (size_t)sh->doc_log, left, point, hpf, hg, blinds, hd, g1, pcp);
     }
     const double check_ms = ms_since(t0);
+    device_matrix_evals(P);                                   // the host checks passed: a tampered record never gets here
+    device_matrix_evals(V);
+    device_ipa_verify(P);
+    device_ipa_verify(V);
 
     std::string steps_list = "[";
     for (size_t k = 0; k < step_ms.size(); ++k) {
@@ -298,10 +343,15 @@ static std::string prove_body(const Shape &shape, const std::string &tamper, boo
              "\"commit_hyrax_ms\": %.3f, \"hyrax_create_ms\": %.3f, \"total_prove_device_ms\": %.3f, "
              "\"timed\": \"first instance, folding steps (N2 sum-check step, comm_W, commit_T, challenge, fold per curve), last fold, Spartan and opening per curve, "
              "consistency argument; host glue included; witness and matrix generation, the document commitment and the checks excluded\", "
-             "\"check_ms\": %.3f, \"points_checked\": %d, \"proof_checked\": true}",
+             "\"check_ms\": %.3f, \"points_checked\": %d, \"proof_checked\": true, "
+             "\"verify_evals_ms_pallas\": %.3f, \"verify_evals_ms_vesta\": %.3f, \"verify_evals_host_ms_pallas\": %.3f, \"verify_evals_host_ms_vesta\": %.3f, "
+             "\"verify_evals\": \"A~, B~, C~ at the recorded (r_x, r_y): reef_spartan_eval_matrices host to host (second call; eq tables included) against the loop "
+             "of the host check on one core (eq tables included); A~ + r B~ + r^2 C~ equals claims_inner[0] and the host's value; neither this nor verify_ipa_ms (InnerProductArgument::verify on the opening) is in total_prove_device_ms\", "
+             "\"verify_ipa_ms_pallas\": %.3f, \"verify_ipa_ms_vesta\": %.3f, \"device_verified\": true}",
              sh->name.c_str(), sh->w1, sh->c1, sh->w2, sh->c2, P.ncp, P.nvp, V.ncp, V.nvp, P.n, V.n, P.S.nnz(), V.S.nnz(), sh->steps, P.init_ms + V.init_ms,
              steps_list.c_str(), steps_total / ns, commit_w_ms / ns, nifs_ms / ns, sc_ms / ns, final_fold_ms, P.spartan_ms, V.spartan_ms, P.pf.outer.size(),
              P.pf.inner.size(), V.pf.outer.size(), V.pf.inner.size(), P.open_ms, V.open_ms, P.pf.r_rounds.size(), V.pf.r_rounds.size(), sh->doc_log, left,
-             consistency_ms, hpf.r_rounds.size(), commit_hyrax_ms, hyrax_create_ms, total, check_ms, g_checked);
+             consistency_ms, hpf.r_rounds.size(), commit_hyrax_ms, hyrax_create_ms, total, check_ms, g_checked, P.verify_evals_ms, V.verify_evals_ms,
+             P.verify_evals_host_ms, V.verify_evals_host_ms, P.verify_ipa_ms, V.verify_ipa_ms);
     return std::string(line.data());
 }

@@ -27,6 +27,8 @@ template <int C> struct NifsCtx : DeviceCtx {   // ev: orders the key ctx's stre
     std::vector<u32> h_colptr[3];
     NifsSegs cols;                       // long columns of the CSC
     SpartanState<C> *sp = nullptr;       // row N5 workspace, made by the first reef_spartan_begin
+    struct EvalWs { DevBuf pts, ex, zy, partial, out; } evw;   // the verifier's matrix evaluations (3k): eq factors, eq(r_x) by row, the column
+                                         // weights, block sums, results; empty until the first reef_spartan_eval_matrices
     u64 gen = 0;                         // bumped by every call that changes the matrices or the running instance (or commits T)
     DevBuf z1, z2, E, T, stage, counters;
     bool running = false, committed = false, have_t = false;
@@ -44,6 +46,7 @@ template <int C> static void nifs_free(NifsCtx<C> *c) {
     c->cols.release();
     spartan_release<C>(c->sp);
     for (DevBuf *b : {&c->z1, &c->z2, &c->E, &c->T, &c->stage, &c->counters}) b->release();
+    for (DevBuf *b : {&c->evw.pts, &c->evw.ex, &c->evw.zy, &c->evw.partial, &c->evw.out}) b->release();
     delete c;
 }
 

@@ -2,6 +2,7 @@
 // proof_order.h (the SP_* phases and the call order, the opening's included) and ipa_engine.inc.
 // A prover-side state machine: begin -> outer_round x (ell_x - 1) -> outer_claims -> inner_begin -> inner_round x (ell_y - 1) ->
 // inner_claims, with ell_x = log2(num_cons_pad), ell_y = log2(2 num_vars_pad).  The running instance is read, never written.
+// Beside it, in no order and on no state of the prove: the verifier's matrix evaluations (3k: v_spartan_eval_matrices).
 namespace reef {
 
 template <int C> struct SpartanState {
@@ -75,18 +76,24 @@ template <int C> static reef_status sp_dots(NifsCtx<C> *c, const fe256 *x, const
     return REEF_OK;
 }
 
+// the pad rule of reef_spartan_begin, in the words of the call `name`
+template <int C> static reef_status sp_check_pads(NifsCtx<C> *c, const char *name, size_t num_cons_pad, size_t num_vars_pad) {
+    auto pow2 = [](size_t n) { return n >= 2 && n <= ((size_t)1 << 24) && (n & (n - 1)) == 0; };
+    if (!pow2(num_cons_pad) || !pow2(num_vars_pad) || num_cons_pad < c->num_cons || num_vars_pad < c->num_vars || c->num_io >= num_vars_pad) {
+        set_error("%s: need powers of two 2 <= num_cons_pad, num_vars_pad <= 2^24 with num_cons_pad >= num_cons (%zu), "
+                  "num_vars_pad >= num_vars (%zu) and num_vars_pad > num_io (%zu); got %zu, %zu", name, c->num_cons, c->num_vars, c->num_io, num_cons_pad,
+                  num_vars_pad);
+        return REEF_ERR_ARG;
+    }
+    return REEF_OK;
+}
+
 template <int C>
 static reef_status v_spartan_begin(void *impl, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *tau, bool is_mont, reef_fe *evals) {
     constexpr int F = NifsCtx<C>::F;
     NifsCtx<C> *c = (NifsCtx<C> *)impl;
     if (!tau || !evals) { set_error("null argument"); return REEF_ERR_ARG; }
-    auto pow2 = [](size_t n) { return n >= 2 && n <= ((size_t)1 << 24) && (n & (n - 1)) == 0; };
-    if (!pow2(num_cons_pad) || !pow2(num_vars_pad) || num_cons_pad < c->num_cons || num_vars_pad < c->num_vars || c->num_io >= num_vars_pad) {
-        set_error("reef_spartan_begin: need powers of two 2 <= num_cons_pad, num_vars_pad <= 2^24 with num_cons_pad >= num_cons (%zu), "
-                  "num_vars_pad >= num_vars (%zu) and num_vars_pad > num_io (%zu); got %zu, %zu", c->num_cons, c->num_vars, c->num_io, num_cons_pad,
-                  num_vars_pad);
-        return REEF_ERR_ARG;
-    }
+    REEF_TRY(sp_check_pads(c, "reef_spartan_begin", num_cons_pad, num_vars_pad));
     const u32 ell_x = sp_log2(num_cons_pad);
     std::vector<fe> t(ell_x);
     REEF_TRY(fe_import_all<F>(tau, ell_x, is_mont, "reef_spartan_begin", "tau", t.data()));
@@ -272,9 +279,67 @@ template <int C> static reef_status v_spartan_inner_claims(void *impl, const ree
     return call.done(SP_DONE);
 }
 
+// The verifier's matrix evaluations (3k): A~, B~, C~ at (r_x, r_y) from the CSR alone -- no running instance, no prove: the phase, the
+// tables and gen of a prove or an opening on this ctx are neither read nor written, and the workspace is the call's own (c->evw).
+// One pass over the rows (k_sp_eval_short; long rows by k_nifs_rows_long's segments and k_sp_eval_long) and one k_sp_finish: one wait.
+template <int C>
+static reef_status v_spartan_eval_matrices(void *impl, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *r_x, const reef_fe *r_y, bool is_mont,
+                                           reef_fe *evals) {
+    constexpr int F = NifsCtx<C>::F;
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    if (!r_x || !r_y || !evals) { set_error("null argument"); return REEF_ERR_ARG; }
+    REEF_TRY(sp_check_pads(c, "reef_spartan_eval_matrices", num_cons_pad, num_vars_pad));
+    const u32 ell_x = sp_log2(num_cons_pad), ell_y = sp_log2(2 * num_vars_pad);
+    std::vector<fe> p(ell_x + ell_y);
+    REEF_TRY(fe_import_all<F>(r_x, ell_x, is_mont, "reef_spartan_eval_matrices", "r_x", p.data()));
+    REEF_TRY(fe_import_all<F>(r_y, ell_y, is_mont, "reef_spartan_eval_matrices", "r_y", p.data() + ell_x));
+    std::vector<fe256> f(2 * p.size());                       // {1 - p_j, p_j}: r_x's factors, then r_y's
+    for (size_t j = 0; j < p.size(); ++j) {
+        f[2 * j] = fe_to_table<F>(fe_sub<F, 2>(fe_one<F>(), p[j]));
+        f[2 * j + 1] = fe_to_table<F>(p[j]);
+    }
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    if (!c->has[0] || !c->has[1] || !c->has[2]) {
+        set_error("reef_spartan_eval_matrices: set the matrices A, B and C first (reef_nifs_set_matrix)");
+        return REEF_ERR_ARG;
+    }
+    REEF_TRY(call.enter());
+    REEF_TRY(nifs_prepare(c));
+    auto &w = c->evw;
+    const u32 nblocks = (u32)ceil_div(c->num_cons, SP_THREADS), nlong = c->rows.nlong;
+    REEF_TRY(w.pts.ensure(f.size() * sizeof(fe256)));
+    REEF_TRY(w.ex.ensure(c->num_cons * sizeof(fe256)));        // only rows < num_cons and columns < nz are ever read: partial eq tables
+    REEF_TRY(w.zy.ensure(c->nz * sizeof(fe256)));
+    REEF_TRY(w.partial.ensure(((size_t)nblocks + nlong) * 27 * sizeof(unsigned long long)));   // a row per block, then a row per long row
+    REEF_TRY(w.out.ensure(3 * sizeof(fe256)));
+    const fe256 *pts = w.pts.template as<fe256>();
+    fe256 *ex = w.ex.template as<fe256>(), *zy = w.zy.template as<fe256>();
+    unsigned long long *partial = w.partial.template as<unsigned long long>();
+    REEF_HIP_TRY(hipMemcpyAsync(w.pts.p, f.data(), f.size() * sizeof(fe256), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_sp_eq<F>, dim3(nblocks), dim3(256), 0, c->stream, pts, ell_x, (u32)c->num_cons, ex);
+    hipLaunchKernelGGL(k_sp_eq_cols<F>, dim3(ceil_div(c->nz, 256)), dim3(256), 0, c->stream, pts + 2 * ell_x, ell_y, (u32)c->nz, (u32)c->num_vars,
+                       (u32)(num_vars_pad - c->num_vars), zy);
+    NifsArgs a = nifs_args(c);
+    a.z1 = a.z2 = zy;
+    hipLaunchKernelGGL(k_sp_eval_short<F>, dim3(nblocks), dim3(SP_THREADS), 0, c->stream, a, (const fe256 *)ex, partial);
+    if (nlong) {
+        const u32 *seg_row = c->rows.seg_row.template as<u32>(), *seg_first = c->rows.seg_first.template as<u32>();
+        fe_limbs *part = c->rows.part.template as<fe_limbs>();
+        hipLaunchKernelGGL((k_nifs_rows_long<F, NIFS_MODE_SPARTAN>), dim3(c->rows.nseg), dim3(256), 0, c->stream, a, seg_row, seg_first, part);
+        hipLaunchKernelGGL(k_sp_eval_long<F>, dim3(nlong), dim3(64), 0, c->stream, a, seg_first, (const fe_limbs *)part, (const fe256 *)ex,
+                           partial + (size_t)nblocks * 27);
+    }
+    hipLaunchKernelGGL(k_sp_finish<F>, dim3(1), dim3(SP_THREADS), 0, c->stream, (const unsigned long long *)partial, nblocks + nlong, 3u,
+                       is_mont ? (int)SP_FORM_MONT : (int)SP_FORM_INTEGER, w.out.template as<fe256>());
+    REEF_HIP_TRY(hipGetLastError());
+    REEF_HIP_TRY(hipMemcpyAsync(evals, w.out.p, 3 * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));             // the one wait; f goes out of scope
+    return REEF_OK;
+}
+
 template <int C> SpartanVTable make_spartan_vtable() {
     return SpartanVTable{v_spartan_begin<C>, v_spartan_outer_round<C>, v_spartan_outer_claims<C>, v_spartan_inner_begin<C>, v_spartan_inner_round<C>,
-                         v_spartan_inner_claims<C>};
+                         v_spartan_inner_claims<C>, v_spartan_eval_matrices<C>};
 }
 
 }  // namespace reef

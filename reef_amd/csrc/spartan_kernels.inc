@@ -8,6 +8,7 @@
 //   ABC          sum_row eq(r_x)[row] (A + r B + r^2 C)[row][col] per column (the NIFS row pass over the CSC copy, MODE_ABC)
 //   inner rounds sum ABC z at 0 and 2                                                              (k_sp_round<F, 0>)
 //   inner claims ABC(r_y), z(r_y): the last bind; eval_W = W . eq(r_y[1..])
+// and, for the verifier, without a prove (3k): A~, B~, C~ at (r_x, r_y) over the CSR      (k_sp_eq_cols, k_sp_eval_short, k_sp_eval_long)
 //
 // Tables hold the resident internal form, canonical and packed (fe_to_table), like the NIFS vectors.  Round sums are lazy: each
 // term is one product (< 2M, exact 29-bit limbs) whose limbs go into 64-bit column sums per thread, then per wave (DPP), per block
@@ -21,13 +22,24 @@ static constexpr u32 SP_THREADS = 256;
 
 // eq(p)[i] = prod_j (bit_{ell-1-j}(i) ? p_j : 1 - p_j) (p_0 pairs with the most significant bit, as EqPolynomial::evals [R]).
 // f[2 j] = 1 - p_j, f[2 j + 1] = p_j (internal form); one thread per entry, ell - 1 products.
+template <int F> __device__ __forceinline__ fe256 sp_eq_at(const fe256 *__restrict__ f, u32 ell, u32 i) {
+    fe acc = fe_from_table(load_fe256(f + ((i >> (ell - 1)) & 1u)));
+    for (u32 j = 1; j < ell; ++j) acc = fe_mul<F>(acc, fe_from_table(load_fe256(f + 2 * j + ((i >> (ell - 1 - j)) & 1u))));
+    return fe_to_table<F>(acc);
+}
 template <int F>
 __global__ void __launch_bounds__(256) k_sp_eq(const fe256 *__restrict__ f, u32 ell, u32 n, fe256 *__restrict__ out) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    fe acc = fe_from_table(load_fe256(f + ((i >> (ell - 1)) & 1u)));
-    for (u32 j = 1; j < ell; ++j) acc = fe_mul<F>(acc, fe_from_table(load_fe256(f + 2 * j + ((i >> (ell - 1 - j)) & 1u))));
-    store_fe256(out + i, fe_to_table<F>(acc));
+    store_fe256(out + i, sp_eq_at<F>(f, ell, i));
+}
+// out[c] = eq(p)[c'] for the n matrix columns in their own numbering, c' = renumber(c) of R1CSShape::pad [R]: c' = c for c < num_vars,
+// c + shift otherwise (c' < 2^ell is the caller's pad rule).  The column weights of k_sp_eval_short: a row gathers out + col, no shift.
+template <int F>
+__global__ void __launch_bounds__(256) k_sp_eq_cols(const fe256 *__restrict__ f, u32 ell, u32 n, u32 num_vars, u32 shift, fe256 *__restrict__ out) {
+    const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    store_fe256(out + c, sp_eq_at<F>(f, ell, c + (c >= num_vars ? shift : 0u)));
 }
 
 // the value at t of the line through lo (t = 0) and hi (t = 1), canonical: lo + t (hi - lo) for t = 2, 3
@@ -174,6 +186,65 @@ __global__ void __launch_bounds__(64) k_sp_bind_last(SpRound a, u32 nt, int form
     const fe v = sp_bind<F>(a.t[k], 0, 1, fe_from_table(a.r));
     store_fe256(a.t[k], fe_pack(v));
     store_fe256(out + k, sp_out<F>(v, form));
+}
+
+// ---- the verifier's matrix evaluations (include/reef_msm.h 3k): M~(r_x, r_y) = sum_entries val eq(r_x)[row] eq(r_y)[col'] for M = A, B, C.
+// One product per ENTRY goes into the row's dot product with the column weights zy (k_sp_eq_cols) -- nifs_dot, with its +-1 adds and
+// one-word magnitudes -- then three products per ROW with ex = eq(r_x)[row], whose limbs are summed over the rows as the round sums
+// are: per wave, per block into partial[block][27], once over the blocks by k_sp_finish.  No per-row table is written.
+// a: the CSR (m, num_cons, long_rows, k254) with z1 = z2 = zy.  One thread per row; a row of more than NIFS_LONG_ROW entries, a row
+// past num_cons and an empty row add zero HERE and stay in the block: sp_block_sums needs whole waves and has two barriers, so no
+// thread returns before it.
+// Bound: at most 2^24 rows (the pad rule), long rows included, each adding one product with limbs < 2^29 to a value's nine columns:
+// a block's column < 2^37, the columns k_sp_finish adds up < 2^53, inside its stated bound (< 2^24 terms of < 2^29 each).
+template <int F>
+__global__ void __launch_bounds__(SP_THREADS) k_sp_eval_short(NifsArgs a, const fe256 *__restrict__ ex, unsigned long long *__restrict__ partial) {
+    const u32 row = blockIdx.x * blockDim.x + threadIdx.x;
+    u64 acc[3][9];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int i = 0; i < 9; ++i) acc[k][i] = 0;
+    u32 b[3] = {0, 0, 0}, e[3] = {0, 0, 0};
+    if (row < a.num_cons) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { b[k] = a.m[k].rowptr[row]; e[k] = a.m[k].rowptr[row + 1]; }
+    }
+    const u32 len = (e[0] - b[0]) + (e[1] - b[1]) + (e[2] - b[2]);
+    if (len != 0 && len <= NIFS_LONG_ROW) {                 // a predicate, not a return
+        const fe k254 = fe_from_table(a.k254);
+        const fe w = fe_from_table(load_fe256(ex + row));
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            fe d;
+            nifs_dot<F, 0>(a.m[k], b[k], e[k], 1, a.z1, a.z2, k254, &d);
+            sp_acc(acc[k], fe_mul<F>(w, d));
+        }
+    }
+    sp_block_sums<3>(acc, partial);
+}
+// One wave per long row, after k_nifs_rows_long left its segments' sums in part: the row's three dot products, times eq(r_x)[row], as
+// one more row of partial (lane 0 writes all 27 slots): rows[l] of `partial` here is the caller's row (blocks of k_sp_eval_short) + l.
+template <int F>
+__global__ void __launch_bounds__(64) k_sp_eval_long(NifsArgs a, const u32 *__restrict__ seg_first, const fe_limbs *__restrict__ part,
+                                                     const fe256 *__restrict__ ex, unsigned long long *__restrict__ partial) {
+    const u32 l = blockIdx.x, row = a.long_rows[l];
+    const u32 s0 = seg_first[l], s1 = seg_first[l + 1];
+    fe d[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        d[j] = fe_zero();
+        for (u32 s = s0 + threadIdx.x; s < s1; s += WAVE) d[j] = fe_canon<F>(fe_add<F>(d[j], fe_from_limbs(part[(size_t)s * 3 + j], 1.0)));
+        nifs_wave_sum<F>(d[j]);
+    }
+    if (threadIdx.x != 0) return;
+    const fe w = fe_from_table(load_fe256(ex + row));
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const fe p = fe_mul<F>(w, d[k]);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) partial[(size_t)l * 27 + 9 * k + i] = p.l[i];
+    }
 }
 
 }  // namespace reef

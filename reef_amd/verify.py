@@ -1,4 +1,4 @@
-"""Python front-end of the verifier's IPA check (include/reef_msm.h 3j).
+"""Python front-end of the verifier's device calls: the IPA check (include/reef_msm.h 3j) and the matrix evaluations (3k).
 
 `ipa_check` / `ipa_check_eq` are the two C-ABI calls: P_hat rebuilt from the proof, the challenges expanded into s on the device,
 G_hat = <s, key>, b_hat = <s, b>, and the two sides compared as group elements.  `verify_opening` is the device counterpart of
@@ -9,6 +9,10 @@ raise ReefError (REEF_ERR_ARG).  The C calls take no curve -- the key's curve is
 check of THIS module, not of the library: pass curve= and a key of another curve raises ReefError(1) before any call is made.
 Scalars cross as Python ints (canonical, or pasta Montgomery form with is_mont=True); points as numpy uint64 arrays in the C-ABI
 layouts: affine (8 limbs) or Jacobian (12 limbs).
+
+`matrix_evals` is reef_spartan_eval_matrices: A~, B~, C~ at (r_x, r_y) on the matrices a `Nifs` holds, no witness needed.
+`verify_sumchecks` is the verifier of 3g's transcript -- RelaxedR1CSSNARK::verify [R] up to the opening: O(log n) host arithmetic and that
+one device call -- and `verify_snark` adds `verify_opening` with eval_E = claims_outer[3], eval_W = claims_inner[2].
 """
 from __future__ import annotations
 
@@ -20,6 +24,7 @@ import numpy as np
 from ._ffi import REEF_DEVICE, REEF_HOST, ReefError, check
 from ._fe import _arr, _ints
 from .msm import DeviceBuffer, MsmContext, curve_id, decompress, normalize
+from .nifs import Nifs
 from .spartan import compress
 
 
@@ -171,3 +176,100 @@ def verify_eval(key: MsmContext, q, row_comms32, point: Sequence[int], left: int
     fn = check_fn or ipa_check_eq
     blind = None if blind_total is None else blind_total % p
     return fn(key, n, clz, eval_ % p, q, proof["L"], proof["R"], rs, proof["a_hat"], [list(point[left:])], [1], h=h, blind=blind)["accept"]
+
+
+# ---------------------------------------------------------------------------------------------------- 3k and the sum-check verifier
+def matrix_evals(nifs: Nifs, num_cons_pad: int, num_vars_pad: int, r_x: Sequence[int], r_y: Sequence[int], *, is_mont: bool = False) -> List[int]:
+    """reef_spartan_eval_matrices: [A~, B~, C~] at (r_x, r_y), len(r_x) = log2(num_cons_pad), len(r_y) = log2(2 num_vars_pad); ints in
+    the form is_mont names.  The ctx needs its three matrices only."""
+    def pow2(n):
+        return n >= 2 and n & (n - 1) == 0
+    if pow2(num_cons_pad) and pow2(num_vars_pad) and (len(r_x) != _rounds(num_cons_pad) or len(r_y) != _rounds(2 * num_vars_pad)):
+        raise ValueError(f"pads ({num_cons_pad}, {num_vars_pad}) take {_rounds(num_cons_pad)} and {_rounds(2 * num_vars_pad)} point entries: "
+                         f"r_x and r_y have {len(r_x)}, {len(r_y)}")
+    xa, ya = (_arr(v) if len(v) else np.zeros((1, 4), np.uint64) for v in (r_x, r_y))   # illegal pads: the library says what is wrong
+    out = np.zeros((3, 4), dtype=np.uint64)
+    check(nifs._lib.reef_spartan_eval_matrices(nifs._h, num_cons_pad, num_vars_pad, xa.ctypes.data, ya.ctypes.data, bool(is_mont), out.ctypes.data))
+    return _ints(out)
+
+
+def _interp(ys: Sequence[int], r: int, p: int) -> int:
+    """the polynomial through (0, ys[0]), (1, ys[1]), ... at r"""
+    out = 0
+    for i, y in enumerate(ys):
+        num = den = 1
+        for j in range(len(ys)):
+            if j != i:
+                num = num * (r - j) % p
+                den = den * (i - j) % p
+        out = (out + y * num * pow(den, -1, p)) % p
+    return out
+
+
+def _eq_entry(point: Sequence[int], i: int, p: int) -> int:
+    """eq(point)[i], point[0] pairing with the most significant bit"""
+    out, ell = 1, len(point)
+    for j, t in enumerate(point):
+        out = out * (t if (i >> (ell - 1 - j)) & 1 else 1 - t) % p
+    return out
+
+
+def _sumchecks(nifs, num_cons_pad, num_vars_pad, u, X, proof, challenge, p, evals_fn):
+    ell_x, ell_y = _rounds(num_cons_pad), _rounds(2 * num_vars_pad)
+    outer, inner, co, ci = proof["outer"], proof["inner"], list(proof["claims_outer"]), list(proof["claims_inner"])
+    if len(outer) != ell_x or len(inner) != ell_y or len(co) != 4 or len(ci) != 3 or 1 + len(X) > num_vars_pad:
+        return False, [], []
+    if any(len(ev) != 3 for ev in outer) or any(len(ev) != 2 for ev in inner):
+        return False, [], []
+    tau = [challenge("t", []) for _ in range(ell_x)]
+    claim, r_x = 0, []
+    for e0, e2, e3 in outer:
+        r_x.append(challenge("outer", [e0, e2, e3]))
+        claim = _interp([e0, (claim - e0) % p, e2, e3], r_x[-1], p)
+    az, bz, cz, ex = co
+    eq_tau = 1
+    for a, b in zip(tau, r_x):
+        eq_tau = eq_tau * (a * b + (1 - a) * (1 - b)) % p
+    ok = claim == eq_tau * (az * bz - u * cz - ex) % p
+    r = challenge("r", co)
+    claim, r_y = (az + r * bz + r * r * cz) % p, []
+    for e0, e2 in inner:
+        r_y.append(challenge("inner", [e0, e2]))
+        claim = _interp([e0, (claim - e0) % p, e2], r_y[-1], p)
+    for name, drawn in (("tau", tau), ("r_x", r_x), ("r", r), ("r_y", r_y)):         # a transcript that records its challenges must agree
+        ok = ok and (name not in proof or proof[name] == drawn)
+    if not ok:
+        return False, r_x, r_y
+    eval_w = ci[2] % p
+    eval_x = sum(_eq_entry(r_y[1:], j, p) * v for j, v in enumerate([u] + list(X))) % p
+    z_ry = ((1 - r_y[0]) * eval_w + r_y[0] * eval_x) % p
+    ea, eb, ec = (evals_fn or matrix_evals)(nifs, num_cons_pad, num_vars_pad, r_x, r_y)
+    abc = (ea + r * eb + r * r * ec) % p
+    return claim == abc * z_ry % p and ci[0] == abc and ci[1] == z_ry, r_x, r_y
+
+
+def verify_sumchecks(nifs: Optional[Nifs], num_cons_pad: int, num_vars_pad: int, u: int, X: Sequence[int], proof: dict,
+                     challenge: Callable[[str, List[Any]], int], p: int, *, evals_fn=None) -> bool:
+    """The verifier of 3g's transcript for an instance of which only u and X are known.  proof: {"outer", "claims_outer", "inner",
+    "claims_inner"} as `spartan.prove` returns them (its "tau", "r_x", "r", "r_y", where present, must equal the re-drawn ones).
+    Challenges in the prover's order: "t" x log2(num_cons_pad), "outer" per round, "r" after claims_outer, "inner" per round.  On the
+    host: the round sums chained with e1 = claim - e0, claim_outer == eq(tau, r_x) (az bz - u cz - ex) with claims_outer as claimed
+    (the opening proves eval_E; az, bz, cz are bound by the inner sum-check), eval_X = sum_j eq(r_y[1..])[j] (u || X)[j] and
+    z(r_y) = (1 - r_y[0]) eval_W + r_y[0] eval_X.  On the device: `matrix_evals` on nifs (its matrices; no witness).  Then
+    claim_inner == (A~ + r B~ + r^2 C~) z(r_y), claims_inner[0] against the same combination and claims_inner[1] against z(r_y).
+    evals_fn(nifs, num_cons_pad, num_vars_pad, r_x, r_y) stands in for the device call (tests).  Canonical ints; False, never an
+    exception, for a transcript that does not verify."""
+    return _sumchecks(nifs, num_cons_pad, num_vars_pad, u % p, [x % p for x in X], proof, challenge, p, evals_fn)[0]
+
+
+def verify_snark(nifs: Optional[Nifs], key: MsmContext, gens_s, comm_e, comm_w, num_cons_pad: int, num_vars_pad: int, u: int, X: Sequence[int],
+                 proof: dict, challenge: Callable[[str, List[Any]], int], p: int, *, evals_fn=None, check_fn=None) -> bool:
+    """RelaxedR1CSSNARK::verify [R] on the device calls: `verify_sumchecks`, then `verify_opening` of [E, W] at (r_x, r_y[1..]) with
+    eval_E = claims_outer[3] and eval_W = claims_inner[2], on one `challenge` in the prover's order.  proof: what
+    `spartan.prove_with_opening` returns (the cross term as "cross_term" or "cross")."""
+    ok, r_x, r_y = _sumchecks(nifs, num_cons_pad, num_vars_pad, u % p, [x % p for x in X], proof, challenge, p, evals_fn)
+    if not ok:
+        return False
+    opening = {"cross": proof["cross"] if "cross" in proof else proof["cross_term"], "L": proof["L"], "R": proof["R"], "a_hat": proof["a_hat"]}
+    return verify_opening(key, gens_s, comm_e, r_x, proof["claims_outer"][3], comm_w, r_y, proof["claims_inner"][2], opening, challenge, p,
+                          check_fn=check_fn)
