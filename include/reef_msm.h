@@ -31,6 +31,8 @@
  *      Later, still 7 (symbols added, none changed): K4's inverse, reef_decompress, and reef_hyrax_eval_comm_compressed on top of it.
  *      Later, still 7 (symbols added, none changed): the verifier's IPA check on a key ctx (reef_ipa_check, reef_ipa_check_eq, section 3j).
  *      Later, still 7 (symbols added, none changed): the verifier's matrix evaluations on a NIFS ctx (reef_spartan_eval_matrices, section 3k).
+ *      Later, still 7 (symbols added, none changed): the sum-check table set from parts -- field elements, a fill, document symbols
+ *      (reef_sc_set_table_parts, section 3b).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -306,6 +308,24 @@ reef_status reef_sc_create(reef_sc_ctx **out, int curve, size_t table_len);
 void reef_sc_destroy(reef_sc_ctx *ctx);
 /* which: 0 = T, 1 = EQ.  n <= table_len values; the rest is zero-padded (r1cs.rs:2323-2330). */
 reef_status reef_sc_set_table(reef_sc_ctx *ctx, int which, const reef_fe *values, size_t n, int loc);
+/* T from what the caller knows it to be: runs of field elements, of one repeated value, of document symbols.  Reef's tables
+ * are such runs -- "nldoc" (r1cs.rs:2322-2329): [SYMBOLS doc]; "nlhybrid" (r1cs.rs:2101-2112, :481-484): [FE table,
+ * FILL calc_fill x (half - |table|), SYMBOLS proj_doc] -- and a host symbol part uploads count * elem_bytes bytes, not 32 per entry. */
+enum { REEF_SC_PART_FE = 0, REEF_SC_PART_SYMBOLS = 1, REEF_SC_PART_FILL = 2 };
+#define REEF_SC_MAX_PARTS 8
+typedef struct {
+    uint32_t kind;        /* REEF_SC_PART_*                                                         */
+    uint32_t elem_bytes;  /* SYMBOLS: 1, 2 or 4 (unsigned little-endian); otherwise 0               */
+    const void *data;     /* FE: count canonical 32-byte integers; SYMBOLS: count symbols;          */
+                          /* FILL: ONE canonical 32-byte integer, always host memory                */
+    size_t count;         /* entries of T this part covers (FILL: repetitions); 0 = part is skipped */
+    int loc;              /* REEF_HOST / REEF_DEVICE for data (FE, SYMBOLS)                         */
+} reef_sc_part;
+/* T <- the parts laid end to end from entry 0, zero beyond their total (<= table_len).  Same effect on the ctx as
+ * reef_sc_set_table(ctx, 0, ..) on the table written out as integers: same coefficients, folds, reads and reset.
+ * nparts <= REEF_SC_MAX_PARTS (0: the all-zero table); device symbols are aligned to elem_bytes.  An argument error
+ * (REEF_ERR_ARG) is found before anything of the ctx is touched: the table set before stays usable. */
+reef_status reef_sc_set_table_parts(reef_sc_ctx *ctx, const reef_sc_part *parts, size_t nparts);
 /* EQ[i] = sum_{k: qs[k] = i} rs[k] + rs[nq] * prod_j (bit_j(i) ? last_q[j] : 1 - last_q[j]);
  * rs has nq + 1 entries, last_q has ell entries (host arrays). */
 reef_status reef_sc_gen_eq_table(reef_sc_ctx *ctx, const reef_fe *rs, const uint32_t *qs, size_t nq,

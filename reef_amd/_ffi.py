@@ -68,6 +68,13 @@ class KeyCacheStats(ctypes.Structure):
     _fields_ = [(n, c_uint64) for n in ("entries", "resident_keys", "resident_bytes", "builds", "hits", "clones", "misspeculated", "spares")]
 
 
+class ScPart(ctypes.Structure):      # reef_sc_part: one run of the sum-check table (reef_sc_set_table_parts)
+    _fields_ = [("kind", c_uint32), ("elem_bytes", c_uint32), ("data", c_void_p), ("count", c_size_t), ("loc", c_int)]
+
+
+SC_PART_FE, SC_PART_SYMBOLS, SC_PART_FILL = 0, 1, 2
+SC_MAX_PARTS = 8
+
 ABI_VERSION = 7     # REEF_ABI_VERSION of include/reef_msm.h this binding was written against
 
 
@@ -152,6 +159,7 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_sc_create": (c_int, [POINTER(vp), c_int, c_size_t]),
         "reef_sc_destroy": (None, [vp]),
         "reef_sc_set_table": (c_int, [vp, c_int, vp, c_size_t, c_int]),
+        "reef_sc_set_table_parts": (c_int, [vp, POINTER(ScPart), c_size_t]),
         "reef_sc_gen_eq_table": (c_int, [vp, vp, vp, c_size_t, vp, c_size_t]),
         "reef_sc_round_coeffs": (c_int, [vp, c_size_t, vp]),
         "reef_sc_fold": (c_int, [vp, c_size_t, vp]),

@@ -453,6 +453,9 @@ void reef_sc_destroy(reef_sc_ctx *ctx) { destroy_handle(ctx, &CurveVTable::sc_de
 reef_status reef_sc_set_table(reef_sc_ctx *ctx, int which, const reef_fe *values, size_t n, int loc) {
     return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_set(impl, which, values, n, loc); });
 }
+reef_status reef_sc_set_table_parts(reef_sc_ctx *ctx, const reef_sc_part *parts, size_t nparts) {
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_set_parts(impl, parts, nparts); });
+}
 reef_status reef_sc_gen_eq_table(reef_sc_ctx *ctx, const reef_fe *rs, const uint32_t *qs, size_t nq, const reef_fe *last_q, size_t ell) {
     return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_gen_eq(impl, rs, qs, nq, last_q, ell); });
 }

@@ -289,6 +289,12 @@ class SumCheck {
     SumCheck &operator=(const SumCheck &) = delete;
 
     void set_table(const reef_fe *values, size_t n, int loc = REEF_HOST) { have_next_ = false; check(reef_sc_set_table(sc_, 0, values, n, loc), "reef_sc_set_table"); }
+    // the table as the runs Reef builds it from -- "nldoc": {SYMBOLS doc}; "nlhybrid": {FE table, FILL calc_fill x (half - |table|), SYMBOLS proj_doc} --
+    // zero beyond them: a host symbol part uploads its bytes, not 32 per entry
+    void set_table_parts(const std::vector<reef_sc_part> &parts) {
+        have_next_ = false;
+        check(reef_sc_set_table_parts(sc_, parts.data(), parts.size()), "reef_sc_set_table_parts");
+    }
     void start_step() { have_next_ = false; check(reef_sc_reset_table(sc_), "reef_sc_reset_table"); }   // every folding step starts from the unfolded table
     void gen_eq_table(const std::vector<reef_fe> &rs, const std::vector<uint32_t> &qs, const std::vector<reef_fe> &last_q) {
         if (rs.size() != qs.size() + 1 || last_q.size() != ell_) throw std::logic_error("gen_eq_table: |rs| = |qs| + 1, |last_q| = ell");

@@ -31,6 +31,7 @@ template <int C> struct ScCtx : DeviceCtx {   // device: where the tables live; 
     fe256 defer_r1 = {};
     size_t defer_pow = 0;                // the pow of that next call
     u32 defer_hq = 0;
+    fe256 parts_fill[2 * SC_MAX_PARTS] = {};   // reef_sc_set_table_parts: the FILL values (integer, table form) on their way to the device
     fe256 *pinned3 = nullptr;            // pinned host landing zone for the three coefficients
     // gen_eq_table's inputs (last_q, rs, qs) go through pinned staging in ONE asynchronous copy: two halves used in turn, each
     // with the event of its last copy (a half is reused two calls later; a step's own rounds have long waited for the stream by then)
@@ -51,6 +52,7 @@ template <int C> struct ScCtx : DeviceCtx {   // device: where the tables live; 
         u32 split_blocks = 64;             // REEF_SC_SPLIT_BLOCKS: the most workgroups of such a round (every one adds 27 words to the shared sums: 256 of them cost the 2^14-pair round 7 us)
         u32 items = 8;                   // pairs a thread of a dense round takes at least (its three lazy reductions and the block's sums are per thread)
         u32 order = 2;                   // REEF_SC_FENCE: how a multi-block one-launch round orders its additions before the ticket (sumcheck_kernels.inc: SC_ORDER_*)
+        u32 set_sub = 8;                 // REEF_SC_SET_SUB: the most 128-entry tiles a wave of k_sc_set_parts takes (two entries per lane and tile)
     } sw;
 };
 // REEF_SC_ONE_LAUNCH=0: the sums of a round are finished by a second kernel and copied back (rounds 1-2 form), for A/B runs.
@@ -78,6 +80,8 @@ template <int C> static void sc_read_switches(ScCtx<C> *c) {
     c->sw.one_launch_max = (e && *e) ? (u32)std::min<long long>(8192, std::max<long long>(1, atoll(e))) : 64u;
     e = getenv("REEF_SC_FENCE");             // 2 (default since round 6): acq_rel ticket; 1: __threadfence before the ticket; 0: returning atomics + s_waitcnt only
     c->sw.order = (e && *e) ? (u32)std::min<long long>(2, std::max<long long>(0, atoll(e))) : 2u;
+    e = exp_env("REEF_SC_SET_SUB");
+    c->sw.set_sub = (e && *e) ? (u32)std::min<long long>(64, std::max<long long>(1, atoll(e))) : 8u;
     e = exp_env("REEF_SC_FLOOR");
     c->sw.floor_blocks = (e && *e) ? (u32)std::min<long long>(8192, std::max<long long>(1, atoll(e))) : 256u;
 }
@@ -233,15 +237,19 @@ template <int C> static reef_status sc_r1_finish(ScCtx<C> *c, u32 blocks, size_t
     return REEF_OK;
 }
 
-// Classify the rows of the table just set (`src_int`: the caller's integers on the device, n of them, zero beyond) and build the
-// row lists of round one.  Only for tables the rank-one rounds serve, and only kept when at least half the rows are K or S.
-template <int C> static reef_status sc_struct_build(ScCtx<C> *c, const fe256 *src_int, size_t n) {
+// The row structure of the table just set, in three parts: sc_struct_open decides whether this table gets one (only tables the
+// rank-one rounds serve) and presets the row flags, a kernel clears them and writes the 4-byte copy -- k_sc_classify from the caller's
+// integers (reef_sc_set_table), k_sc_set_parts while it writes the table (reef_sc_set_table_parts) -- and sc_struct_lists builds the
+// row lists of round one from the flags.  The structure is only kept when at least half the rows are K or S.
+template <int C> static reef_status sc_struct_open(ScCtx<C> *c, u32 *lo_bits, u32 *rows) {
     c->st_ok = false;
     c->defer_on = false;                 // the table is replaced
+    *rows = 0;
     sc_read_switches<C>(c);
     size_t ell = 0;
     while (((size_t)1 << ell) < c->len) ++ell;
     const u32 lo = (u32)(ell / 2), hi = (u32)ell - lo;
+    *lo_bits = lo;
     if (!c->sw.rank1 || !c->sw.structured || hi < 2 || c->len / 2 < c->sw.r1_min_pow) return REEF_OK;
     const u32 H = 1u << hi;
     REEF_TRY(c->st_s32.ensure(c->len * sizeof(u32)));
@@ -251,9 +259,10 @@ template <int C> static reef_status sc_struct_build(ScCtx<C> *c, const fe256 *sr
         REEF_HIP_TRY(hipMemcpyAsync(c->st_flags.p, three.data(), (size_t)H * sizeof(u32), hipMemcpyHostToDevice, c->stream));
         REEF_HIP_TRY(hipStreamSynchronize(c->stream));     // `three` is a local
     }
-    hipLaunchKernelGGL(k_sc_classify, dim3(ceil_div(c->len, 256)), dim3(256), 0, c->stream, src_int, (u32)n, (u32)c->len, lo, c->st_flags.template as<u32>(),
-                       c->st_s32.template as<u32>());
-    REEF_HIP_TRY(hipGetLastError());
+    *rows = H;
+    return REEF_OK;
+}
+template <int C> static reef_status sc_struct_lists(ScCtx<C> *c, u32 H) {
     std::vector<u32> flags(H);
     REEF_HIP_TRY(hipMemcpyAsync(flags.data(), c->st_flags.p, (size_t)H * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -314,6 +323,16 @@ template <int C> static reef_status sc_struct_build(ScCtx<C> *c, const fe256 *sr
     REEF_TRY(c->st_sumfl.ensure(sizeof(fe256)));
     c->st_ok = true;
     return REEF_OK;
+}
+// reef_sc_set_table: `src_int` are the caller's integers on the device, n of them, zero beyond
+template <int C> static reef_status sc_struct_build(ScCtx<C> *c, const fe256 *src_int, size_t n) {
+    u32 lo = 0, H = 0;
+    REEF_TRY(sc_struct_open<C>(c, &lo, &H));
+    if (!H) return REEF_OK;
+    hipLaunchKernelGGL(k_sc_classify, dim3(ceil_div(c->len, 256)), dim3(256), 0, c->stream, src_int, (u32)n, (u32)c->len, lo, c->st_flags.template as<u32>(),
+                       c->st_s32.template as<u32>());
+    REEF_HIP_TRY(hipGetLastError());
+    return sc_struct_lists<C>(c, H);
 }
 // the first round of a step on a structured table: tables are whole (2*pow = len), T is pristine, EQ is rank-one with all its FH bits
 template <int C> static bool sc_struct_round(const ScCtx<C> *c, size_t pow) {
@@ -426,6 +445,86 @@ template <int C> static reef_status v_sc_set(void *impl, int which, const reef_f
     else c->r1 = false;                  // a table given by the caller is a dense table
     REEF_HIP_TRY(hipGetLastError());
     if (which == 0) REEF_TRY(sc_struct_build<C>(c, src, n));
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    return REEF_OK;
+}
+
+// T from parts (include/reef_msm.h 3b): field elements, one value repeated, document symbols -- what the caller knows the table to be,
+// not 32 bytes per entry.  Host parts are staged packed (count x element size, every part's start padded to 32 bytes; a FILL is two
+// fe256: its integer and its table form); k_sc_set_parts writes T0, the 4-byte copy and the row flags in one pass.  Ends in the
+// state v_sc_set(which = 0) leaves for the same values.
+template <int C> static reef_status v_sc_set_parts(void *impl, const reef_sc_part *parts, size_t nparts) {
+    static_assert(REEF_SC_MAX_PARTS == SC_MAX_PARTS && REEF_SC_PART_FE == SC_PART_FE && REEF_SC_PART_SYMBOLS == SC_PART_SYMBOLS && REEF_SC_PART_FILL == SC_PART_FILL,
+                  "the header's part kinds are the kernel's");
+    ScCtx<C> *c = (ScCtx<C> *)impl;
+    if (!c) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (nparts > REEF_SC_MAX_PARTS) { set_error("reef_sc_set_table_parts: %zu parts, at most %d", nparts, (int)REEF_SC_MAX_PARTS); return REEF_ERR_ARG; }
+    if (nparts && !parts) { set_error("reef_sc_set_table_parts: parts is NULL"); return REEF_ERR_ARG; }
+    size_t total = 0, stage_bytes = 0, at[REEF_SC_MAX_PARTS] = {};      // at[p]: where part p is staged
+    for (size_t p = 0; p < nparts; ++p) {
+        const reef_sc_part &q = parts[p];
+        if (q.kind != REEF_SC_PART_FE && q.kind != REEF_SC_PART_SYMBOLS && q.kind != REEF_SC_PART_FILL) {
+            set_error("reef_sc_set_table_parts: part %zu has the unknown kind %u", p, q.kind);
+            return REEF_ERR_ARG;
+        }
+        if (q.kind == REEF_SC_PART_SYMBOLS && q.elem_bytes != 1 && q.elem_bytes != 2 && q.elem_bytes != 4) {
+            set_error("reef_sc_set_table_parts: part %zu has symbols of %u bytes (1, 2 or 4)", p, q.elem_bytes);
+            return REEF_ERR_ARG;
+        }
+        if (q.count && !q.data) { set_error("reef_sc_set_table_parts: part %zu has %zu entries and no data", p, q.count); return REEF_ERR_ARG; }
+        const bool on_device = q.kind != REEF_SC_PART_FILL && q.loc == REEF_DEVICE;
+        if (q.count && on_device && q.kind == REEF_SC_PART_SYMBOLS && reinterpret_cast<uintptr_t>(q.data) % q.elem_bytes) {
+            set_error("reef_sc_set_table_parts: part %zu: device symbols of %u bytes at an address that is no multiple of it", p, q.elem_bytes);
+            return REEF_ERR_ARG;
+        }
+        if (q.count > c->len - total) { set_error("reef_sc_set_table_parts: the parts hold more than the table's %zu entries", c->len); return REEF_ERR_ARG; }
+        total += q.count;
+        if (q.count && !on_device) {
+            at[p] = stage_bytes;
+            const size_t bytes = q.kind == REEF_SC_PART_FILL ? 2 * sizeof(fe256) : q.count * (q.kind == REEF_SC_PART_FE ? sizeof(fe256) : (size_t)q.elem_bytes);
+            stage_bytes += (bytes + 31) & ~(size_t)31;
+        }
+    }
+    DeviceCall call(c, OnExit::RELEASE_IF_IDLE);
+    REEF_TRY(call.enter());
+    c->defer_on = false;                    // T is replaced
+    c->valid_t = c->len;
+    c->r1_prev_pow = 0;
+    REEF_HIP_TRY(hipMemsetAsync(c->gacc.p, 0, 28 * sizeof(u64), c->stream));       // as v_sc_set
+    REEF_HIP_TRY(hipMemsetAsync(c->r1acc.p, 0, R1_GROUPS * R1_SLOTS * sizeof(u64), c->stream));
+    if (stage_bytes) REEF_TRY(c->stage.ensure(stage_bytes));
+    ScPartsArg a = {};
+    size_t start = 0;
+    for (size_t p = 0; p < SC_MAX_PARTS; ++p) {
+        a.start[p] = (u32)start;
+        if (p >= nparts || !parts[p].count) continue;
+        const reef_sc_part &q = parts[p];
+        a.kind_eb[p] = q.kind | (q.kind == REEF_SC_PART_SYMBOLS ? q.elem_bytes << 8 : 0u);
+        start += q.count;
+        if (q.kind != REEF_SC_PART_FILL && q.loc == REEF_DEVICE) { a.ptr[p] = (const unsigned char *)q.data; continue; }
+        unsigned char *dst = c->stage.template as<unsigned char>() + at[p];
+        a.ptr[p] = dst;
+        if (q.kind == REEF_SC_PART_FILL) {
+            fe256 *pair = c->parts_fill + 2 * p;                                    // lives in the ctx: the copy reads it after this loop
+            memcpy(&pair[0], q.data, sizeof(fe256));
+            pair[1] = fe_to_table<ScCtx<C>::F>(fe_from_caller<ScCtx<C>::F>(pair[0], false));
+            REEF_HIP_TRY(hipMemcpyAsync(dst, pair, 2 * sizeof(fe256), hipMemcpyHostToDevice, c->stream));
+        } else {
+            const size_t bytes = q.count * (q.kind == REEF_SC_PART_FE ? sizeof(fe256) : (size_t)q.elem_bytes);
+            REEF_HIP_TRY(hipMemcpyAsync(dst, q.data, bytes, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    a.start[SC_MAX_PARTS] = (u32)start;
+    u32 lo = 0, H = 0;
+    REEF_TRY(sc_struct_open<C>(c, &lo, &H));
+    // tiles per wave: 8 (16 entries per lane) where that still leaves 8192 waves -- by measurement at 2^26 entries, where the kernel
+    // alone takes a quarter less time with 4 tiles than with 1 (the sweep: profiles/r12_sc_set_parts_timing.txt)
+    const u32 tiles = (u32)ceil_div(c->len, 128), sub = std::max<u32>(1u, std::min<u32>(c->sw.set_sub, tiles / 8192u));
+    hipLaunchKernelGGL(k_sc_set_parts<ScCtx<C>::F>, dim3(ceil_div(ceil_div(tiles, sub), 4)), dim3(256), 0, c->stream, a, (u32)c->len, lo, sub,
+                       c->T0.template as<fe256>(), H ? c->st_flags.template as<u32>() : nullptr, H ? c->st_s32.template as<u32>() : nullptr);
+    REEF_HIP_TRY(hipGetLastError());
+    c->fresh = true;
+    if (H) REEF_TRY(sc_struct_lists<C>(c, H));
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));
     return REEF_OK;
 }

@@ -856,6 +856,159 @@ template <int F> __device__ __forceinline__ fe fe_reduce_small(const u64 (&w)[9]
     return r;
 }
 
+// ---- the table set from parts (reef_sc_set_table_parts) ---------------------------------------------------------------------
+// What the caller knows about the table, by value: up to SC_MAX_PARTS runs laid end to end from entry 0.  start[p] .. start[p + 1]
+// are the entries of part p (an empty part matches nothing; the starts past the last part repeat the total, beyond it T is zero).
+// ptr[p]: device memory -- canonical integers (FE), unsigned little-endian symbols of `elem_bytes` (SYMBOLS), or for a FILL TWO
+// fe256: the value as an integer and in the resident table form (the host converts the one value).
+static constexpr u32 SC_MAX_PARTS = 8;
+static constexpr u32 SC_PART_FE = 0, SC_PART_SYMBOLS = 1, SC_PART_FILL = 2, SC_PART_NONE = 3;
+struct ScPartsArg {
+    const unsigned char *ptr[SC_MAX_PARTS];
+    u32 start[SC_MAX_PARTS + 1];
+    u32 kind_eb[SC_MAX_PARTS];           // kind | elem_bytes << 8
+};
+struct ScPartRef { const unsigned char *ptr; u32 kind, eb, off, end; };
+// the part entry i lies in (constant indices only: the descriptors stay in scalar registers, nothing goes to scratch)
+static __device__ __forceinline__ ScPartRef sc_part_of(const ScPartsArg &a, u32 i) {
+    ScPartRef r = {nullptr, SC_PART_NONE, 0u, 0u, 0u};
+#pragma unroll
+    for (u32 p = 0; p < SC_MAX_PARTS; ++p)
+        if (i >= a.start[p] && i < a.start[p + 1]) {
+            r.ptr = a.ptr[p];
+            r.kind = a.kind_eb[p] & 0xffu;
+            r.eb = a.kind_eb[p] >> 8;
+            r.off = i - a.start[p];
+            r.end = a.start[p + 1];
+        }
+    return r;
+}
+// entry i of the table as the canonical integer the caller would have written out; never reads outside the part
+static __device__ __forceinline__ fe256 sc_part_value(const ScPartRef &r) {
+    fe256 v = {};
+    if (r.kind == SC_PART_FE) v = load_fe256(reinterpret_cast<const fe256 *>(r.ptr) + r.off);
+    else if (r.kind == SC_PART_FILL) v = load_fe256(reinterpret_cast<const fe256 *>(r.ptr));
+    else if (r.kind == SC_PART_SYMBOLS)
+        v.w[0] = r.eb == 1 ? (u32)r.ptr[r.off] : r.eb == 2 ? (u32)reinterpret_cast<const unsigned short *>(r.ptr)[r.off] : reinterpret_cast<const u32 *>(r.ptr)[r.off];
+    return v;
+}
+// the resident table form of v < 2^32: v * ONE (ONE = R' mod M, canonical limbs) is below 2^32 M < 2^286, fe_reduce_small's
+// range, and the canonical residue is unique -- the words fe_to_table(fe_from_caller(v, 0)) gives, for 9 multiplies
+template <int F> static __device__ __forceinline__ fe256 sc_table_form_u32(u32 v) {
+    u64 w[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) w[i] = (u64)v * FC<F>::ONE[i];
+    return fe_pack(fe_reduce_small<F>(w));
+}
+static __device__ __forceinline__ u32 sc_swap_pair(u32 v) {          // the value of lane ^ 1: quad_perm:[1,0,3,2]
+    return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xb1, 0xf, 0xf, false);
+}
+
+// T0 <- the parts (resident form), s32 <- their low words, flags cleared as k_sc_classify clears them: ONE pass over the len entries
+// in place of k_fe_import, the zero fill of the tail and k_sc_classify.  flags == nullptr: the table is too small for the row
+// structure, T0 alone is written.  The kernel stores 36 bytes per entry and reads 1 to 4 for a symbol, so the stores decide:
+// a wave takes `sub` consecutive tiles of 128 entries; in a tile lane 2k computes entries k and 64 + k, lane 2k + 1 entries 32 + k
+// and 96 + k, the two lanes of a pair swap halves (8 DPP moves per lane), and each of the four store instructions of the tile
+// writes 1 KiB without a gap: lane l the 16 bytes at l * 16.  Symbols of 1 or 2 bytes are read a dword per lane where the tile
+// lies in one part and its first symbol is 4-byte aligned (then handed to the lane that needs them through ds_bpermute), 4-byte
+// symbols a dword per entry; tiles that straddle parts, and unaligned ones, take the part lookup entry by entry.
+template <int F>
+static __global__ void __launch_bounds__(256) k_sc_set_parts(const ScPartsArg a, u32 len, u32 lo_bits, u32 sub, fe256 *__restrict__ T0, u32 *__restrict__ flags,
+                                                             u32 *__restrict__ s32) {
+    const u32 lane = threadIdx.x & 63u, k = lane >> 1, odd = lane & 1u;
+    const u32 wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    for (u32 s = 0; s < sub; ++s) {
+        const u64 t64 = ((u64)wave * sub + s) << 7;
+        if (t64 >= len) break;                              // the same for every lane of the wave
+        const u32 t0 = (u32)t64;
+        u32 e[2] = {t0 + k + 32u * odd, t0 + 64u + k + 32u * odd};
+        fe256 v[2] = {};
+        u32 kind[2];
+        const unsigned char *src[2];
+        const ScPartRef r0 = sc_part_of(a, t0);
+        const bool wide = r0.kind == SC_PART_SYMBOLS && r0.eb < 4u && (u64)t0 + 128u <= r0.end && t0 + 128u <= len &&
+                          ((reinterpret_cast<size_t>(r0.ptr) + (size_t)r0.off * r0.eb) & 3u) == 0;
+        if (wide) {                                          // 128 or 256 bytes of symbols, all inside the part: a dword per lane
+            const u32 *dw = reinterpret_cast<const u32 *>(r0.ptr + (size_t)r0.off * r0.eb);
+            const u32 d = lane < 32u * r0.eb ? dw[lane] : 0u;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const u32 byte = (e[j] - t0) * r0.eb;
+                const u32 got = (u32)__shfl((int)d, (int)(byte >> 2)) >> ((byte & 3u) * 8u);
+                v[j].w[0] = r0.eb == 1 ? got & 0xffu : got & 0xffffu;
+                kind[j] = SC_PART_SYMBOLS;
+                src[j] = nullptr;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                ScPartRef r = sc_part_of(a, e[j]);
+                if (e[j] >= len) r.kind = SC_PART_NONE;          // only a table shorter than a tile
+                v[j] = sc_part_value(r);
+                kind[j] = r.kind;
+                src[j] = r.ptr;
+            }
+        }
+        if (flags) {
+            u32 bad[2];
+            fe256 f = {};
+            u32 first_at = 0xffffffffu;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const u32 first = (e[j] >> lo_bits) << lo_bits;
+                if (first != first_at) {                      // a row may straddle parts: its first entry through the same lookup
+                    f = sc_part_value(sc_part_of(a, first));
+                    first_at = first;
+                }
+                bool small = v[j].w[0] < (1u << SC_SMALL_BITS), same = v[j].w[0] == f.w[0];
+#pragma unroll
+                for (int w = 1; w < 8; ++w) {
+                    small = small && v[j].w[w] == 0;
+                    same = same && v[j].w[w] == f.w[w];
+                }
+                bad[j] = (small ? 0u : 1u) | (same ? 0u : 2u);
+                if (e[j] < len) s32[e[j]] = v[j].w[0];
+            }
+            if (lo_bits >= 6) {                               // the 64 entries of slot j lie in one row: one atomic for them
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const u32 wbad = (__any(bad[j] & 1u) ? 1u : 0u) | (__any(bad[j] & 2u) ? 2u : 0u);
+                    if (wbad && lane == 0) atomicAnd(&flags[e[j] >> lo_bits], ~wbad);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    if (bad[j] && e[j] < len) atomicAnd(&flags[e[j] >> lo_bits], ~bad[j]);
+            }
+        }
+        fe256 out[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (kind[j] == SC_PART_FE) out[j] = fe_to_table<F>(fe_from_caller<F>(v[j], 0));
+            else if (kind[j] == SC_PART_FILL) out[j] = load_fe256(reinterpret_cast<const fe256 *>(src[j]) + 1);
+            else out[j] = sc_table_form_u32<F>(v[j].w[0]);      // a symbol, or zero past the parts
+        }
+        // every lane is here again: the even lane keeps the low halves of its two entries and takes the low halves of its
+        // neighbour's, the odd lane the high halves
+        u32x4 *q = reinterpret_cast<u32x4 *>(T0 + t0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            u32 fst[4], snd[4];                             // what this lane writes of entries k and 32 + k of the slot
+            const u32 pick = 0u - odd;                      // bit selects, not `odd ? .. : ..`: the compiler turns that into an indexed
+#pragma unroll                                              // read from scratch
+            for (int w = 0; w < 4; ++w) {
+                const u32 l = out[j].w[w], h = out[j].w[4 + w];
+                const u32 mine = (h & pick) | (l & ~pick), theirs = sc_swap_pair((l & pick) | (h & ~pick));
+                fst[w] = (theirs & pick) | (mine & ~pick);
+                snd[w] = (mine & pick) | (theirs & ~pick);
+            }
+            const u32 ea = t0 + 64u * j + k, eb = ea + 32u;   // the entries the two stores write a half of
+            if (ea < len) q[128u * j + lane] = mk_u32x4(fst[0], fst[1], fst[2], fst[3]);
+            if (eb < len) q[128u * j + 64u + lane] = mk_u32x4(snd[0], snd[1], snd[2], snd[3]);
+        }
+    }
+}
+
 // Round-one sums of the rows of ONE side and ONE class (WIDE: W rows, 32-byte entries; else S rows, 4-byte entries): with
 // t = T0[h + row_off, u],  A[u] = sum fa[h] t,  B[u] = sum fd[h] t  over the listed h (fa = f0 on side 0, f1 on side 1; row_off = side * hn).
 // Side 0 leaves (sum FL A, sum FL B) as (con, what is taken from xsq), side 1 as (sum t1 e1, what adds to xsq).

@@ -21,6 +21,52 @@ ints_to_array = _arr        # the public names of _fe's pair: Python ints <-> (n
 array_to_ints = _ints
 
 
+_SYMBOL_BYTES = {np.dtype(np.uint8): 1, np.dtype(np.uint16): 2, np.dtype(np.uint32): 4}
+
+
+def _symbol_bytes(dtype) -> int:
+    """1, 2 or 4 for the unsigned symbol types; anything signed or wider is refused -- its values are never wrapped silently."""
+    try:
+        return _SYMBOL_BYTES[np.dtype(dtype)]
+    except (KeyError, TypeError):
+        raise ValueError(f"document symbols are uint8, uint16 or uint32, not {dtype!r}") from None
+
+
+def sc_part_descriptors(parts):
+    """The parts of SumCheck.set_table_parts as reef_sc_part structures, and the host arrays their pointers point into (keep them
+    until the call has returned).  No device is touched."""
+    descs, keep = [], []
+    for part in parts:
+        kind = part[0]
+        if kind == "fe" and len(part) == 2:
+            arr = part[1] if isinstance(part[1], np.ndarray) else ints_to_array(part[1])
+            arr = np.ascontiguousarray(arr, dtype=np.uint64).reshape(-1, 4)
+            keep.append(arr)
+            descs.append(_ffi.ScPart(_ffi.SC_PART_FE, 0, arr.ctypes.data if arr.shape[0] else None, arr.shape[0], REEF_HOST))
+        elif kind == "symbols" and len(part) == 2:
+            if not isinstance(part[1], np.ndarray):
+                raise ValueError("host symbols are a numpy array of uint8, uint16 or uint32")
+            eb = _symbol_bytes(part[1].dtype)
+            arr = np.ascontiguousarray(part[1]).reshape(-1)
+            keep.append(arr)
+            descs.append(_ffi.ScPart(_ffi.SC_PART_SYMBOLS, eb, arr.ctypes.data if arr.size else None, arr.size, REEF_HOST))
+        elif kind == "symbols" and len(part) == 4:
+            buf, dtype, count = part[1:]
+            eb = _symbol_bytes(dtype)
+            ptr = buf.ptr if hasattr(buf, "ptr") else int(buf)
+            if hasattr(buf, "nbytes") and int(count) * eb > buf.nbytes:
+                raise ValueError("device buffer too small")
+            keep.append(buf)
+            descs.append(_ffi.ScPart(_ffi.SC_PART_SYMBOLS, eb, ptr, int(count), REEF_DEVICE))
+        elif kind == "fill" and len(part) == 3:
+            arr = ints_to_array([part[1]])
+            keep.append(arr)
+            descs.append(_ffi.ScPart(_ffi.SC_PART_FILL, 0, arr.ctypes.data, int(part[2]), REEF_HOST))
+        else:
+            raise ValueError(f"not a part of a sum-check table: {part[0]!r} with {len(part) - 1} values")
+    return descs, keep
+
+
 class SumCheck(_Handle):
     """Resident (T, EQ) tables of 2^ell entries over the scalar field of `curve`."""
     _destroy = "reef_sc_destroy"
@@ -43,6 +89,17 @@ class SumCheck(_Handle):
     def set_table_device(self, which: int, ptr: int, n: int) -> None:
         self._pending = None
         check(self._lib.reef_sc_set_table(self._h, which, ptr, n, REEF_DEVICE))
+
+    def set_table_parts(self, parts) -> None:
+        """T <- the parts laid end to end from entry 0, zero beyond them (reef_sc_set_table_parts).  A part is one of
+        ("fe", ints | (n, 4) uint64 array), ("symbols", uint8 / uint16 / uint32 ndarray), ("symbols", DeviceBuffer, dtype, count)
+        and ("fill", value, count).  Reef's "nldoc" table is [("symbols", doc)], its "nlhybrid" table
+        [("fe", table), ("fill", calc_fill, half - len(table)), ("symbols", proj_doc)]."""
+        descs, keep = sc_part_descriptors(parts)
+        arr = (_ffi.ScPart * max(1, len(descs)))(*descs)
+        self._pending = None
+        check(self._lib.reef_sc_set_table_parts(self._h, arr, len(descs)))
+        del keep
 
     def gen_eq_table(self, rs: Sequence[int], qs: Sequence[int], last_q: Sequence[int]) -> None:
         """gen_eq_table(rs, qs, last_q) (r1cs_helper.rs:508-544) into the EQ table."""
