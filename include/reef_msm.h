@@ -413,6 +413,43 @@ reef_status reef_merkle_commit(int curve, const reef_poseidon_params *params, co
 reef_status reef_merkle_commit_devices(int curve, const reef_poseidon_params *params, const uint32_t *doc, size_t n, bool is_mont,
                                        const int *devices, size_t ndev, reef_fe *tree_out, reef_fe *root_out, uint32_t *blocks_out);
 
+/* (3d, continued) The same tree KEPT on one device, and the openings Reef takes from it.
+ *
+ * The only reader of MerkleCommitment.tree is make_wits(&merkle_lookups) (src/backend/merkle_tree.rs:116-190), once per folding step: a few
+ * openings of `levels` siblings each.  A prover that holds the document rebuilds the tree on the device instead of loading it from the
+ * .cmt file and never has it on the host.  reef_merkle_create builds it with reef_merkle_commit's kernels and keeps, on `device`, for the
+ * life of the ctx: the document (32 bits a symbol), every level in the library's table form, the Poseidon constants and tags.  No copy
+ * of the tree in the caller's form is made: 2^27 symbols hold 0.5 GiB + 4 GiB.  Argument errors are reef_merkle_commit's, and an unknown
+ * device.  is_mont is remembered: it is the form of every field element the ctx hands out or takes in.
+ * reef_merkle_info: the document length, L = the number of levels, reef_merkle_nodes(n), the root; each may be NULL.
+ * reef_merkle_open: make_wits as arrays.  idx, symbols, opposite_idx: HOST, k entries; opposite, path: HOST, k * L entries.
+ *   symbols[j]          = doc[idx[j]]
+ *   opposite_idx[j]     = the document index of the leaf's sibling symbol; 0 when idx[j] is even and idx[j] + 1 >= n (:134-139)
+ *   opposite[j*L]       = that symbol as a field element; 0 when missing
+ *   opposite[j*L+1+h]   = tree[h][quo ^ 1], quo = idx[j] >> (h + 1), h = 0 .. L-2; 0 when quo is even and quo + 1 >= len(tree[h])
+ *   path[j*L+h]         = tree[h][idx[j] >> (h + 1)], h = 0 .. L-1: the digests on the way up, the root last -- what the step circuit's
+ *                         Merkle gadget recomputes as witness values (src/backend/nova.rs:392-511)
+ *   l_or_r at depth h is "bit h of idx[j] is clear" and is not returned.  symbols, opposite_idx and path may be NULL; k = 0 is REEF_OK.
+ *   An idx[j] >= n is REEF_ERR_ARG naming the first such j, and nothing is written.  One gather kernel, one copy back, one wait.
+ * reef_merkle_read_level: nodes [first, first + count) of level `level`, to the host or the device (out_loc), in the caller's form; a
+ *   range past the level's end is REEF_ERR_ARG.
+ * reef_merkle_check_paths: the root recomputed from CLAIMED openings (opposite: k * L entries in reef_merkle_open's layout; all HOST),
+ *   without a look at the stored tree but for its root: the loop of the reference's make_mt test (:220-256).  Depth 0 hashes
+ *   H4(idx, sym, opp_idx, opp), or H4(opp_idx, opp, idx, sym) when bit 0 of idx is set; depth h >= 1 hashes H2(hash, opp), or H2(opp, hash)
+ *   when bit h is set.  accept[j] = 1 when the result is the ctx's root, else 0: a failing path is REEF_OK.  REEF_ERR_ARG only for an index
+ *   out of range or an opposite[] not below the modulus.  k paths up to 12 a wave cost one chain of L hashes whatever k is.
+ * A ctx serialises its calls; different ctxs run concurrently. */
+typedef struct reef_merkle_ctx reef_merkle_ctx;
+reef_status reef_merkle_create(reef_merkle_ctx **out, int curve, const reef_poseidon_params *params, const uint32_t *doc, size_t n,
+                               int doc_loc, bool is_mont, int device);
+void        reef_merkle_destroy(reef_merkle_ctx *ctx);
+reef_status reef_merkle_info(reef_merkle_ctx *ctx, uint64_t *n, uint32_t *levels, uint64_t *nodes, reef_fe *root);
+reef_status reef_merkle_open(reef_merkle_ctx *ctx, const uint64_t *idx, size_t k, uint32_t *symbols, uint64_t *opposite_idx,
+                             reef_fe *opposite, reef_fe *path);
+reef_status reef_merkle_read_level(reef_merkle_ctx *ctx, uint32_t level, uint64_t first, uint64_t count, reef_fe *out, int out_loc);
+reef_status reef_merkle_check_paths(reef_merkle_ctx *ctx, const uint64_t *idx, const uint32_t *symbols, const uint64_t *opposite_idx,
+                                    const reef_fe *opposite, size_t k, uint32_t *accept);
+
 /* ---------------------------------------------------------------------------------------------
  * (3e) Row N1: derivation of a commitment key from a label.
  *

@@ -202,6 +202,12 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_merkle_nodes": (c_uint64, [c_uint64]),
         "reef_merkle_commit": (c_int, [c_int, vp, vp, c_size_t, c_int, c_bool, vp, c_int, vp]),
         "reef_merkle_commit_devices": (c_int, [c_int, vp, vp, c_size_t, c_bool, vp, c_size_t, vp, vp, vp]),
+        "reef_merkle_create": (c_int, [POINTER(vp), c_int, vp, vp, c_size_t, c_int, c_bool, c_int]),
+        "reef_merkle_destroy": (None, [vp]),
+        "reef_merkle_info": (c_int, [vp, POINTER(c_uint64), POINTER(c_uint32), POINTER(c_uint64), vp]),
+        "reef_merkle_open": (c_int, [vp, vp, c_size_t, vp, vp, vp, vp]),
+        "reef_merkle_read_level": (c_int, [vp, c_uint32, c_uint64, c_uint64, vp, c_int]),
+        "reef_merkle_check_paths": (c_int, [vp, vp, vp, vp, vp, c_size_t, vp]),
         "reef_derive_generators": (c_int, [c_int, vp, c_size_t, c_size_t, vp, c_bool, vp, c_int]),
         "reef_shake256": (None, [vp, c_size_t, vp, c_size_t]),
         "reef_test_field_op": (c_int, [c_int, c_int, vp, vp, vp, c_size_t]),

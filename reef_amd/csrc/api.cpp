@@ -169,6 +169,7 @@ struct reef_msm_ctx : reef_handle {};
 struct reef_sc_ctx : reef_handle {};
 struct reef_nifs_ctx : reef_handle {};     // rows N6 and N5 and the opening (3f-3h) share it
 struct reef_hyrax_ctx : reef_handle {};
+struct reef_merkle_ctx : reef_handle {};
 
 // The table of a curve's entry points, one per row (common.h); NULL with the error set for a curve that does not exist.
 template <class VT> static const VT *table(int curve) {
@@ -179,6 +180,7 @@ template <class VT> static const VT *table(int curve) {
     else if constexpr (std::is_same<VT, SpartanVTable>::value) return p ? pallas_spartan_vtable() : vesta_spartan_vtable();
     else if constexpr (std::is_same<VT, OpenVTable>::value) return p ? pallas_open_vtable() : vesta_open_vtable();
     else if constexpr (std::is_same<VT, IpaCheckVTable>::value) return p ? pallas_ipa_check_vtable() : vesta_ipa_check_vtable();
+    else if constexpr (std::is_same<VT, MerkleVTable>::value) return p ? pallas_merkle_vtable() : vesta_merkle_vtable();
     else return p ? pallas_hyrax_vtable() : vesta_hyrax_vtable();
 }
 
@@ -690,6 +692,26 @@ reef_status reef_merkle_commit_devices(int curve, const reef_poseidon_params *pa
         if (root_out) *root_out = root;
         return REEF_OK;
     });
+}
+
+// The tree kept on one device (include/reef_msm.h 3d, continued): the document, the levels and the constants stay; openings come from them
+reef_status reef_merkle_create(reef_merkle_ctx **out, int curve, const reef_poseidon_params *params, const uint32_t *doc, size_t n, int doc_loc, bool is_mont,
+                               int device) {
+    return create_handle(out, curve, [&](const CurveVTable *, void **impl) { return table<MerkleVTable>(curve)->create(impl, params, doc, n, doc_loc, is_mont, device); });
+}
+void reef_merkle_destroy(reef_merkle_ctx *ctx) { destroy_handle(ctx, &MerkleVTable::destroy); }
+reef_status reef_merkle_info(reef_merkle_ctx *ctx, uint64_t *n, uint32_t *levels, uint64_t *nodes, reef_fe *root) {
+    return dispatch<MerkleVTable>(ctx, [&](auto *v, void *impl) { return v->info(impl, n, levels, nodes, root); });
+}
+reef_status reef_merkle_open(reef_merkle_ctx *ctx, const uint64_t *idx, size_t k, uint32_t *symbols, uint64_t *opposite_idx, reef_fe *opposite, reef_fe *path) {
+    return dispatch<MerkleVTable>(ctx, [&](auto *v, void *impl) { return v->open(impl, idx, k, symbols, opposite_idx, opposite, path); });
+}
+reef_status reef_merkle_read_level(reef_merkle_ctx *ctx, uint32_t level, uint64_t first, uint64_t count, reef_fe *out, int out_loc) {
+    return dispatch<MerkleVTable>(ctx, [&](auto *v, void *impl) { return v->read_level(impl, level, first, count, out, out_loc); });
+}
+reef_status reef_merkle_check_paths(reef_merkle_ctx *ctx, const uint64_t *idx, const uint32_t *symbols, const uint64_t *opposite_idx, const reef_fe *opposite,
+                                    size_t k, uint32_t *accept) {
+    return dispatch<MerkleVTable>(ctx, [&](auto *v, void *impl) { return v->check_paths(impl, idx, symbols, opposite_idx, opposite, k, accept); });
 }
 
 reef_status reef_derive_generators(int curve, const uint8_t *label, size_t label_len, size_t n, const reef_keygen_params *params, bool is_mont,

@@ -94,6 +94,15 @@ struct DevBuf {
         cap = want;
         return REEF_OK;
     }
+    // the same without head-room, for what lives as long as its owner and never grows (a resident tree of gigabytes)
+    reef_status ensure_exact(size_t bytes) {
+        if (bytes <= cap) return REEF_OK;
+        ++g_devbuf_gen;
+        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        REEF_HIP_TRY(hipMalloc(&p, bytes));
+        cap = bytes;
+        return REEF_OK;
+    }
     void release() {
         if (p) { (void)hipFree(p); ++g_devbuf_gen; }
         p = nullptr;
@@ -553,5 +562,18 @@ struct IpaCheckVTable {
 };
 const IpaCheckVTable *pallas_ipa_check_vtable();
 const IpaCheckVTable *vesta_ipa_check_vtable();
+
+// Row N4 with the tree kept on the device (merkle_resident_engine.inc; include/reef_msm.h 3d): openings from it, claimed openings back to its root.
+struct MerkleVTable {
+    reef_status (*create)(void **impl, const reef_poseidon_params *pp, const uint32_t *doc, size_t n, int doc_loc, bool is_mont, int device);
+    void (*destroy)(void *impl);
+    reef_status (*info)(void *impl, uint64_t *n, uint32_t *levels, uint64_t *nodes, reef_fe *root);
+    reef_status (*open)(void *impl, const uint64_t *idx, size_t k, uint32_t *symbols, uint64_t *opposite_idx, reef_fe *opposite, reef_fe *path);
+    reef_status (*read_level)(void *impl, uint32_t level, uint64_t first, uint64_t count, reef_fe *out, int out_loc);
+    reef_status (*check_paths)(void *impl, const uint64_t *idx, const uint32_t *symbols, const uint64_t *opposite_idx, const reef_fe *opposite, size_t k,
+                               uint32_t *accept);
+};
+const MerkleVTable *pallas_merkle_vtable();
+const MerkleVTable *vesta_merkle_vtable();
 
 }  // namespace reef

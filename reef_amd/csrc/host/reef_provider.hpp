@@ -15,6 +15,7 @@
 //   decompress()                                  CompressedCommitment::decompress [R]   src/backend/commitment.rs:192-197 (a batch per call)
 //   CommitmentGens<CURVE>(label, n, params [, h]) CommitmentGens::new(label, n) / new_with_blinding_gen      src/backend/framework.rs:297-303, commitment.rs:146-149,176-180
 //   MerkleCommitment<CURVE>(doc, pc)              MerkleCommitment::new(&doc, &pc), path_wits, make_wits     src/backend/merkle_tree.rs:25-190
+//   MerkleCommitmentResident<CURVE>(doc, pc)      the same with the tree kept on the device: make_wits from it, check_paths  src/backend/merkle_tree.rs:116-256
 //   Nifs<CURVE>                                   NIFS::prove's vector work (row N6)     RecursiveSNARK::prove_step, framework.rs:668-675
 //   RelaxedR1CSSnark<CURVE>                       RelaxedR1CSSNARK::prove: sum-checks + EE::prove_batch      CompressedSNARK::prove, framework.rs:695-698
 //   HyraxEval<CURVE>                              HyraxPC::prove_eval on a resident document                 src/backend/commitment.rs:287-405
@@ -404,6 +405,69 @@ template <int CURVE> class MerkleCommitment {
     reef_fe commitment = {};
     std::vector<std::vector<reef_fe>> tree;
     std::vector<uint32_t> doc;
+};
+// The same commitment with the tree KEPT ON THE DEVICE (reef_merkle_create): no `tree` member, no copy of it on the host; make_wits is
+// one reef_merkle_open, check_paths hashes claimed openings back to the root on the device.  Field elements cross as canonical integers.
+template <int CURVE> class MerkleCommitmentResident {
+  public:
+    MerkleCommitmentResident(const std::vector<uint32_t> &document, const reef_poseidon_params &pc, int device = 0) {
+        if (document.empty()) throw std::invalid_argument("MerkleCommitment::new: empty document");
+        check(reef_merkle_create(&ctx_, CURVE, &pc, document.data(), document.size(), REEF_HOST, false, device), "reef_merkle_create");
+        uint64_t n = 0;
+        uint32_t lv = 0;
+        const reef_status s = reef_merkle_info(ctx_, &n, &lv, nullptr, &commitment);
+        if (s != REEF_OK) { reef_merkle_destroy(ctx_); check(s, "reef_merkle_info"); }
+        len = (size_t)n;
+        levels = lv;
+    }
+    ~MerkleCommitmentResident() { reef_merkle_destroy(ctx_); }
+    MerkleCommitmentResident(const MerkleCommitmentResident &) = delete;
+    MerkleCommitmentResident &operator=(const MerkleCommitmentResident &) = delete;
+    // merkle_tree.rs:116-126; `path` (may be NULL): the digests on the way up, lookups x levels, the root last
+    std::vector<std::vector<MerkleWit>> make_wits(const std::vector<size_t> &m_lookups, std::vector<reef_fe> *path = nullptr) const {
+        for (size_t q : m_lookups)
+            if (q >= len) throw std::out_of_range("path_wits: idx < doc.len()");
+        const size_t k = m_lookups.size();
+        std::vector<uint64_t> idx(m_lookups.begin(), m_lookups.end()), oidx(k);
+        std::vector<reef_fe> opp(k * levels);
+        if (path) path->assign(k * levels, reef_fe{});
+        check(reef_merkle_open(ctx_, idx.data(), k, nullptr, oidx.data(), opp.data(), path ? path->data() : nullptr), "reef_merkle_open");
+        std::vector<std::vector<MerkleWit>> wits(k);
+        for (size_t j = 0; j < k; ++j)
+            for (uint32_t h = 0; h < levels; ++h) wits[j].push_back({((idx[j] >> h) & 1) == 0, h == 0, h == 0 ? oidx[j] : 0, opp[j * levels + h]});
+        return wits;
+    }
+    std::vector<MerkleWit> path_wits(size_t idx) const { return make_wits({idx})[0]; }
+    // accept flags of claimed openings of m_lookups with the claimed symbols (reef_merkle_check_paths)
+    std::vector<uint32_t> check_paths(const std::vector<size_t> &m_lookups, const std::vector<uint32_t> &symbols, const std::vector<std::vector<MerkleWit>> &wits) const {
+        const size_t k = m_lookups.size();
+        if (symbols.size() != k || wits.size() != k) throw std::invalid_argument("check_paths: one symbol and one opening per lookup");
+        std::vector<uint64_t> idx(m_lookups.begin(), m_lookups.end()), oidx(k);
+        std::vector<reef_fe> opp(k * levels);
+        for (size_t j = 0; j < k; ++j) {
+            if (wits[j].size() != levels) throw std::invalid_argument("check_paths: an opening has one wit per level");
+            oidx[j] = wits[j][0].opposite_idx;
+            for (uint32_t h = 0; h < levels; ++h) opp[j * levels + h] = wits[j][h].opposite;
+        }
+        std::vector<uint32_t> accept(k);
+        check(reef_merkle_check_paths(ctx_, idx.data(), symbols.data(), oidx.data(), opp.data(), k, accept.data()), "reef_merkle_check_paths");
+        return accept;
+    }
+    std::vector<uint32_t> symbols(const std::vector<size_t> &m_lookups) const {
+        const size_t k = m_lookups.size();
+        std::vector<uint64_t> idx(m_lookups.begin(), m_lookups.end());
+        std::vector<uint32_t> sym(k);
+        std::vector<reef_fe> opp(k * levels);
+        check(reef_merkle_open(ctx_, idx.data(), k, sym.data(), nullptr, opp.data(), nullptr), "reef_merkle_open");
+        return sym;
+    }
+
+    reef_fe commitment = {};
+    size_t len = 0;
+    uint32_t levels = 0;
+
+  private:
+    reef_merkle_ctx *ctx_ = nullptr;
 };
 
 // nova's transcript as the rows below see it [R]: absorb `len` bytes under `label`, squeeze the next challenge (below the

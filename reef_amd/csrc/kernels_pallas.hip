@@ -21,6 +21,7 @@
 #include "spartan_engine.inc"
 #include "open_engine.inc"
 #include "hyrax_engine.inc"
+#include "merkle_resident_engine.inc"
 namespace reef {
 const CurveVTable *pallas_vtable() {
     static const CurveVTable vt = make_vtable<0>();
@@ -44,6 +45,10 @@ const HyraxVTable *pallas_hyrax_vtable() {
 }
 const IpaCheckVTable *pallas_ipa_check_vtable() {
     static const IpaCheckVTable vt = make_ipa_check_vtable<0>();
+    return &vt;
+}
+const MerkleVTable *pallas_merkle_vtable() {
+    static const MerkleVTable vt = make_merkle_vtable<0>();
     return &vt;
 }
 }

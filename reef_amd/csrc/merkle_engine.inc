@@ -119,19 +119,29 @@ template <int F> static void pos_derive_sparse(const reef_poseidon_params *pp, b
     }
 }
 
-template <int C>
-static reef_status v_merkle_commit(const reef_poseidon_params *pp, const uint32_t *doc, size_t n, int doc_loc, bool is_mont, reef_fe *tree_out,
-                                   int out_loc, reef_fe *root_out, const MerkleSlice *sl) {
-    constexpr int F = 1 - C;
-    const bool from_nodes = sl && sl->nodes_in;
-    if (from_nodes) n = 2 * sl->nodes_n;               // as many bottom nodes as a document of this length has
-    if (!pp || !pp->round_constants || !pp->mds || (n && !doc && !from_nodes) || (!tree_out && !root_out && !sl)) { set_error("null argument"); return REEF_ERR_ARG; }
-    if (sl && (sl->index_base & 1)) { set_error("a block of the tree starts at an even symbol"); return REEF_ERR_ARG; }
+// ---- what reef_merkle_commit and the resident tree (merkle_resident_engine.inc) share: the argument checks, the constants on the
+// device, the kernels of the levels ----
+static reef_status merkle_check_params(const reef_poseidon_params *pp) {
     if (pp->width != POS_T) { set_error("Poseidon width %u: only width 5 (arity 4, Reef's U4) is built", pp->width); return REEF_ERR_ARG; }
     if (pp->full_rounds == 0 || (pp->full_rounds & 1) || pp->full_rounds > 64 || pp->partial_rounds > 1024) { set_error("bad round numbers"); return REEF_ERR_ARG; }
-    if (n == 0 || n >= (1ull << 33)) { set_error("document length out of range"); return REEF_ERR_ARG; }
-    ScratchStream ss;
-    REEF_TRY(ss.init());
+    return REEF_OK;
+}
+static std::vector<u64> merkle_level_sizes(u64 n) {   // node counts of the levels of an n-symbol document, level 0 first
+    std::vector<u64> sizes;
+    u64 m = (n + 1) / 2;
+    sizes.push_back(m);
+    while (m > 1) { m = (m + 1) / 2; sizes.push_back(m); }
+    return sizes;
+}
+template <int F> struct PosSetup {
+    PoseidonDev pd{};
+    fe256 tags[2];          // leaf, node: internal form, handed to the kernels by value
+    bool sparse = false;
+};
+// The permutation's constants on the device, in table form; alloc(which, void **, bytes) gives the two device buffers: 0 the constants, 1 a
+// staging one of at least two elements that the caller may reuse once this has returned.  Waits for `s`.
+template <int F, class Alloc>
+static reef_status pos_setup(hipStream_t s, const reef_poseidon_params *pp, bool is_mont, Alloc &&alloc, PosSetup<F> &out) {
     const u32 rf = pp->full_rounds, rp = pp->partial_rounds;
     const u32 nrc = POS_T * (rf + rp), nmat = POS_T * POS_T;
     // Sparse partial rounds: constants derived once per parameter set on the host (a few ms), then looked up by the caller's
@@ -154,21 +164,21 @@ static reef_status v_merkle_commit(const reef_poseidon_params *pp, const uint32_
         if (sp_entry.ok) sparse_consts = sp_entry.consts;
     }
     const bool sparse = !sparse_consts.empty();
-    void *raw = nullptr, *cst = nullptr, *tree = nullptr;
+    void *raw = nullptr, *cst = nullptr;
     PoseidonDev pd{};
     pd.rf = rf; pd.rp = rp;
     const fe256 *d_tags = nullptr;
     if (sparse) {                                   // table form already: rc_full | mds | sparse | last, then the two tags through the import kernel
         const size_t nsp = sparse_consts.size();
-        REEF_TRY(ss.alloc(&cst, (nsp + 2) * sizeof(fe256)));
-        REEF_TRY(ss.alloc(&raw, 2 * sizeof(fe256)));
+        REEF_TRY(alloc(0, &cst, (nsp + 2) * sizeof(fe256)));
+        REEF_TRY(alloc(1, &raw, 2 * sizeof(fe256)));
         fe256 tg[2];
         memcpy(&tg[0], &pp->tag_leaf, sizeof(fe256));
         memcpy(&tg[1], &pp->tag_node, sizeof(fe256));
-        REEF_HIP_TRY(hipMemcpyAsync(cst, sparse_consts.data(), nsp * sizeof(fe256), hipMemcpyHostToDevice, ss.s));
-        REEF_HIP_TRY(hipMemcpyAsync(raw, tg, sizeof tg, hipMemcpyHostToDevice, ss.s));
-        hipLaunchKernelGGL(k_fe_import<F>, dim3(1), dim3(256), 0, ss.s, (const fe256 *)raw, 2u, (int)is_mont, (fe256 *)cst + nsp);
-        REEF_HIP_TRY(hipStreamSynchronize(ss.s));   // sparse_consts and tg leave scope below; the kernels read device copies
+        REEF_HIP_TRY(hipMemcpyAsync(cst, sparse_consts.data(), nsp * sizeof(fe256), hipMemcpyHostToDevice, s));
+        REEF_HIP_TRY(hipMemcpyAsync(raw, tg, sizeof tg, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_fe_import<F>, dim3(1), dim3(256), 0, s, (const fe256 *)raw, 2u, (int)is_mont, (fe256 *)cst + nsp);
+        REEF_HIP_TRY(hipStreamSynchronize(s));      // sparse_consts and tg leave scope below; the kernels read device copies
         pd.rc = (const fe256 *)cst;
         pd.mds = pd.rc + (size_t)rf * POS_T;
         const fe256 *sp = pd.mds + nmat;
@@ -182,58 +192,87 @@ static reef_status v_merkle_commit(const reef_poseidon_params *pp, const uint32_
         memcpy(hc.data() + nrc, pp->mds, nmat * sizeof(fe256));
         memcpy(hc.data() + nrc + nmat, &pp->tag_leaf, sizeof(fe256));
         memcpy(hc.data() + nrc + nmat + 1, &pp->tag_node, sizeof(fe256));
-        REEF_TRY(ss.alloc(&raw, nconst * sizeof(fe256)));
-        REEF_TRY(ss.alloc(&cst, nconst * sizeof(fe256)));
-        REEF_HIP_TRY(hipMemcpyAsync(raw, hc.data(), nconst * sizeof(fe256), hipMemcpyHostToDevice, ss.s));
-        hipLaunchKernelGGL(k_fe_import<F>, dim3(ceil_div(nconst, 256)), dim3(256), 0, ss.s, (const fe256 *)raw, nconst, (int)is_mont, (fe256 *)cst);
-        REEF_HIP_TRY(hipStreamSynchronize(ss.s));   // hc leaves scope
+        REEF_TRY(alloc(1, &raw, nconst * sizeof(fe256)));
+        REEF_TRY(alloc(0, &cst, nconst * sizeof(fe256)));
+        REEF_HIP_TRY(hipMemcpyAsync(raw, hc.data(), nconst * sizeof(fe256), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_fe_import<F>, dim3(ceil_div(nconst, 256)), dim3(256), 0, s, (const fe256 *)raw, nconst, (int)is_mont, (fe256 *)cst);
+        REEF_HIP_TRY(hipStreamSynchronize(s));      // hc leaves scope
         pd.rc = (const fe256 *)cst;
         pd.mds = pd.rc + nrc;
         d_tags = pd.mds + nmat;
     }
-    // node counts: the whole tree stops at one node; a block runs the levels it was told to (a ragged last block carries its single node on)
-    std::vector<u64> sizes;
-    {
-        u64 m_ = (n + 1) / 2;
-        sizes.push_back(m_);
-        if (sl) for (u32 h = 0; h < sl->levels; ++h) { m_ = (m_ + 1) / 2; sizes.push_back(m_); }
-        else while (m_ > 1) { m_ = (m_ + 1) / 2; sizes.push_back(m_); }
-    }
-    u64 total = 0;
-    for (u64 v : sizes) total += v;
-    const u32 *d_doc = nullptr;
-    if (!from_nodes) REEF_TRY(stage_in<u32>(ss, &d_doc, doc, n, doc_loc));
-    REEF_TRY(ss.alloc(&tree, total * sizeof(fe256)));
-    fe256 tags[2];
-    REEF_HIP_TRY(hipMemcpyAsync(tags, d_tags, 2 * sizeof(fe256), hipMemcpyDeviceToHost, ss.s));
-    REEF_HIP_TRY(hipStreamSynchronize(ss.s));                          // the tags go to the kernels by value (internal form)
-    fe256 *lvl = (fe256 *)tree;
-    u64 m = sizes[0];
-    const u64 index_base = sl ? sl->index_base : 0;
-    // levels that do not fill the chip are latency chains of one hash: five lanes per hash there (merkle_kernels.inc);
-    // REEF_POSEIDON_SPREAD=0 keeps a thread per node everywhere
+    REEF_HIP_TRY(hipMemcpyAsync(out.tags, d_tags, 2 * sizeof(fe256), hipMemcpyDeviceToHost, s));
+    REEF_HIP_TRY(hipStreamSynchronize(s));                              // the tags go to the kernels by value (internal form)
+    out.pd = pd;
+    out.sparse = sparse;
+    return REEF_OK;
+}
+// levels that do not fill the chip are latency chains of one hash: five lanes per hash there (merkle_kernels.inc);
+// REEF_POSEIDON_SPREAD=0 keeps a thread per node everywhere
+template <int F> static bool pos_spread_form(const PosSetup<F> &ps, u64 nodes) {
     static const bool spread_on = !(exp_env("REEF_POSEIDON_SPREAD") && atoi(exp_env("REEF_POSEIDON_SPREAD")) == 0);
-    const bool spread = spread_on && sparse;
     static const u64 spread_max = [] { const char *e = exp_env("REEF_POSEIDON_SPREAD_MAX"); return e ? (u64)strtoull(e, nullptr, 10) : (u64)POS_SPREAD_MAX_NODES; }();
-    if (from_nodes) {
-        void *nraw = nullptr;
-        REEF_TRY(ss.alloc(&nraw, m * sizeof(fe256)));
-        REEF_HIP_TRY(hipMemcpyAsync(nraw, sl->nodes_in, m * sizeof(fe256), hipMemcpyHostToDevice, ss.s));
-        hipLaunchKernelGGL(k_fe_import<F>, dim3((u32)ceil_div(m, 256)), dim3(256), 0, ss.s, (const fe256 *)nraw, (u32)m, (int)is_mont, lvl);
-    } else if (spread && m <= spread_max)
-        hipLaunchKernelGGL((k_pos_spread<F, true>), dim3((u32)ceil_div(m, POS_SPREAD_PER_WAVE)), dim3(64), 0, ss.s, d_doc, (const fe256 *)nullptr, (u64)n, index_base, pd, tags[0], lvl);
+    return spread_on && ps.sparse && nodes <= spread_max;
+}
+// Enqueues the levels sizes[0..] into `tree`, level 0 first, from the n symbols of d_doc (a slice that starts at symbol index_base) -- or,
+// d_doc == nullptr, from a level 0 that is in place already.
+template <int F>
+static void merkle_hash_levels(hipStream_t s, const u32 *d_doc, u64 n, u64 index_base, const std::vector<u64> &sizes, const PosSetup<F> &ps, fe256 *tree) {
+    fe256 *lvl = tree;
+    u64 m = sizes[0];
+    const PoseidonDev &pd = ps.pd;
+    if (!d_doc) {}
+    else if (pos_spread_form<F>(ps, m))
+        hipLaunchKernelGGL((k_pos_spread<F, true>), dim3((u32)ceil_div(m, POS_SPREAD_PER_WAVE)), dim3(64), 0, s, d_doc, (const fe256 *)nullptr, (u64)n, index_base, pd, ps.tags[0], lvl);
     else
-        hipLaunchKernelGGL(k_pos_leaves<F>, dim3((u32)ceil_div(m, 256)), dim3(256), 0, ss.s, d_doc, (u64)n, index_base, pd, tags[0], lvl);
+        hipLaunchKernelGGL(k_pos_leaves<F>, dim3((u32)ceil_div(m, 256)), dim3(256), 0, s, d_doc, (u64)n, index_base, pd, ps.tags[0], lvl);
     for (size_t h = 1; h < sizes.size(); ++h) {
         const u64 up = sizes[h];
-        if (spread && up <= spread_max)
-            hipLaunchKernelGGL((k_pos_spread<F, false>), dim3((u32)ceil_div(up, POS_SPREAD_PER_WAVE)), dim3(64), 0, ss.s, (const u32 *)nullptr, (const fe256 *)lvl, m, (u64)0, pd,
-                               tags[1], lvl + m);
+        if (pos_spread_form<F>(ps, up))
+            hipLaunchKernelGGL((k_pos_spread<F, false>), dim3((u32)ceil_div(up, POS_SPREAD_PER_WAVE)), dim3(64), 0, s, (const u32 *)nullptr, (const fe256 *)lvl, m, (u64)0, pd,
+                               ps.tags[1], lvl + m);
         else
-            hipLaunchKernelGGL(k_pos_nodes<F>, dim3((u32)ceil_div(up, 256)), dim3(256), 0, ss.s, (const fe256 *)lvl, m, pd, tags[1], lvl + m);
+            hipLaunchKernelGGL(k_pos_nodes<F>, dim3((u32)ceil_div(up, 256)), dim3(256), 0, s, (const fe256 *)lvl, m, pd, ps.tags[1], lvl + m);
         lvl += m;
         m = up;
     }
+}
+
+template <int C>
+static reef_status v_merkle_commit(const reef_poseidon_params *pp, const uint32_t *doc, size_t n, int doc_loc, bool is_mont, reef_fe *tree_out,
+                                   int out_loc, reef_fe *root_out, const MerkleSlice *sl) {
+    constexpr int F = 1 - C;
+    const bool from_nodes = sl && sl->nodes_in;
+    if (from_nodes) n = 2 * sl->nodes_n;               // as many bottom nodes as a document of this length has
+    if (!pp || !pp->round_constants || !pp->mds || (n && !doc && !from_nodes) || (!tree_out && !root_out && !sl)) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (sl && (sl->index_base & 1)) { set_error("a block of the tree starts at an even symbol"); return REEF_ERR_ARG; }
+    REEF_TRY(merkle_check_params(pp));
+    if (n == 0 || n >= (1ull << 33)) { set_error("document length out of range"); return REEF_ERR_ARG; }
+    ScratchStream ss;
+    REEF_TRY(ss.init());
+    PosSetup<F> ps;
+    REEF_TRY(pos_setup<F>(ss.s, pp, is_mont, [&](int, void **p, size_t bytes) { return ss.alloc(p, bytes); }, ps));
+    // node counts: the whole tree stops at one node; a block runs the levels it was told to (a ragged last block carries its single node on)
+    std::vector<u64> sizes;
+    if (sl) {
+        u64 m_ = (n + 1) / 2;
+        sizes.push_back(m_);
+        for (u32 h = 0; h < sl->levels; ++h) { m_ = (m_ + 1) / 2; sizes.push_back(m_); }
+    } else sizes = merkle_level_sizes(n);
+    u64 total = 0;
+    for (u64 v : sizes) total += v;
+    const u32 *d_doc = nullptr;
+    void *tree = nullptr;
+    if (!from_nodes) REEF_TRY(stage_in<u32>(ss, &d_doc, doc, n, doc_loc));
+    REEF_TRY(ss.alloc(&tree, total * sizeof(fe256)));
+    if (from_nodes) {
+        const u64 m = sizes[0];
+        void *nraw = nullptr;
+        REEF_TRY(ss.alloc(&nraw, m * sizeof(fe256)));
+        REEF_HIP_TRY(hipMemcpyAsync(nraw, sl->nodes_in, m * sizeof(fe256), hipMemcpyHostToDevice, ss.s));
+        hipLaunchKernelGGL(k_fe_import<F>, dim3((u32)ceil_div(m, 256)), dim3(256), 0, ss.s, (const fe256 *)nraw, (u32)m, (int)is_mont, (fe256 *)tree);
+    }
+    merkle_hash_levels<F>(ss.s, from_nodes ? nullptr : d_doc, n, sl ? sl->index_base : 0, sizes, ps, (fe256 *)tree);
     REEF_HIP_TRY(hipGetLastError());
     // export: the whole tree (level by level, leaves' parents first) and / or the root, in the form the caller's field elements have
     void *exp = nullptr;

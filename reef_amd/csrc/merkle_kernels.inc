@@ -270,4 +270,122 @@ __global__ void __launch_bounds__(64) k_pos_spread(const u32 *__restrict__ doc, 
     if (live && elem == 1) store_fe256(out + i, fe_to_table<F>(s));
 }
 
+// ---- the resident tree (merkle_resident_engine.inc): openings gathered from it, and the root recomputed from claimed openings ----
+static constexpr u32 MERKLE_MAX_LEVELS = 33;           // documents are shorter than 2^33 symbols
+struct MerkleShape {                                   // the levels of a resident tree: level h is tree[off[h] .. off[h] + len[h])
+    u64 off[MERKLE_MAX_LEVELS], len[MERKLE_MAX_LEVELS];
+    u64 n;                                             // symbols of the document
+    u32 levels;
+};
+// make_wits as arrays (merkle_tree.rs:116-190), one thread per (query, depth), into a packed staging buffer in the caller's form:
+// opposite[k * L] | path[k * L] (want_path) | opposite_idx[k] | symbols[k].  Every idx[j] < n (checked on the host).
+template <int F>
+__global__ void __launch_bounds__(256) k_merkle_open(const u32 *__restrict__ doc, const fe256 *__restrict__ tree, MerkleShape sh, const u64 *__restrict__ idx, u64 k,
+                                                   int to_mont, int want_path, fe256 *__restrict__ opposite, fe256 *__restrict__ path,
+                                                   u64 *__restrict__ opposite_idx, u32 *__restrict__ symbols) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const u32 L = sh.levels;
+    if (t >= k * L) return;
+    const u64 j = t / L;
+    const u32 h = (u32)(t - j * L);
+    const u64 q = idx[j];
+    fe256 opp = fe256_of_u64(0);                       // zero is zero in either form
+    if (h == 0) {
+        const u64 sib = q ^ 1;
+        const bool have = sib < sh.n;                  // only an even last symbol has no sibling
+        const u32 v = have ? doc[sib] : 0u;
+        if (v) opp = to_mont ? fe_to_abi<F>(fe_from_integer<F>(fe256_of_u64(v))) : fe256_of_u64(v);
+        opposite_idx[j] = have ? sib : 0;
+        symbols[j] = doc[q];
+    } else {
+        const u64 sib = (q >> h) ^ 1;                  // the sibling of the path's node in level h - 1
+        if (sib < sh.len[h - 1]) opp = fe_to_caller<F>(fe_from_table(load_fe256(tree + sh.off[h - 1] + sib)), to_mont);
+    }
+    store_fe256(opposite + t, opp);
+    if (want_path) store_fe256(path + t, fe_to_caller<F>(fe_from_table(load_fe256(tree + sh.off[h] + (q >> (h + 1)))), to_mont));
+}
+
+// The inputs of one depth of a claimed opening: `self` is the symbol's side (depth 0) or the running digest, `opp` the claimed sibling.
+// Depth 0 is H4(idx, sym, opp_idx, opp) or H4(opp_idx, opp, idx, sym) by bit 0 of idx; depth h >= 1 is H2(digest, opp) or H2(opp, digest) by
+// bit h (merkle_tree.rs:222-249).  Returns element `elem` of the state the hash starts from.
+template <int F>
+__device__ __forceinline__ fe merkle_path_input(int elem, u32 h, u64 q, u32 sym, u64 oidx, const fe256 &opp_raw, int is_mont, const fe &digest, const fe256 &tag_leaf,
+                                                const fe256 &tag_node) {
+    fe z = fe_zero();
+    REEF_SET_BOUND(z, 1.0);
+    const bool left = ((q >> h) & 1) == 0;             // the path's node is the left child
+    if (elem == 0) return fe_from_table(h == 0 ? tag_leaf : tag_node);
+    if (h == 0) {
+        const bool own = left ? elem <= 2 : elem >= 3; // elements 1, 2: the left (index, symbol); 3, 4: the right
+        if (elem & 1) return fe_from_integer<F>(fe256_of_u64(own ? q : oidx));
+        return own ? fe_from_integer<F>(fe256_of_u64(sym)) : fe_from_caller<F>(opp_raw, is_mont);
+    }
+    if (elem > 2) return z;
+    return (elem == 1) == left ? digest : fe_from_caller<F>(opp_raw, is_mont);
+}
+// Five lanes per hash, 12 paths per wave, one wave per block: a path is a chain of L dependent hashes, the running digest kept in lane
+// elem == 1 of its group.  The permutation meets at barriers, so EVERY lane runs all L depths: idle groups hash zeros to the end.
+// opposite: k * L elements in the caller's form (below the modulus: checked on the host); accept[j] = the recomputed root is `root`'s.
+template <int F>
+__global__ void __launch_bounds__(64) k_pos_paths(const u64 *__restrict__ idx, const u32 *__restrict__ symbols, const u64 *__restrict__ opposite_idx,
+                                                 const fe256 *__restrict__ opposite, u64 k, u32 levels, int is_mont, PoseidonDev p, fe256 tag_leaf, fe256 tag_node,
+                                                 const fe256 *__restrict__ root, u32 *__restrict__ accept) {
+    __shared__ PosSpreadLds L;
+    const int lane = threadIdx.x, elem = lane % POS_T, base = lane - elem;
+    const bool in_group = lane < (int)(POS_SPREAD_PER_WAVE * POS_T);
+    const u64 j = (u64)blockIdx.x * POS_SPREAD_PER_WAVE + (u32)(lane / POS_T);
+    const bool live = in_group && j < k;
+    const int safe_base = in_group ? base : 55, safe_elem = in_group ? elem : 0;         // idle lanes 60..63 read a live group's slots
+    const u64 q = live ? idx[j] : 0, oidx = live ? opposite_idx[j] : 0;
+    const u32 sym = live ? symbols[j] : 0;
+    fe s = fe_zero();
+    REEF_SET_BOUND(s, 1.0);
+    for (u32 h = 0; h < levels; ++h) {
+        fe digest;                                                                       // of depth h - 1: every lane takes it from lane elem == 1 of its group
+#pragma unroll
+        for (int i = 0; i < 9; ++i) digest.l[i] = (u32)__shfl((int)s.l[i], safe_base + 1, 64);
+        REEF_SET_BOUND(digest, 2.0);
+        fe in = fe_zero();
+        REEF_SET_BOUND(in, 1.0);
+        if (live) {
+            fe256 opp_raw = fe256_of_u64(0);
+            if (elem == 1 || elem == 2 || elem == 4) opp_raw = load_fe256(opposite + j * levels + h);
+            in = merkle_path_input<F>(elem, h, q, sym, oidx, opp_raw, is_mont, digest, tag_leaf, tag_node);
+        }
+        s = poseidon_permute_spread<F>(in, safe_elem, safe_base, lane, p, L);
+    }
+    if (live && elem == 1) {
+        const fe256 got = fe_to_table<F>(s), want = load_fe256(root);
+        u32 diff = 0;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) diff |= got.w[w] ^ want.w[w];
+        accept[j] = diff == 0 ? 1u : 0u;
+    }
+}
+// The same check with a thread per path, for more paths than fill the chip five lanes at a time (as the tree's wide levels).
+template <int F>
+__global__ void __launch_bounds__(256) k_pos_paths_wide(const u64 *__restrict__ idx, const u32 *__restrict__ symbols, const u64 *__restrict__ opposite_idx,
+                                                       const fe256 *__restrict__ opposite, u64 k, u32 levels, int is_mont, PoseidonDev p, fe256 tag_leaf, fe256 tag_node,
+                                                       const fe256 *__restrict__ root, u32 *__restrict__ accept) {
+    const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    const u64 q = idx[j], oidx = opposite_idx[j];
+    const u32 sym = symbols[j];
+    fe digest = fe_zero();
+    REEF_SET_BOUND(digest, 1.0);
+    for (u32 h = 0; h < levels; ++h) {
+        const fe256 opp_raw = load_fe256(opposite + j * levels + h);
+        fe s[POS_T];
+#pragma unroll
+        for (int e = 0; e < POS_T; ++e) s[e] = merkle_path_input<F>(e, h, q, sym, oidx, opp_raw, is_mont, digest, tag_leaf, tag_node);
+        poseidon_permute<F>(s, p);
+        digest = s[1];
+    }
+    const fe256 got = fe_to_table<F>(digest), want = load_fe256(root);
+    u32 diff = 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) diff |= got.w[w] ^ want.w[w];
+    accept[j] = diff == 0 ? 1u : 0u;
+}
+
 }  // namespace reef

@@ -140,3 +140,122 @@ class MerkleCommitment:
 
     def make_wits(self, m_lookups: Sequence[int]) -> List[List[MerkleWit]]:
         return [self.path_wits(int(q)) for q in m_lookups]
+
+
+def _limbs_to_int(row) -> int:
+    return int(row[0]) | int(row[1]) << 64 | int(row[2]) << 128 | int(row[3]) << 192
+
+
+def wits_from_arrays(idx: Sequence[int], n: int, levels: int, opposite_idx, opposite) -> List[List[MerkleWit]]:
+    """reef_merkle_open's arrays -> the `MerkleWit` lists of make_wits (merkle_tree.rs:116-190).  idx: k document indices; opposite_idx: k
+    entries; opposite: (k * levels, 4) uint64 limbs of canonical integers, query-major.  Pure host code: l_or_r at depth h is "bit h of
+    the index is clear", and only the leaf's wit carries a sibling index."""
+    opp = np.asarray(opposite, dtype=np.uint64).reshape(-1, 4)
+    oidx = np.asarray(opposite_idx, dtype=np.uint64).reshape(-1)
+    k = len(idx)
+    if opp.shape[0] != k * levels or oidx.shape[0] != k:
+        raise ValueError(f"{k} queries of {levels} levels need {k * levels} siblings and {k} sibling indices, got {opp.shape[0]} and {oidx.shape[0]}")
+    out = []
+    for j, q in enumerate(idx):
+        q = int(q)
+        if not 0 <= q < n:
+            raise IndexError(f"document index {q} out of range (the reference asserts idx < doc.len())")
+        row = opp[j * levels:(j + 1) * levels]
+        out.append([MerkleWit((q >> h) & 1 == 0, int(oidx[j]) if h == 0 else None, _limbs_to_int(row[h])) for h in range(levels)])
+    return out
+
+
+class ResidentMerkleCommitment:
+    """`MerkleCommitment` with the tree KEPT ON THE DEVICE (reef_merkle_create, include/reef_msm.h 3d): the document, every level and the
+    constants stay there, no copy of the tree reaches the host, and the openings are gathered from it -- `make_wits(lookups)` is one
+    reef_merkle_open.  Same `commitment`, same `MerkleWit` lists as the host mirror.  Field elements cross as canonical integers."""
+
+    def __init__(self, handle, curve):
+        self._h, self._curve = handle, curve
+        lib = _ffi.load()
+        n, lv, nodes_ = ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+        root = np.zeros((1, 4), dtype=np.uint64)
+        check(lib.reef_merkle_info(self._h, ctypes.byref(n), ctypes.byref(lv), ctypes.byref(nodes_), root.ctypes.data))
+        self.n, self.levels, self.nodes, self.commitment = n.value, lv.value, nodes_.value, array_to_ints(root)[0]
+
+    @classmethod
+    def new(cls, curve, doc, width: int, full_rounds: int, partial_rounds: int, round_constants: Sequence[int], mds: Sequence[Sequence[int]],
+            tag_leaf: int, tag_node: int, device: int = 0) -> "ResidentMerkleCommitment":
+        d = np.ascontiguousarray(np.asarray(doc, dtype=np.uint32))
+        if d.shape[0] == 0:
+            raise ValueError("empty document")
+        rc = ints_to_array(list(round_constants))
+        m = ints_to_array([x for row in mds for x in row])
+        pp = PoseidonParams(width, full_rounds, partial_rounds, 0, rc.ctypes.data, m.ctypes.data,
+                            (ctypes.c_uint64 * 4)(*[(tag_leaf >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]),
+                            (ctypes.c_uint64 * 4)(*[(tag_node >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]))
+        h = ctypes.c_void_p()
+        check(_ffi.load().reef_merkle_create(ctypes.byref(h), curve_id(curve), ctypes.byref(pp), d.ctypes.data, d.shape[0], REEF_HOST, False, device))
+        return cls(h, curve)
+
+    def open_arrays(self, lookups: Sequence[int], want_path: bool = False):
+        """-> (symbols (k,) uint32, opposite_idx (k,) uint64, opposite (k * levels, 4) uint64, path the same shape or None)"""
+        idx = np.ascontiguousarray(np.asarray(list(lookups), dtype=np.uint64))
+        k, L = idx.shape[0], self.levels
+        sym = np.zeros(max(k, 1), dtype=np.uint32)
+        oidx = np.zeros(max(k, 1), dtype=np.uint64)
+        opp = np.zeros((max(k * L, 1), 4), dtype=np.uint64)
+        path = np.zeros((max(k * L, 1), 4), dtype=np.uint64) if want_path else None
+        check(_ffi.load().reef_merkle_open(self._h, idx.ctypes.data, k, sym.ctypes.data, oidx.ctypes.data, opp.ctypes.data, path.ctypes.data if want_path else None))
+        return sym[:k], oidx[:k], opp[:k * L], (path[:k * L] if want_path else None)
+
+    def make_wits(self, m_lookups: Sequence[int]) -> List[List[MerkleWit]]:
+        lookups = [int(q) for q in m_lookups]
+        _, oidx, opp, _ = self.open_arrays(lookups)
+        return wits_from_arrays(lookups, self.n, self.levels, oidx, opp)
+
+    def path_wits(self, idx: int) -> List[MerkleWit]:
+        if not 0 <= idx < self.n:
+            raise IndexError(f"document index {idx} out of range (the reference asserts idx < doc.len())")
+        return self.make_wits([idx])[0]
+
+    def level(self, h: int, first: int = 0, count: Optional[int] = None) -> List[int]:
+        """Nodes [first, first + count) of level h as integers (count None: to the level's end)."""
+        if count is None:
+            m = (self.n + 1) // 2
+            for _ in range(h):
+                m = (m + 1) // 2
+            count = m - first
+        out = np.zeros((max(count, 1), 4), dtype=np.uint64)
+        check(_ffi.load().reef_merkle_read_level(self._h, h, first, count, out.ctypes.data, REEF_HOST))
+        return array_to_ints(out[:count])
+
+    def check(self, lookups: Sequence[int], wits: Sequence[Sequence[MerkleWit]], symbols: Optional[Sequence[int]] = None) -> List[bool]:
+        """The root recomputed on the device from the claimed openings `wits` of `lookups` (reef_merkle_check_paths); symbols: the claimed
+        document symbols (None: the document's own).  -> one flag per lookup."""
+        idx = np.ascontiguousarray(np.asarray([int(q) for q in lookups], dtype=np.uint64))
+        k, L = idx.shape[0], self.levels
+        if k == 0:
+            return []
+        if symbols is None:
+            symbols = self.open_arrays(idx)[0]
+        sym = np.ascontiguousarray(np.asarray(symbols, dtype=np.uint32))
+        if len(wits) != k or any(len(w) != L for w in wits):
+            raise ValueError(f"{k} lookups need {k} openings of {L} wits each")
+        oidx = np.ascontiguousarray(np.asarray([w[0][1] or 0 for w in wits], dtype=np.uint64))      # MerkleWit fields by position: plain tuples do too
+        opp = ints_to_array([w[h][2] for w in wits for h in range(L)])
+        accept = np.zeros(k, dtype=np.uint32)
+        check(_ffi.load().reef_merkle_check_paths(self._h, idx.ctypes.data, sym.ctypes.data, oidx.ctypes.data, opp.ctypes.data, k, accept.ctypes.data))
+        return [bool(a) for a in accept]
+
+    def close(self) -> None:
+        if self._h:
+            _ffi.load().reef_merkle_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
