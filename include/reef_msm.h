@@ -33,6 +33,8 @@
  *      Later, still 7 (symbols added, none changed): the verifier's matrix evaluations on a NIFS ctx (reef_spartan_eval_matrices, section 3k).
  *      Later, still 7 (symbols added, none changed): the sum-check table set from parts -- field elements, a fill, document symbols
  *      (reef_sc_set_table_parts, section 3b).
+ *      Later, still 7 (symbols added, none changed): the row commitments of a resident Hyrax document from its own ctx
+ *      (reef_hyrax_commit, reef_hyrax_eval_comm_own, section 3i).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -638,6 +640,23 @@ reef_status reef_spartan_open_read(reef_nifs_ctx *ctx, int which, size_t count, 
  *                       buffer the key is built from: no affine point visits the host.  The same host bytes as the previous call skip the
  *                       decode and the re-key.  An invalid row is REEF_ERR_ARG naming the first such row; the ctx stays usable and keeps
  *                       the row commitments it had.
+ * reef_hyrax_commit     HyraxPC::commit (commitment.rs:187) of the resident document: C_i = <Z_i, key> (+ blind_i h) for every row i < 2^left_vars
+ *                       of the zero-padded matrix.  key: gens_v as eval_begin takes it (same curve and device, exactly 2^(num_vars - left_vars)
+ *                       points, any kind; no window split).  h: host, affine, pasta Montgomery coordinates; given exactly when create took
+ *                       row_blinds.  comms32: 2^left_vars x 32 bytes in reef_normalize's encoding (the identity: 32 zero bytes);
+ *                       comms_affine: the same rows as affine points (the identity: (0, 0)); both where out_loc says (device buffers
+ *                       16-byte aligned), either or both NULL.  The rows stay on the device as the ctx's own row commitments (the
+ *                       plain key of eval_comm, made or re-keyed device to device).  The symbol width is no argument: for elem_bytes
+ *                       1 / 2 / 4 the bit length of the largest resident symbol is measured on the device, once per ctx, and the rows
+ *                       take reef_msm_rows_symbols[_wide]'s route at that width; elem_bytes 32 takes reef_msm_rows' with
+ *                       max_scalar_bits = 0.  A row wholly beyond n is blind_i h, or the identity.  In no call order: legal any time
+ *                       after create, also between two IPA rounds, and it changes nothing of an argument in flight.  Any error
+ *                       (REEF_ERR_ARG: a key of another curve, device or length -- the message names both lengths --, a window split, h
+ *                       without blinds or blinds without h, a misaligned device output, a limit of the row route in its own words)
+ *                       leaves the ctx usable with the row commitments it had.
+ * reef_hyrax_eval_comm_own  reef_hyrax_eval_comm over the ctx's own rows: no argument, no upload.  After eval_begin, as eval_comm.
+ *                       REEF_ERR_ARG naming reef_hyrax_commit when the ctx has never committed, or when a later
+ *                       reef_hyrax_eval_comm[_compressed] replaced the rows.
  * reef_hyrax_ipa_begin  q: affine, pasta Montgomery coordinates; h: the optional blinding point, blinds[2]: its blinds for round 0
  *                       (the term is on when both are given, for the whole argument); round 0's L and R.
  * reef_hyrax_ipa_round  folds a and b with r; the next round's L and R; blinds: that round's two blinds (NULL = zeros; an error
@@ -646,7 +665,7 @@ reef_status reef_spartan_open_read(reef_nifs_ctx *ctx, int which, size_t count, 
  * reef_hyrax_read       which: 0 a, 1 b, as they stand now (2^right, 2^(right-1), ... entries); the first `count` to the host.
  * Every challenge, blind and point entry must be below the modulus, the IPA's challenges non-zero (REEF_ERR_ARG).  is_mont: scalar
  * inputs and outputs in pasta Montgomery form, else canonical integers.  Outputs are HOST memory.  A call out of order -- a round
- * before ipa_begin, one round too many, finish too early, anything but eval_begin before the first eval_begin -- is REEF_ERR_ARG
+ * before ipa_begin, one round too many, finish too early, anything but eval_begin or commit before the first eval_begin -- is REEF_ERR_ARG
  * naming the call expected, and changes nothing; so is a key of another curve, device or length (the message names both lengths).
  * L and R are computed on the key ctx's stream with c_L q, c_R q (and bl h, br h) added on the device: one host wait per round. */
 typedef struct reef_hyrax_ctx reef_hyrax_ctx;
@@ -657,6 +676,9 @@ reef_status reef_hyrax_eval_begin(reef_hyrax_ctx *ctx, reef_msm_ctx *key, const 
 reef_status reef_hyrax_eval_comm(reef_hyrax_ctx *ctx, const reef_affine *row_comms, int loc, reef_jacobian *comm_lz);
 /* reef_hyrax_eval_comm from the rows as Reef holds them (PolyCommit.comm): 2^left_vars x 32 bytes, host or device. */
 reef_status reef_hyrax_eval_comm_compressed(reef_hyrax_ctx *ctx, const uint8_t *row_comms32, int loc, reef_jacobian *comm_lz);
+/* The row commitments of the resident document, kept on the ctx and handed out; comm_LZ over them. */
+reef_status reef_hyrax_commit(reef_hyrax_ctx *ctx, reef_msm_ctx *key, const reef_affine *h, uint8_t *comms32, reef_affine *comms_affine, int out_loc);
+reef_status reef_hyrax_eval_comm_own(reef_hyrax_ctx *ctx, reef_jacobian *comm_lz);
 reef_status reef_hyrax_ipa_begin(reef_hyrax_ctx *ctx, const reef_affine *q, const reef_affine *h, const reef_fe *blinds, bool is_mont,
                                  reef_jacobian *L, reef_jacobian *R);
 reef_status reef_hyrax_ipa_round(reef_hyrax_ctx *ctx, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R);

@@ -193,6 +193,8 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_hyrax_eval_begin": (c_int, [vp, vp, vp, c_bool, vp, vp]),
         "reef_hyrax_eval_comm": (c_int, [vp, vp, c_int, vp]),
         "reef_hyrax_eval_comm_compressed": (c_int, [vp, vp, c_int, vp]),
+        "reef_hyrax_commit": (c_int, [vp, vp, vp, vp, vp, c_int]),
+        "reef_hyrax_eval_comm_own": (c_int, [vp, vp]),
         "reef_hyrax_ipa_begin": (c_int, [vp, vp, vp, vp, c_bool, vp, vp]),
         "reef_hyrax_ipa_round": (c_int, [vp, vp, vp, c_bool, vp, vp]),
         "reef_hyrax_finish": (c_int, [vp, vp, c_bool, vp, vp]),

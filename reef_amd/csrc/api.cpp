@@ -568,6 +568,13 @@ reef_status reef_hyrax_eval_comm(reef_hyrax_ctx *ctx, const reef_affine *row_com
 reef_status reef_hyrax_eval_comm_compressed(reef_hyrax_ctx *ctx, const uint8_t *row_comms32, int loc, reef_jacobian *comm_lz) {
     return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->eval_comm_compressed(impl, row_comms32, loc, comm_lz); });
 }
+reef_status reef_hyrax_commit(reef_hyrax_ctx *ctx, reef_msm_ctx *key, const reef_affine *h, uint8_t *comms32, reef_affine *comms_affine, int out_loc) {
+    REEF_TRY(require_same_curve(ctx, key, "reef_hyrax_commit", "Hyrax"));
+    return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->commit(impl, key->impl, h, comms32, comms_affine, out_loc); });
+}
+reef_status reef_hyrax_eval_comm_own(reef_hyrax_ctx *ctx, reef_jacobian *comm_lz) {
+    return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->eval_comm_own(impl, comm_lz); });
+}
 reef_status reef_hyrax_ipa_begin(reef_hyrax_ctx *ctx, const reef_affine *q, const reef_affine *h, const reef_fe *blinds, bool is_mont,
                                  reef_jacobian *L, reef_jacobian *R) {
     return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->ipa_begin(impl, q, h, blinds, is_mont, L, R); });

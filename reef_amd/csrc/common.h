@@ -545,6 +545,8 @@ struct HyraxVTable {
     reef_status (*finish)(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat);
     reef_status (*read)(void *impl, int which, size_t count, reef_fe *out, bool to_mont);
     reef_status (*eval_comm_compressed)(void *impl, const uint8_t *row_comms32, int loc, reef_jacobian *comm_lz);
+    reef_status (*commit)(void *impl, void *key_impl, const reef_affine *h, uint8_t *comms32, reef_affine *comms_affine, int out_loc);
+    reef_status (*eval_comm_own)(void *impl, reef_jacobian *comm_lz);
 };
 const HyraxVTable *pallas_hyrax_vtable();
 const HyraxVTable *vesta_hyrax_vtable();

@@ -17,7 +17,7 @@ struct Name { const char *name; bool opening; };
 static const Name SP_NAMES[] = {{SP("begin"), false},         {SP("outer_round"), false},   {SP("outer_claims"), false}, {SP("inner_begin"), false},
                                 {SP("inner_round"), false},   {SP("inner_claims"), false},  {SP("open_begin"), true},    {SP("open_fold"), true},
                                 {SP("open_ipa_begin"), true}, {SP("open_ipa_round"), true}, {SP("open_finish"), true},   {SP("open_read"), true}};
-static const char *HY_NAMES[] = {HY("eval_begin"), HY("eval_comm"), HY("eval_comm_compressed"), HY("ipa_begin"), HY("ipa_round"), HY("finish"), HY("read")};
+static const char *HY_NAMES[] = {HY("eval_begin"), HY("eval_comm"), HY("eval_comm_compressed"), HY("eval_comm_own"), HY("ipa_begin"), HY("ipa_round"), HY("finish"), HY("read")};
 
 // the next call of a prove at {phase, rounds, ell_x, ell_y, log2 n}: for a call of N5, for a call of the opening
 struct SpCase { SpOrder s; const char *next, *next_open; };
@@ -77,7 +77,7 @@ static Expect sp_rule(const Name &n, const SpCase *k, bool stale) {
 }
 static Expect hy_rule(const std::string &name, const HyCase &k) {
     if (name == HY("eval_begin")) return accept();
-    if (name == HY("eval_comm") || name == HY("eval_comm_compressed"))
+    if (name == HY("eval_comm") || name == HY("eval_comm_compressed") || name == HY("eval_comm_own"))
         return k.phase != HY_NONE ? accept() : refuse(name + ": the point is set by reef_hyrax_eval_begin, the next call");
     if (name == HY("read")) return k.phase != HY_NONE ? accept() : refuse(name + ": a and b exist from reef_hyrax_eval_begin on, the next call");
     return name == k.next ? accept() : refuse(name + ": out of order, the next call is " + k.next);

@@ -644,6 +644,25 @@ template <int CURVE> class HyraxEval {
     HyraxEval &operator=(const HyraxEval &) = delete;
     size_t rounds() const { return num_vars_ - left_; }
 
+    // HyraxPC::commit of the resident document: PolyCommit.comm, 2^left_vars compressed rows (host).  gens_v: the key prove takes; h:
+    // exactly when the ctx holds row blinds.  The rows also stay on the device: eval_comm_own and prove_own take them from there.
+    std::vector<Compressed> commit(reef_msm_ctx *gens_v, const reef_affine *h) {
+        std::vector<Compressed> comm((size_t)1 << left_);
+        check(reef_hyrax_commit(ctx_, gens_v, h, comm.data()->data(), nullptr, REEF_HOST), "reef_hyrax_commit");
+        return comm;
+    }
+    // comm_LZ = sum_i L_i C_i over the committed rows, after a prove's eval_begin
+    reef_jacobian eval_comm_own() const {
+        reef_jacobian out;
+        check(reef_hyrax_eval_comm_own(ctx_, &out), "reef_hyrax_eval_comm_own");
+        return out;
+    }
+    // prove on the ctx's own commitment (commit came first): no row commitment is uploaded
+    void prove_own(reef_msm_ctx *gens_v, const reef_fe *point, const Transcript &transcript, const std::function<reef_affine(const reef_fe &)> &q_of,
+                   Proof &pf) const {
+        prove_with(gens_v, point, transcript, q_of, pf, [&] { pf.comm_lz = eval_comm_own(); });
+    }
+
     // proof_dot_prod_prover -> prove_eval at `point` (num_vars entries).  gens_v: a key of exactly 2^rounds() points; row_comms:
     // the 2^left_vars affine row commitments (row_comms_loc memory); q_of(r): the caller's gens_1.scale(r), affine.
     void prove(reef_msm_ctx *gens_v, const reef_fe *point, const reef_affine *row_comms, int row_comms_loc, const Transcript &transcript,

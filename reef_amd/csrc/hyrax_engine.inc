@@ -1,7 +1,8 @@
 // Host side of the Hyrax consistency argument (hyrax_kernels.inc; include/reef_msm.h 3i) on a resident document; included after
 // proof_order.h (the HY_* phases and the call order) and ipa_engine.inc.  create -> eval_begin -> [eval_comm] -> ipa_begin ->
 // ipa_round x (right - 1) -> finish, right = num_vars - left_vars; eval_begin may come at any time and starts the argument over.  The
-// rounds are IpaRun's, driven from this ctx's stream.
+// rounds are IpaRun's, driven from this ctx's stream.  commit (the row commitments of the resident document, HyraxPC::commit) is in no
+// call order; eval_comm_own stands where eval_comm does.
 namespace reef {
 
 template <int C> struct HyraxCtx : DeviceCtx {   // ev: orders the key ctx's stream after this one (IpaRun::ipa_cross)
@@ -19,6 +20,10 @@ template <int C> struct HyraxCtx : DeviceCtx {   // ev: orders the key ctx's str
     std::vector<reef_affine> comms_host; // the host row commitments that key holds (empty: device bases, compared never)
     std::vector<uint8_t> comms_bytes;    // or the host rows it was decoded from, 32 bytes each (eval_comm_compressed); at most one of the two is set
     DevBuf cenc, cdec, cstat;            // eval_comm_compressed: the encodings of host rows, the decoded rows the key is built from, the decode's two counters
+                                         // commit: the encoded rows, the affine rows the key is built from, the OR of the symbols
+    DevBuf cjac;                         // commit: the row sums as they leave the row route (Jacobian)
+    u32 sym_bits = 0;                    // elem_bytes 1 / 2 / 4: the bit length of the largest resident symbol, at least 1 (0: not measured yet)
+    bool own = false, committed = false; // comms holds the rows commit made of this document (eval_comm_own); commit has succeeded at least once
     int phase = HY_NONE;
     u32 rounds = 0;
 };
@@ -27,7 +32,7 @@ template <int C> struct HyraxCtx : DeviceCtx {   // ev: orders the key ctx's str
 template <int C> static void hyrax_free(HyraxCtx<C> *c) {
     if (!c) return;
     retire_device_ctx(c);
-    for (DevBuf *b : {&c->z, &c->rb, &c->eqs, &c->part, &c->dot, &c->pts, &c->lint, &c->stage, &c->cenc, &c->cdec, &c->cstat}) b->release();
+    for (DevBuf *b : {&c->z, &c->rb, &c->eqs, &c->part, &c->dot, &c->pts, &c->lint, &c->stage, &c->cenc, &c->cdec, &c->cstat, &c->cjac}) b->release();
     c->ip.release();
     if (c->comms) v_ctx_destroy<C>(c->comms);
     delete c;
@@ -72,8 +77,11 @@ static reef_status v_hyrax_create(void **impl, const void *z, size_t n, int elem
         c->bchunks = bchunks;
         c->brpc = brpc;
         c->has_blinds = row_blinds != nullptr;
+        // z holds whole rows, in whole 16-byte words: the tail past the document is zeroed, so that commit's row route and width measure read no
+        // further than the allocation and see the padding the matrix has there
         const size_t bytes = n * (size_t)elem_bytes;
-        REEF_TRY(c->z.ensure(std::max<size_t>(bytes, 1)));
+        const size_t zbytes = std::max<size_t>(round_up((u64)ceil_div(n, cols) * cols * (u64)elem_bytes, 16), 16);
+        REEF_TRY(c->z.ensure(zbytes));
         if (c->has_blinds) REEF_TRY(c->rb.ensure(rows * sizeof(fe256)));
         REEF_TRY(c->eqs.ensure(((size_t)rows + cols + 1) * sizeof(fe_limbs)));
         REEF_TRY(c->part.ensure(std::max<size_t>((size_t)chunks * cols, bchunks) * sizeof(fe256)));   // bchunks: 0 without blinds
@@ -83,6 +91,10 @@ static reef_status v_hyrax_create(void **impl, const void *z, size_t n, int elem
         REEF_TRY(ipa_alloc(&c->ip, cols));
         DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
         REEF_TRY(scope.enter());
+        if (hipMemsetAsync((char *)c->z.p + bytes, 0, zbytes - bytes, c->stream) != hipSuccess) {
+            set_error("reef_hyrax_create: clearing the tail of z failed");
+            return REEF_ERR_HIP;
+        }
         if (bytes && hipMemcpyAsync(c->z.p, z, bytes, z_loc == REEF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream) != hipSuccess) {
             set_error("reef_hyrax_create: the copy of z failed");
             return REEF_ERR_HIP;
@@ -207,6 +219,7 @@ template <int C> static reef_status v_hyrax_eval_comm(void *impl, const reef_aff
         REEF_TRY(hy_set_comms(c, row_comms, loc));
     }
     if (!same) {
+        c->own = false;                                       // the caller's rows replace those of reef_hyrax_commit
         if (loc != REEF_DEVICE) c->comms_host.assign(row_comms, row_comms + c->rows);
         else c->comms_host.clear();
     }
@@ -250,9 +263,114 @@ template <int C> static reef_status v_hyrax_eval_comm_compressed(void *impl, con
     if (!same) {
         c->comms_host.clear();
         c->comms_bytes.clear();
+        c->own = false;                                       // the caller's rows replace those of reef_hyrax_commit
         REEF_TRY(hy_set_comms(c, (const reef_affine *)c->cdec.p, REEF_DEVICE));
         if (loc != REEF_DEVICE) c->comms_bytes.assign(row_comms32, row_comms32 + bytes);
     }
+    return v_msm<C>(c->comms, (const reef_fe *)c->lint.p, c->rows, REEF_DEVICE, false, comm_lz, REEF_HOST);
+}
+
+// HyraxPC::commit (commitment.rs:187) of the resident document: C_i = <Z_i, key> (+ blind_i h) for every row of the matrix, through K2's row
+// routes on the key ctx's stream with z and rb where create left them.  The rows that hold document entries go through the route of their
+// element width (the symbol width is the measured one); the rows wholly beyond n start as the identity; one k_add_blind_tab launch adds
+// blind_i h to all of them, one k_normalize launch writes the affine rows (cdec) and the encodings.  The key ctx's stream is waited for
+// before the comms key is touched, so that an error leaves the ctx with the row commitments it had.
+template <int C>
+static reef_status hy_commit_finish(HyraxCtx<C> *c, Ctx<C> *key, size_t used, const reef_affine *h, uint8_t *comms32, reef_affine *comms_affine, int out_loc) {
+    std::lock_guard<std::mutex> lk(key->mu);
+    CtxScope<C> scope(key);
+    REEF_TRY(scope.enter());
+    hipStream_t st = key->stream;
+    jacobian256 *jac = c->cjac.template as<jacobian256>();
+    if (used < c->rows) REEF_HIP_TRY(hipMemsetAsync(jac + used, 0, (c->rows - used) * sizeof(jacobian256), st));
+    if (h) {
+        struct HostH {                                        // launch_blind takes h's nibble table from key->h_host (rebuilt only when h changes)
+            Ctx<C> *k;
+            ~HostH() { k->h_host = nullptr; }
+        } host_h{key};
+        key->h_host = h;
+        REEF_TRY(launch_blind<C>(key, jac, c->rb.template as<fe256>(), nullptr, false, c->rows));
+    }
+    affine256 *aff = c->cdec.template as<affine256>();
+    fe256 *enc = !comms32 ? nullptr : out_loc == REEF_DEVICE ? (fe256 *)comms32 : c->cenc.template as<fe256>();
+    hipLaunchKernelGGL(k_normalize<C>, dim3(ceil_div(ceil_div(c->rows, NORM_PER), 256)), dim3(256), 0, st, (const jacobian256 *)jac, c->rows, aff, enc);
+    REEF_HIP_TRY(hipGetLastError());
+    const hipMemcpyKind kind = out_loc == REEF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (comms_affine) REEF_HIP_TRY(hipMemcpyAsync(comms_affine, aff, c->rows * sizeof(affine256), kind, st));
+    if (comms32 && out_loc != REEF_DEVICE) REEF_HIP_TRY(hipMemcpyAsync(comms32, enc, (size_t)c->rows * 32, kind, st));
+    REEF_HIP_TRY(hipStreamSynchronize(st));
+    return REEF_OK;
+}
+template <int C>
+static reef_status v_hyrax_commit(void *impl, void *key_impl, const reef_affine *h, uint8_t *comms32, reef_affine *comms_affine, int out_loc) {
+    HyraxCtx<C> *c = (HyraxCtx<C> *)impl;
+    Ctx<C> *key = (Ctx<C> *)key_impl;
+    if (!key) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (out_loc == REEF_DEVICE && (((uintptr_t)comms32 | (uintptr_t)comms_affine) & 15)) { set_error("reef_hyrax_commit: device outputs must be 16-byte aligned"); return REEF_ERR_ARG; }
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    if (c->has_blinds && !h) { set_error("reef_hyrax_commit: the ctx holds row blinds, the commitment needs their point h"); return REEF_ERR_ARG; }
+    if (!c->has_blinds && h) { set_error("reef_hyrax_commit: h given, but reef_hyrax_create took no row blinds"); return REEF_ERR_ARG; }
+    size_t key_n = 0;
+    REEF_TRY(key_matches(key, c->device, "reef_hyrax_commit", "Hyrax", &key_n));
+    if (key_n != c->cols) {
+        set_error("reef_hyrax_commit: the key holds %zu points, a row has exactly 2^(num_vars - left_vars) = %u", key_n, c->cols);
+        return REEF_ERR_ARG;
+    }
+    u32 split = 1;
+    {
+        std::lock_guard<std::mutex> kl(key->mu);
+        split = key->wsplit_world;
+    }
+    if (split > 1) { set_error("reef_hyrax_commit: the key has a window split set (its MSMs are partial sums)"); return REEF_ERR_ARG; }
+    REEF_TRY(call.enter());                                   // the phase, a, b and the rounds of an argument in flight stay as they are
+    if (c->eb != 32 && !c->sym_bits) {                        // the width of the document's symbols, once per ctx
+        REEF_TRY(c->cstat.ensure(2 * sizeof(u64)));
+        u32 *d_or = c->cstat.template as<u32>(), w = 0;
+        const u64 n16 = round_up((u64)ceil_div(c->n, c->cols) * c->cols * (u64)c->eb, 16) / 16;   // the whole rows create zero-padded
+        REEF_HIP_TRY(hipMemsetAsync(d_or, 0, sizeof(u32), c->stream));
+        if (n16) hipLaunchKernelGGL(k_hy_sym_or, dim3((u32)std::min<u64>(1024, ceil_div(n16, (u64)256))), dim3(256), 0, c->stream, (const uint4 *)c->z.p, n16, d_or);
+        REEF_HIP_TRY(hipGetLastError());
+        REEF_HIP_TRY(hipMemcpyAsync(&w, d_or, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+        REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->eb <= 2) w |= w >> 16;                         // the OR of the words' halves, then of their bytes: the OR of the symbols
+        if (c->eb == 1) w |= w >> 8;
+        w &= c->eb == 1 ? 0xffu : c->eb == 2 ? 0xffffu : ~0u;
+        c->sym_bits = w ? 32u - (u32)__builtin_clz(w) : 1u;
+    }
+    REEF_TRY(c->cjac.ensure(c->rows * sizeof(jacobian256)));
+    REEF_TRY(c->cdec.ensure(c->rows * sizeof(affine256)));
+    if (comms32 && out_loc != REEF_DEVICE) REEF_TRY(c->cenc.ensure((size_t)c->rows * 32));
+    call.leave();                                             // the rest is the key ctx's work, on its stream; z and rb have been at rest since create
+    const size_t used = ceil_div(c->n, (size_t)c->cols);      // the rows that hold document entries (the last one zero-padded)
+    reef_jacobian *jac = c->cjac.template as<reef_jacobian>();
+    if (used && c->eb == 32)
+        REEF_TRY(v_msm_rows<C>(key, (const reef_fe *)c->z.p, used, c->cols, REEF_DEVICE, false, 0, nullptr, nullptr, jac, REEF_DEVICE));
+    else if (used && c->eb == 1)
+        REEF_TRY(v_msm_rows_symbols<C>(key, (const uint8_t *)c->z.p, used, c->cols, REEF_DEVICE, c->sym_bits, nullptr, nullptr, false, jac, REEF_DEVICE));
+    else if (used)
+        REEF_TRY(v_msm_rows_symbols_wide<C>(key, c->z.p, (u32)c->eb, used, c->cols, REEF_DEVICE, c->sym_bits, nullptr, nullptr, false, jac, REEF_DEVICE));
+    REEF_TRY(hy_commit_finish(c, key, used, h, comms32, comms_affine, out_loc));
+    REEF_TRY(hy_set_comms(c, (const reef_affine *)c->cdec.p, REEF_DEVICE));   // device to device: no affine point visits the host unless asked for
+    c->comms_host.clear();
+    c->comms_bytes.clear();
+    c->own = c->committed = true;
+    return REEF_OK;
+}
+
+// reef_hyrax_eval_comm over the rows reef_hyrax_commit left in the comms key: no argument, no upload
+template <int C> static reef_status v_hyrax_eval_comm_own(void *impl, reef_jacobian *comm_lz) {
+    HyraxCtx<C> *c = (HyraxCtx<C> *)impl;
+    if (!comm_lz) { set_error("null argument"); return REEF_ERR_ARG; }
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    REEF_TRY(hy_expect(c, "reef_hyrax_eval_comm_own"));
+    if (!c->own || !c->comms) {
+        set_error(c->committed ? "reef_hyrax_eval_comm_own: a later reef_hyrax_eval_comm[_compressed] replaced the ctx's own row commitments; reef_hyrax_commit makes them again"
+                               : "reef_hyrax_eval_comm_own: the ctx has no row commitments of its own yet; reef_hyrax_commit makes them");
+        return REEF_ERR_ARG;
+    }
+    REEF_TRY(call.enter());
+    REEF_TRY(hy_row_weights(c));
+    call.leave();                                             // the rest is the key ctx's own work, on its stream
     return v_msm<C>(c->comms, (const reef_fe *)c->lint.p, c->rows, REEF_DEVICE, false, comm_lz, REEF_HOST);
 }
 
@@ -331,7 +449,7 @@ template <int C> static reef_status v_hyrax_read(void *impl, int which, size_t c
 
 template <int C> HyraxVTable make_hyrax_vtable() {
     return HyraxVTable{v_hyrax_create<C>, v_hyrax_destroy<C>, v_hyrax_eval_begin<C>, v_hyrax_eval_comm<C>, v_hyrax_ipa_begin<C>,
-                       v_hyrax_ipa_round<C>, v_hyrax_finish<C>, v_hyrax_read<C>, v_hyrax_eval_comm_compressed<C>};
+                       v_hyrax_ipa_round<C>, v_hyrax_finish<C>, v_hyrax_read<C>, v_hyrax_eval_comm_compressed<C>, v_hyrax_commit<C>, v_hyrax_eval_comm_own<C>};
 }
 
 }  // namespace reef

@@ -68,8 +68,8 @@ inline OrderVerdict sp_check(const char *name, const SpOrder *s, bool stale) {
     return strcmp(want, name) == 0 ? v : v.refuse("%s: out of order, the next call is %s", name, want);
 }
 
-// The same for 3i.  reef_hyrax_eval_begin may always come and starts the argument over; eval_comm, eval_comm_compressed and read need
-// the point it set and nothing else; the IPA calls go in order.
+// The same for 3i.  reef_hyrax_eval_begin may always come and starts the argument over; eval_comm, eval_comm_compressed, eval_comm_own
+// and read need the point it set and nothing else; the IPA calls go in order.  reef_hyrax_commit is in no order and is not asked here.
 inline const char *hy_next(int phase, uint32_t rounds, uint32_t right) {
     switch (phase) {
     case HY_EVAL: return "reef_hyrax_ipa_begin";

@@ -118,6 +118,36 @@ class HyraxEval(_Handle):
         check(self._lib.reef_hyrax_eval_comm_compressed(self._h, ptr, loc, out.ctypes.data))
         return out
 
+    def commit(self, key: MsmContext, h: Optional[np.ndarray] = None, *, affine: bool = False):
+        """HyraxPC::commit of the resident document: the 2^left row commitments C_i = <Z_i, key> (+ blind_i h) as rows x 32 bytes in
+        compress()'s encoding, and with affine=True also as a (2^left, 8) uint64 array.  key: gens_v, exactly 2^right points; h
+        (affine, 8 limbs) exactly when the ctx holds row blinds.  The rows stay on the device for eval_comm_own.  Any time after
+        creation; an argument in flight is not disturbed."""
+        rows = 1 << self.left
+        ha = None if h is None else np.ascontiguousarray(h, dtype=np.uint64).reshape(8)
+        enc = np.zeros(32 * rows, dtype=np.uint8)
+        aff = np.zeros((rows, 8), dtype=np.uint64) if affine else None
+        check(self._lib.reef_hyrax_commit(self._h, key._h, None if ha is None else ha.ctypes.data, enc.ctypes.data,
+                                          None if aff is None else aff.ctypes.data, REEF_HOST))
+        return (enc.tobytes(), aff) if affine else enc.tobytes()
+
+    def commit_to_device(self, key: MsmContext, h: Optional[np.ndarray] = None, comms32: Optional[DeviceBuffer] = None,
+                         comms_affine: Optional[DeviceBuffer] = None) -> None:
+        """commit with the outputs left in device memory (32 and 64 bytes a row; either or both None: the rows are only kept)"""
+        rows = 1 << self.left
+        for buf, per in ((comms32, 32), (comms_affine, 64)):
+            if buf is not None and buf.nbytes < per * rows:
+                raise ValueError(f"{rows} rows of {per} bytes need {per * rows}, the device buffer holds {buf.nbytes}")
+        ha = None if h is None else np.ascontiguousarray(h, dtype=np.uint64).reshape(8)
+        check(self._lib.reef_hyrax_commit(self._h, key._h, None if ha is None else ha.ctypes.data, None if comms32 is None else comms32.ptr,
+                                          None if comms_affine is None else comms_affine.ptr, REEF_DEVICE))
+
+    def eval_comm_own(self) -> np.ndarray:
+        """comm_LZ = sum_i L_i C_i over the rows commit() left on the device: no upload; Jacobian out"""
+        out = np.zeros(12, dtype=np.uint64)
+        check(self._lib.reef_hyrax_eval_comm_own(self._h, out.ctypes.data))
+        return out
+
     def ipa_begin(self, q: np.ndarray, h: Optional[np.ndarray] = None, blinds: Optional[Sequence[int]] = None, *,
                   is_mont: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """Round 0's L and R.  q (and h): affine, 8 uint64 limbs in pasta Montgomery coordinates; blinds: round 0's (bl, br)."""
@@ -150,16 +180,17 @@ class HyraxEval(_Handle):
 def prove_eval(hx: HyraxEval, key: MsmContext, point: Sequence[int], challenge: Callable[[str, List[Any]], int], p: int,
                q_of: Callable[[int], np.ndarray], *, row_comms: Optional[np.ndarray] = None, row_comms_compressed=None,
                h: Optional[np.ndarray] = None,
-               blinds_of: Optional[Callable[[int], Tuple[int, int]]] = None, is_mont: bool = False) -> dict:
+               blinds_of: Optional[Callable[[int], Tuple[int, int]]] = None, is_mont: bool = False, own_comms: bool = False) -> dict:
     """The whole argument with `challenge(label, absorbed)`: eval_begin, comm_LZ when row_comms (affine) or row_comms_compressed (the
-    32-byte rows of PolyCommit.comm, see HyraxEval.eval_comm_compressed) are given, "r" after (comm_LZ, eval)
+    32-byte rows of PolyCommit.comm, see HyraxEval.eval_comm_compressed) are given or, with own_comms, over the rows
+    HyraxEval.commit left on the device, "r" after (comm_LZ, eval)
     for q = q_of(r), then "challenge_r" per round after L and R (compressed).  With h, blinds_of(round) gives that round's (bl, br).
     key: gens_v, exactly 2^right points.  Canonical ints in and out (is_mont: the library calls take Montgomery form)."""
     to, frm = _mont_forms(p, is_mont)
     ev, lb = (frm(v) for v in hx.eval_begin(key, [to(x) for x in point], is_mont=is_mont))
-    if row_comms is not None and row_comms_compressed is not None:
-        raise ValueError("row_comms or row_comms_compressed, not both")
-    comm_lz = hx.eval_comm(row_comms) if row_comms is not None else None
+    if (row_comms is not None) + (row_comms_compressed is not None) + bool(own_comms) > 1:
+        raise ValueError("row_comms, row_comms_compressed or own_comms: one of them")
+    comm_lz = hx.eval_comm(row_comms) if row_comms is not None else hx.eval_comm_own() if own_comms else None
     if row_comms_compressed is not None:
         comm_lz = hx.eval_comm_compressed(row_comms_compressed)
     r_ipa = challenge("r", ([compress(key, comm_lz)] if comm_lz is not None else []) + [ev])
