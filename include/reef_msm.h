@@ -35,6 +35,8 @@
  *      (reef_sc_set_table_parts, section 3b).
  *      Later, still 7 (symbols added, none changed): the row commitments of a resident Hyrax document from its own ctx
  *      (reef_hyrax_commit, reef_hyrax_eval_comm_own, section 3i).
+ *      Later, still 7 (symbols added, none changed): a document's bytes turned into alphabet symbols on the device
+ *      (reef_doc_transform, section 3l).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -742,6 +744,54 @@ reef_status reef_ipa_check_eq(reef_msm_ctx *key, size_t n, const reef_jacobian *
  * products with eq(r_x)[row], a sum over the rows.  One host wait; three field elements cross PCIe. */
 reef_status reef_spartan_eval_matrices(reef_nifs_ctx *ctx, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *r_x, const reef_fe *r_y,
                                        bool is_mont, reef_fe evals[3]);
+
+/* ---------------------------------------------------------------------------------------------
+ * (3l) A document's bytes -> alphabet symbols: Reef's doc_transform [R] (src/backend/framework.rs:978-1011) over the characters
+ * read_doc / BaseParser::read_file hand it (src/main.rs:162-174, src/config.rs:216-284, transforms :290-420), on the device.  The file's
+ * bytes cross PCIe once, as they are; the symbols are written in device memory in the width the next call wants (reef_hyrax_create:
+ * 1 / 2 / 4; reef_merkle_create, the SYMBOLS part of reef_sc_set_table_parts: 4).  Stateless, on the calling thread's current device.
+ *
+ *   out[0 .. kept)        map[c] for every kept character c, in document order
+ *   out[kept]             eof_symbol         (EOF first, then EPSILON: framework.rs:997-1003)
+ *   out[kept + 1]         epsilon_symbol
+ *   out[kept + 2 .. padded)   0
+ *
+ * Elements are elem_bytes (1, 2 or 4) wide.  text: nbytes bytes at text_loc; out: room for out_cap elements at out_loc; device buffers
+ * 16-byte aligned.  map (HOST memory, map_len entries) is indexed by the byte value (REEF_DOC_BYTES) or by the code point
+ * (REEF_DOC_UTF8); an entry is a symbol, REEF_DOC_DROP (the character is filtered out) or REEF_DOC_BAD (not in the alphabet); a
+ * character beyond map_len is BAD.  map == NULL is the encoding's own alphabet, and no table is read: BYTES is the identity on 0..127
+ * and BAD above (AsciiParser); UTF8 is Utf8Parser's alphabet order, cp below 0xD800 and cp - 0x800 from 0xE000 up.  In both, character
+ * 0x1A gives eof_symbol (framework.rs:986 inserts it last and the insert overrides the alphabet's own entry).
+ * padded is the plain next power of two of kept + 2.  The reference's logmn goes through f32 (costs.rs:10-15): for kept + 2 just above
+ * 2^24 (16 777 217, for one) it rounds down and doc_transform then underflows, so the reference cannot run those lengths; that quirk is
+ * NOT reproduced here.
+ * UTF-8 follows Rust's rule (read_to_string): overlong forms, surrogates (ED A0..BF ..), values above U+10FFFF, the bytes C0, C1 and
+ * F5..FF as lead bytes, truncated sequences and stray continuation bytes are malformed; malformed_at is Utf8Error::valid_up_to().
+ *
+ * REEF_OK whenever the text was examined.  If malformed_at < nbytes or bad > 0 nothing is written to out and info says why (bad and
+ * first_bad are defined only for well-formed text).  out == NULL measures only: info is filled, nothing is written.  info may be NULL.
+ * REEF_ERR_ARG: a null text with nbytes > 0; an unknown encoding or location; elem_bytes outside {1, 2, 4}; a device buffer that is not
+ * 16-byte aligned; nbytes >= 2^32; a map entry, eof_symbol or epsilon_symbol that does not fit elem_bytes (a given map is checked on
+ * the host; for a NULL map the limit follows from the encoding: 1 byte holds BYTES, UTF8 needs 4) -- all found before the device is
+ * touched -- and out_cap < padded, with info filled first and both numbers in the message.
+ * Three launches (count the kept characters per 4096-byte tile; scan the counts; decode again, map, write) and the tail; two host waits
+ * (info before anything is written; the end).  No workgroup waits for another. */
+enum { REEF_DOC_BYTES = 0,   /* one character per byte: AsciiParser / DnaParser, `i as char` (config.rs:229-284) */
+       REEF_DOC_UTF8  = 1 }; /* Utf8Parser: read_to_string + chars() (config.rs:252-264) */
+#define REEF_DOC_DROP 0xFFFFFFFEu   /* map entry: the character is filtered out (a transform whose apply() gives None) */
+#define REEF_DOC_BAD  0xFFFFFFFFu   /* map entry: not in the alphabet (Reef panics, framework.rs:990-992) */
+typedef struct {
+    uint64_t chars;         /* characters decoded */
+    uint64_t kept;          /* characters not dropped */
+    uint64_t padded;        /* the smallest power of two >= kept + 2 */
+    uint64_t bad;           /* characters whose map entry is BAD or lies beyond map_len */
+    uint64_t first_bad;     /* byte offset of the first such character; nbytes when none */
+    uint64_t malformed_at;  /* UTF-8 only: length of the longest well-formed prefix; nbytes when all of it is */
+} reef_doc_info;
+reef_status reef_doc_transform(const uint8_t *text, size_t nbytes, int text_loc, int encoding,
+                               const uint32_t *map, size_t map_len,        /* host; NULL = the encoding's own alphabet */
+                               uint32_t eof_symbol, uint32_t epsilon_symbol,
+                               void *out, uint32_t elem_bytes, size_t out_cap, int out_loc, reef_doc_info *info);
 
 /* ---------------------------------------------------------------------------------------------
  * (4) Runtime plumbing.

@@ -72,6 +72,12 @@ class ScPart(ctypes.Structure):      # reef_sc_part: one run of the sum-check ta
     _fields_ = [("kind", c_uint32), ("elem_bytes", c_uint32), ("data", c_void_p), ("count", c_size_t), ("loc", c_int)]
 
 
+class DocInfo(ctypes.Structure):     # reef_doc_info: what reef_doc_transform found in the text
+    _fields_ = [(n, c_uint64) for n in ("chars", "kept", "padded", "bad", "first_bad", "malformed_at")]
+
+
+DOC_BYTES, DOC_UTF8 = 0, 1
+DOC_DROP, DOC_BAD = 0xFFFFFFFE, 0xFFFFFFFF
 SC_PART_FE, SC_PART_SYMBOLS, SC_PART_FILL = 0, 1, 2
 SC_MAX_PARTS = 8
 
@@ -119,6 +125,7 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_fold": (c_int, [c_int, vp, c_size_t, c_int, vp, vp, vp]),
         "reef_normalize": (c_int, [c_int, vp, c_size_t, c_int, vp, vp]),
         "reef_decompress": (c_int, [c_int, vp, c_size_t, c_int, vp, POINTER(c_uint64), POINTER(c_uint64)]),
+        "reef_doc_transform": (c_int, [vp, c_size_t, c_int, c_int, vp, c_size_t, c_uint32, c_uint32, vp, c_uint32, c_size_t, c_int, POINTER(DocInfo)]),
         "reef_mle_bound_rows": (c_int, [c_int, vp, c_size_t, c_int, c_int, c_bool, vp, c_size_t, c_size_t, vp, c_int, vp]),
         "reef_sum_points": (c_int, [c_int, vp, c_size_t, c_int, vp]),
         "reef_gen_bases": (c_int, [c_int, c_uint64, c_uint64, c_size_t, vp, c_int]),

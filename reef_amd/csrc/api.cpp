@@ -423,6 +423,15 @@ reef_status reef_normalize(int curve, const reef_jacobian *in, size_t n, int loc
 reef_status reef_decompress(int curve, const uint8_t *in, size_t n, int loc, reef_affine *out_affine, uint64_t *invalid, uint64_t *first_invalid) {
     return stateless(curve, [&](const CurveVTable *v) { return v->decompress(in, n, loc, out_affine, invalid, first_invalid); });
 }
+reef_status reef_doc_transform(const uint8_t *text, size_t nbytes, int text_loc, int encoding, const uint32_t *map, size_t map_len, uint32_t eof_symbol,
+                               uint32_t epsilon_symbol, void *out, uint32_t elem_bytes, size_t out_cap, int out_loc, reef_doc_info *info) {
+    // no curve in it: either table serves.  The text-independent argument errors come before the device is asked for.
+    return stateless(REEF_PALLAS, [&](const CurveVTable *v) -> reef_status {
+        REEF_TRY(v->doc_check(text, nbytes, text_loc, encoding, map, map_len, eof_symbol, epsilon_symbol, out, elem_bytes, out_loc));
+        REEF_TRY(require_gpu());
+        return v->doc_transform(text, nbytes, text_loc, encoding, map, map_len, eof_symbol, epsilon_symbol, out, elem_bytes, out_cap, out_loc, info);
+    }, false);
+}
 reef_status reef_sum_points(int curve, const reef_jacobian *in, size_t n, int loc, reef_jacobian *out) {
     return stateless(curve, [&](const CurveVTable *v) { return v->sum_points(in, n, loc, out); });
 }

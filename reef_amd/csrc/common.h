@@ -486,7 +486,17 @@ struct CurveVTable {
                                      int out_loc);
     reef_status (*plan_for)(size_t n, uint32_t c_opt, uint32_t g_opt, uint32_t *c, uint32_t *w, uint32_t *g, uint32_t *t);    // K4's inverse: 32-byte encodings -> affine points (coordinates in the curve's base field)
     reef_status (*decompress)(const uint8_t *in, size_t n, int loc, reef_affine *out_aff, uint64_t *invalid, uint64_t *first_invalid);
+    // a document's bytes -> alphabet symbols (3l): no field arithmetic, one implementation behind both curves' tables (doc_engine.inc).
+    // doc_check: the argument errors that do not depend on the text, pure host logic; doc_transform: the rest, arguments as doc_check left them
+    reef_status (*doc_check)(const uint8_t *text, size_t nbytes, int text_loc, int encoding, const uint32_t *map, size_t map_len, uint32_t eof_symbol,
+                             uint32_t epsilon_symbol, void *out, uint32_t elem_bytes, int out_loc);
+    reef_status (*doc_transform)(const uint8_t *text, size_t nbytes, int text_loc, int encoding, const uint32_t *map, size_t map_len, uint32_t eof_symbol,
+                                 uint32_t epsilon_symbol, void *out, uint32_t elem_bytes, size_t out_cap, int out_loc, reef_doc_info *info);
 };
+reef_status doc_check(const uint8_t *text, size_t nbytes, int text_loc, int encoding, const uint32_t *map, size_t map_len, uint32_t eof_symbol,
+                      uint32_t epsilon_symbol, void *out, uint32_t elem_bytes, int out_loc);
+reef_status doc_transform(const uint8_t *text, size_t nbytes, int text_loc, int encoding, const uint32_t *map, size_t map_len, uint32_t eof_symbol,
+                          uint32_t epsilon_symbol, void *out, uint32_t elem_bytes, size_t out_cap, int out_loc, reef_doc_info *info);
 
 const CurveVTable *pallas_vtable();
 const CurveVTable *vesta_vtable();

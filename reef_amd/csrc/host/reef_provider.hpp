@@ -13,6 +13,7 @@
 //   SumCheck                                      gen_eq_table / linear_mle_product      src/backend/r1cs_helper.rs:441-544, driven as in r1cs.rs:2318-2385
 //   compress()                                    Commitment::compress                   src/backend/commitment.rs:195,351,365
 //   decompress()                                  CompressedCommitment::decompress [R]   src/backend/commitment.rs:192-197 (a batch per call)
+//   char_map() / doc_transform()                  doc_transform(&ab, &doc) [R] from the file's bytes      src/backend/framework.rs:978-1011, config.rs:216-284
 //   CommitmentGens<CURVE>(label, n, params [, h]) CommitmentGens::new(label, n) / new_with_blinding_gen      src/backend/framework.rs:297-303, commitment.rs:146-149,176-180
 //   MerkleCommitment<CURVE>(doc, pc)              MerkleCommitment::new(&doc, &pc), path_wits, make_wits     src/backend/merkle_tree.rs:25-190
 //   MerkleCommitmentResident<CURVE>(doc, pc)      the same with the tree kept on the device: make_wits from it, check_paths  src/backend/merkle_tree.rs:116-256
@@ -25,6 +26,7 @@
 // Error behaviour: Reef treats every failure as a panic (framework.rs:683,702); here every failed
 // call throws reef_provider::Error carrying reef_last_error().
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstring>
 #include <functional>
@@ -60,6 +62,50 @@ template <int CURVE> inline std::vector<reef_affine> decompress(const Compressed
     check(reef_decompress(CURVE, n ? c->data() : nullptr, n, REEF_HOST, out.data(), &bad, &first), "reef_decompress");
     if (bad) throw std::invalid_argument("reef_decompress: encoding " + std::to_string(first) + " is not a point (" + std::to_string(bad) + " invalid)");
     return out;
+}
+
+// The map reef_doc_transform takes, indexed by code point (REEF_DOC_BYTES: by byte value), with doc_transform's rules [R]
+// (src/backend/framework.rs:978-986): a character's symbol is its position in `alphabet`, a later duplicate overriding an earlier one; 0x1A
+// gives alphabet.size() + 2 (EOF is inserted last and overrides the alphabet's own entry); everything else is REEF_DOC_BAD.  `remap`: the
+// characters a transform rewrites before the lookup (CaseInsensitive: {'a', 'A'}) take the entry of what they become; `drop`: the characters
+// a transform filters out (IgnoreWhitespace) are REEF_DOC_DROP, whatever else is said about them.  Pure host logic (host/doc_map_selftest.cpp).
+inline std::vector<uint32_t> char_map(const std::u32string &alphabet, const std::vector<std::pair<char32_t, char32_t>> &remap = {},
+                                      const std::u32string &drop = {}) {
+    char32_t top = 0x1A;
+    for (char32_t c : alphabet) top = std::max(top, c);
+    for (const auto &r : remap) top = std::max(top, std::max(r.first, r.second));
+    for (char32_t c : drop) top = std::max(top, c);
+    std::vector<uint32_t> m((size_t)top + 1, REEF_DOC_BAD);
+    for (size_t i = 0; i < alphabet.size(); ++i) m[alphabet[i]] = (uint32_t)i;
+    m[0x1A] = (uint32_t)alphabet.size() + 2;
+    std::vector<uint32_t> becomes(remap.size());
+    for (size_t i = 0; i < remap.size(); ++i) becomes[i] = m[remap[i].second];
+    for (size_t i = 0; i < remap.size(); ++i) m[remap[i].first] = becomes[i];
+    for (char32_t c : drop) m[c] = REEF_DOC_DROP;
+    return m;
+}
+
+// doc_transform(&ab, &doc) [R] (framework.rs:978-1011) from the file's bytes: the document's symbols, EOF, EPSILON and zeros up to a power of
+// two, elem_bytes wide, written to `out` (out_cap elements at out_loc: device memory for reef_hyrax_create / reef_merkle_create / the
+// SYMBOLS part of reef_sc_set_table_parts).  `map`: char_map(ab, ...); alphabet_len: ab's length.  Returns what the call found; throws
+// where the reference panics (a character outside the alphabet, text that is not UTF-8).  out == nullptr measures only.
+inline reef_doc_info doc_transform(const uint8_t *doc, size_t nbytes, int doc_loc, int encoding, const std::vector<uint32_t> &map, size_t alphabet_len,
+                                   void *out, uint32_t elem_bytes, size_t out_cap, int out_loc) {
+    reef_doc_info info = {};
+    check(reef_doc_transform(doc, nbytes, doc_loc, encoding, map.empty() ? nullptr : map.data(), map.size(), (uint32_t)alphabet_len + 2,
+                             (uint32_t)alphabet_len + 1, out, elem_bytes, out_cap, out_loc, &info), "reef_doc_transform");
+    if (info.malformed_at < nbytes) throw std::invalid_argument("doc_transform: the document is not UTF-8 (valid up to byte " + std::to_string(info.malformed_at) + ")");
+    if (info.bad) throw std::invalid_argument("doc_transform: Character in document that's not in alphabet (byte " + std::to_string(info.first_bad) + ", " + std::to_string(info.bad) + " in all)");
+    return info;
+}
+// the same to host memory under the reference's signature: the Vec<usize> it returns
+inline std::vector<size_t> doc_transform(const std::u32string &ab, const std::vector<uint8_t> &doc, int encoding = REEF_DOC_BYTES) {
+    const std::vector<uint32_t> map = char_map(ab);
+    size_t cap = 2;
+    while (cap < doc.size() + 2) cap <<= 1;
+    std::vector<uint32_t> sym(cap);
+    const reef_doc_info info = doc_transform(doc.data(), doc.size(), REEF_HOST, encoding, map, ab.size(), sym.data(), 4, cap, REEF_HOST);
+    return std::vector<size_t>(sym.begin(), sym.begin() + info.padded);
 }
 
 // nova-snark CommitmentGens<G>: a vector of generators (+ blinding generator h) resident on the GPU,

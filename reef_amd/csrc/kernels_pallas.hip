@@ -12,6 +12,7 @@
 #include "open_kernels.inc"
 #include "hyrax_kernels.inc"
 #include "ipa_check_kernels.inc"
+#include "doc_kernels.inc"
 #include "engine.inc"
 #include "fe_host.inc"
 #include "nifs_engine.inc"
@@ -22,6 +23,7 @@
 #include "open_engine.inc"
 #include "hyrax_engine.inc"
 #include "merkle_resident_engine.inc"
+#include "doc_engine.inc"      // once: both curves' tables point at it
 namespace reef {
 const CurveVTable *pallas_vtable() {
     static const CurveVTable vt = make_vtable<0>();

@@ -9,8 +9,8 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
-from ._ffi import REEF_HOST, check
-from .msm import curve_id
+from ._ffi import REEF_DEVICE, REEF_HOST, check
+from .msm import DeviceBuffer, curve_id
 from .sumcheck import array_to_ints, ints_to_array
 
 
@@ -180,17 +180,24 @@ class ResidentMerkleCommitment:
 
     @classmethod
     def new(cls, curve, doc, width: int, full_rounds: int, partial_rounds: int, round_constants: Sequence[int], mds: Sequence[Sequence[int]],
-            tag_leaf: int, tag_node: int, device: int = 0) -> "ResidentMerkleCommitment":
-        d = np.ascontiguousarray(np.asarray(doc, dtype=np.uint32))
-        if d.shape[0] == 0:
-            raise ValueError("empty document")
+            tag_leaf: int, tag_node: int, device: int = 0, n: Optional[int] = None) -> "ResidentMerkleCommitment":
+        """doc: the symbols as a sequence (host), or a DeviceBuffer of n 32-bit symbols on `device` (reef_amd.doc.transform writes one)"""
+        if isinstance(doc, DeviceBuffer):
+            if n is None or n <= 0 or doc.nbytes < 4 * n:
+                raise ValueError("a device document needs n, and 4 n bytes in the buffer")
+            d_ptr, d_n, d_loc = doc.ptr, n, REEF_DEVICE
+        else:
+            d = np.ascontiguousarray(np.asarray(doc, dtype=np.uint32))
+            if d.shape[0] == 0:
+                raise ValueError("empty document")
+            d_ptr, d_n, d_loc = d.ctypes.data, d.shape[0], REEF_HOST
         rc = ints_to_array(list(round_constants))
         m = ints_to_array([x for row in mds for x in row])
         pp = PoseidonParams(width, full_rounds, partial_rounds, 0, rc.ctypes.data, m.ctypes.data,
                             (ctypes.c_uint64 * 4)(*[(tag_leaf >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]),
                             (ctypes.c_uint64 * 4)(*[(tag_node >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]))
         h = ctypes.c_void_p()
-        check(_ffi.load().reef_merkle_create(ctypes.byref(h), curve_id(curve), ctypes.byref(pp), d.ctypes.data, d.shape[0], REEF_HOST, False, device))
+        check(_ffi.load().reef_merkle_create(ctypes.byref(h), curve_id(curve), ctypes.byref(pp), d_ptr, d_n, d_loc, False, device))
         return cls(h, curve)
 
     def open_arrays(self, lookups: Sequence[int], want_path: bool = False):
