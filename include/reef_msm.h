@@ -504,6 +504,22 @@ void reef_shake256(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_le
  * reef_nifs_read        which: 0 W, 1 E, 2 T, 3 u, 4 X; the first `count` entries to the host, Montgomery form if to_mont.
  * reef_nifs_check_relaxed  AZ o BZ == u CZ + E on the running instance (nova's is_sat_relaxed without the commitment
  *                       check): *violations = rows that fail, *first_bad_row = the lowest of them (UINT64_MAX: none).
+ * reef_nifs_commit_step  reef_nifs_commit_T and the fresh witness's commitment from ONE upload: also *comm_W2 (HOST, Jacobian) =
+ *                       MSM(W2, key[0 .. num_vars)).  A host W2 crosses PCIe once, a device W2 is read once: one pass writes z2 and
+ *                       the integers of W2 next to T, and the key commits the two rows as one batch of its row pipeline (a small key
+ *                       that serves single rows from nibble tables takes each row that way); one host wait.  State, T, z2, the fold that
+ *                       may follow and reef_nifs_read(.., 2, ..) are exactly commit_T's.  The key: same curve and device, at least
+ *                       max(num_cons, num_vars) points, no window split -- REEF_ERR_ARG otherwise, naming the key's length and both
+ *                       lengths it must cover, and the ctx is left as it was (no prove voided, the previous T readable).  NO BLINDS:
+ *                       a CE::commit that adds blind * h adds it to the two points itself.
+ * reef_nifs_commit_running  *comm_W = MSM(W, key), *comm_E = MSM(E, key) of the running instance as it stands (HOST, Jacobian; E = 0
+ *                       gives the identity).  Either output may be NULL, not both.  The key rule of commit_step; no blinds.  With
+ *                       check_relaxed this is nova's is_sat_relaxed.  The call READS ONLY: it is legal at any time after set_running,
+ *                       between commit_T / commit_step and fold, and between any two calls of a 3g prove or a 3h opening, which go on
+ *                       unchanged (the rule of reef_spartan_eval_matrices, 3k).
+ * reef_nifs_check_fresh AZ2 o BZ2 == CZ2 on the fresh instance (W2, 1, X2) the ctx last took (commit_T or commit_step; before the
+ *                       first, REEF_ERR_ARG), reported as check_relaxed reports; both outputs may be NULL.  Reads only, as
+ *                       commit_running: it tells which step's witness is bad before the fold hides it.
  * is_mont: inputs in pasta Montgomery form, else canonical integers.  Calls on one context are serialised and return
  * with their work done. */
 typedef struct reef_nifs_ctx reef_nifs_ctx;
@@ -518,6 +534,10 @@ reef_status reef_nifs_commit_T(reef_nifs_ctx *ctx, reef_msm_ctx *key, const reef
 reef_status reef_nifs_fold(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont);
 reef_status reef_nifs_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont);
 reef_status reef_nifs_check_relaxed(reef_nifs_ctx *ctx, uint64_t *violations, uint64_t *first_bad_row);
+reef_status reef_nifs_commit_step(reef_nifs_ctx *ctx, reef_msm_ctx *key, const reef_fe *W2, const reef_fe *X2, int loc, bool is_mont,
+                                  reef_jacobian *comm_W2, reef_jacobian *comm_T);
+reef_status reef_nifs_commit_running(reef_nifs_ctx *ctx, reef_msm_ctx *key, reef_jacobian *comm_W, reef_jacobian *comm_E);
+reef_status reef_nifs_check_fresh(reef_nifs_ctx *ctx, uint64_t *violations, uint64_t *first_bad_row);
 
 /* ---------------------------------------------------------------------------------------------
  * (3g) Row N5: the two sum-checks of the final SNARK, nova-snark's RelaxedR1CSSNARK::prove [R] (Reef: S1 / S2,

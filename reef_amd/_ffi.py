@@ -182,6 +182,9 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_nifs_fold": (c_int, [vp, vp, c_bool]),
         "reef_nifs_read": (c_int, [vp, c_int, c_size_t, vp, c_bool]),
         "reef_nifs_check_relaxed": (c_int, [vp, POINTER(c_uint64), POINTER(c_uint64)]),
+        "reef_nifs_commit_step": (c_int, [vp, vp, vp, vp, c_int, c_bool, vp, vp]),
+        "reef_nifs_commit_running": (c_int, [vp, vp, vp, vp]),
+        "reef_nifs_check_fresh": (c_int, [vp, POINTER(c_uint64), POINTER(c_uint64)]),
         "reef_spartan_begin": (c_int, [vp, c_size_t, c_size_t, vp, c_bool, vp]),
         "reef_spartan_outer_round": (c_int, [vp, vp, c_bool, vp]),
         "reef_spartan_outer_claims": (c_int, [vp, vp, c_bool, vp]),

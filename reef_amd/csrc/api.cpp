@@ -513,6 +513,18 @@ reef_status reef_nifs_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe 
 reef_status reef_nifs_check_relaxed(reef_nifs_ctx *ctx, uint64_t *violations, uint64_t *first_bad_row) {
     return dispatch<NifsVTable>(ctx, [&](auto *v, void *impl) { return v->check(impl, violations, first_bad_row); });
 }
+reef_status reef_nifs_commit_step(reef_nifs_ctx *ctx, reef_msm_ctx *key, const reef_fe *W2, const reef_fe *X2, int loc, bool is_mont,
+                                  reef_jacobian *comm_W2, reef_jacobian *comm_T) {
+    REEF_TRY(require_same_curve(ctx, key, "reef_nifs_commit_step", "NIFS"));
+    return dispatch<NifsVTable>(ctx, [&](auto *v, void *impl) { return v->commit_step(impl, key->impl, W2, X2, loc, is_mont, comm_W2, comm_T); });
+}
+reef_status reef_nifs_commit_running(reef_nifs_ctx *ctx, reef_msm_ctx *key, reef_jacobian *comm_W, reef_jacobian *comm_E) {
+    REEF_TRY(require_same_curve(ctx, key, "reef_nifs_commit_running", "NIFS"));
+    return dispatch<NifsVTable>(ctx, [&](auto *v, void *impl) { return v->commit_running(impl, key->impl, comm_W, comm_E); });
+}
+reef_status reef_nifs_check_fresh(reef_nifs_ctx *ctx, uint64_t *violations, uint64_t *first_bad_row) {
+    return dispatch<NifsVTable>(ctx, [&](auto *v, void *impl) { return v->check_fresh(impl, violations, first_bad_row); });
+}
 
 // ---- row N5: the sum-checks of the final SNARK on a NIFS ctx
 reef_status reef_spartan_begin(reef_nifs_ctx *ctx, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *tau, bool is_mont, reef_fe evals[3]) {

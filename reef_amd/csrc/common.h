@@ -512,6 +512,10 @@ struct NifsVTable {
     reef_status (*fold)(void *impl, const reef_fe *r, bool is_mont);
     reef_status (*read)(void *impl, int which, size_t count, reef_fe *out, bool to_mont);
     reef_status (*check)(void *impl, uint64_t *violations, uint64_t *first_bad_row);
+    reef_status (*commit_step)(void *impl, void *key_impl, const reef_fe *W2, const reef_fe *X2, int loc, bool is_mont, reef_jacobian *comm_w2,
+                               reef_jacobian *comm_t);
+    reef_status (*commit_running)(void *impl, void *key_impl, reef_jacobian *comm_w, reef_jacobian *comm_e);
+    reef_status (*check_fresh)(void *impl, uint64_t *violations, uint64_t *first_bad_row);
 };
 const NifsVTable *pallas_nifs_vtable();
 const NifsVTable *vesta_nifs_vtable();

@@ -557,6 +557,25 @@ template <int CURVE> class Nifs {
         check(reef_nifs_commit_T(ctx_, key, W2, X2, loc, is_mont, &comm_T), "reef_nifs_commit_T");
         return comm_T;
     }
+    // commit_T and CE::commit of the fresh witness from one upload of W2: {comm_W2, comm_T}, both over `key` (at least
+    // max(num_cons, num_vars) points), no blinds.  State as after commit_T.
+    struct StepCommitments { reef_jacobian comm_W2, comm_T; };
+    StepCommitments commit_step(reef_msm_ctx *key, const reef_fe *W2, const reef_fe *X2, int loc = REEF_HOST, bool is_mont = true) {
+        StepCommitments o;
+        check(reef_nifs_commit_step(ctx_, key, W2, X2, loc, is_mont, &o.comm_W2, &o.comm_T), "reef_nifs_commit_step");
+        return o;
+    }
+    // comm_W and comm_E of the running instance as it stands (either may be NULL); reads only
+    void commit_running(reef_msm_ctx *key, reef_jacobian *comm_W, reef_jacobian *comm_E) const {
+        check(reef_nifs_commit_running(ctx_, key, comm_W, comm_E), "reef_nifs_commit_running");
+    }
+    // AZ o BZ == CZ on the fresh instance of the last commit_T / commit_step: the number of rows that fail
+    uint64_t check_fresh(uint64_t *first_bad_row = nullptr) const {
+        uint64_t bad = 0, first = 0;
+        check(reef_nifs_check_fresh(ctx_, &bad, &first), "reef_nifs_check_fresh");
+        if (first_bad_row) *first_bad_row = first;
+        return bad;
+    }
     // W += r W2, E += r T, u += r, X += r X2
     void fold(const reef_fe &r, bool is_mont = true) { check(reef_nifs_fold(ctx_, &r, is_mont), "reef_nifs_fold"); }
     // which: 0 W, 1 E, 2 T, 3 u, 4 X; the first `count` entries

@@ -5,7 +5,7 @@
 // ==== the prove leg (`reef_replay cfgN prove`) =========================================================================================
 // Every device row of one proof, through the C ABI and the provider mirror (reef_provider.hpp), in the order `reef --prove` runs
 // them (framework.rs:642-754): per folding step the N2 sum-check step and, per curve, comm_W, NIFS commit_T, a challenge and the
-// fold (3f); the last fold; per curve the Spartan sum-checks (3g) and the batched IPA opening (3h) on the instance the folds left
+// fold (3f; with `paired` the two commitments are one reef_nifs_commit_step, and the folded instance's comm_W, comm_E come from the ctx); the last fold; per curve the Spartan sum-checks (3g) and the batched IPA opening (3h) on the instance the folds left
 // on the device; the Hyrax consistency argument over the committed document (3i).  The R1CS matrices are SYNTHETIC (layered,
 // satisfiable, of the shape's sizes), the transcript is a stand-in hash, and the point operations the Rust host does on
 // commitments (comm_W, comm_E of a folded instance, comm_a) are tracked as discrete logarithms, which every generator here has.
@@ -35,6 +35,7 @@ template <int CURVE> struct ProveSide {
     reef_affine q_open = {};
     double verify_ipa_ms = 0;                       // 3j on the opening, after the host checks
     double verify_evals_ms = 0, verify_evals_host_ms = 0;   // 3k on the device (warm: the second call) against the host loop of proof_check.hpp alone
+    bool paired = false;                            // `paired`: comm_W and comm_T of a step from one reef_nifs_commit_step, the running instance's points from the ctx
     ProveSide(const Mod &mod, const char *nm, size_t cons, size_t vars, uint64_t domain) : m(mod), name(nm), num_cons(cons), num_vars(vars), tr(mod, domain) {}
     Inst fresh(uint64_t seed) const { return fresh_instance(m, S, seed); }
 };
@@ -88,7 +89,8 @@ template <int CURVE> static void nifs_init(ProveSide<CURVE> &s, const Inst &f0) 
     const auto t0 = clk::now();
     s.nifs->set_running(f0.W.data(), nullptr, f0.u, f0.X.data(), REEF_HOST, true);
     reef_jacobian cw;
-    CK(reef_msm(s.c.key, f0.W.data(), s.num_vars, REEF_HOST, true, &cw, REEF_HOST));
+    if (s.paired) s.nifs->commit_running(s.c.key, &cw, nullptr);      // the ctx holds W already: no second upload
+    else CK(reef_msm(s.c.key, f0.W.data(), s.num_vars, REEF_HOST, true, &cw, REEF_HOST));
     s.tr.absorb("U1", &cw, sizeof cw);
     s.init_ms = ms_since(t0);
     s.rec.dW = dot(s.m, f0.W.data(), s.g.data(), s.num_vars);
@@ -96,15 +98,20 @@ template <int CURVE> static void nifs_init(ProveSide<CURVE> &s, const Inst &f0) 
     s.rec.X = f0.X;
     s.rec.points.push_back({cw, s.rec.dW, "comm_W of the first instance"});
 }
-// one NIFS::prove of a folding step: comm_W of the fresh witness (scalars from host memory), commit_T, the challenge, the fold
+// one NIFS::prove of a folding step: comm_W of the fresh witness (scalars from host memory), commit_T, the challenge, the fold;
+// `paired`: both commitments from one reef_nifs_commit_step (one upload of W, counted under nifs_ms)
 struct StepOut { reef_jacobian comm_W, comm_T; reef_fe r; double commit_w_ms, nifs_ms; };
 template <int CURVE> static StepOut step_fold(ProveSide<CURVE> &s, const Inst &f) {
     StepOut o;
     const auto t0 = clk::now();
-    CK(reef_msm(s.c.key, f.W.data(), s.num_vars, REEF_HOST, true, &o.comm_W, REEF_HOST));
+    if (!s.paired) CK(reef_msm(s.c.key, f.W.data(), s.num_vars, REEF_HOST, true, &o.comm_W, REEF_HOST));
     const auto t1 = clk::now();
     o.commit_w_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    o.comm_T = s.nifs->commit_T(s.c.key, f.W.data(), f.X.data(), REEF_HOST, true);
+    if (s.paired) {
+        const auto both = s.nifs->commit_step(s.c.key, f.W.data(), f.X.data(), REEF_HOST, true);
+        o.comm_W = both.comm_W2;
+        o.comm_T = both.comm_T;
+    } else o.comm_T = s.nifs->commit_T(s.c.key, f.W.data(), f.X.data(), REEF_HOST, true);
     const reef_jacobian both[2] = {o.comm_W, o.comm_T};
     s.tr.absorb("fold", both, sizeof both);
     o.r = s.tr.squeeze();
@@ -184,15 +191,22 @@ template <int CURVE> static void read_back(ProveSide<CURVE> &s) {
     s.fin.u = s.nifs->read(3, 1, true)[0];
     s.fin.X = s.nifs->read(4, s.S.num_io, true);
     s.violations = s.nifs->check_relaxed();
+    if (s.paired) {   // the device's comm_W and comm_E of the folded instance against the host's tracked point operations
+        reef_jacobian cw, ce;
+        s.nifs->commit_running(s.c.key, &cw, &ce);
+        s.rec.points.push_back({cw, s.rec.dW, "comm_W of the folded instance (reef_nifs_commit_running)"});
+        s.rec.points.push_back({ce, s.rec.dE, "comm_E of the folded instance (reef_nifs_commit_running)"});
+    }
 }
 
-static std::string prove_body(const Shape &shape, const std::string &tamper, bool tables) {
+static std::string prove_body(const Shape &shape, const std::string &tamper, bool tables, bool paired = false) {
     const Shape *sh = &shape;
     check_tamper_name(tamper);
     if (tamper == "hyrax" && !sh->doc_log) fail("tamper=hyrax: " + sh->name + " has no Hyrax consistency argument");
     const Mod mp(ORDER[REEF_PALLAS]), mv(ORDER[REEF_VESTA]);
     ProveSide<REEF_PALLAS> P(mp, "pallas", sh->c1, sh->w1, 0xA11A5);
     ProveSide<REEF_VESTA> V(mv, "vesta", sh->c2, sh->w2, 0x7E57A);
+    P.paired = V.paired = paired;
     prove_setup(P, tables);
     prove_setup(V, tables);
     sc_ptr sc;
@@ -260,6 +274,15 @@ static std::string prove_body(const Shape &shape, const std::string &tamper, boo
         reef_jacobian w;
         CK(reef_msm(P.c.key, f0p.W.data(), P.num_vars, REEF_HOST, true, &w, REEF_HOST));
         CK(reef_msm(V.c.key, f0v.W.data(), V.num_vars, REEF_HOST, true, &w, REEF_HOST));
+        if (paired) {   // and the workspaces of a batch of two rows, which commit_step's first call would otherwise allocate on the clock
+            reef_jacobian w2[2];
+            std::vector<reef_fe> two(f0p.W);
+            two.insert(two.end(), f0p.W.begin(), f0p.W.end());
+            CK(reef_msm_rows(P.c.key, two.data(), 2, P.num_vars, REEF_HOST, true, 255, nullptr, nullptr, w2, REEF_HOST));
+            two.assign(f0v.W.begin(), f0v.W.end());
+            two.insert(two.end(), f0v.W.begin(), f0v.W.end());
+            CK(reef_msm_rows(V.c.key, two.data(), 2, V.num_vars, REEF_HOST, true, 255, nullptr, nullptr, w2, REEF_HOST));
+        }
     }
     nifs_init(P, f0p);
     nifs_init(V, f0v);
@@ -347,11 +370,11 @@ static std::string prove_body(const Shape &shape, const std::string &tamper, boo
              "\"verify_evals_ms_pallas\": %.3f, \"verify_evals_ms_vesta\": %.3f, \"verify_evals_host_ms_pallas\": %.3f, \"verify_evals_host_ms_vesta\": %.3f, "
              "\"verify_evals\": \"A~, B~, C~ at the recorded (r_x, r_y): reef_spartan_eval_matrices host to host (second call; eq tables included) against the loop "
              "of the host check on one core (eq tables included); A~ + r B~ + r^2 C~ equals claims_inner[0] and the host's value; neither this nor verify_ipa_ms (InnerProductArgument::verify on the opening) is in total_prove_device_ms\", "
-             "\"verify_ipa_ms_pallas\": %.3f, \"verify_ipa_ms_vesta\": %.3f, \"device_verified\": true}",
+             "\"verify_ipa_ms_pallas\": %.3f, \"verify_ipa_ms_vesta\": %.3f, \"device_verified\": true%s}",
              sh->name.c_str(), sh->w1, sh->c1, sh->w2, sh->c2, P.ncp, P.nvp, V.ncp, V.nvp, P.n, V.n, P.S.nnz(), V.S.nnz(), sh->steps, P.init_ms + V.init_ms,
              steps_list.c_str(), steps_total / ns, commit_w_ms / ns, nifs_ms / ns, sc_ms / ns, final_fold_ms, P.spartan_ms, V.spartan_ms, P.pf.outer.size(),
              P.pf.inner.size(), V.pf.outer.size(), V.pf.inner.size(), P.open_ms, V.open_ms, P.pf.r_rounds.size(), V.pf.r_rounds.size(), sh->doc_log, left,
              consistency_ms, hpf.r_rounds.size(), commit_hyrax_ms, hyrax_create_ms, total, check_ms, g_checked, P.verify_evals_ms, V.verify_evals_ms,
-             P.verify_evals_host_ms, V.verify_evals_host_ms, P.verify_ipa_ms, V.verify_ipa_ms);
+             P.verify_evals_host_ms, V.verify_evals_host_ms, P.verify_ipa_ms, V.verify_ipa_ms, paired ? ", \"paired\": true" : "");
     return std::string(line.data());
 }

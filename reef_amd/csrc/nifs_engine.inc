@@ -30,9 +30,13 @@ template <int C> struct NifsCtx : DeviceCtx {   // ev: orders the key ctx's stre
     struct EvalWs { DevBuf pts, ex, zy, partial, out; } evw;   // the verifier's matrix evaluations (3k): eq factors, eq(r_x) by row, the column
                                          // weights, block sums, results; empty until the first reef_spartan_eval_matrices
     u64 gen = 0;                         // bumped by every call that changes the matrices or the running instance (or commits T)
-    DevBuf z1, z2, E, T, stage, counters;
-    bool running = false, committed = false, have_t = false;
+    DevBuf z1, z2, E, step, run, pts, stage, counters;   // step: the rows W2 and T of the step's commitments, run: W and E (commit_running),
+                                         // both two rows of row_len() canonical integers with zero tails; pts: two points
+    bool running = false, committed = false, have_t = false, have_z2 = false;
     fe256 k254 = {};
+    size_t row_len() const { return std::max(num_vars, num_cons); }
+    fe256 *w2_row() { return step.template as<fe256>(); }
+    fe256 *t_row() { return step.template as<fe256>() + row_len(); }      // T of the last commit_T / commit_step
 };
 
 // Every call enqueues on a pool stream and waits for it before it returns: the ctx holds no stream between calls
@@ -45,7 +49,7 @@ template <int C> static void nifs_free(NifsCtx<C> *c) {
     c->rows.release();
     c->cols.release();
     spartan_release<C>(c->sp);
-    for (DevBuf *b : {&c->z1, &c->z2, &c->E, &c->T, &c->stage, &c->counters}) b->release();
+    for (DevBuf *b : {&c->z1, &c->z2, &c->E, &c->step, &c->run, &c->pts, &c->stage, &c->counters}) b->release();
     for (DevBuf *b : {&c->evw.pts, &c->evw.ex, &c->evw.zy, &c->evw.partial, &c->evw.out}) b->release();
     delete c;
 }
@@ -66,7 +70,10 @@ template <int C> static reef_status v_nifs_create(void **impl, size_t num_cons, 
         constexpr int F = NifsCtx<C>::F;
         c->k254 = fe_to_table<F>(fe_mul<F>(x254, fe_const<F>(FC<F>::C_R2, 1.0)));     // 2^254 R'
         for (DevBuf *b : {&c->z1, &c->z2}) REEF_TRY(b->ensure(c->nz * sizeof(fe256)));
-        for (DevBuf *b : {&c->E, &c->T}) REEF_TRY(b->ensure(num_cons * sizeof(fe256)));
+        REEF_TRY(c->E.ensure(num_cons * sizeof(fe256)));
+        REEF_TRY(c->step.ensure(2 * c->row_len() * sizeof(fe256)));
+        REEF_HIP_TRY(hipMemset(c->step.p, 0, 2 * c->row_len() * sizeof(fe256)));   // the rows' tails: nothing writes them afterwards
+        REEF_TRY(c->pts.ensure(2 * sizeof(jacobian256)));
         return c->counters.ensure(2 * sizeof(u32));
     });
 }
@@ -186,7 +193,7 @@ template <int C> static NifsArgs nifs_args(NifsCtx<C> *c) {
     a.z1 = c->z1.template as<fe256>();
     a.z2 = c->z2.template as<fe256>();
     a.E = c->E.template as<fe256>();
-    a.T = c->T.template as<fe256>();
+    a.T = c->t_row();
     a.num_cons = (u32)c->num_cons;
     a.num_vars = (u32)c->num_vars;
     a.k254 = c->k254;
@@ -282,11 +289,124 @@ static reef_status v_nifs_commit_t(void *impl, void *key_impl, const reef_fe *W2
     REEF_HIP_TRY(hipEventRecord(c->ev, c->stream));
     REEF_HIP_TRY(hipStreamWaitEvent(ks, c->ev, 0));
     REEF_TRY((nifs_row_pass<C, NIFS_MODE_T>(c, ks)));
-    c->have_t = true;
-    REEF_TRY(v_msm<C>(key, (const reef_fe *)c->T.p, c->num_cons, REEF_DEVICE, false, comm_t, REEF_HOST));
+    c->have_t = c->have_z2 = true;
+    REEF_TRY(v_msm<C>(key, (const reef_fe *)c->t_row(), c->num_cons, REEF_DEVICE, false, comm_t, REEF_HOST));
     REEF_HIP_TRY(hipStreamSynchronize(ks));
     c->committed = true;
     return REEF_OK;
+}
+
+// The key of a step's or the running instance's two commitments: of this device, without a window split, and long enough for both rows.
+template <int C> static reef_status nifs_pair_key(NifsCtx<C> *c, Ctx<C> *key, const char *name) {
+    size_t key_n = 0;
+    REEF_TRY(key_matches(key, c->device, name, "NIFS", &key_n));
+    if (key_n < c->row_len()) {
+        set_error("%s: the key holds %zu points, the rows have %zu (num_vars) and %zu (num_cons) entries", name, key_n, c->num_vars, c->num_cons);
+        return REEF_ERR_ARG;
+    }
+    u32 split = 1;
+    {
+        std::lock_guard<std::mutex> kl(key->mu);
+        split = key->wsplit_world;
+    }
+    if (split > 1) { set_error("%s: the key has a window split set (its MSMs are partial sums)", name); return REEF_ERR_ARG; }
+    return REEF_OK;
+}
+// MSM(rows[0 .. n0)) and MSM(rows[row_len .. row_len + n1)) over the key, on its stream, to the host: one wait.  The rows hold canonical
+// integers and zero tails.  out0 or out1 may be NULL.  The two rows go through the key's row pipeline as one batch, whatever the key's
+// kind: measured (profiles/r16_nifs_step_timing.txt), the batch is not slower than two single rows on a pre-shifted key, on a plain
+// key, or on a key with byte tables (where v_msm_rows would serve a single row from the tables: wide_path).  A small key that serves
+// single rows from its nibble tables (small_path; at most 1024 points, not measured) takes each row that way, as v_msm_rows would,
+// with device results -- as does a lone row.
+template <int C>
+static reef_status nifs_commit_rows(NifsCtx<C> *c, Ctx<C> *key, hipStream_t ks, const fe256 *rows, size_t n0, size_t n1, reef_jacobian *out0,
+                                    reef_jacobian *out1) {
+    const size_t len = c->row_len();
+    jacobian256 got[2];
+    bool single = !out0 || !out1;
+    if (!single) {
+        std::lock_guard<std::mutex> kl(key->mu);
+        single = small_path(key->key->small_tab, key->key->small_n, len, key->wsplit_world);
+    }
+    if (single) {
+        jacobian256 *d = c->pts.template as<jacobian256>();
+        if (out0) REEF_TRY(v_msm<C>(key, (const reef_fe *)rows, n0, REEF_DEVICE, false, (reef_jacobian *)d, REEF_DEVICE));
+        if (out1) REEF_TRY(v_msm<C>(key, (const reef_fe *)(rows + len), n1, REEF_DEVICE, false, (reef_jacobian *)(d + 1), REEF_DEVICE));
+        REEF_HIP_TRY(hipMemcpyAsync(got, d, sizeof got, hipMemcpyDeviceToHost, ks));
+        REEF_HIP_TRY(hipStreamSynchronize(ks));
+    } else {
+        REEF_TRY(v_msm_rows<C>(key, (const reef_fe *)rows, 2, len, REEF_DEVICE, false, 255, nullptr, nullptr, (reef_jacobian *)got, REEF_HOST));
+        REEF_HIP_TRY(hipStreamSynchronize(ks));
+    }
+    if (out0) memcpy(out0, &got[0], sizeof got[0]);
+    if (out1) memcpy(out1, &got[1], sizeof got[1]);
+    return REEF_OK;
+}
+
+// reef_nifs_commit_T and comm_W2 = MSM(W2, key) from one upload: k_nifs_import_step writes z2 and the integers of W2 (row 0 of `step`),
+// the row pass writes T into row 1, and the two rows are committed together.  Row 0 is ordered behind the import and row 1 behind the
+// row pass by the event on the key ctx's stream, where the row pass runs.
+template <int C>
+static reef_status v_nifs_commit_step(void *impl, void *key_impl, const reef_fe *W2, const reef_fe *X2, int loc, bool is_mont, reef_jacobian *comm_w2,
+                                      reef_jacobian *comm_t) {
+    constexpr int F = NifsCtx<C>::F;
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    Ctx<C> *key = (Ctx<C> *)key_impl;
+    if (!key || !comm_w2 || !comm_t || (c->num_vars && !W2) || (c->num_io && !X2)) { set_error("null argument"); return REEF_ERR_ARG; }
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    if (!c->running) { set_error("reef_nifs_commit_step: no running instance (reef_nifs_set_running first)"); return REEF_ERR_ARG; }
+    REEF_TRY(nifs_pair_key(c, key, "reef_nifs_commit_step"));
+    REEF_TRY(call.enter());
+    REEF_TRY(nifs_prepare(c));
+    c->committed = false;
+    ++c->gen;
+    fe256 *z2 = c->z2.template as<fe256>();
+    const fe256 *w = (const fe256 *)W2, *x = (const fe256 *)X2;
+    if (loc != REEF_DEVICE) {                // the raw W2 and X2 land in their places in z2 and are converted there; a device W2 is read where it is
+        REEF_TRY(nifs_copy_in(c, z2, W2, c->num_vars, loc));
+        REEF_TRY(nifs_copy_in(c, z2 + c->num_vars + 1, X2, c->num_io, loc));
+        w = z2;
+        x = z2 + c->num_vars + 1;
+    }
+    hipLaunchKernelGGL(k_nifs_import_step<F>, dim3(ceil_div(c->nz, 256)), dim3(256), 0, c->stream, w, x, (u32)c->num_vars, (u32)c->nz, (int)is_mont, z2,
+                       c->w2_row());
+    REEF_HIP_TRY(hipGetLastError());
+    hipStream_t ks = (hipStream_t)v_ctx_stream<C>(key);
+    if (!ks) return REEF_ERR_HIP;
+    REEF_HIP_TRY(hipEventRecord(c->ev, c->stream));
+    REEF_HIP_TRY(hipStreamWaitEvent(ks, c->ev, 0));
+    REEF_TRY((nifs_row_pass<C, NIFS_MODE_T>(c, ks)));
+    c->have_t = c->have_z2 = true;
+    REEF_TRY(nifs_commit_rows(c, key, ks, c->w2_row(), c->num_vars, c->num_cons, comm_w2, comm_t));
+    c->committed = true;
+    return REEF_OK;
+}
+
+// comm_W and comm_E of the running instance as it stands: one kernel exports W and E as integers into rows of their own, the key commits
+// them.  Reads only: no state of the ctx changes, and a prove or an opening in flight goes on.
+template <int C> static reef_status v_nifs_commit_running(void *impl, void *key_impl, reef_jacobian *comm_w, reef_jacobian *comm_e) {
+    constexpr int F = NifsCtx<C>::F;
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    Ctx<C> *key = (Ctx<C> *)key_impl;
+    if (!key || (!comm_w && !comm_e)) { set_error("null argument"); return REEF_ERR_ARG; }
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    if (!c->running) { set_error("reef_nifs_commit_running: no running instance (reef_nifs_set_running first)"); return REEF_ERR_ARG; }
+    REEF_TRY(nifs_pair_key(c, key, "reef_nifs_commit_running"));
+    REEF_TRY(call.enter());
+    const size_t len = c->row_len();
+    if (!c->run.p) {
+        REEF_TRY(c->run.ensure(2 * len * sizeof(fe256)));
+        REEF_HIP_TRY(hipMemsetAsync(c->run.p, 0, 2 * len * sizeof(fe256), c->stream));
+    }
+    fe256 *rows = c->run.template as<fe256>();
+    hipLaunchKernelGGL(k_nifs_export_running<F>, dim3(ceil_div(len, 256)), dim3(256), 0, c->stream, (const fe256 *)c->z1.p, (const fe256 *)c->E.p,
+                       (u32)c->num_vars, (u32)c->num_cons, rows, rows + len);
+    REEF_HIP_TRY(hipGetLastError());
+    hipStream_t ks = (hipStream_t)v_ctx_stream<C>(key);
+    if (!ks) return REEF_ERR_HIP;
+    REEF_HIP_TRY(hipEventRecord(c->ev, c->stream));
+    REEF_HIP_TRY(hipStreamWaitEvent(ks, c->ev, 0));
+    return nifs_commit_rows(c, key, ks, rows, c->num_vars, c->num_cons, comm_w, comm_e);
 }
 
 template <int C> static reef_status v_nifs_fold(void *impl, const reef_fe *r, bool is_mont) {
@@ -303,7 +423,7 @@ template <int C> static reef_status v_nifs_fold(void *impl, const reef_fe *r, bo
     REEF_TRY(call.enter());
     ++c->gen;
     hipLaunchKernelGGL(k_nifs_axpy<F>, dim3(ceil_div(c->nz, 256)), dim3(256), 0, c->stream, c->z1.template as<fe256>(), (const fe256 *)c->z2.p, (u32)c->nz, r_int);
-    hipLaunchKernelGGL(k_nifs_axpy<F>, dim3(ceil_div(c->num_cons, 256)), dim3(256), 0, c->stream, c->E.template as<fe256>(), (const fe256 *)c->T.p,
+    hipLaunchKernelGGL(k_nifs_axpy<F>, dim3(ceil_div(c->num_cons, 256)), dim3(256), 0, c->stream, c->E.template as<fe256>(), (const fe256 *)c->t_row(),
                        (u32)c->num_cons, r_sq);
     REEF_HIP_TRY(hipGetLastError());
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -321,7 +441,7 @@ template <int C> static reef_status v_nifs_read(void *impl, int which, size_t co
     switch (which) {
     case 0: src = c->z1.template as<fe256>(); len = c->num_vars; break;
     case 1: src = c->E.template as<fe256>(); len = c->num_cons; break;
-    case 2: src = c->T.template as<fe256>(); len = c->num_cons; break;
+    case 2: src = c->t_row(); len = c->num_cons; break;
     case 3: src = c->z1.template as<fe256>() + c->num_vars; len = 1; break;
     case 4: src = c->z1.template as<fe256>() + c->num_vars + 1; len = c->num_io; break;
     default: set_error("reef_nifs_read: which must be 0 (W), 1 (E), 2 (T), 3 (u) or 4 (X)"); return REEF_ERR_ARG;
@@ -356,9 +476,29 @@ template <int C> static reef_status v_nifs_check(void *impl, uint64_t *violation
     return REEF_OK;
 }
 
+// AZ2 o BZ2 == CZ2 on the fresh instance (W2, 1, X2) of the last commit_T / commit_step: the row pass over z2.  Reads only.
+template <int C> static reef_status v_nifs_check_fresh(void *impl, uint64_t *violations, uint64_t *first_bad_row) {
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    if (!c->have_z2) { set_error("reef_nifs_check_fresh: no fresh instance (reef_nifs_commit_T or reef_nifs_commit_step first)"); return REEF_ERR_ARG; }
+    REEF_TRY(call.enter());
+    REEF_TRY(nifs_prepare(c));
+    const u32 init[2] = {0u, 0xffffffffu};
+    REEF_HIP_TRY(hipMemcpyAsync(c->counters.p, init, sizeof init, hipMemcpyHostToDevice, c->stream));
+    NifsArgs a = nifs_args(c);
+    a.z1 = a.z2;
+    REEF_TRY((nifs_line_pass<C, NIFS_MODE_FRESH>(a, c->rows, c->stream)));
+    u32 got[2] = {0, 0};
+    REEF_HIP_TRY(hipMemcpyAsync(got, c->counters.p, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (violations) *violations = got[0];
+    if (first_bad_row) *first_bad_row = got[0] ? (uint64_t)got[1] : UINT64_MAX;
+    return REEF_OK;
+}
+
 template <int C> NifsVTable make_nifs_vtable() {
     return NifsVTable{v_nifs_create<C>, v_nifs_destroy<C>, v_nifs_set_matrix<C>, v_nifs_set_running<C>, v_nifs_commit_t<C>, v_nifs_fold<C>,
-                      v_nifs_read<C>, v_nifs_check<C>};
+                      v_nifs_read<C>, v_nifs_check<C>, v_nifs_commit_step<C>, v_nifs_commit_running<C>, v_nifs_check_fresh<C>};
 }
 
 }  // namespace reef

@@ -19,12 +19,16 @@
 //
 // Resident vectors (z1, z2, E) hold the internal form, canonical and packed (fe_to_table); T is kept as canonical
 // INTEGERS: that is what the MSM of comm_T reads (is_mont = false), and the fold reads it with a pre-scaled r.
+//
+// The step's two commitments (reef_nifs_commit_step) read one buffer of two rows of max(num_vars, num_cons) canonical integers:
+// row 0 is W2, written by k_nifs_import_step in the pass that converts the raw z2, row 1 is T, written by the MODE_T row pass.
+// MODE_FRESH is MODE_CHECK on the fresh instance (z2, u = 1, E = 0): AZ2 o BZ2 == CZ2.
 
 namespace reef {
 
 static constexpr u32 NIFS_GENERAL = 1u << 31, NIFS_NEG = 1u << 30, NIFS_MAG = 0xffffu;
 static constexpr u32 NIFS_LONG_ROW = 128;        // rows with more entries (A + B + C) go to k_nifs_rows_long, one block each
-enum { NIFS_MODE_T = 0, NIFS_MODE_CHECK = 1, NIFS_MODE_SPARTAN = 2, NIFS_MODE_ABC = 3 };
+enum { NIFS_MODE_T = 0, NIFS_MODE_CHECK = 1, NIFS_MODE_SPARTAN = 2, NIFS_MODE_ABC = 3, NIFS_MODE_FRESH = 4 };
 
 struct NifsMat {
     const u32 *rowptr;       // num_cons + 1
@@ -33,7 +37,7 @@ struct NifsMat {
 };
 struct NifsArgs {
     NifsMat m[3];            // A, B, C
-    const fe256 *z1, *z2;    // num_vars + 1 + num_io each; z[num_vars] = u
+    const fe256 *z1, *z2;    // num_vars + 1 + num_io each; z[num_vars] = u.  MODE_FRESH: z1 is the fresh z2
     const fe256 *E;          // MODE_CHECK
     fe256 *T;                // MODE_T
     u32 num_cons, num_vars;
@@ -67,6 +71,29 @@ __global__ void __launch_bounds__(256) k_nifs_classify(const u32 *__restrict__ c
         store_fe256(side + e, fe_to_table<F>(fe_from_integer<F>(v)));
     }
     ent[e] = make_uint2(cols[e], cls);
+}
+
+// The fresh z2 = W2 || 1 || X2 from the caller's W2 and X2 (raw, in the caller's form; they may be the raw entries of z2 itself:
+// every thread reads its own element before it writes it) in one pass: z2 in internal form for the row pass, and the canonical
+// integers of W2 into w_int (row 0 of the step's commitment rows; its tail beyond num_vars is not touched).
+template <int F>
+__global__ void __launch_bounds__(256) k_nifs_import_step(const fe256 *w, const fe256 *x, u32 num_vars, u32 nz, int is_mont, fe256 *z2,
+                                                          fe256 *__restrict__ w_int) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nz) return;
+    if (i == num_vars) { store_fe256(z2 + i, fe_to_table<F>(fe_one<F>())); return; }
+    const fe256 raw = load_fe256(i < num_vars ? w + i : x + (i - num_vars - 1));
+    store_fe256(z2 + i, fe_to_table<F>(fe_from_caller<F>(raw, is_mont)));
+    if (i < num_vars) store_fe256(w_int + i, is_mont ? fe_abi_to_integer<F>(raw) : fe_pack(fe_canon<F>(fe_unpack(raw))));
+}
+// W (the first num_vars entries of z1) and E of the running instance as canonical integers: the two rows reef_nifs_commit_running
+// commits.  The rows' tails are not touched.
+template <int F>
+__global__ void __launch_bounds__(256) k_nifs_export_running(const fe256 *__restrict__ z1, const fe256 *__restrict__ E, u32 num_vars, u32 num_cons,
+                                                             fe256 *__restrict__ w_int, fe256 *__restrict__ e_int) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < num_vars) store_fe256(w_int + i, fe_to_integer<F>(fe_from_table(load_fe256(z1 + i))));
+    if (i < num_cons) store_fe256(e_int + i, fe_to_integer<F>(fe_from_table(load_fe256(E + i))));
 }
 
 // dst[i] = dst[i] + r * src[i], r pre-scaled so that the product lands in internal form (r R' against an internal src,
@@ -139,8 +166,8 @@ __device__ __forceinline__ void nifs_dot(const NifsMat &m, u32 b, u32 e, u32 ste
     for (int v = 0; v < NV; ++v) out[v] = nifs_reduce<F>(acc[v], k254);
 }
 
-// The row's epilogue on its canonical dot products d: MODE_T d = {AZ1, AZ2, BZ1, BZ2, CZ1, CZ2}, MODE_CHECK and MODE_SPARTAN
-// d = {AZ, BZ, CZ}.
+// The row's epilogue on its canonical dot products d: MODE_T d = {AZ1, AZ2, BZ1, BZ2, CZ1, CZ2}, MODE_CHECK, MODE_FRESH and
+// MODE_SPARTAN d = {AZ, BZ, CZ}.
 template <int F, int MODE>
 __device__ __forceinline__ void nifs_epilogue(const NifsArgs &a, u32 row, const fe *d, const fe &u1) {
     if constexpr (MODE == NIFS_MODE_T) {
@@ -158,6 +185,15 @@ __device__ __forceinline__ void nifs_epilogue(const NifsArgs &a, u32 row, const 
             atomicAdd(a.viol, 1u);
             atomicMin(a.first_bad, row);
         }
+    } else if constexpr (MODE == NIFS_MODE_FRESH) {
+        const fe diff = fe_canon<F>(fe_sub<F, 2>(fe_mul<F>(d[0], d[1]), d[2]));
+        bool nz = false;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) nz |= diff.l[i] != 0;
+        if (nz) {
+            atomicAdd(a.viol, 1u);
+            atomicMin(a.first_bad, row);
+        }
     } else if constexpr (MODE == NIFS_MODE_SPARTAN) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) store_fe256(a.out[k] + row, fe_pack(d[k]));
@@ -168,9 +204,9 @@ __device__ __forceinline__ void nifs_epilogue(const NifsArgs &a, u32 row, const 
         store_fe256(a.out[0] + row + (row >= a.num_vars ? a.shift : 0u), fe_to_table<F>(v));
     }
 }
-// u of the running instance (MODE_ABC has no z: its `z1` is eq(r_x), and the epilogue takes no u)
+// u of the running instance (MODE_ABC has no z: its `z1` is eq(r_x), and the epilogue takes no u; nor does MODE_FRESH's, u2 = 1)
 template <int MODE> __device__ __forceinline__ fe nifs_u1(const NifsArgs &a) {
-    return MODE == NIFS_MODE_ABC ? fe_zero() : fe_from_table(load_fe256(a.z1 + a.num_vars));
+    return MODE == NIFS_MODE_ABC || MODE == NIFS_MODE_FRESH ? fe_zero() : fe_from_table(load_fe256(a.z1 + a.num_vars));
 }
 
 // One thread per row; rows with more than NIFS_LONG_ROW entries are left to k_nifs_rows_long.  The products of A and B are

@@ -14,8 +14,8 @@ import numpy as np
 
 from . import _ffi
 from ._fe import _Handle, _arr
-from ._ffi import REEF_HOST, check
-from .msm import MsmContext, curve_id
+from ._ffi import REEF_DEVICE, REEF_HOST, check
+from .msm import DeviceBuffer, MsmContext, curve_id
 
 W, E, T, U, X = 0, 1, 2, 3, 4          # reef_nifs_read: which
 A, B, C = 0, 1, 2                      # reef_nifs_set_matrix: which
@@ -26,6 +26,16 @@ def _fe(arr, n: Optional[int] = None) -> np.ndarray:
     if n is not None and a.shape[0] != n:
         raise ValueError(f"expected {n} field elements, got {a.shape[0]}")
     return a
+
+
+def _fe_in(arr, n: int):
+    """(loc, address, keep-alive) of n field elements: an array of canonical limbs, or a DeviceBuffer of exactly that many."""
+    if isinstance(arr, DeviceBuffer):
+        if arr.nbytes != 32 * n:
+            raise ValueError(f"expected {n} field elements, the device buffer holds {arr.nbytes // 32}")
+        return REEF_DEVICE, arr.ptr, arr
+    a = _fe(arr, n)
+    return REEF_HOST, a.ctypes.data, a
 
 
 class Nifs(_Handle):
@@ -63,8 +73,31 @@ class Nifs(_Handle):
         check(self._lib.reef_nifs_commit_T(self._h, key._h, wa.ctypes.data, xa.ctypes.data, REEF_HOST, is_mont, out.ctypes.data))
         return out
 
+    def commit_step(self, key: MsmContext, w2, x2, *, is_mont: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """commit_t and the fresh witness's commitment from one upload of w2: (comm_W2, comm_T), uint64[12] Jacobian each, no blinds.
+        w2 and x2 are arrays, or DeviceBuffers (both of one kind)."""
+        wloc, wp, _wk = _fe_in(w2, self.num_vars)
+        xloc, xp, _xk = _fe_in(x2, self.num_io)
+        if wloc != xloc:
+            raise ValueError("w2 and x2 must both be host arrays or both DeviceBuffers")
+        cw, ct = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
+        check(self._lib.reef_nifs_commit_step(self._h, key._h, wp, xp, wloc, is_mont, cw.ctypes.data, ct.ctypes.data))
+        return cw, ct
+
+    def commit_running(self, key: MsmContext) -> Tuple[np.ndarray, np.ndarray]:
+        """(comm_W, comm_E) of the running instance as it stands, uint64[12] Jacobian each, no blinds; reads only."""
+        cw, ce = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
+        check(self._lib.reef_nifs_commit_running(self._h, key._h, cw.ctypes.data, ce.ctypes.data))
+        return cw, ce
+
+    def check_fresh(self) -> Tuple[int, Optional[int]]:
+        """(rows of the last fresh instance (W2, 1, X2) violating AZ o BZ == CZ, the first of them or None)."""
+        v, f = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.reef_nifs_check_fresh(self._h, ctypes.byref(v), ctypes.byref(f)))
+        return v.value, (None if v.value == 0 else f.value)
+
     def fold(self, r: int, *, is_mont: bool = False) -> None:
-        """W, E, u, X of the running instance folded with the last commit_t's fresh instance and T."""
+        """W, E, u, X of the running instance folded with the last commit_t's / commit_step's fresh instance and T."""
         ra = _arr([r])
         check(self._lib.reef_nifs_fold(self._h, ra.ctypes.data, is_mont))
 

@@ -9,6 +9,7 @@ run_prove() is the harness's prove leg: every device row of one proof on synthet
 from __future__ import annotations
 
 import ctypes
+import functools
 import json
 import os
 
@@ -78,14 +79,10 @@ def _phase_of(text: str):
     return None
 
 
-def run_prove(config: str = "cfg3", tamper: str | None = None, tables: bool = False, shapes_path: str | None = None) -> dict:
-    """The prove leg: every device row of one proof (NIFS steps, the last fold, Spartan sum-checks and the batched opening on both
-    curves, the Hyrax consistency argument) through the C ABI, then checked with the verifier's equations on the host.  Returns the
-    JSON line as a dict.  A rejected proof raises ProofRejected naming the phase; tamper=<phase> alters one recorded value before
-    the checks, so that it must."""
+def _prove(config: str, tamper: str | None, tables: bool, shapes_path: str | None, paired: bool) -> dict:
     if tamper is not None and tamper not in PROVE_PHASES:
         raise ValueError(f"tamper must be one of {PROVE_PHASES}")
-    flags = " ".join(([f"tamper={tamper}"] if tamper else []) + (["tables"] if tables else []))
+    flags = " ".join(([f"tamper={tamper}"] if tamper else []) + (["tables"] if tables else []) + (["paired"] if paired else []))
     buf = ctypes.create_string_buffer(32768)
     rc = _load().reef_replay_run_prove((shapes_path or SHAPES_PATH).encode(), config.encode(), flags.encode(), buf, len(buf))
     text = buf.value.decode(errors="replace")
@@ -95,6 +92,22 @@ def run_prove(config: str = "cfg3", tamper: str | None = None, tables: bool = Fa
             raise ProofRejected(f"reef_replay_run_prove({config}): {text}", phase)
         raise RuntimeError(f"reef_replay_run_prove({config}) failed with {rc}: {text}")
     return json.loads(text)
+
+
+def _run_prove(config: str = "cfg3", tamper: str | None = None, tables: bool = False, shapes_path: str | None = None) -> dict:
+    """The prove leg: every device row of one proof (NIFS steps, the last fold, Spartan sum-checks and the batched opening on both
+    curves, the Hyrax consistency argument) through the C ABI, then checked with the verifier's equations on the host.  Returns the
+    JSON line as a dict.  A rejected proof raises ProofRejected naming the phase; tamper=<phase> alters one recorded value before
+    the checks, so that it must.  One keyword-only option beside the four parameters (which tests/test_replay_prove_host.py pins):
+    paired=True takes every step's comm_W and comm_T from one reef_nifs_commit_step and the first comm_W from reef_nifs_commit_running,
+    and checks the folded instance's comm_W and comm_E from the device against the host's point operations; the line then carries
+    "paired": true."""
+    return _prove(config, tamper, tables, shapes_path, False)
+
+
+@functools.wraps(_run_prove, assigned=("__module__", "__doc__", "__annotations__"))
+def run_prove(config: str = "cfg3", tamper: str | None = None, tables: bool = False, shapes_path: str | None = None, *, paired: bool = False) -> dict:
+    return _prove(config, tamper, tables, shapes_path, paired)
 
 
 def check_selftest(tamper: str | None = None) -> dict:
