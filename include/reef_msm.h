@@ -875,6 +875,12 @@ reef_status reef_msm_ctx_last_timing(reef_msm_ctx *ctx, float *total_ms, float *
  * ctx's stream around each launch; the call waits for MSMs still in flight). */
 reef_status reef_msm_ctx_timing_stats(reef_msm_ctx *ctx, int reset, uint64_t *calls, double *total_ms,
                                       double *accumulate_ms);
+/* Which form the row / column sums of the bucket reduction took, counted over the bucket-pipeline MSMs
+ * issued on this ctx since the last reset: four waves per sum (the shortest chain: what a lone MSM
+ * gets), or several sums per wave (fewer instructions: taken by MSMs with a bucket matrix of 2^16 or
+ * more buckets while another caller is at work on the device).  Diagnostics; both give the same point. */
+reef_status reef_msm_ctx_rowcol_forms(reef_msm_ctx *ctx, int reset, uint64_t *latency_calls,
+                                      uint64_t *throughput_calls);
 /* Sum of n Jacobian points, enqueued on the ctx's stream (device buffers only): combines the
  * per-rank partial MSMs after an RCCL all-gather ordered on the same stream. */
 reef_status reef_msm_ctx_sum_points(reef_msm_ctx *ctx, const reef_jacobian *in, size_t n, reef_jacobian *out);

@@ -149,6 +149,7 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_msm_ctx_enable_timing": (c_int, [vp, c_int]),
         "reef_msm_ctx_set_window_split": (c_int, [vp, c_uint32, c_uint32]),
         "reef_msm_ctx_timing_stats": (c_int, [vp, c_int, POINTER(c_uint64), POINTER(c_double), POINTER(c_double)]),
+        "reef_msm_ctx_rowcol_forms": (c_int, [vp, c_int, POINTER(c_uint64), POINTER(c_uint64)]),
         "reef_msm_ctx_sum_points": (c_int, [vp, vp, c_size_t, vp]),
         "reef_msm_ctx_plan": (c_int, [vp, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]),
         "reef_msm_ctx_byte_tables": (c_int, [vp]),

@@ -338,6 +338,9 @@ reef_status reef_msm_ctx_enable_timing(reef_msm_ctx *ctx, int on) {
 reef_status reef_msm_ctx_timing_stats(reef_msm_ctx *ctx, int reset, uint64_t *calls, double *total_ms, double *accumulate_ms) {
     return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_timing_stats(impl, reset, calls, total_ms, accumulate_ms); });
 }
+reef_status reef_msm_ctx_rowcol_forms(reef_msm_ctx *ctx, int reset, uint64_t *latency_calls, uint64_t *throughput_calls) {
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_rowcol_forms(impl, reset, latency_calls, throughput_calls); });
+}
 reef_status reef_msm_ctx_sum_points(reef_msm_ctx *ctx, const reef_jacobian *in, size_t n, reef_jacobian *out) {
     return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->ctx_sum_points(impl, in, n, out); });
 }

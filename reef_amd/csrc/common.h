@@ -132,6 +132,11 @@ struct PoolNoGrowth {
     PoolNoGrowth() : prev(t_pool_no_growth) { t_pool_no_growth = true; }
     ~PoolNoGrowth() { t_pool_no_growth = prev; }
 };
+// Callers at work per device: the sum of PoolStream::active over the device's streams, kept beside it wherever it is counted up or down, so
+// that a hot call can ask "is anybody else at work on this device right now?" with one relaxed load.  The pool's stream list grows under the
+// pool lock and is not walked without it (engine.inc, rowcol_lanes: the form an MSM's row / column sums take).
+inline std::atomic<int> g_callers_at_work[64];
+inline std::atomic<int> &callers_at_work(int device) { return g_callers_at_work[(unsigned)device & 63u]; }
 struct PoolStream {
     hipStream_t s = nullptr;
     int device = 0;
@@ -215,7 +220,7 @@ struct StreamPool {
     static void count_in(PoolStream *p, bool for_pin) {
         if (for_pin) p->pins.fetch_add(1, std::memory_order_relaxed);
         else if (t_pool_no_growth) p->background.fetch_add(1, std::memory_order_relaxed);
-        else p->active.fetch_add(1, std::memory_order_relaxed);
+        else { p->active.fetch_add(1, std::memory_order_relaxed); callers_at_work(p->device).fetch_add(1, std::memory_order_relaxed); }
     }
     // counted for the caller from here on (*background: as a no-growth thread): leave() with the same flag when idle again
     reef_status pick(int device, PoolStream **out, bool *background = nullptr) {
@@ -237,7 +242,7 @@ struct StreamPool {
     static void leave(PoolStream *p, bool background = false) {
         if (!p) return;
         if (background) p->background.fetch_sub(1, std::memory_order_relaxed);
-        else p->active.fetch_sub(1, std::memory_order_relaxed);
+        else { p->active.fetch_sub(1, std::memory_order_relaxed); callers_at_work(p->device).fetch_sub(1, std::memory_order_relaxed); }
     }
     // Creating a stream is expensive while the runtime still has hardware queues to create (several ms each, measured: the first
     // concurrent use of three contexts read 23 ms instead of 6), so it is done where contexts are CREATED, never in a hot call if
@@ -306,6 +311,7 @@ struct StreamLease {
                     if (a >= StreamPool::RESERVED) { std::this_thread::yield(); a = ps->active.load(std::memory_order_relaxed); continue; }
                     if (ps->active.compare_exchange_weak(a, a + 1, std::memory_order_acq_rel)) break;
                 }
+                callers_at_work(ps->device).fetch_add(1, std::memory_order_relaxed);
                 bg = false;
             }
             else REEF_TRY(stream_pool().pick(device, &ps, &bg));
@@ -440,6 +446,7 @@ struct CurveVTable {
     reef_status (*ctx_enable_timing)(void *impl, int on);
     reef_status (*ctx_window_split)(void *impl, uint32_t rank, uint32_t world);
     reef_status (*ctx_timing_stats)(void *impl, int reset, uint64_t *calls, double *total_ms, double *acc_ms);
+    reef_status (*ctx_rowcol_forms)(void *impl, int reset, uint64_t *latency_calls, uint64_t *throughput_calls);
     reef_status (*ctx_sum_points)(void *impl, const reef_jacobian *in, size_t n, reef_jacobian *out);
     reef_status (*ctx_plan)(void *impl, uint32_t *c, uint32_t *w, uint32_t *g, uint32_t *t);
     int (*ctx_byte_tables)(void *impl);

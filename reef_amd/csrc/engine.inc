@@ -110,9 +110,12 @@ template <int C> struct Ctx {
     bool h_valid = false;
     bool coop = true;                        // tail kernels with four waves per group operation (ec_coop.h); REEF_MSM_COOP=0: one wave
     DevBuf wsum;                             // coop bucket reduction: weighted and plain sums of the rows / columns per group
+    int rowcol_force = -1;                   // row / column sums of a coop ctx: -1 by the rule (rowcol_lanes), 0 always four waves per sum, 16 / 32 / 64 always
+                                             // that many lanes per sum (REEF_MSM_ROWCOL)
+    u64 rowcol_calls[2] = {};                // MSMs of a coop ctx whose row / column sums took the latency form [0] / the throughput form [1]
     // hipGraphs of the bucket pipeline, one per (scalars pointer, result pointer, n, ...) this ctx keeps seeing (REEF_MSM_GRAPH=1)
     struct GraphEntry {
-        const void *scalars; void *out; size_t n; bool is_mont; u32 wr, ww; uint64_t gen; int seen;
+        const void *scalars; void *out; size_t n; bool is_mont; u32 wr, ww; int rowcol; uint64_t gen; int seen;
         hipGraph_t graph; hipGraphExec_t exec;
     };
     std::vector<GraphEntry> graphs;
@@ -534,6 +537,10 @@ template <int C> static reef_status ctx_new(Ctx<C> **out, const reef_msm_opts *o
     Ctx<C> *ctx = new Ctx<C>();
     if (const char *e = exp_env("REEF_MSM_SORT2")) ctx->two_level = atoi(e);   // tuning knob: -1 by size (default), 0 off, 1 on
     if (const char *e = exp_env("REEF_MSM_COOP")) ctx->coop = atoi(e) != 0;
+    if (const char *e = exp_env("REEF_MSM_ROWCOL")) {  // A/B: 0 = the four-wave row / column sums always, 16 / 32 / 64 = that many lanes per sum always
+        const int v = atoi(e);
+        if (v == 0 || v == 16 || v == 32 || v == 64) ctx->rowcol_force = v;
+    }
     if (opts) {
         ctx->opt_c = opts->window_bits;
         ctx->opt_G = opts->bucket_groups;
@@ -593,6 +600,7 @@ template <int C> static reef_status v_ctx_clone(void **impl, void *src_) {
     ctx->wsplit_rank = src->wsplit_rank;
     ctx->wsplit_world = src->wsplit_world;
     ctx->coop = src->coop;
+    ctx->rowcol_force = src->rowcol_force;
     *impl = ctx;
     return REEF_OK;
 }
@@ -691,6 +699,14 @@ template <int C> static reef_status v_ctx_timing_stats(void *impl, int reset, ui
     if (reset) { ctx->timed_calls = 0; ctx->sum_total_ms = ctx->sum_accum_ms = 0; }
     return REEF_OK;
 }
+template <int C> static reef_status v_ctx_rowcol_forms(void *impl, int reset, uint64_t *latency_calls, uint64_t *throughput_calls) {
+    Ctx<C> *ctx = (Ctx<C> *)impl;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (latency_calls) *latency_calls = ctx->rowcol_calls[0];
+    if (throughput_calls) *throughput_calls = ctx->rowcol_calls[1];
+    if (reset) ctx->rowcol_calls[0] = ctx->rowcol_calls[1] = 0;
+    return REEF_OK;
+}
 // Sum of n Jacobian points on the ctx's own stream (device buffers), e.g. right after an
 // RCCL all-gather of per-rank partial MSMs that was ordered on the same stream.
 template <int C> static reef_status v_ctx_sum_points(void *impl, const reef_jacobian *in, size_t n, reef_jacobian *out) {
@@ -764,9 +780,30 @@ static void launch_partial_merge(Ctx<C> *ctx, u32 nchunks0, xyzz_mem *acc, bool 
     }
 }
 
+// The form the row / column sums of the bucket reduction take in this call: 0 = one four-wave workgroup per sum (k_reduce_rowcol_coop), else
+// the lanes per sum of k_reduce_rowcol.  The four-wave form has the shortest chain (10 shared additions of 3.7 us) and issues 38.7 M VALU
+// wave-instructions per MSM at c = 17; with 64 / 32 / 16 lanes per sum it is 27.1 / 17.2 / 13.0 M on a chain of 9 / 12 / 19 additions of
+// 7.2 us.  A caller who waits for ONE MSM sees the chain; a device that other work fills sees only the issue slots: with three MSMs in
+// flight every lane count beat the four-wave form in every run, 32 by the most (+1.4 %).  So that form runs where both hold: the bucket
+// matrix is large (NB >= 2^16, plans with c >= 17: below, an MSM is a latency chain the IPA rounds wait for), and the device is shared at the
+// moment of the launch: another caller is at work on it (profiles/r17_rowcol_forms.txt).  Work this ctx itself still has queued does NOT
+// count: it is on the same stream, the new MSM runs after it and not beside it, so a lone caller that queues MSMs back to back would pay the
+// longer chain in full.  (A caller counts from its first enqueue to the wait that finds it idle: a ctx whose device-side result was never
+// waited for through the library still counts, and the rule then errs towards the throughput form.)  Both forms return the same group
+// element.  A ctx without coop tails (REEF_MSM_COOP=0) keeps every tail on one wave: 64 lanes per sum.
+static constexpr u32 ROWCOL_SHARED_MIN_BUCKETS = 1u << 16;
+static constexpr int ROWCOL_SHARED_LANES = 32;
+template <int C> static int rowcol_lanes(const Ctx<C> *ctx, u32 NB) {
+    if (!ctx->coop) return 64;
+    if (ctx->rowcol_force >= 0) return ctx->rowcol_force;
+    if (NB < ROWCOL_SHARED_MIN_BUCKETS) return 0;
+    const bool shared = callers_at_work(ctx->key->device).load(std::memory_order_relaxed) > 1;   // this ctx counts as one
+    return shared ? ROWCOL_SHARED_LANES : 0;
+}
+
 template <int C>
 static reef_status run_core(Ctx<C> *ctx, const fe256 *d_scalars, const CorePlan &pl, bool is_mont, const fe256 *d_blinds,
-                            const affine256 *d_h, jacobian256 *d_out, const xyzz_mem **group_sums_out = nullptr) {
+                            const affine256 *d_h, jacobian256 *d_out, const xyzz_mem **group_sums_out = nullptr, int rowcol = -1) {
     hipStream_t st = ctx->stream;
     const u64 N = (u64)pl.rows * pl.row_len;
     const u32 NB = 1u << (pl.c - 1);
@@ -963,11 +1000,22 @@ static reef_status run_core(Ctx<C> *ctx, const fe256 *d_scalars, const CorePlan 
     // only.  What a window would be worth if its bucket reduction were free: the upper bound on anything a faster reduction can buy
     // (profiles/r06_free_reduction_bound.txt: VERDICT r5 item 3's kill criterion, measured before any kernel was written).
     static const int skip_reduce = [] { const char *e = exp_env("REEF_MSM_SKIP_REDUCE"); return e ? atoi(e) : 0; }();
+    const int lanes = rowcol >= 0 ? rowcol : rowcol_lanes<C>(ctx, NB);   // rc_waves sums: on four waves each (0), or `lanes` lanes each
+    auto launch_rowcol = [&](auto lps) {
+        constexpr int LPS = decltype(lps)::value;
+        hipLaunchKernelGGL((k_reduce_rowcol<C, LPS>), dim3(ceil_div(ceil_div(rc_waves, 64u / LPS), 4)), dim3(256), 0, st, ctx->bucket_acc.template as<xyzz_mem>(),
+                           bstart, c1, c2, groups_total, ctx->rowcol.template as<xyzz_mem>());
+    };
     if (skip_reduce == 1) {
         if (group_sums_out) *group_sums_out = gsum;
     } else if (ctx->coop) {
         REEF_TRY(ctx->wsum.ensure((u64)groups_total * 4 * sizeof(xyzz_mem)));
-        if (skip_reduce != 2)
+        ++ctx->rowcol_calls[lanes != 0];
+        if (skip_reduce == 2) {}
+        else if (lanes == 16) launch_rowcol(std::integral_constant<int, 16>{});
+        else if (lanes == 32) launch_rowcol(std::integral_constant<int, 32>{});
+        else if (lanes == 64) launch_rowcol(std::integral_constant<int, 64>{});
+        else
         hipLaunchKernelGGL(k_reduce_rowcol_coop<C>, dim3(rc_waves), dim3(256), 0, st, ctx->bucket_acc.template as<xyzz_mem>(), bstart, c1, c2,
                            groups_total, ctx->rowcol.template as<xyzz_mem>());
         hipLaunchKernelGGL(k_reduce_weighted_coop<C>, dim3(groups_total, 2), dim3(256), 0, st, ctx->rowcol.template as<xyzz_mem>(), c1, c2,
@@ -975,9 +1023,7 @@ static reef_status run_core(Ctx<C> *ctx, const fe256 *d_scalars, const CorePlan 
         hipLaunchKernelGGL(k_reduce_combine_coop<C>, dim3(groups_total), dim3(256), 0, st, ctx->wsum.template as<xyzz_mem>(), c2, gsum,
                            direct ? d_out : (jacobian256 *)nullptr);
     } else {
-        if (skip_reduce != 2)
-        hipLaunchKernelGGL(k_reduce_rowcol<C>, dim3(ceil_div(rc_waves, 4)), dim3(256), 0, st, ctx->bucket_acc.template as<xyzz_mem>(),
-                           bstart, c1, c2, groups_total, ctx->rowcol.template as<xyzz_mem>());
+        if (skip_reduce != 2) launch_rowcol(std::integral_constant<int, 64>{});
         hipLaunchKernelGGL(k_reduce_weighted<C>, dim3(groups_total), dim3(128), 0, st, ctx->rowcol.template as<xyzz_mem>(), c1, c2, gsum,
                            direct ? d_out : (jacobian256 *)nullptr);
     }
@@ -1049,6 +1095,7 @@ template <int C>
 static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const CorePlan &pl, bool is_mont, jacobian256 *d_out) {
     hipStream_t st = ctx->stream;
     const uint64_t gen = g_devbuf_gen.load();
+    const int rowcol = rowcol_lanes<C>(ctx, 1u << (pl.c - 1));     // a captured chain holds ONE form of the row / column sums: part of the key
     typename Ctx<C>::GraphEntry *hit = nullptr;
     for (size_t i = 0; i < ctx->graphs.size();) {
         auto &e = ctx->graphs[i];
@@ -1058,10 +1105,11 @@ static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const C
             ctx->graphs.erase(ctx->graphs.begin() + i);
             continue;
         }
-        if (e.scalars == d_scalars && e.out == d_out && e.n == pl.row_len && e.is_mont == is_mont && e.wr == ctx->wsplit_rank && e.ww == ctx->wsplit_world) hit = &e;
+        if (e.scalars == d_scalars && e.out == d_out && e.n == pl.row_len && e.is_mont == is_mont && e.wr == ctx->wsplit_rank && e.ww == ctx->wsplit_world && e.rowcol == rowcol) hit = &e;
         ++i;
     }
     if (hit && hit->exec) {
+        if (ctx->coop) ++ctx->rowcol_calls[rowcol != 0];
         REEF_HIP_TRY(hipGraphLaunch(hit->exec, st));
         return REEF_OK;
     }
@@ -1073,7 +1121,7 @@ static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const C
         // reserved stream to nobody, and a context pinned to it waits the microseconds the capture lasts (common.h).  Otherwise this
         // call runs the plain path and the capture is tried again at the next one.
         PoolStream *ps = ctx->lease.ps;
-        if (!ps || ctx->lease.bg || !stream_pool().try_reserve(ps, ctx->lease.pinned ? 1 : 0)) return run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out);
+        if (!ps || ctx->lease.bg || !stream_pool().try_reserve(ps, ctx->lease.pinned ? 1 : 0)) return run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out, nullptr, rowcol);
         hit->seen = 2;
         struct Reserve {                                      // until the capture has ended
             PoolStream *p;
@@ -1081,7 +1129,7 @@ static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const C
             ~Reserve() { StreamPool::unreserve(p); }
         } reserve(ps);
         if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const reef_status rs = run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out);
+            const reef_status rs = run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out, nullptr, rowcol);
             hipGraph_t g = nullptr;
             const hipError_t ee = hipStreamEndCapture(st, &g);
             if (rs == REEF_OK && ee == hipSuccess && g && g_devbuf_gen.load() == gen && hipGraphInstantiate(&hit->exec, g, nullptr, nullptr, 0) == hipSuccess) {
@@ -1095,9 +1143,9 @@ static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const C
         } else {
             (void)hipGetLastError();
         }
-        return run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out);   // capture refused: the plain path, from now on
+        return run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out, nullptr, rowcol);   // capture refused: the plain path, from now on
     }
-    REEF_TRY(run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out));
+    REEF_TRY(run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out, nullptr, rowcol));
     if (!hit) {
         if (ctx->graphs.size() >= 4) {
             auto &v = ctx->graphs.front();
@@ -1105,7 +1153,7 @@ static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const C
             if (v.graph) (void)hipGraphDestroy(v.graph);
             ctx->graphs.erase(ctx->graphs.begin());
         }
-        ctx->graphs.push_back({d_scalars, d_out, pl.row_len, is_mont, ctx->wsplit_rank, ctx->wsplit_world, g_devbuf_gen.load(), 1, nullptr, nullptr});
+        ctx->graphs.push_back({d_scalars, d_out, pl.row_len, is_mont, ctx->wsplit_rank, ctx->wsplit_world, rowcol, g_devbuf_gen.load(), 1, nullptr, nullptr});
     }
     return REEF_OK;
 }
@@ -2073,7 +2121,7 @@ static reef_status plan_for(size_t n, uint32_t c_opt, uint32_t g_opt, uint32_t *
 
 template <int C> static CurveVTable make_vtable() {
     return CurveVTable{v_ctx_create<C>, v_ctx_rekey<C>, v_ctx_clone<C>, v_ctx_attach<C>, v_ctx_destroy<C>, v_ctx_sync<C>, v_ctx_stream<C>,
-                       v_ctx_timing<C>, v_ctx_enable_timing<C>, v_ctx_window_split<C>, v_ctx_timing_stats<C>, v_ctx_sum_points<C>, v_ctx_plan<C>, v_ctx_byte_tables<C>, v_msm<C>, v_msm_rows<C>, v_msm_rows_symbols<C>, v_msm_rows_symbols_wide<C>, v_ipa_cross<C>, v_msm_folded<C>, v_fold<C>, v_normalize<C>, v_sum_points<C>,
+                       v_ctx_timing<C>, v_ctx_enable_timing<C>, v_ctx_window_split<C>, v_ctx_timing_stats<C>, v_ctx_rowcol_forms<C>, v_ctx_sum_points<C>, v_ctx_plan<C>, v_ctx_byte_tables<C>, v_msm<C>, v_msm_rows<C>, v_msm_rows_symbols<C>, v_msm_rows_symbols_wide<C>, v_ipa_cross<C>, v_msm_folded<C>, v_fold<C>, v_normalize<C>, v_sum_points<C>,
                        v_gen_bases<C>, v_gen_scalars<C>, v_test_field_op<C>, v_test_ec_op<C>, v_bench_fmul<C>,
                        v_sc_create<C>, v_sc_destroy<C>, v_sc_set<C>, v_sc_set_parts<C>, v_sc_read<C>, v_sc_coeffs<C>, v_sc_fold<C>, v_sc_fold_coeffs<C>, v_sc_gen_eq<C>, v_sc_reset<C>, v_sc_sync<C>, v_mle_bound<C>, v_merkle_commit<C>, v_derive_generators<C>, plan_for, v_decompress<C>, doc_check, doc_transform};
 }

@@ -211,9 +211,6 @@ static __global__ void __launch_bounds__(1024) k_count(const u32 *__restrict__ d
 // k_recode and k_count as one launch, for a single MSM whose histogram fits one LDS part (one bucket group or coarse
 // pass, <= 32768 keys): the thread that recodes a scalar also counts its digits.  One kernel boundary less on the chain
 // a mid-size MSM waits for; the digit planes are still written (the scatter pass reads them).
-// (amdgpu_num_vgpr(32), here and on k_fine_scatter: a 1024-thread workgroup is four waves per SIMD, and two resident k_accum0 waves
-// leave 512 - 2 * 184 = 144 registers per lane there -- at 32 registers per wave the sort's workgroups fit NEXT to the running
-// accumulation of another MSM, at 40 they wait for it to drain; round 4)
 template <int C>
 __global__ void __launch_bounds__(1024) k_recode_count(const fe256 *__restrict__ scalars, int is_mont, u32 c, u32 wrank, u32 wworld, SortShape sh,
                                                       u32 *__restrict__ dig, u32 *__restrict__ counts) {
@@ -922,44 +919,51 @@ __global__ void __launch_bounds__(256) k_merge_chunks(const u32 *__restrict__ in
 // Same two additions per bucket as a running sum, but the dependent chain is two short
 // weighted sums over 2^(c/2) elements instead of one over 2^c: the tail of an MSM is a
 // latency chain of ~5 us group operations, so depth is what matters.
-// k_reduce_rowcol: one wave per row or column sum.  Grid: groups * (rows + cols) waves.
-template <int C>
+// k_reduce_rowcol: LPS lanes per row or column sum, 64 / LPS sums per wave.  Grid: ceil(groups * (rows + cols) * LPS / 64) waves.
+// LPS = 64 is one wave per sum, the shortest chain a lone wave offers (REEF_MSM_COOP=0).  LPS = 32 / 16 are the THROUGHPUT forms
+// run_core takes for a large bucket matrix while the device is shared: a lane first sums its count / LPS strided elements, the lane
+// tree then has log2(LPS) levels inside the sum's lane group -- fewer steps with idle lanes, and none of the exchange the four-wave
+// form pays per addition.  The chain is longer (9 / 12 / 19 dependent additions at count = 256), which only a caller who waits for
+// this one MSM sees.  As in k_reduce_rowcol_coop the additions go through ONE call site in a step loop (instruction cache).
+template <int C, int LPS>
 __global__ void __launch_bounds__(256) k_reduce_rowcol(const xyzz_mem *__restrict__ bucket_acc,
                                                       const u32 *__restrict__ bucket_start, u32 c1, u32 c2, u32 groups,
                                                       xyzz_mem *__restrict__ rowcol) {
+    static_assert(LPS == 64 || LPS == 32 || LPS == 16, "lanes per sum");
     latency_critical();
-    const u32 rows = 1u << c1, cols = 1u << c2, per_group = rows + cols;
+    constexpr u32 SPW = 64 / LPS;                      // sums per wave
+    const u32 rows = 1u << c1, cols = 1u << c2, per_group = rows + cols, sums = groups * per_group;
     const u32 wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (wave >= groups * per_group) return;
-    const u32 g = wave / per_group, idx = wave - g * per_group;
+    const int lane = threadIdx.x & 63, l = lane & (LPS - 1);      // l: the lane's place in its sum's group
+    if (wave * SPW >= sums) return;                    // the whole wave leaves together
+    const u32 sum = wave * SPW + (u32)lane / LPS;
+    const bool valid = sum < sums;                     // the last wave may hold fewer than SPW sums
+    const u32 g = sum / per_group, idx = sum - g * per_group;
     const bool is_row = idx < rows;
     const u32 key0 = g << (c1 + c2);
-    const u32 count = is_row ? cols : rows;            // elements of this sum
+    const u32 count = valid ? (is_row ? cols : rows) : 0u;        // elements of this lane's sum (rows and columns may share a wave)
     const u32 first = is_row ? key0 + (idx << c2) : key0 + (idx - rows);
     const u32 stride = is_row ? 1u : cols;
     xyzz acc = xyzz_identity();
     bool live = false;
-    for (u32 e = lane; e < count; e += 64) {           // same trip count for every lane that has work
-        const u32 key = first + e * stride;
-        const bool nonempty = bucket_start[key + 1] != bucket_start[key];
-        if (__any(nonempty)) {
-            xyzz b = xyzz_identity();
-            if (nonempty) b = load_xyzz(bucket_acc + key);
-            if (__any(live && nonempty)) {
-                const xyzz s = xyzz_add<C>(acc, b);
-                acc = xyzz_select(nonempty, live ? s : b, acc);
-            } else {
-                acc = xyzz_select(nonempty, b, acc);
-            }
-            live = live || nonempty;
+    const u32 nload = (max(rows, cols) + LPS - 1) / LPS;          // the longer of the two chains, the same for every wave
+    u32 levels = 0;
+    while ((1u << levels) < LPS) ++levels;
+    for (u32 step = 0; step < nload + levels; ++step) {            // nload rounds of bucket loads, then the levels of the lane tree
+        xyzz o = xyzz_identity();
+        bool take;
+        if (step < nload) {
+            const u32 e = step * LPS + (u32)l;
+            const u32 key = first + e * stride;
+            take = e < count && bucket_start[key + 1] != bucket_start[key];
+            if (take) o = load_xyzz(bucket_acc + key);
+        } else {
+            const int d = (LPS / 2) >> (step - nload);
+            const bool o_live = __shfl(live ? 1 : 0, (lane + d) & 63, WAVE) != 0;
+            take = l < d && o_live;                    // l < d: lane + d is a lane of the same sum
+            if (__any(take)) o = shfl_xyzz(acc, (lane + d) & 63);
         }
-    }
-    for (int d = 32; d > 0; d >>= 1) {
-        const bool o_live = __shfl(live ? 1 : 0, (lane + d) & 63, WAVE) != 0;
-        const bool take = lane < d && o_live;
         if (__any(take)) {
-            const xyzz o = shfl_xyzz(acc, (lane + d) & 63);
             if (__any(take && live)) {
                 const xyzz s = xyzz_add<C>(acc, o);
                 acc = xyzz_select(take, live ? s : o, acc);
@@ -969,7 +973,7 @@ __global__ void __launch_bounds__(256) k_reduce_rowcol(const xyzz_mem *__restric
             live = live || take;
         }
     }
-    if (lane == 0) store_xyzz(rowcol + (size_t)g * per_group + idx, acc);
+    if (valid && l == 0) store_xyzz(rowcol + (size_t)g * per_group + idx, acc);
 }
 
 // Weighted sum  X = sum_e e*in[e]  and plain total  T = sum_e in[e]  of `count` (power of two)

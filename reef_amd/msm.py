@@ -167,6 +167,13 @@ class MsmContext(_Handle):
         check(self._lib.reef_msm_ctx_timing_stats(self._h, int(reset), ctypes.byref(calls), ctypes.byref(tot), ctypes.byref(acc)))
         return {"calls": calls.value, "total_ms": tot.value, "accumulate_ms": acc.value}
 
+    def rowcol_forms(self, reset: bool = True) -> dict:
+        """How many MSMs since the last reset summed their bucket rows / columns on four waves per sum ("latency") and how many with
+        several sums per wave ("throughput": large bucket matrix, another caller at work on the device)."""
+        lat, thr = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.reef_msm_ctx_rowcol_forms(self._h, int(reset), ctypes.byref(lat), ctypes.byref(thr)))
+        return {"latency": lat.value, "throughput": thr.value}
+
     def sum_points(self, jac: Buf, n: int, out: Buf) -> Buf:
         """Sum n device-resident Jacobian points on this context's stream."""
         loc, ptr = _loc_ptr(jac, 96 * n)
