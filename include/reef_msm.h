@@ -252,6 +252,25 @@ reef_status reef_ipa_cross_terms(reef_msm_ctx *ctx, const reef_fe *a, size_t n_k
 reef_status reef_msm_folded(reef_msm_ctx *ctx, const reef_fe *v, size_t len, size_t off, int v_loc, bool is_mont,
                             const reef_fe *w1s, const reef_fe *w2s, size_t k, reef_jacobian *out, int out_loc);
 
+/* K3, deep: the generators k folds away from the resident key of src, in ONE pass instead of k folds.  After k rounds of
+ * G'_i = w1*G_i + w2*G_{i+half},
+ *     G^(k)_j = sum_{t < 2^k} s_t * G_{t*n_k + j},    n_k = n / 2^k,    s_t = prod_m (bit_{k-1-m}(t) ? w2s[m] : w1s[m]),
+ * so the n_k outputs all use the SAME 2^k scalars: one bucket pass whose digit is the same for every output (no sort, no
+ * divergence), then one window combine per output.  out[j] = G^(k)_j for j < n_k: the points k successive reef_fold calls
+ * produce, affine in ABI form, the identity as (0, 0).  w1s, w2s: canonical integers on the host, in the convention and order
+ * of reef_ipa_cross_terms and reef_msm_folded; any scalar below the modulus is legal, 0 included.  k = 0 copies the key,
+ * k = log2(n) gives one point.  Works on a plain, a pre-shifted, a byte-table and a nibble-table key alike (table 0 is read).
+ * REEF_ERR_ARG, with nothing written: a key length that is not a multiple of 2^k, k > 31, a scalar not below the modulus, a
+ * ctx with a window split.  The call waits for its work. */
+reef_status reef_fold_deep(reef_msm_ctx *src, const reef_fe *w1s, const reef_fe *w2s, size_t k, reef_affine *out, int out_loc);
+
+/* The same points as a resident key of their own: reef_fold_deep into a device buffer, then reef_msm_ctx_create from it;
+ * nothing visits the host.  Same curve and device as src (opts->device is ignored); the other opts as in reef_msm_ctx_create:
+ * with bucket_groups = 1 and at most 1024 points the key gets its nibble tables, as any small key does.  The late rounds of
+ * an IPA then run over n_k points with only the challenges drawn since (reef_ipa_cross_terms on the new key). */
+reef_status reef_msm_ctx_create_folded(reef_msm_ctx **out, reef_msm_ctx *src, const reef_fe *w1s, const reef_fe *w2s, size_t k,
+                                       const reef_msm_opts *opts);
+
 /* ---------------------------------------------------------------------------------------------
  * (3) Stateless helpers around the MSMs.
  * ------------------------------------------------------------------------------------------- */
@@ -621,6 +640,12 @@ reef_status reef_spartan_open_ipa_begin(reef_nifs_ctx *ctx, const reef_affine *q
 reef_status reef_spartan_open_ipa_round(reef_nifs_ctx *ctx, const reef_fe *r, bool is_mont, reef_jacobian *L, reef_jacobian *R);
 reef_status reef_spartan_open_finish(reef_nifs_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe *a_hat);
 reef_status reef_spartan_open_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont);
+/* The late rounds on a small key (opt-in; 0 = never, the default).  n_small: a power of two.  In the openings begun
+ * (reef_spartan_open_begin) after the call, the round at which a and b reach n_small entries makes the n_small folded
+ * generators a resident key of the run's own (reef_msm_ctx_create_folded from the challenges so far, bucket_groups = 1) and
+ * every later L, R is computed over it with the challenges drawn since.  L and R are the same points, a_hat, c and the reads
+ * the same values; an opening of n <= n_small entries never switches.  REEF_ERR_ARG: n_small not a power of two. */
+reef_status reef_spartan_open_set_small_key(reef_nifs_ctx *ctx, size_t n_small);
 
 /* ---------------------------------------------------------------------------------------------
  * (3i) The Hyrax consistency argument: NLDocCommitment::proof_dot_prod_prover -> HyraxPC::prove_eval [R]
@@ -706,6 +731,8 @@ reef_status reef_hyrax_ipa_begin(reef_hyrax_ctx *ctx, const reef_affine *q, cons
 reef_status reef_hyrax_ipa_round(reef_hyrax_ctx *ctx, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R);
 reef_status reef_hyrax_finish(reef_hyrax_ctx *ctx, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat);
 reef_status reef_hyrax_read(reef_hyrax_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont);
+/* The same switch as reef_spartan_open_set_small_key for the arguments begun (reef_hyrax_eval_begin) after the call. */
+reef_status reef_hyrax_set_small_key(reef_hyrax_ctx *ctx, size_t n_small);
 
 /* ---------------------------------------------------------------------------------------------
  * (3j) The verifier's half of an inner-product argument: the check EE::verify_batch ends CompressedSNARK::verify with [R] and

@@ -123,6 +123,10 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_msm_rows_symbols_wide": (c_int, [vp, vp, c_uint32, c_size_t, c_size_t, c_int, c_uint32, vp, vp, c_bool, vp, c_int]),
         "reef_ipa_cross_terms": (c_int, [vp, vp, c_size_t, c_int, c_bool, vp, vp, c_size_t, vp, vp]),
         "reef_fold": (c_int, [c_int, vp, c_size_t, c_int, vp, vp, vp]),
+        "reef_fold_deep": (c_int, [vp, vp, vp, c_size_t, vp, c_int]),
+        "reef_msm_ctx_create_folded": (c_int, [POINTER(vp), vp, vp, vp, c_size_t, POINTER(MsmOpts)]),
+        "reef_spartan_open_set_small_key": (c_int, [vp, c_size_t]),
+        "reef_hyrax_set_small_key": (c_int, [vp, c_size_t]),
         "reef_normalize": (c_int, [c_int, vp, c_size_t, c_int, vp, vp]),
         "reef_decompress": (c_int, [c_int, vp, c_size_t, c_int, vp, POINTER(c_uint64), POINTER(c_uint64)]),
         "reef_doc_transform": (c_int, [vp, c_size_t, c_int, c_int, vp, c_size_t, c_uint32, c_uint32, vp, c_uint32, c_size_t, c_int, POINTER(DocInfo)]),

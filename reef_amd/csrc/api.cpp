@@ -416,6 +416,15 @@ reef_status reef_fold(int curve, const reef_affine *gens, size_t half, int loc, 
                       reef_affine *out) {
     return stateless(curve, [&](const CurveVTable *v) { return v->fold(gens, half, loc, w1, w2, out); });
 }
+// K3, deep: the generators k folds away from a resident key, and a resident key made of them
+reef_status reef_fold_deep(reef_msm_ctx *src, const reef_fe *w1s, const reef_fe *w2s, size_t k, reef_affine *out, int out_loc) {
+    return dispatch<CurveVTable>(src, [&](auto *v, void *impl) { return v->fold_deep(impl, w1s, w2s, k, out, out_loc); });
+}
+reef_status reef_msm_ctx_create_folded(reef_msm_ctx **out, reef_msm_ctx *src, const reef_fe *w1s, const reef_fe *w2s, size_t k,
+                                       const reef_msm_opts *opts) {
+    if (!src) { set_error("null argument"); return REEF_ERR_ARG; }
+    return create_handle(out, src->curve, [&](const CurveVTable *v, void **impl) { return v->ctx_create_folded(impl, src->impl, w1s, w2s, k, opts); });
+}
 reef_status reef_mle_bound_rows(int curve, const void *z, size_t n, int elem_bytes, int z_loc, bool is_mont, const reef_fe *point,
                                 size_t num_vars, size_t left_vars, reef_fe *lz_out, int out_loc, reef_fe *eval_out) {
     return stateless(curve, [&](const CurveVTable *v) { return v->mle_bound(z, n, elem_bytes, z_loc, is_mont, point, num_vars, left_vars, lz_out, out_loc, eval_out); });
@@ -573,6 +582,15 @@ reef_status reef_spartan_open_finish(reef_nifs_ctx *ctx, const reef_fe *r_last, 
 reef_status reef_spartan_open_read(reef_nifs_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont) {
     return dispatch<OpenVTable>(ctx, [&](auto *v, void *impl) { return v->read(impl, which, count, out, to_mont); });
 }
+// the length at which the rounds of an argument move to a folded key: 0 (never) or a power of two
+static reef_status check_small_key(const char *name, size_t n_small) {
+    if (n_small & (n_small - 1)) { set_error("%s: n_small = %zu is not a power of two (0: never switch)", name, n_small); return REEF_ERR_ARG; }
+    return REEF_OK;
+}
+reef_status reef_spartan_open_set_small_key(reef_nifs_ctx *ctx, size_t n_small) {
+    REEF_TRY(check_small_key("reef_spartan_open_set_small_key", n_small));
+    return dispatch<OpenVTable>(ctx, [&](auto *v, void *impl) { return v->set_small_key(impl, n_small); });
+}
 
 // ---- the Hyrax consistency argument on a resident document
 reef_status reef_hyrax_create(reef_hyrax_ctx **out, int curve, const void *z, size_t n, int elem_bytes, int z_loc, bool is_mont, size_t num_vars,
@@ -611,6 +629,10 @@ reef_status reef_hyrax_finish(reef_hyrax_ctx *ctx, const reef_fe *r_last, bool i
 }
 reef_status reef_hyrax_read(reef_hyrax_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont) {
     return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->read(impl, which, count, out, to_mont); });
+}
+reef_status reef_hyrax_set_small_key(reef_hyrax_ctx *ctx, size_t n_small) {
+    REEF_TRY(check_small_key("reef_hyrax_set_small_key", n_small));
+    return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->set_small_key(impl, n_small); });
 }
 
 // ---- the verifier's IPA check on a key ctx (the curve is the key's)

@@ -499,6 +499,9 @@ struct CurveVTable {
                              uint32_t epsilon_symbol, void *out, uint32_t elem_bytes, int out_loc);
     reef_status (*doc_transform)(const uint8_t *text, size_t nbytes, int text_loc, int encoding, const uint32_t *map, size_t map_len, uint32_t eof_symbol,
                                  uint32_t epsilon_symbol, void *out, uint32_t elem_bytes, size_t out_cap, int out_loc, reef_doc_info *info);
+    // K3, deep: the generators k folds away from a resident key in one pass, and a resident key made of them (engine.inc: deep_fold_run)
+    reef_status (*fold_deep)(void *impl, const reef_fe *w1s, const reef_fe *w2s, size_t k, reef_affine *out, int out_loc);
+    reef_status (*ctx_create_folded)(void **impl, void *src_impl, const reef_fe *w1s, const reef_fe *w2s, size_t k, const reef_msm_opts *opts);
 };
 reef_status doc_check(const uint8_t *text, size_t nbytes, int text_loc, int encoding, const uint32_t *map, size_t map_len, uint32_t eof_symbol,
                       uint32_t epsilon_symbol, void *out, uint32_t elem_bytes, int out_loc);
@@ -549,6 +552,7 @@ struct OpenVTable {
     reef_status (*ipa_round)(void *impl, const reef_fe *r, bool is_mont, reef_jacobian *L, reef_jacobian *R);
     reef_status (*finish)(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *a_hat);
     reef_status (*read)(void *impl, int which, size_t count, reef_fe *out, bool to_mont);
+    reef_status (*set_small_key)(void *impl, size_t n_small);
 };
 const OpenVTable *pallas_open_vtable();
 const OpenVTable *vesta_open_vtable();
@@ -568,6 +572,7 @@ struct HyraxVTable {
     reef_status (*eval_comm_compressed)(void *impl, const uint8_t *row_comms32, int loc, reef_jacobian *comm_lz);
     reef_status (*commit)(void *impl, void *key_impl, const reef_affine *h, uint8_t *comms32, reef_affine *comms_affine, int out_loc);
     reef_status (*eval_comm_own)(void *impl, reef_jacobian *comm_lz);
+    reef_status (*set_small_key)(void *impl, size_t n_small);
 };
 const HyraxVTable *pallas_hyrax_vtable();
 const HyraxVTable *vesta_hyrax_vtable();

@@ -110,6 +110,7 @@ template <int C> struct Ctx {
     bool h_valid = false;
     bool coop = true;                        // tail kernels with four waves per group operation (ec_coop.h); REEF_MSM_COOP=0: one wave
     DevBuf wsum;                             // coop bucket reduction: weighted and plain sums of the rows / columns per group
+    DevBuf deep_dig, deep_part;              // deep fold (v_fold_deep): the coefficients' digits, window sums and folded points
     int rowcol_force = -1;                   // row / column sums of a coop ctx: -1 by the rule (rowcol_lanes), 0 always four waves per sum, 16 / 32 / 64 always
                                              // that many lanes per sum (REEF_MSM_ROWCOL)
     u64 rowcol_calls[2] = {};                // MSMs of a coop ctx whose row / column sums took the latency form [0] / the throughput form [1]
@@ -510,7 +511,7 @@ template <int C> static void ctx_free(Ctx<C> *ctx) {
     for (DevBuf *b : {&ctx->scalars, &ctx->blinds, &ctx->hpoint, &ctx->dig, &ctx->counts, &ctx->bstart, &ctx->bstart1, &ctx->seg_first,
                       &ctx->seg_counts, &ctx->entries1, &ctx->sym_table, &ctx->sym_tmp, &ctx->sym_u8, &ctx->tile_sums,
                       &ctx->entries, &ctx->bucket_acc, &ctx->rowcol, &ctx->group_sums, &ctx->result,
-                      &ctx->tmp_xyzz, &ctx->maxbits, &ctx->wsum, &ctx->h_tab, &ctx->small_partial, &ctx->wide_dig, &ctx->wide_partial, &ctx->lkeys[0], &ctx->lkeys[1], &ctx->lvals[0], &ctx->lvals[1]})
+                      &ctx->tmp_xyzz, &ctx->maxbits, &ctx->wsum, &ctx->deep_dig, &ctx->deep_part, &ctx->h_tab, &ctx->small_partial, &ctx->wide_dig, &ctx->wide_partial, &ctx->lkeys[0], &ctx->lkeys[1], &ctx->lvals[0], &ctx->lvals[1]})
         b->release();
     for (auto &q : ctx->evr)
         for (auto &e : q)
@@ -1583,7 +1584,7 @@ template <int C> static reef_status launch_blind_tab(Ctx<C> *ctx, jacobian256 *d
     return REEF_OK;
 }
 
-// The three routes of the cross terms (pre-shifted key, byte tables, plain key) on a ctx already entered, a on the device.  With
+// The four routes of the cross terms (byte tables, nibble tables, pre-shifted key, plain key) on a ctx already entered, a on the device.  With
 // d_blinds (two canonical integers on the device) L += d_blinds[0] h and R += d_blinds[1] h through h's nibble table (h: affine,
 // host); with d_blinds2 also L += d_blinds2[0] P, R += d_blinds2[1] P through P's nibble table tab2 (point_table_build; only with
 // d_blinds); without them nothing is added and the launches are those of reef_ipa_cross_terms.
@@ -1652,6 +1653,18 @@ static reef_status ipa_cross_run(Ctx<C> *ctx, const fe256 *d_a, size_t n_k, bool
         return REEF_OK;
     }
     hipLaunchKernelGGL(k_ipa_expand<C>, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_a, (u32)n_k, coef, (u32)n, (int)is_mont, s_l, s_r);
+    if (small_path(key->small_tab, key->small_n, n, ctx->wsplit_world)) {
+        // a small key (a folded one above all: reef_msm_ctx_create_folded): L and R are two sums over its nibble tables, no sort, no buckets
+        REEF_TRY(run_small<C>(ctx, s_l, n, false, nullptr, false, land));
+        REEF_TRY(run_small<C>(ctx, s_r, n, false, nullptr, false, land + 1));
+        if (d_blinds) REEF_TRY(launch_blind<C>(ctx, land, d_blinds, nullptr, false, 2));
+        if (d_blinds2) REEF_TRY(launch_blind_tab<C>(ctx, land, d_blinds2, tab2, 2));
+        REEF_HIP_TRY(hipGetLastError());
+        REEF_HIP_TRY(hipStreamSynchronize(st));
+        memcpy(out_l, &land[0], sizeof(jacobian256));
+        memcpy(out_r, &land[1], sizeof(jacobian256));
+        return REEF_OK;
+    }
     CorePlan pl{key->c, key->W, key->G, 1u, (u32)n, (u32)key->n};
     if (pl.G == 1) {   // L and R as a batch of two MSMs: one pass of the pipeline, one result copy
         CorePlan two = pl;
@@ -1903,6 +1916,172 @@ static reef_status v_fold(const reef_affine *gens, size_t half, int loc, const r
     return finish_out<affine256>(ss, d_out, out, half, loc);
 }
 
+// ---- deep fold (K3, deep): G^(k)_j = sum_t s_t * G_{t*n_k + j} in one bucket pass (k_deep_accum) ----
+// The 2^k coefficients s_t on the host, canonical integers: s_t = prod_m (bit_{k-1-m}(t) ? w2_m : w1_m), what k_ipa_coef forms.
+template <int C> static void deep_coefs(const fe256 *w1s, const fe256 *w2s, size_t k, std::vector<hostcombine::f4> &coef) {
+    using namespace hostcombine;
+    constexpr int F = 1 - C;
+    const Field<F> &fd = field<F>();
+    static const f4 r2 = [&] {                        // 2^512 mod r: fmul(w, r2) = w * 2^256, and fmul(s, w * 2^256) = s * w
+        f4 v = {{1, 0, 0, 0}};
+        for (int i = 0; i < 512; ++i) v = fdbl(fd, v);
+        return v;
+    }();
+    auto load = [](const fe256 &w) {
+        f4 v;
+        for (int i = 0; i < 4; ++i) v.l[i] = (u64)w.w[2 * i] | ((u64)w.w[2 * i + 1] << 32);
+        return v;
+    };
+    coef.assign(1, f4{{1, 0, 0, 0}});
+    for (size_t m = 0; m < k; ++m) {
+        const f4 m1 = fmul(fd, load(w1s[m]), r2), m2 = fmul(fd, load(w2s[m]), r2);
+        std::vector<f4> next(coef.size() * 2);
+        for (size_t t = 0; t < coef.size(); ++t) {
+            next[2 * t] = fmul(fd, coef[t], m1);
+            next[2 * t + 1] = fmul(fd, coef[t], m2);
+        }
+        coef.swap(next);
+    }
+}
+// magnitude (nw 32-bit words) -> signed 3-bit digits in [-4, 4] at dig[w * stride], negated when neg; returns the windows used
+static inline u32 deep_recode(const u32 *mag, int nw, bool neg, signed char *dig, size_t stride) {
+    u32 carry = 0, used = 0;
+    for (u32 w = 0; w < DEEP_WMAX; ++w) {
+        const u32 bit = DEEP_C * w;
+        u32 raw = carry;
+        for (u32 b = 0; b < DEEP_C; ++b) {
+            const u32 pos = bit + b;
+            if ((int)(pos >> 5) < nw) raw += ((mag[pos >> 5] >> (pos & 31u)) & 1u) << b;
+        }
+        int d = (int)raw;
+        carry = 0;
+        if (raw > 4) { d = (int)raw - 8; carry = 1; }
+        if (d) used = w + 1;
+        dig[(size_t)w * stride] = (signed char)(neg ? -d : d);
+    }
+    return used;
+}
+// The deep fold of ctx's key on ctx's stream (ctx entered, its key's device current): d_out[j] = G^(k)_j for j < n >> k, ABI affine on the
+// device.  Arguments checked by the caller (k <= 31, n a multiple of 2^k, canonical scalars).  Waited for.
+template <int C>
+static reef_status deep_fold_run(Ctx<C> *ctx, const fe256 *w1s, const fe256 *w2s, size_t k, affine256 *d_out) {
+    Key<C> *key = ctx->key;
+    const size_t n = key->n, T = (size_t)1 << k, n_k = n >> k;
+    if (n_k == 0) return REEF_OK;
+    hipStream_t st = ctx->stream;
+    std::vector<hostcombine::f4> coef;
+    deep_coefs<C>(w1s, w2s, k, coef);
+    // the GLV halves of every coefficient; one that does not split (or REEF_FOLD_DEEP_GLV=0 in the +experiment build) sends all of them
+    // down the 255-bit form, one half
+    const char *glv_env = exp_env("REEF_FOLD_DEEP_GLV");     // read per call: a test sets it for one fold
+    const bool glv_on = !(glv_env && glv_env[0] == '0');
+    std::vector<GlvSplit> halves(glv_on ? T : 0);
+    bool glv = glv_on;
+    for (size_t t = 0; t < T && glv; ++t) {
+        u32 w8[8];
+        for (int i = 0; i < 4; ++i) { w8[2 * i] = (u32)coef[t].l[i]; w8[2 * i + 1] = (u32)(coef[t].l[i] >> 32); }
+        glv = glv_split<C>(w8, &halves[t]);
+    }
+    const u32 H = glv ? 2u : 1u;
+    std::vector<signed char> dig((size_t)H * DEEP_WMAX * T);
+    u32 W = 1;
+    for (size_t t = 0; t < T; ++t) {
+        if (glv) {
+            W = std::max(W, deep_recode(halves[t].k1, 5, halves[t].neg1, dig.data() + t, T));
+            W = std::max(W, deep_recode(halves[t].k2, 5, halves[t].neg2, dig.data() + (size_t)DEEP_WMAX * T + t, T));
+        } else {
+            u32 w8[8];
+            for (int i = 0; i < 4; ++i) { w8[2 * i] = (u32)coef[t].l[i]; w8[2 * i + 1] = (u32)(coef[t].l[i] >> 32); }
+            W = std::max(W, deep_recode(w8, 8, false, dig.data() + t, T));
+        }
+    }
+    REEF_TRY(ctx->deep_dig.ensure(dig.size()));
+    REEF_HIP_TRY(hipMemcpyAsync(ctx->deep_dig.p, dig.data(), dig.size(), hipMemcpyHostToDevice, st));
+    // outputs in slabs of at most 2^14 (the window sums of a slab: 144 B * W * slab); few outputs of many terms split their terms over
+    // S chunks (of at least 8) so that the device still sees 2^17 lanes: two waves on every SIMD
+    const size_t slab = std::min<size_t>(n_k, (size_t)1 << 14);
+    size_t S = std::max<size_t>(1, std::min<size_t>(T / 8, ((size_t)131072 + slab * W - 1) / (slab * W)));
+    const u32 t_per = (u32)((T + S - 1) / S);
+    S = (T + t_per - 1) / t_per;
+    REEF_TRY(ctx->deep_part.ensure((S * W + 1) * slab * sizeof(xyzz_mem)));
+    xyzz_mem *part = ctx->deep_part.template as<xyzz_mem>(), *folded = part + S * W * slab;
+    const signed char *d_dig = ctx->deep_dig.template as<signed char>();
+    for (size_t j0 = 0; j0 < n_k; j0 += slab) {
+        const u32 cnt = (u32)std::min(slab, n_k - j0);
+        hipLaunchKernelGGL(k_deep_accum<C>, dim3(ceil_div(cnt, 64), W, (u32)S), dim3(64), 0, st, (const affine256 *)key->tables, (u32)n_k, (u32)j0, cnt, (u32)T,
+                           t_per, H, d_dig, part);
+        if (S > 1) hipLaunchKernelGGL(k_deep_reduce<C>, dim3(ceil_div((u64)W * cnt, 64)), dim3(64), 0, st, part, W * cnt, (u32)S);
+        hipLaunchKernelGGL(k_deep_horner_coop<C>, dim3(ceil_div(cnt, 64)), dim3(256), 0, st, (const xyzz_mem *)part, cnt, W, folded);
+        hipLaunchKernelGGL((k_xyzz_normalize<C, true>), dim3(ceil_div(ceil_div(cnt, NORM_PER), 256)), dim3(256), 0, st, (const xyzz_mem *)folded, cnt, d_out + j0);
+    }
+    REEF_HIP_TRY(hipGetLastError());
+    REEF_HIP_TRY(hipStreamSynchronize(st));               // the digits' host copy and the workspace are free again
+    return REEF_OK;
+}
+// the argument errors of the deep fold: nothing is written when one is found
+template <int C> static reef_status deep_fold_check(Ctx<C> *ctx, const reef_fe *w1s, const reef_fe *w2s, size_t k) {
+    using namespace hostcombine;
+    const size_t n = ctx->key->n;
+    if (k > 31 || ((n >> k) << k) != n) { set_error("the key length (%zu) must be a multiple of 2^k (k = %zu, at most 31)", n, k); return REEF_ERR_ARG; }
+    if (ctx->wsplit_world > 1) { set_error("a ctx with a window split cannot fold its key"); return REEF_ERR_ARG; }
+    const Field<1 - C> &fd = field<1 - C>();
+    for (size_t m = 0; m < k; ++m)
+        for (const reef_fe *w : {w1s + m, w2s + m}) {
+            fe256 v;
+            memcpy(&v, w, sizeof v);
+            f4 x;
+            for (int i = 0; i < 4; ++i) x.l[i] = (u64)v.w[2 * i] | ((u64)v.w[2 * i + 1] << 32);
+            if (geq(x, fd.p)) { set_error("challenge %zu is not below the modulus (canonical integers are expected)", m); return REEF_ERR_ARG; }
+        }
+    return REEF_OK;
+}
+template <int C>
+static reef_status v_fold_deep(void *impl, const reef_fe *w1s, const reef_fe *w2s, size_t k, reef_affine *out, int out_loc) {
+    Ctx<C> *ctx = (Ctx<C> *)impl;
+    if (!ctx || !out || (k && (!w1s || !w2s))) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    REEF_TRY(deep_fold_check<C>(ctx, w1s, w2s, k));
+    Key<C> *key = ctx->key;
+    const size_t n_k = key->n >> k;
+    if (n_k == 0) return REEF_OK;
+    REEF_ON_DEVICE(key->device);
+    CtxScope<C> scope(ctx);
+    REEF_TRY(scope.enter());
+    if (out_loc == REEF_DEVICE) return deep_fold_run<C>(ctx, (const fe256 *)w1s, (const fe256 *)w2s, k, (affine256 *)out);
+    REEF_TRY(ctx->hpoint.ensure(n_k * sizeof(affine256)));
+    REEF_TRY(deep_fold_run<C>(ctx, (const fe256 *)w1s, (const fe256 *)w2s, k, ctx->hpoint.template as<affine256>()));
+    REEF_HIP_TRY(hipMemcpyAsync(out, ctx->hpoint.p, n_k * sizeof(affine256), hipMemcpyDeviceToHost, ctx->stream));
+    REEF_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return REEF_OK;
+}
+// A resident key of the folded points: the deep fold into a device buffer, then the key built from it.  Nothing visits the host.
+template <int C>
+static reef_status v_ctx_create_folded(void **impl, void *src_, const reef_fe *w1s, const reef_fe *w2s, size_t k, const reef_msm_opts *opts) {
+    Ctx<C> *src = (Ctx<C> *)src_;
+    if (!impl || !src || (k && (!w1s || !w2s))) { set_error("null argument"); return REEF_ERR_ARG; }
+    reef_msm_opts o = {};
+    if (opts) o = *opts;
+    o.device = src->key->device;
+    REEF_ON_DEVICE(src->key->device);
+    DevBuf pts;
+    struct Release {
+        DevBuf &b;
+        ~Release() { b.release(); }
+    } release{pts};
+    size_t n_k = 0;
+    {
+        std::lock_guard<std::mutex> lk(src->mu);
+        REEF_TRY(deep_fold_check<C>(src, w1s, w2s, k));
+        n_k = src->key->n >> k;
+        REEF_TRY(plan_for(n_k, o.window_bits, o.bucket_groups, nullptr, nullptr, nullptr, nullptr));
+        CtxScope<C> scope(src);
+        REEF_TRY(scope.enter());
+        REEF_TRY(pts.ensure(std::max<size_t>(n_k, 1) * sizeof(affine256)));
+        REEF_TRY(deep_fold_run<C>(src, (const fe256 *)w1s, (const fe256 *)w2s, k, (affine256 *)pts.p));
+    }
+    return v_ctx_create<C>(impl, (const reef_affine *)pts.p, n_k, REEF_DEVICE, &o);
+}
+
 template <int C>
 static reef_status v_normalize(const reef_jacobian *in, size_t n, int loc, reef_affine *out_aff, uint8_t *out_comp) {
     if (!in || (!out_aff && !out_comp)) { set_error("null argument"); return REEF_ERR_ARG; }
@@ -2123,7 +2302,8 @@ template <int C> static CurveVTable make_vtable() {
     return CurveVTable{v_ctx_create<C>, v_ctx_rekey<C>, v_ctx_clone<C>, v_ctx_attach<C>, v_ctx_destroy<C>, v_ctx_sync<C>, v_ctx_stream<C>,
                        v_ctx_timing<C>, v_ctx_enable_timing<C>, v_ctx_window_split<C>, v_ctx_timing_stats<C>, v_ctx_rowcol_forms<C>, v_ctx_sum_points<C>, v_ctx_plan<C>, v_ctx_byte_tables<C>, v_msm<C>, v_msm_rows<C>, v_msm_rows_symbols<C>, v_msm_rows_symbols_wide<C>, v_ipa_cross<C>, v_msm_folded<C>, v_fold<C>, v_normalize<C>, v_sum_points<C>,
                        v_gen_bases<C>, v_gen_scalars<C>, v_test_field_op<C>, v_test_ec_op<C>, v_bench_fmul<C>,
-                       v_sc_create<C>, v_sc_destroy<C>, v_sc_set<C>, v_sc_set_parts<C>, v_sc_read<C>, v_sc_coeffs<C>, v_sc_fold<C>, v_sc_fold_coeffs<C>, v_sc_gen_eq<C>, v_sc_reset<C>, v_sc_sync<C>, v_mle_bound<C>, v_merkle_commit<C>, v_derive_generators<C>, plan_for, v_decompress<C>, doc_check, doc_transform};
+                       v_sc_create<C>, v_sc_destroy<C>, v_sc_set<C>, v_sc_set_parts<C>, v_sc_read<C>, v_sc_coeffs<C>, v_sc_fold<C>, v_sc_fold_coeffs<C>, v_sc_gen_eq<C>, v_sc_reset<C>, v_sc_sync<C>, v_mle_bound<C>, v_merkle_commit<C>, v_derive_generators<C>, plan_for, v_decompress<C>, doc_check, doc_transform,
+                       v_fold_deep<C>, v_ctx_create_folded<C>};
 }
 
 }  // namespace reef

@@ -182,6 +182,13 @@ template <int CURVE> class CommitmentGens {
         check(reef_msm_folded(ctx_, v, len, off, v_loc, true, w1s.data(), w2s.data(), w1s.size(), &out, REEF_HOST), "reef_msm_folded");
         return out;
     }
+    // K3, deep: the len() / 2^k generators k = w1s.size() folds away from this key, in one pass (reef_fold_deep); w canonical
+    std::vector<reef_affine> fold_deep(const std::vector<reef_fe> &w1s, const std::vector<reef_fe> &w2s) const {
+        if (w1s.size() != w2s.size()) throw std::invalid_argument("challenge vectors differ in length");
+        std::vector<reef_affine> out(n_ >> w1s.size());
+        check(reef_fold_deep(ctx_, w1s.data(), w2s.data(), w1s.size(), out.data(), REEF_HOST), "reef_fold_deep");
+        return out;
+    }
     std::pair<reef_jacobian, reef_jacobian> ipa_cross_terms(const reef_fe *a, size_t n_k, const std::vector<reef_fe> &w1s,
                                                             const std::vector<reef_fe> &w2s, int a_loc = REEF_HOST) const {
         if (w1s.size() != w2s.size()) throw std::logic_error("one (w1, w2) pair per round");
@@ -195,6 +202,30 @@ template <int CURVE> class CommitmentGens {
     size_t n_;
     reef_affine h_ = {};
     bool has_h_;
+};
+
+// `gens.fold(w1, w2)` that records the folds instead of performing them (reef_amd/provider.py FoldedGens): commit() is one MSM over the
+// root's resident key (reef_msm_folded); materialize() makes the folded generators a resident key of their own, in one deep fold on the
+// device (reef_msm_ctx_create_folded; with bucket_groups = 1 and at most 1024 points it has nibble tables).  The caller destroys it.
+template <int CURVE> struct FoldedGens {
+    const CommitmentGens<CURVE> &root;
+    std::vector<reef_fe> w1s, w2s;       // canonical little-endian, one pair per fold
+    size_t len() const { return root.len() >> w1s.size(); }
+    FoldedGens fold(const reef_fe &w1, const reef_fe &w2) const {
+        FoldedGens f{root, w1s, w2s};
+        f.w1s.push_back(w1);
+        f.w2s.push_back(w2);
+        return f;
+    }
+    reef_jacobian commit(const reef_fe *v, size_t n, size_t off = 0) const { return root.commit_folded(v, n, off, w1s, w2s); }
+    reef_msm_ctx *materialize(uint32_t bucket_groups = 1) const {
+        reef_msm_opts o = {};
+        o.bucket_groups = bucket_groups;
+        o.device = -1;
+        reef_msm_ctx *out = nullptr;
+        check(reef_msm_ctx_create_folded(&out, root.handle(), w1s.data(), w2s.data(), w1s.size(), &o), "reef_msm_ctx_create_folded");
+        return out;
+    }
 };
 
 // The same commitment key kept on several GPUs of ONE process -- Reef's prover is one process (src/backend/main.rs:82) -- through the
@@ -647,10 +678,12 @@ template <int CURVE> class RelaxedR1CSSnark {
         }
     }
     // 3h, after prove_sumchecks.  gens_v: a key of exactly opening_len() points.  comm_a(r): the caller's comm_E + r comm_W, as the
-    // bytes it absorbs; q_of(r_ipa): the caller's gens_s.scale(r_ipa), affine.
+    // bytes it absorbs; q_of(r_ipa): the caller's gens_s.scale(r_ipa), affine.  small_key: the late rounds on a folded key of that many
+    // points (reef_spartan_open_set_small_key; a power of two, 0: never).
     void prove_opening(reef_msm_ctx *gens_v, const Transcript &transcript, const std::function<std::vector<uint8_t>(const reef_fe &)> &comm_a,
-                       const std::function<reef_affine(const reef_fe &)> &q_of, Proof &pf) const {
+                       const std::function<reef_affine(const reef_fe &)> &q_of, Proof &pf, size_t small_key = 0) const {
         reef_nifs_ctx *h = nifs_.handle();
+        check(reef_spartan_open_set_small_key(h, small_key), "reef_spartan_open_set_small_key");
         pf.L.clear(); pf.R.clear(); pf.r_rounds.clear();
         check(reef_spartan_open_begin(h, gens_v, true, &pf.cross_term), "reef_spartan_open_begin");
         pf.r_fold = transcript("r", &pf.cross_term, sizeof pf.cross_term);
@@ -724,20 +757,21 @@ template <int CURVE> class HyraxEval {
     }
     // prove on the ctx's own commitment (commit came first): no row commitment is uploaded
     void prove_own(reef_msm_ctx *gens_v, const reef_fe *point, const Transcript &transcript, const std::function<reef_affine(const reef_fe &)> &q_of,
-                   Proof &pf) const {
-        prove_with(gens_v, point, transcript, q_of, pf, [&] { pf.comm_lz = eval_comm_own(); });
+                   Proof &pf, size_t small_key = 0) const {
+        prove_with(gens_v, point, transcript, q_of, pf, small_key, [&] { pf.comm_lz = eval_comm_own(); });
     }
 
     // proof_dot_prod_prover -> prove_eval at `point` (num_vars entries).  gens_v: a key of exactly 2^rounds() points; row_comms:
-    // the 2^left_vars affine row commitments (row_comms_loc memory); q_of(r): the caller's gens_1.scale(r), affine.
+    // the 2^left_vars affine row commitments (row_comms_loc memory); q_of(r): the caller's gens_1.scale(r), affine.  small_key: the late
+    // rounds on a folded key of that many points (reef_hyrax_set_small_key; a power of two, 0: never).
     void prove(reef_msm_ctx *gens_v, const reef_fe *point, const reef_affine *row_comms, int row_comms_loc, const Transcript &transcript,
-               const std::function<reef_affine(const reef_fe &)> &q_of, Proof &pf) const {
-        prove_with(gens_v, point, transcript, q_of, pf, [&] { check(reef_hyrax_eval_comm(ctx_, row_comms, row_comms_loc, &pf.comm_lz), "reef_hyrax_eval_comm"); });
+               const std::function<reef_affine(const reef_fe &)> &q_of, Proof &pf, size_t small_key = 0) const {
+        prove_with(gens_v, point, transcript, q_of, pf, small_key, [&] { check(reef_hyrax_eval_comm(ctx_, row_comms, row_comms_loc, &pf.comm_lz), "reef_hyrax_eval_comm"); });
     }
     // the same with the rows as Reef holds them, PolyCommit.comm: 2^left_vars compressed commitments (host), decoded on the device
     void prove(reef_msm_ctx *gens_v, const reef_fe *point, const Compressed *row_comms, const Transcript &transcript,
-               const std::function<reef_affine(const reef_fe &)> &q_of, Proof &pf) const {
-        prove_with(gens_v, point, transcript, q_of, pf, [&] {
+               const std::function<reef_affine(const reef_fe &)> &q_of, Proof &pf, size_t small_key = 0) const {
+        prove_with(gens_v, point, transcript, q_of, pf, small_key, [&] {
             check(reef_hyrax_eval_comm_compressed(ctx_, row_comms->data(), REEF_HOST, &pf.comm_lz), "reef_hyrax_eval_comm_compressed");
         });
     }
@@ -745,7 +779,8 @@ template <int CURVE> class HyraxEval {
   private:
     template <class CommLz>
     void prove_with(reef_msm_ctx *gens_v, const reef_fe *point, const Transcript &transcript, const std::function<reef_affine(const reef_fe &)> &q_of,
-                    Proof &pf, CommLz &&comm_lz) const {
+                    Proof &pf, size_t small_key, CommLz &&comm_lz) const {
+        check(reef_hyrax_set_small_key(ctx_, small_key), "reef_hyrax_set_small_key");
         pf.L.clear(); pf.R.clear(); pf.r_rounds.clear();
         check(reef_hyrax_eval_begin(ctx_, gens_v, point, true, &pf.eval, &pf.lz_blind), "reef_hyrax_eval_begin");
         comm_lz();

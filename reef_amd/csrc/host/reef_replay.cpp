@@ -62,12 +62,14 @@ int reef_replay_run(const char *shapes_json, const char *config, int nofold, int
 
 // The prove leg of the config whose name contains `config`.  flags: space-separated options -- "tamper=<phase>" (nifs | spartan |
 // open | hyrax) alters one recorded value before the checks, so the run must fail naming that phase; "tables" builds the keys'
-// byte tables; "paired" takes a step's comm_W and comm_T from one reef_nifs_commit_step (the line then carries "paired": true).  Returns 0 and the JSON line, 1 and the message (a failed call or a rejected proof), 3 without a GPU.
+// byte tables; "paired" takes a step's comm_W and comm_T from one reef_nifs_commit_step (the line then carries "paired": true);
+// "small_key=N" runs the late rounds of the openings and of the Hyrax argument on a folded key of N points (a power of two).  Returns 0 and the JSON line, 1 and the message (a failed call or a rejected proof), 3 without a GPU.
 extern "C" __attribute__((visibility("default")))
 int reef_replay_run_prove(const char *shapes_json, const char *config, const char *flags, char *out, size_t cap) {
     return entry_point(out, cap, 1, [&] {
         std::string tamper;
         bool tables = false, paired = false;
+        size_t small_key = 0;
         const std::string f = flags ? flags : "";
         for (size_t p = 0; p < f.size();) {
             const size_t e = std::min(f.find(' ', p), f.size());
@@ -75,12 +77,14 @@ int reef_replay_run_prove(const char *shapes_json, const char *config, const cha
             if (w.rfind("tamper=", 0) == 0) tamper = w.substr(7);
             else if (w == "tables") tables = true;
             else if (w == "paired") paired = true;
+            else if (w.rfind("small_key=", 0) == 0) small_key = (size_t)strtoull(w.c_str() + 10, nullptr, 10);
             else if (!w.empty()) fail("reef_replay_run_prove: unknown flag '" + w + "'");
             p = e + 1;
         }
         check_tamper_name(tamper);
         const Shape sh = find_shape(shapes_json, config);
         g_checked = 0;
+        g_small_key = small_key;
         return prove_body(sh, tamper, tables, paired);
     });
 }
@@ -112,8 +116,8 @@ int main(int argc, char **argv) {
         else if (strncmp(argv[i], "shapes=", 7) == 0) shapes = argv[i] + 7;
         else if (strncmp(argv[i], "devices=", 8) == 0) members = atoi(argv[i] + 8);     // the multi-device leg on N members (ordinal i mod the visible devices)
         else if (strcmp(argv[i], "prove") == 0) prove = true;                          // the prove leg: every device row of one proof, checked
-        else if (strncmp(argv[i], "tamper=", 7) == 0 || strcmp(argv[i], "paired") == 0) prove_flags += std::string(" ") + argv[i];
-        else { fprintf(stderr, "usage: reef_replay [cfg1|cfg3|cfg4|cfg4b|cfg5] [nofold] [tables] [devices=N] [shapes=<replay_shapes.json>] | [prove [paired] [tamper=<phase>]]\n"); return 2; }
+        else if (strncmp(argv[i], "tamper=", 7) == 0 || strcmp(argv[i], "paired") == 0 || strncmp(argv[i], "small_key=", 10) == 0) prove_flags += std::string(" ") + argv[i];
+        else { fprintf(stderr, "usage: reef_replay [cfg1|cfg3|cfg4|cfg4b|cfg5] [nofold] [tables] [devices=N] [shapes=<replay_shapes.json>] | [prove [paired] [small_key=N] [tamper=<phase>]]\n"); return 2; }
     }
     if (shapes.empty() && !getenv("REEF_REPLAY_SHAPES")) {   // the executable lives in reef_amd/_lib/: the shapes are two levels up, under tests/golden/
         char exe[4096];

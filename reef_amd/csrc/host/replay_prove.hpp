@@ -130,6 +130,8 @@ template <int CURVE> static void step_record(ProveSide<CURVE> &s, const Inst &f,
     s.rec.u = fadd(s.m, s.rec.u, o.r);
     s.rec.X = lin(s.m, s.rec.X, o.r, f.X);
 }
+// "small_key=N" of the prove leg: the openings and the Hyrax argument move their late rounds to a folded key of N points (0: never)
+static size_t g_small_key = 0;
 // RelaxedR1CSSNARK::prove on the folded instance: 3g, then 3h with the same key as commit_T
 template <int CURVE> static void final_snark(ProveSide<CURVE> &s) {
     const typename ProveSide<CURVE>::Snark snark(*s.nifs, s.ncp, s.nvp);
@@ -146,7 +148,7 @@ template <int CURVE> static void final_snark(ProveSide<CURVE> &s) {
             s.comm_a_dlog = d;
             return std::vector<uint8_t>((const uint8_t *)&d, (const uint8_t *)&d + sizeof d);
         },
-        [&](const reef_fe &r) { return s.q_open = scaled_G(s, fmul(s.m, s.gs, r)); }, s.pf);
+        [&](const reef_fe &r) { return s.q_open = scaled_G(s, fmul(s.m, s.gs, r)); }, s.pf, g_small_key);
     s.open_ms = ms_since(t0);
 }
 // After the host checks: the verifier's matrix evaluations on the device (3k) at the recorded (r_x, r_y), on the ctx the prove ran on.
@@ -314,7 +316,7 @@ static std::string prove_body(const Shape &shape, const std::string &tamper, boo
         t0 = clk::now();
         point.clear();
         for (int j = 0; j < sh->doc_log; ++j) point.push_back(tr("q", nullptr, 0));   // running_q: the proof's, a stand-in here
-        hyrax->prove(row_key, point.data(), row_aff.data(), REEF_HOST, tr, [&](const reef_fe &r) { return scaled_G(P, fmul(mp, g1, r)); }, hpf);
+        hyrax->prove(row_key, point.data(), row_aff.data(), REEF_HOST, tr, [&](const reef_fe &r) { return scaled_G(P, fmul(mp, g1, r)); }, hpf, g_small_key);
         consistency_ms = ms_since(t0);
     }
     double steps_total = 0;

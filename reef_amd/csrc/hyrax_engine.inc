@@ -26,6 +26,7 @@ template <int C> struct HyraxCtx : DeviceCtx {   // ev: orders the key ctx's str
     bool own = false, committed = false; // comms holds the rows commit made of this document (eval_comm_own); commit has succeeded at least once
     int phase = HY_NONE;
     u32 rounds = 0;
+    size_t n_small = 0;                  // reef_hyrax_set_small_key: the arguments begun from now on move to a folded key at this length (0: never)
 };
 
 // Every call enqueues on a pool stream and waits for it before it returns (common.h: OnExit::WAIT_AND_IDLE)
@@ -88,7 +89,7 @@ static reef_status v_hyrax_create(void **impl, const void *z, size_t n, int elem
         REEF_TRY(c->dot.ensure(20 * sizeof(u64) + 2 * sizeof(fe256)));
         REEF_TRY(c->pts.ensure(2 * std::max(c->left, c->right) * sizeof(fe256)));
         REEF_TRY(c->lint.ensure(rows * sizeof(fe256)));
-        REEF_TRY(ipa_alloc(&c->ip, cols));
+        REEF_TRY(ipa_alloc(&c->ip, cols, 0));
         DeviceScope scope(c, OnExit::WAIT_AND_IDLE);
         REEF_TRY(scope.enter());
         if (hipMemsetAsync((char *)c->z.p + bytes, 0, zbytes - bytes, c->stream) != hipSuccess) {
@@ -133,7 +134,7 @@ static reef_status v_hyrax_eval_begin(void *impl, void *key_impl, const reef_fe 
     }
     REEF_TRY(call.enter(&c->phase));
     c->pt = pt;
-    REEF_TRY(ipa_alloc(&c->ip, c->cols));
+    REEF_TRY(ipa_alloc(&c->ip, c->cols, c->n_small));
     MlePoint mp;
     memset(&mp, 0, sizeof mp);
     memcpy(mp.r, point, nv * sizeof(fe256));
@@ -447,9 +448,18 @@ template <int C> static reef_status v_hyrax_read(void *impl, int which, size_t c
     return ipa_read(&c->ip, c->stream, c->stage, which, count, out, to_mont);
 }
 
+// n_small (0 or a power of two: api.cpp checks) holds for the arguments begun (eval_begin) after the call; no device work
+template <int C> static reef_status v_hyrax_set_small_key(void *impl, size_t n_small) {
+    HyraxCtx<C> *c = (HyraxCtx<C> *)impl;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->n_small = n_small;
+    return REEF_OK;
+}
+
 template <int C> HyraxVTable make_hyrax_vtable() {
     return HyraxVTable{v_hyrax_create<C>, v_hyrax_destroy<C>, v_hyrax_eval_begin<C>, v_hyrax_eval_comm<C>, v_hyrax_ipa_begin<C>,
-                       v_hyrax_ipa_round<C>, v_hyrax_finish<C>, v_hyrax_read<C>, v_hyrax_eval_comm_compressed<C>, v_hyrax_commit<C>, v_hyrax_eval_comm_own<C>};
+                       v_hyrax_ipa_round<C>, v_hyrax_finish<C>, v_hyrax_read<C>, v_hyrax_eval_comm_compressed<C>, v_hyrax_commit<C>, v_hyrax_eval_comm_own<C>,
+                       v_hyrax_set_small_key<C>};
 }
 
 }  // namespace reef

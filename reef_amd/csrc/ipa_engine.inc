@@ -1,6 +1,7 @@
 // The IPA rounds of the batched opening (3h: open_engine.inc, on a NIFS ctx) and of the Hyrax consistency argument (3i:
 // hyrax_engine.inc); included after nifs_engine.inc.  IpaRun holds a, b, the cross terms over the resident key and the folds
 // (open_kernels.inc): the owner fills a and b, then drives ipa_cross / ipa_round / ipa_last on its own stream, and releases it.
+// With n_small set (reef_spartan_open_set_small_key / reef_hyrax_set_small_key) the rounds from length n_small on run over a folded key.
 namespace reef {
 
 template <int C> struct IpaRun {
@@ -14,14 +15,25 @@ template <int C> struct IpaRun {
     bool with_h = false;                 // L, R also take blinds[0] h, blinds[1] h (htab)
     fe256 hb[2] = {};                    // host copy of the blinds being uploaded
     std::vector<fe256> w1s, w2s;         // the IPA challenges so far: r^-1 and r, canonical integers (reef_fold's convention)
+    size_t n_small = 0;                  // the length at which the rounds move to a folded key (0: never); the owner's setting at ipa_alloc
+    Ctx<C> *folded = nullptr;            // the key of the n_small generators folded_at rounds away (reef_msm_ctx_create_folded), this run's own
+    size_t folded_at = 0;                // the challenges the folded key holds: L, R over it take w1s, w2s from here on
+    void drop_folded() {
+        if (folded) v_ctx_destroy<C>(folded);
+        folded = nullptr;
+        folded_at = 0;
+    }
     void release() {
+        drop_folded();
         for (DevBuf *d : {&a, &b, &partial, &out, &blinds, &htab}) d->release();
     }
 };
 // the blocks of a reduction over n entries (the sum-check rounds of N5 and the folds here)
 static u32 sp_grid(size_t n) { return (u32)std::max<size_t>(1, std::min<size_t>(SP_BLOCKS, ceil_div(n, SP_THREADS))); }
-// the workspace for n entries; the rounds start over (no key, no challenges, no h term)
-template <int C> static reef_status ipa_alloc(IpaRun<C> *ip, size_t n) {
+// the workspace for n entries; the rounds start over (no key, no folded key, no challenges, no h term) with the owner's n_small
+template <int C> static reef_status ipa_alloc(IpaRun<C> *ip, size_t n, size_t n_small) {
+    ip->drop_folded();
+    ip->n_small = n_small;
     REEF_TRY(ip->a.ensure(n * sizeof(fe256)));
     REEF_TRY(ip->b.ensure(n * sizeof(fe256)));
     REEF_TRY(ip->partial.ensure(SP_BLOCKS * 27 * sizeof(unsigned long long)));
@@ -69,7 +81,7 @@ template <int C> static reef_status ipa_set_blinds(IpaRun<C> *ip, hipStream_t st
 // the owner's stream `st` by the event `ev`, with c_L q, c_R q (out[1], out[2]) added through q's nibble table, and blinds[0] h,
 // blinds[1] h through h's when with_h.  One host wait.
 template <int C> static reef_status ipa_cross(IpaRun<C> *ip, hipStream_t st, hipEvent_t ev, reef_jacobian *L, reef_jacobian *R) {
-    Ctx<C> *key = ip->key;
+    Ctx<C> *key = ip->folded ? ip->folded : ip->key;          // after the switch: the folded key, and only the challenges drawn since
     hipStream_t ks = (hipStream_t)v_ctx_stream<C>(key);
     if (!ks) return REEF_ERR_HIP;
     REEF_HIP_TRY(hipEventRecord(ev, st));
@@ -77,9 +89,9 @@ template <int C> static reef_status ipa_cross(IpaRun<C> *ip, hipStream_t st, hip
     std::lock_guard<std::mutex> kl(key->mu);
     CtxScope<C> scope(key);
     REEF_TRY(scope.enter());
-    const size_t k = ip->w1s.size();
-    return ipa_cross_run<C>(key, ip->a.template as<fe256>(), ip->len, false, k ? (const reef_fe *)ip->w1s.data() : nullptr,
-                            k ? (const reef_fe *)ip->w2s.data() : nullptr, k, ip->out.template as<fe256>() + 1, &ip->q,
+    const size_t k0 = ip->folded ? ip->folded_at : 0, k = ip->w1s.size() - k0;
+    return ipa_cross_run<C>(key, ip->a.template as<fe256>(), ip->len, false, k ? (const reef_fe *)(ip->w1s.data() + k0) : nullptr,
+                            k ? (const reef_fe *)(ip->w2s.data() + k0) : nullptr, k, ip->out.template as<fe256>() + 1, &ip->q,
                             ip->with_h ? ip->blinds.template as<fe256>() : nullptr, ip->with_h ? ip->htab.template as<affine256>() : nullptr, L, R);
 }
 // One IPA round: a, b folded with r (internal form, non-zero) fused with the next round's c_L, c_R; then that round's L, R
@@ -101,6 +113,16 @@ template <int C> static reef_status ipa_round(IpaRun<C> *ip, hipStream_t st, hip
     ip->len /= 2;
     ip->w1s.push_back(fe_to_integer<F>(rinv));
     ip->w2s.push_back(fe_to_integer<F>(ri));
+    if (ip->n_small && !ip->folded && ip->n > ip->n_small && ip->len == ip->n_small) {
+        // the switch: the len generators these challenges lead to become a resident key of their own, made on the key ctx's stream and
+        // waited for (it reads the key's tables and the challenges, nothing of this run's vectors); small enough, it gets nibble tables
+        reef_msm_opts o = {};
+        o.bucket_groups = 1;
+        void *impl = nullptr;
+        REEF_TRY(v_ctx_create_folded<C>(&impl, ip->key, (const reef_fe *)ip->w1s.data(), (const reef_fe *)ip->w2s.data(), ip->w1s.size(), &o));
+        ip->folded = (Ctx<C> *)impl;
+        ip->folded_at = ip->w1s.size();
+    }
     return ipa_cross(ip, st, ev, L, R);
 }
 // The last fold with r: a_hat = a[0] (and b_hat = b[0] when asked) to the host in the caller's form; the key is let go
@@ -119,6 +141,7 @@ template <int C> static reef_status ipa_last(IpaRun<C> *ip, hipStream_t st, cons
     }
     ip->len = 1;
     ip->key = nullptr;
+    ip->drop_folded();
     return REEF_OK;
 }
 // which: 0 a, 1 b: the first `count` (<= len) through `stage` to the host

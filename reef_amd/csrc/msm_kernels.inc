@@ -2151,6 +2151,95 @@ __global__ void __launch_bounds__(256) k_fold_glv_coop(const affine256 *__restri
     if (role == 0 && live) store_xyzz(tmp + i, a);
 }
 
+// ---- deep fold (K3, deep): the generators k folds away in one bucket pass -----------------------------------------
+// After k folds G^(k)_j = sum_{t < T} s_t * G_{t*n_k + j} (T = 2^k, n_k = n/T, s_t the products k_ipa_coef forms): n_k outputs that all
+// use the SAME T scalars.  The host forms the s_t, splits them with the endomorphism (s_t = a_t + b_t*lambda, 128-bit parts) and recodes
+// the parts into signed 3-bit digits in [-4, 4]; dig[(h*DEEP_WMAX + w)*T + t] is digit w of half h (0: a_t, 1: b_t) with the sign
+// of the part folded in.  One lane per (output j, window w): a wave holds 64 consecutive j of ONE window, so the digit of every term is
+// wave-uniform (a scalar load, a scalar branch), and the four signed buckets of the window live in registers.  phi(P) = (beta*x, y) is
+// applied on load for the second half.  One mixed-addition site: the bucket is moved out, added to and moved back.
+// k_deep_accum leaves part[(s*W + w)*cnt + j]: the sum of window w over the t of chunk s; k_deep_reduce sums the chunks (only when
+// there is more than one: few outputs of many terms); k_deep_horner_coop combines the windows per output, 3 doublings and one
+// addition per window, every group operation shared over the four waves of a workgroup (ec_coop.h) as in k_fold_glv_coop.
+static constexpr u32 DEEP_C = 3, DEEP_WMAX = 88;       // 88 windows of 3 bits: a 256-bit magnitude and its carry
+template <int C>
+__global__ void __launch_bounds__(64) k_deep_accum(const affine256 *__restrict__ tab0, u32 n_k, u32 j0, u32 cnt, u32 T, u32 t_per, u32 H,
+                                                  const signed char *__restrict__ dig, xyzz_mem *__restrict__ part) {
+    const u32 jl = blockIdx.x * 64u + threadIdx.x;
+    const u32 w = blockIdx.y, s = blockIdx.z, W = gridDim.y;
+    if (jl >= cnt) return;
+    const u32 t0 = s * t_per, t1 = min(T, t0 + t_per);
+    const fe beta = fe_const<C>(GLV<C>::BETA, 1.0);
+    xyzz b1 = xyzz_identity(), b2 = b1, b3 = b1, b4 = b1;
+    for (u32 t = t0; t < t1; ++t) {
+        const int d0 = dig[(size_t)w * T + t];
+        const int d1 = H > 1 ? (int)dig[((size_t)DEEP_WMAX + w) * T + t] : 0;
+        if ((d0 | d1) == 0) continue;                               // wave-uniform
+        affine p = load_table_point(tab0 + (size_t)t * n_k + j0 + jl);
+        const bool inf = affine_is_inf(p);
+        const fe yneg = fe_select(inf, p.y, fe_canon<C>(fe_neg<C, 2>(p.y)));
+        const fe ypos = p.y;
+#pragma unroll 1
+        for (u32 h = 0; h < 2; ++h) {
+            const int d = h ? d1 : d0;
+            if (h) p.x = fe_canon<C>(fe_mul<C>(p.x, beta));        // phi keeps (0, 0), the affine identity
+            if (d == 0) continue;
+            p.y = d < 0 ? yneg : ypos;
+            const int m = d < 0 ? -d : d;
+            xyzz cur;
+            switch (m) {
+                case 1: cur = b1; break;
+                case 2: cur = b2; break;
+                case 3: cur = b3; break;
+                default: cur = b4; break;
+            }
+            cur = xyzz_madd<C>(cur, p);
+            switch (m) {
+                case 1: b1 = cur; break;
+                case 2: b2 = cur; break;
+                case 3: b3 = cur; break;
+                default: b4 = cur; break;
+            }
+        }
+    }
+    // b1 + 2 b2 + 3 b3 + 4 b4 by running sums
+    xyzz run = b4, acc = b4;
+#pragma unroll 1
+    for (int m = 3; m >= 1; --m) {
+        const xyzz bm = m == 3 ? b3 : m == 2 ? b2 : b1;
+        run = xyzz_add<C>(run, bm);
+        acc = xyzz_add<C>(acc, run);
+    }
+    store_xyzz(part + ((size_t)s * W + w) * cnt + jl, acc);
+}
+// part[e] += part[s*stride + e] for s = 1 .. S-1 (e < stride = W*cnt)
+template <int C>
+__global__ void __launch_bounds__(64) k_deep_reduce(xyzz_mem *__restrict__ part, u32 stride, u32 S) {
+    const u32 e = blockIdx.x * 64u + threadIdx.x;
+    if (e >= stride) return;
+    xyzz acc = load_xyzz(part + e);
+    for (u32 s = 1; s < S; ++s) acc = xyzz_add<C>(acc, load_xyzz(part + (size_t)s * stride + e));
+    store_xyzz(part + e, acc);
+}
+// out[j] = sum_w 8^w * part[w*cnt + j]: 64 outputs per workgroup of four waves
+template <int C>
+__global__ void __launch_bounds__(256) k_deep_horner_coop(const xyzz_mem *__restrict__ part, u32 cnt, u32 W, xyzz_mem *__restrict__ out) {
+    latency_critical();
+    __shared__ CoopLds L;
+    const int lane = threadIdx.x & 63, role = threadIdx.x >> 6;
+    const u32 i0 = blockIdx.x * 64u + lane;
+    const bool live = i0 < cnt;
+    const u32 i = live ? i0 : cnt - 1u;                       // idle lanes repeat the last output and store nothing
+    xyzz a = load_xyzz_coop(part + (size_t)(W - 1u) * cnt + i);
+    for (int w = (int)W - 2; w >= 0; --w) {
+        const xyzz y = load_xyzz_coop(part + (size_t)w * cnt + i);   // requested ahead of the doublings
+#pragma unroll 1
+        for (u32 d = 0; d < DEEP_C; ++d) a = xyzz_dbl_coop<C>(a, L, role, lane);   // one doubling site
+        a = xyzz_add_coop<C>(a, y, L, role, lane);
+    }
+    if (role == 0 && live) store_xyzz(out + i, a);
+}
+
 // ---- IPA rounds without generator folding ----------------------------------------------
 // After k folds G'_i = w1*G_i + w2*G_{i+half} the generators are
 //   G^(k)_i = sum_t coef(t) * G_{i + t*n_k},  n_k = n/2^k,  coef(t) = prod_m (bit_{k-1-m}(t) ? w2_m : w1_m),

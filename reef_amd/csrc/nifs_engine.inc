@@ -27,6 +27,7 @@ template <int C> struct NifsCtx : DeviceCtx {   // ev: orders the key ctx's stre
     std::vector<u32> h_colptr[3];
     NifsSegs cols;                       // long columns of the CSC
     SpartanState<C> *sp = nullptr;       // row N5 workspace, made by the first reef_spartan_begin
+    size_t open_n_small = 0;             // reef_spartan_open_set_small_key: the openings begun from now on move to a folded key at this length (0: never)
     struct EvalWs { DevBuf pts, ex, zy, partial, out; } evw;   // the verifier's matrix evaluations (3k): eq factors, eq(r_x) by row, the column
                                          // weights, block sums, results; empty until the first reef_spartan_eval_matrices
     u64 gen = 0;                         // bumped by every call that changes the matrices or the running instance (or commits T)

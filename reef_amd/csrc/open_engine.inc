@@ -23,7 +23,7 @@ template <int C> static reef_status v_open_begin(void *impl, void *key_impl, boo
     REEF_TRY(s->e1.ensure(s->ncp * sizeof(fe256)));
     REEF_TRY(s->e2.ensure(s->nvp * sizeof(fe256)));
     IpaRun<C> *ip = &s->ip;
-    REEF_TRY(ipa_alloc(ip, n));
+    REEF_TRY(ipa_alloc(ip, n, c->open_n_small));
     const fe256 *e1 = s->e1.template as<fe256>(), *e2 = s->e2.template as<fe256>();
     REEF_TRY(fe_eq_table<F>(c->stream, s->pts, s->rx.data(), s->ell_x, s->e1.template as<fe256>()));
     REEF_TRY(fe_eq_table<F>(c->stream, s->pts, s->ry.data() + 1, s->ell_y - 1, s->e2.template as<fe256>()));
@@ -132,8 +132,16 @@ template <int C> static reef_status v_open_read(void *impl, int which, size_t co
     return ipa_read(&s->ip, c->stream, c->stage, which, count, out, to_mont);
 }
 
+// n_small (0 or a power of two: api.cpp checks) holds for the openings begun after the call; no device work
+template <int C> static reef_status v_open_set_small_key(void *impl, size_t n_small) {
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->open_n_small = n_small;
+    return REEF_OK;
+}
+
 template <int C> OpenVTable make_open_vtable() {
-    return OpenVTable{v_open_begin<C>, v_open_fold<C>, v_open_ipa_begin<C>, v_open_ipa_round<C>, v_open_finish<C>, v_open_read<C>};
+    return OpenVTable{v_open_begin<C>, v_open_fold<C>, v_open_ipa_begin<C>, v_open_ipa_round<C>, v_open_finish<C>, v_open_read<C>, v_open_set_small_key<C>};
 }
 
 }  // namespace reef

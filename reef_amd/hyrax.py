@@ -176,17 +176,25 @@ class HyraxEval(_Handle):
         check(self._lib.reef_hyrax_read(self._h, which, count, out.ctypes.data, to_mont))
         return _ints(out[:count])
 
+    def set_small_key(self, n_small: int) -> None:
+        """The arguments begun (eval_begin) from now on move their rounds to a folded key once a and b have n_small entries
+        (reef_hyrax_set_small_key); a power of two, 0: never (the default)."""
+        check(self._lib.reef_hyrax_set_small_key(self._h, n_small))
+
 
 def prove_eval(hx: HyraxEval, key: MsmContext, point: Sequence[int], challenge: Callable[[str, List[Any]], int], p: int,
                q_of: Callable[[int], np.ndarray], *, row_comms: Optional[np.ndarray] = None, row_comms_compressed=None,
                h: Optional[np.ndarray] = None,
-               blinds_of: Optional[Callable[[int], Tuple[int, int]]] = None, is_mont: bool = False, own_comms: bool = False) -> dict:
+               blinds_of: Optional[Callable[[int], Tuple[int, int]]] = None, is_mont: bool = False, own_comms: bool = False,
+               small_key: Optional[int] = None) -> dict:
     """The whole argument with `challenge(label, absorbed)`: eval_begin, comm_LZ when row_comms (affine) or row_comms_compressed (the
     32-byte rows of PolyCommit.comm, see HyraxEval.eval_comm_compressed) are given or, with own_comms, over the rows
     HyraxEval.commit left on the device, "r" after (comm_LZ, eval)
     for q = q_of(r), then "challenge_r" per round after L and R (compressed).  With h, blinds_of(round) gives that round's (bl, br).
     key: gens_v, exactly 2^right points.  Canonical ints in and out (is_mont: the library calls take Montgomery form)."""
     to, frm = _mont_forms(p, is_mont)
+    if small_key is not None:                 # the late rounds on a folded key of that many points (HyraxEval.set_small_key); None: as the ctx stands
+        hx.set_small_key(small_key)
     ev, lb = (frm(v) for v in hx.eval_begin(key, [to(x) for x in point], is_mont=is_mont))
     if (row_comms is not None) + (row_comms_compressed is not None) + bool(own_comms) > 1:
         raise ValueError("row_comms, row_comms_compressed or own_comms: one of them")

@@ -90,6 +90,12 @@ def scalar_to_limbs(v: int) -> np.ndarray:
     return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
 
 
+def _challenge_limbs(ws) -> np.ndarray:
+    """IPA challenges (ints below 2^256) as a (k, 4) uint64 array; one zero row when there are none, so that the pointer is valid."""
+    k = len(ws)
+    return np.array([list(scalar_to_limbs(w)) for w in ws], dtype=np.uint64).reshape(k, 4) if k else np.zeros((1, 4), np.uint64)
+
+
 class MsmContext(_Handle):
     """A resident commitment key (nova-snark `CommitmentGens<G>`) on one GPU."""
     _destroy = "reef_msm_ctx_destroy"
@@ -280,6 +286,30 @@ class MsmContext(_Handle):
                                         out.ctypes.data, REEF_HOST))
         return out
 
+    def fold_deep(self, w1s, w2s, out: Optional[Buf] = None) -> Buf:
+        """The n / 2^k generators k = len(w1s) folds away from this key (reef_fold_deep): what k successive fold() calls give, in one pass.
+        Challenges as ints (canonical, below the scalar modulus); out: an (n_k, 8) uint64 array (made when None) or a DeviceBuffer."""
+        k = len(w1s)
+        assert len(w2s) == k
+        w1, w2 = _challenge_limbs(w1s), _challenge_limbs(w2s)
+        n_k = self.n >> k
+        if out is None:
+            out = np.zeros((n_k, 8), dtype=np.uint64)
+        oloc, optr = _loc_ptr(out, 64 * n_k)
+        check(self._lib.reef_fold_deep(self._h, w1.ctypes.data, w2.ctypes.data, k, optr, oloc))
+        return out
+
+    def folded(self, w1s, w2s, *, window_bits: int = 0, bucket_groups: int = 1, chunk: int = 0, byte_tables: int = 0) -> "MsmContext":
+        """A resident key of the generators len(w1s) folds away from this one (reef_msm_ctx_create_folded), on the same device; nothing visits
+        the host.  With bucket_groups = 1 (the default here) a key of at most 1024 points gets its nibble tables."""
+        k = len(w1s)
+        assert len(w2s) == k
+        w1, w2 = _challenge_limbs(w1s), _challenge_limbs(w2s)
+        opts = MsmOpts(window_bits, bucket_groups, chunk, byte_tables, -1, (ctypes.c_uint32 * 3)(0, 0, 0))
+        h = ctypes.c_void_p()
+        check(self._lib.reef_msm_ctx_create_folded(ctypes.byref(h), self._h, w1.ctypes.data, w2.ctypes.data, k, ctypes.byref(opts)))
+        return MsmContext(self.curve, None, self.n >> k, _handle=h)
+
     def msm_rows(self, scalars: Buf, rows: int, row_len: int, *, is_mont: bool = True, max_scalar_bits: int = 0,
                  blinds: Optional[Buf] = None, h: Optional[Buf] = None, out: Optional[Buf] = None) -> Buf:
         """reef_msm_rows: rows commitments over the first row_len bases (+ blinds[r] * h).  max_scalar_bits bounds the canonical scalars; 0 measures
@@ -427,6 +457,11 @@ def fold(curve, gens: Buf, half: int, w1: int, w2: int, out: Optional[Buf] = Non
     a, b = scalar_to_limbs(w1), scalar_to_limbs(w2)
     check(_ffi.load().reef_fold(curve_id(curve), ptr, half, loc, a.ctypes.data, b.ctypes.data, optr))
     return out
+
+
+def fold_deep(ctx: "MsmContext", w1s, w2s, out: Optional[Buf] = None) -> Buf:
+    """K3, deep: the generators len(w1s) folds away from ctx's resident key, in one pass (MsmContext.fold_deep)."""
+    return ctx.fold_deep(w1s, w2s, out)
 
 
 def normalize(curve, jac: Buf, n: Optional[int] = None, *, affine: bool = True, compressed: bool = False):

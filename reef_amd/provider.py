@@ -221,6 +221,13 @@ class FoldedGens:
     def split_at(self, k: int) -> Tuple["FoldedGens", "FoldedGens"]:
         return FoldedGens(self.root, self.w1s, self.w2s, self.off, k), FoldedGens(self.root, self.w1s, self.w2s, self.off + k, self.length - k)
 
+    def resident(self, *, bucket_groups: int = 1) -> msm.MsmContext:
+        """The folded generators as a resident key of their own (reef_msm_ctx_create_folded: one deep fold on the device, nothing visits the
+        host); the whole set only.  The caller closes it."""
+        if self.off or self.length != len(self.root) >> len(self.w1s):
+            raise ValueError("a resident key is made of the whole set of folded generators")
+        return self.root._context().folded(self.w1s, self.w2s, bucket_groups=bucket_groups)
+
     def materialize(self) -> "CommitmentGens":
         bases = self.root.bases
         for w1, w2 in zip(self.w1s, self.w2s):

@@ -10,7 +10,7 @@ Points cross as numpy uint64 arrays in the C-ABI layouts: affine (8 limbs) in, J
 """
 from __future__ import annotations
 
-from typing import Any, Callable, List, Sequence, Tuple
+from typing import Any, Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -138,6 +138,11 @@ class Opening:
         check(self._lib.reef_spartan_open_read(self.nifs._h, which, count, out.ctypes.data, to_mont))
         return _ints(out[:count])
 
+    def set_small_key(self, n_small: int) -> None:
+        """The openings begun from now on move their rounds to a folded key once a and b have n_small entries
+        (reef_spartan_open_set_small_key); a power of two, 0: never (the default)."""
+        check(self._lib.reef_spartan_open_set_small_key(self.nifs._h, n_small))
+
 
 def compress(key: MsmContext, jac: np.ndarray) -> bytes:
     """A point's 32-byte compressed encoding (what the transcript absorbs), on the device of the library."""
@@ -162,13 +167,16 @@ def _ipa_rounds(first: Tuple[np.ndarray, np.ndarray], step_fn: Callable[[int, in
 
 
 def prove_with_opening(nifs: Nifs, key: MsmContext, num_cons_pad: int, num_vars_pad: int, challenge: Callable[[str, List[Any]], int],
-                       p: int, comm_a: Callable[[int], Any], q_of: Callable[[int], np.ndarray], *, is_mont: bool = False) -> dict:
+                       p: int, comm_a: Callable[[int], Any], q_of: Callable[[int], np.ndarray], *, is_mont: bool = False,
+                       small_key: Optional[int] = None) -> dict:
     """`prove`, then the batched IPA opening of [E, W] with the same `challenge(label, absorbed)`, in nova's order: "r" (the NIFS
     challenge, after the cross term), "r" again (the IPA's, after comm_a and c), then "challenge_r" per round (after L and R,
     compressed).  The caller's point operations: comm_a(r) = comm_E + r comm_W as the transcript absorbs it, and
     q_of(r) = gens_s.scale(r), affine.  key: gens_v, exactly max(num_cons_pad, num_vars_pad) points.  Canonical ints in and out."""
     out = prove(nifs, num_cons_pad, num_vars_pad, challenge, p, is_mont=is_mont)
     op = Opening(nifs)
+    if small_key is not None:                 # the late rounds on a folded key of that many points (Opening.set_small_key); None: as the ctx stands
+        op.set_small_key(small_key)
     to, frm = _mont_forms(p, is_mont)
     cross = frm(op.begin(key, is_mont=is_mont))
     r_fold = challenge("r", [cross])
