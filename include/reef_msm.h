@@ -37,6 +37,7 @@
  *      (reef_hyrax_commit, reef_hyrax_eval_comm_own, section 3i).
  *      Later, still 7 (symbols added, none changed): a document's bytes turned into alphabet symbols on the device
  *      (reef_doc_transform, section 3l).
+ *      Later, still 7 (symbols added, none changed): entries of the sum-check table as last set, by index (reef_sc_lookup, section 3b).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -364,6 +365,13 @@ reef_status reef_sc_fold(reef_sc_ctx *ctx, size_t pow, const reef_fe *r);
 reef_status reef_sc_fold_and_next_coeffs(reef_sc_ctx *ctx, size_t pow, const reef_fe *r, reef_fe out[3]);
 /* Read back the first `count` entries of a table as canonical integers (host). */
 reef_status reef_sc_read(reef_sc_ctx *ctx, int which, size_t count, reef_fe *out);
+/* out[j] = T[idx[j]] of the table AS LAST SET (what reef_sc_reset_table restores), canonical integers: the v_i of a step's
+ * lookups (r1cs.rs:2066-2077) when the document's symbols live on the device only.  idx is a host array of k indices (repeats
+ * allowed), out has k entries in host or device memory (out_loc); k = 0 is REEF_OK.  In no call order: legal before, between and
+ * after rounds, the answer does not depend on how far T has been folded, and the rounds that follow run the kernels they would
+ * have run without it.  An index >= table_len, or a ctx no table was set on: REEF_ERR_ARG (reef_last_error names the first such
+ * index), nothing written. */
+reef_status reef_sc_lookup(reef_sc_ctx *ctx, const uint64_t *idx, size_t k, reef_fe *out, int out_loc);
 /* T <- the values last given to reef_sc_set_table(ctx, 0, ..): every folding step starts from the
  * unfolded table (the reference clones it per step, r1cs.rs:2320); device-to-device, asynchronous. */
 reef_status reef_sc_reset_table(reef_sc_ctx *ctx);

@@ -177,6 +177,7 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_sc_fold": (c_int, [vp, c_size_t, vp]),
         "reef_sc_fold_and_next_coeffs": (c_int, [vp, c_size_t, vp, vp]),
         "reef_sc_read": (c_int, [vp, c_int, c_size_t, vp]),
+        "reef_sc_lookup": (c_int, [vp, vp, c_size_t, vp, c_int]),
         "reef_sc_reset_table": (c_int, [vp]),
         "reef_sc_sync": (c_int, [vp]),
         "reef_nifs_create": (c_int, [POINTER(vp), c_int, c_size_t, c_size_t, c_size_t, c_int]),

@@ -494,6 +494,9 @@ reef_status reef_sc_fold_and_next_coeffs(reef_sc_ctx *ctx, size_t pow, const ree
 reef_status reef_sc_read(reef_sc_ctx *ctx, int which, size_t count, reef_fe *out) {
     return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_read(impl, which, count, out); });
 }
+reef_status reef_sc_lookup(reef_sc_ctx *ctx, const uint64_t *idx, size_t k, reef_fe *out, int out_loc) {
+    return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_lookup(impl, idx, k, out, out_loc); });
+}
 reef_status reef_sc_reset_table(reef_sc_ctx *ctx) {
     return dispatch<CurveVTable>(ctx, [&](auto *v, void *impl) { return v->sc_reset(impl); });
 }

@@ -475,6 +475,7 @@ struct CurveVTable {
     reef_status (*sc_set)(void *impl, int which, const reef_fe *vals, size_t n, int loc);
     reef_status (*sc_set_parts)(void *impl, const reef_sc_part *parts, size_t nparts);
     reef_status (*sc_read)(void *impl, int which, size_t count, reef_fe *out_host);
+    reef_status (*sc_lookup)(void *impl, const uint64_t *idx, size_t k, reef_fe *out, int out_loc);
     reef_status (*sc_coeffs)(void *impl, size_t pow, reef_fe *out3_host);
     reef_status (*sc_fold)(void *impl, size_t pow, const reef_fe *r);
     reef_status (*sc_fold_coeffs)(void *impl, size_t pow, const reef_fe *r, reef_fe *out3_host);

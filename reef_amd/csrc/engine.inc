@@ -2302,7 +2302,7 @@ template <int C> static CurveVTable make_vtable() {
     return CurveVTable{v_ctx_create<C>, v_ctx_rekey<C>, v_ctx_clone<C>, v_ctx_attach<C>, v_ctx_destroy<C>, v_ctx_sync<C>, v_ctx_stream<C>,
                        v_ctx_timing<C>, v_ctx_enable_timing<C>, v_ctx_window_split<C>, v_ctx_timing_stats<C>, v_ctx_rowcol_forms<C>, v_ctx_sum_points<C>, v_ctx_plan<C>, v_ctx_byte_tables<C>, v_msm<C>, v_msm_rows<C>, v_msm_rows_symbols<C>, v_msm_rows_symbols_wide<C>, v_ipa_cross<C>, v_msm_folded<C>, v_fold<C>, v_normalize<C>, v_sum_points<C>,
                        v_gen_bases<C>, v_gen_scalars<C>, v_test_field_op<C>, v_test_ec_op<C>, v_bench_fmul<C>,
-                       v_sc_create<C>, v_sc_destroy<C>, v_sc_set<C>, v_sc_set_parts<C>, v_sc_read<C>, v_sc_coeffs<C>, v_sc_fold<C>, v_sc_fold_coeffs<C>, v_sc_gen_eq<C>, v_sc_reset<C>, v_sc_sync<C>, v_mle_bound<C>, v_merkle_commit<C>, v_derive_generators<C>, plan_for, v_decompress<C>, doc_check, doc_transform,
+                       v_sc_create<C>, v_sc_destroy<C>, v_sc_set<C>, v_sc_set_parts<C>, v_sc_read<C>, v_sc_lookup<C>, v_sc_coeffs<C>, v_sc_fold<C>, v_sc_fold_coeffs<C>, v_sc_gen_eq<C>, v_sc_reset<C>, v_sc_sync<C>, v_mle_bound<C>, v_merkle_commit<C>, v_derive_generators<C>, plan_for, v_decompress<C>, doc_check, doc_transform,
                        v_fold_deep<C>, v_ctx_create_folded<C>};
 }
 

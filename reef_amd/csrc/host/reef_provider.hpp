@@ -373,6 +373,12 @@ class SumCheck {
         have_next_ = false;
         check(reef_sc_set_table_parts(sc_, parts.data(), parts.size()), "reef_sc_set_table_parts");
     }
+    // T[idx[j]] of the table as last set, whatever has been folded since: the v_i of a step's lookups (r1cs.rs:2066-2077).  Leaves the rounds alone.
+    std::vector<reef_fe> lookup(const std::vector<uint64_t> &idx) {
+        std::vector<reef_fe> v(idx.size());
+        check(reef_sc_lookup(sc_, idx.data(), idx.size(), v.data(), REEF_HOST), "reef_sc_lookup");
+        return v;
+    }
     void start_step() { have_next_ = false; check(reef_sc_reset_table(sc_), "reef_sc_reset_table"); }   // every folding step starts from the unfolded table
     void gen_eq_table(const std::vector<reef_fe> &rs, const std::vector<uint32_t> &qs, const std::vector<reef_fe> &last_q) {
         if (rs.size() != qs.size() + 1 || last_q.size() != ell_) throw std::logic_error("gen_eq_table: |rs| = |qs| + 1, |last_q| = ell");

@@ -32,8 +32,10 @@
 // One translation unit, two artefacts (host/Makefile): libreef_replay.so exports reef_replay_run() -- bench.py calls it
 // in-process after its timed region, tests/test_gpu_replay.py under pytest -- and the reef_replay executable is its main().
 // This file holds the entry points and main(); the rest is its headers: replay_util.hpp (shared helpers), replay_msm.hpp (the MSM
-// replay and the multi-device leg), replay_prove.hpp (the prove leg's device run) and proof_check.hpp (its verifier, host only).
-#include "replay_prove.hpp"   // and through it replay_msm.hpp, replay_util.hpp, proof_check.hpp
+// replay and the multi-device leg), replay_prove.hpp (the prove leg's device run) and proof_check.hpp (its verifier, host only),
+// replay_lookup.hpp (the lookup leg, `reef_replay cfgN lookup`: the lookup argument from the document's bytes to the consistency
+// argument) and lookup_check.hpp (its verifier, host only).
+#include "replay_lookup.hpp"   // and through it replay_prove.hpp, replay_msm.hpp, replay_util.hpp, proof_check.hpp, lookup_check.hpp
 
 // ---- entry points ---------------------------------------------------------------------------------------------------
 // Runs the replay of the config whose name contains `config` ("cfg1" | "cfg3" | "cfg4" | "cfg5") with the shapes of
@@ -96,6 +98,27 @@ int reef_replay_check_selftest(const char *tamper, char *out, size_t cap) {
     return entry_point(out, cap, 2, [&] { return check_selftest(tamper ? tamper : ""); });
 }
 
+// The lookup leg of the config whose name contains `config` (replay_lookup.hpp): the lookup argument of every folding step, from the
+// document's bytes to the claim the consistency argument proves, checked (lookup_check.hpp).  flags: space-separated -- "mode=doc|hybrid"
+// (default: hybrid when the shape's table_log is doc_log + 1), "proj=<k>" (nldoc over an aligned chunk of 2^(doc_log - k) symbols),
+// "width=1|2|4" (bytes per device symbol), "tamper=<phase>" (lookup | claim | hyrax).  Returns as reef_replay_run_prove does.
+extern "C" __attribute__((visibility("default")))
+int reef_replay_run_lookup(const char *shapes_json, const char *config, const char *flags, char *out, size_t cap) {
+    return entry_point(out, cap, 1, [&] {
+        const LookupFlags fl = parse_lookup_flags(flags);
+        const Shape sh = find_shape(shapes_json, config);
+        g_checked = 0;
+        g_small_key = 0;
+        return lookup_body(sh, fl);
+    });
+}
+// The lookup leg's checks on a tiny honest transcript made on the host (no GPU); tamper: NULL / "" or lookup | claim | hyrax.  Returns 0
+// and the JSON line (both transcripts in full), 1 and the message naming the phase, 2 on a usage error.
+extern "C" __attribute__((visibility("default")))
+int reef_replay_lookup_selftest(const char *tamper, char *out, size_t cap) {
+    return entry_point(out, cap, 2, [&] { return lookup_selftest(tamper ? tamper : ""); });
+}
+
 #if !defined(REEF_REPLAY_NO_MAIN)
 #include <unistd.h>
 int main(int argc, char **argv) {
@@ -103,8 +126,8 @@ int main(int argc, char **argv) {
     bool nofold = false, tables = false;
     std::string shapes;
     int members = 0;
-    bool prove = false;
-    std::string prove_flags;
+    bool prove = false, lookup = false;
+    std::string prove_flags, lookup_flags;
     {   // an embedder's first call: eight hardware queues for the concurrent arguments, asked for before the first HIP call
         reef_runtime_opts ro = {};
         ro.hw_queues = 8;
@@ -116,8 +139,11 @@ int main(int argc, char **argv) {
         else if (strncmp(argv[i], "shapes=", 7) == 0) shapes = argv[i] + 7;
         else if (strncmp(argv[i], "devices=", 8) == 0) members = atoi(argv[i] + 8);     // the multi-device leg on N members (ordinal i mod the visible devices)
         else if (strcmp(argv[i], "prove") == 0) prove = true;                          // the prove leg: every device row of one proof, checked
-        else if (strncmp(argv[i], "tamper=", 7) == 0 || strcmp(argv[i], "paired") == 0 || strncmp(argv[i], "small_key=", 10) == 0) prove_flags += std::string(" ") + argv[i];
-        else { fprintf(stderr, "usage: reef_replay [cfg1|cfg3|cfg4|cfg4b|cfg5] [nofold] [tables] [devices=N] [shapes=<replay_shapes.json>] | [prove [paired] [small_key=N] [tamper=<phase>]]\n"); return 2; }
+        else if (strcmp(argv[i], "lookup") == 0) lookup = true;                        // the lookup leg: the lookup argument, bytes to consistency, checked
+        else if (strncmp(argv[i], "tamper=", 7) == 0) { prove_flags += std::string(" ") + argv[i]; lookup_flags += std::string(" ") + argv[i]; }
+        else if (strcmp(argv[i], "paired") == 0 || strncmp(argv[i], "small_key=", 10) == 0) prove_flags += std::string(" ") + argv[i];
+        else if (strncmp(argv[i], "mode=", 5) == 0 || strncmp(argv[i], "proj=", 5) == 0 || strncmp(argv[i], "width=", 6) == 0) lookup_flags += std::string(" ") + argv[i];
+        else { fprintf(stderr, "usage: reef_replay [cfg1|cfg3|cfg4|cfg4b|cfg5] [nofold] [tables] [devices=N] [shapes=<replay_shapes.json>] | [prove [paired] [small_key=N] [tamper=<phase>]] | [lookup [mode=doc|hybrid] [proj=K] [width=1|2|4] [tamper=<phase>]]\n"); return 2; }
     }
     if (shapes.empty() && !getenv("REEF_REPLAY_SHAPES")) {   // the executable lives in reef_amd/_lib/: the shapes are two levels up, under tests/golden/
         char exe[4096];
@@ -131,7 +157,9 @@ int main(int argc, char **argv) {
     }
     std::vector<char> out(32768);
     int rc;
-    if (prove) {
+    if (lookup) {
+        rc = reef_replay_run_lookup(shapes.empty() ? nullptr : shapes.c_str(), which, lookup_flags.c_str(), out.data(), out.size());
+    } else if (prove) {
         if (tables) prove_flags += " tables";
         rc = reef_replay_run_prove(shapes.empty() ? nullptr : shapes.c_str(), which, prove_flags.c_str(), out.data(), out.size());
     } else {

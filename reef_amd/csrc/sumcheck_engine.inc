@@ -9,6 +9,8 @@ template <int C> struct ScCtx : DeviceCtx {   // device: where the tables live; 
     DevBuf T, T0, E, partial, out3, stage, fac, qs, misc;   // T0: pristine copy of T (a fold consumes T)
     u32 nblocks = 0;
     bool fresh = false;                  // T has not been folded since it was set / reset: its content is T0
+    bool has_table = false;              // T0 holds a table: reef_sc_set_table(ctx, 0, ..) or reef_sc_set_table_parts has run
+    DevBuf lk;                           // reef_sc_lookup: the indices, then the answers of a host caller
     // EQ as gen_eq_table made it and the folds left it: FH (x) FL + point masses, never written out while the rounds fold FH
     // bits (sumcheck_kernels.inc, "rank-one").  fac holds FH (2^r1_hi0 entries, folded in place) followed by FL.
     bool r1 = false;
@@ -96,7 +98,7 @@ template <int C> static u32 sc_dense_blocks(const ScCtx<C> *c, size_t work) {
 template <int C> static void sc_free(ScCtx<C> *c) {
     if (!c) return;
     retire_device_ctx(c);
-    for (DevBuf *b : {&c->T, &c->T0, &c->E, &c->partial, &c->out3, &c->stage, &c->fac, &c->qs, &c->misc, &c->r1rows, &c->r1mq, &c->r1mw, &c->gacc, &c->st_s32, &c->st_flags, &c->st_lists, &c->st_k, &c->st_sumfl, &c->r1acc}) b->release();
+    for (DevBuf *b : {&c->T, &c->T0, &c->E, &c->partial, &c->out3, &c->stage, &c->fac, &c->qs, &c->misc, &c->r1rows, &c->r1mq, &c->r1mw, &c->gacc, &c->st_s32, &c->st_flags, &c->st_lists, &c->st_k, &c->st_sumfl, &c->r1acc, &c->lk}) b->release();
     if (c->pinned3) (void)hipHostFree(c->pinned3);
     if (c->pin_in) (void)hipHostFree(c->pin_in);
     for (auto &e : c->pin_ev) if (e) (void)hipEventDestroy(e);
@@ -441,7 +443,7 @@ template <int C> static reef_status v_sc_set(void *impl, int which, const reef_f
     }
     if (n) hipLaunchKernelGGL(k_fe_import<ScCtx<C>::F>, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, src, (u64)n, 0, dst);
     if (n < c->len) REEF_HIP_TRY(hipMemsetAsync(dst + n, 0, (c->len - n) * sizeof(fe256), c->stream));
-    if (which == 0) c->fresh = true;
+    if (which == 0) c->fresh = c->has_table = true;
     else c->r1 = false;                  // a table given by the caller is a dense table
     REEF_HIP_TRY(hipGetLastError());
     if (which == 0) REEF_TRY(sc_struct_build<C>(c, src, n));
@@ -523,7 +525,7 @@ template <int C> static reef_status v_sc_set_parts(void *impl, const reef_sc_par
     hipLaunchKernelGGL(k_sc_set_parts<ScCtx<C>::F>, dim3(ceil_div(ceil_div(tiles, sub), 4)), dim3(256), 0, c->stream, a, (u32)c->len, lo, sub,
                        c->T0.template as<fe256>(), H ? c->st_flags.template as<u32>() : nullptr, H ? c->st_s32.template as<u32>() : nullptr);
     REEF_HIP_TRY(hipGetLastError());
-    c->fresh = true;
+    c->fresh = c->has_table = true;
     if (H) REEF_TRY(sc_struct_lists<C>(c, H));
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));
     return REEF_OK;
@@ -548,6 +550,37 @@ template <int C> static reef_status v_sc_read(void *impl, int which, size_t coun
                        c->stage.template as<fe256>());
     REEF_HIP_TRY(hipGetLastError());
     REEF_HIP_TRY(hipMemcpyAsync(out_host, c->stage.p, count * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));
+    return REEF_OK;
+}
+
+// out[j] = T[idx[j]] of the table as last set -- the v_i of a step's lookups (r1cs.rs:2066-2077) once the document lives on the device
+// only.  Reads the pristine copy and touches nothing a round depends on: no flush of a deferred fold, no change to fresh / valid / the
+// rank-one state, buffers of its own.  It ends with a wait for the stream like reef_sc_read, which leaves the rounds that follow
+// the kernels and the operands they would have had without it.
+template <int C> static reef_status v_sc_lookup(void *impl, const uint64_t *idx, size_t k, reef_fe *out, int out_loc) {
+    ScCtx<C> *c = (ScCtx<C> *)impl;
+    if (!c) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (k == 0) return REEF_OK;
+    if (!idx || !out) { set_error("reef_sc_lookup: %s is NULL", !idx ? "idx" : "out"); return REEF_ERR_ARG; }
+    if (k > ((size_t)1 << 31)) { set_error("reef_sc_lookup: %zu indices, at most 2^31 per call", k); return REEF_ERR_ARG; }
+    DeviceCall call(c, OnExit::RELEASE_IF_IDLE);
+    if (!c->has_table) { set_error("reef_sc_lookup: no table has been set on this ctx"); return REEF_ERR_ARG; }
+    for (size_t j = 0; j < k; ++j)
+        if (idx[j] >= c->len) {
+            set_error("reef_sc_lookup: idx[%zu] = %llu is not below the table length %zu", j, (unsigned long long)idx[j], c->len);
+            return REEF_ERR_ARG;
+        }
+    REEF_TRY(call.enter());
+    const bool to_host = out_loc != REEF_DEVICE;
+    const size_t idx_bytes = (k * sizeof(u64) + 31) & ~(size_t)31;
+    REEF_TRY(c->lk.ensure(idx_bytes + (to_host ? k * sizeof(fe256) : 0)));
+    REEF_HIP_TRY(hipMemcpyAsync(c->lk.p, idx, k * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    fe256 *dst = to_host ? reinterpret_cast<fe256 *>(c->lk.template as<unsigned char>() + idx_bytes) : (fe256 *)out;
+    hipLaunchKernelGGL(k_sc_lookup<ScCtx<C>::F>, dim3((u32)ceil_div(k, 256)), dim3(256), 0, c->stream, (const fe256 *)c->T0.template as<fe256>(), (u64)c->len,
+                       (const u64 *)c->lk.template as<u64>(), (u32)k, dst);
+    REEF_HIP_TRY(hipGetLastError());
+    if (to_host) REEF_HIP_TRY(hipMemcpyAsync(out, dst, k * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));
     return REEF_OK;
 }

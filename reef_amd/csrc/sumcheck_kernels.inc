@@ -1406,4 +1406,17 @@ __global__ void __launch_bounds__(256) k_sc_r2_fold_coeffs_cs(const u32 *__restr
     r1_block_sums<F, S11>(aq, a11, ac, live, fl, u, acc, partial);
 }
 
+// reef_sc_lookup: out[j] = T0[idx[j]] as a canonical integer, one index per lane.  T0 is the pristine table in resident form whatever it
+// was set from -- k_fe_import (integers) and k_sc_set_parts (FE runs, the FILL's table form, symbols of every width, zero past the
+// parts) both write all `len` entries of it -- and no fold ever writes it, so the answer is the same before, between and after rounds.
+// The host has checked every index against len; the kernel checks again and writes nothing for one that is not below it.
+template <int F>
+static __global__ void __launch_bounds__(256) k_sc_lookup(const fe256 *__restrict__ T0, u64 len, const u64 *__restrict__ idx, u32 k, fe256 *__restrict__ out) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    const u64 i = idx[j];
+    if (i >= len) return;
+    store_fe256(out + j, fe_to_caller<F>(fe_from_table(load_fe256(T0 + i)), 0));
+}
+
 }  // namespace reef

@@ -35,6 +35,10 @@ def _load() -> ctypes.CDLL:
         lib.reef_replay_run_prove.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
         lib.reef_replay_check_selftest.restype = ctypes.c_int
         lib.reef_replay_check_selftest.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+        lib.reef_replay_run_lookup.restype = ctypes.c_int
+        lib.reef_replay_run_lookup.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+        lib.reef_replay_lookup_selftest.restype = ctypes.c_int
+        lib.reef_replay_lookup_selftest.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
         lib.reef_replay_run_devices.restype = ctypes.c_int
         lib.reef_replay_run_devices.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_size_t,
                                                 ctypes.c_char_p, ctypes.c_size_t]
@@ -62,10 +66,11 @@ def shapes(shapes_path: str | None = None) -> dict:
 
 
 PROVE_PHASES = ("nifs", "spartan", "open", "hyrax")
+LOOKUP_PHASES = ("lookup", "claim", "hyrax")
 
 
 class ProofRejected(RuntimeError):
-    """A check of the prove leg failed; .phase names it (nifs | spartan | open | hyrax)."""
+    """A check of the prove leg (.phase: nifs | spartan | open | hyrax) or of the lookup leg (lookup | claim | hyrax) failed."""
 
     def __init__(self, message: str, phase: str | None):
         super().__init__(message)
@@ -73,7 +78,7 @@ class ProofRejected(RuntimeError):
 
 
 def _phase_of(text: str):
-    for p in PROVE_PHASES:
+    for p in PROVE_PHASES + LOOKUP_PHASES:
         if text.startswith(f"proof check failed [{p}]"):
             return p
     return None
@@ -120,4 +125,41 @@ def check_selftest(tamper: str | None = None) -> dict:
         raise ProofRejected(text, _phase_of(text))
     if rc != 0:
         raise RuntimeError(f"reef_replay_check_selftest failed with {rc}: {text}")
+    return json.loads(text)
+
+
+def run_lookup(config: str = "cfg3", mode: str | None = None, proj: int = 0, width: int = 1, tamper: str | None = None,
+               shapes_path: str | None = None) -> dict:
+    """The lookup leg: the lookup argument of every folding step as one chain of device rows -- the document's bytes through
+    reef_doc_transform into device symbols, reef_hyrax_create / _commit and reef_sc_set_table_parts on that buffer, per step
+    reef_sc_lookup and the N2 rounds under a stand-in transcript, the last running claim handed to reef_hyrax_eval_begin and its IPA --
+    then checked on the host: every round's equations, T~ at the step's point recomputed outside the sum-check rows, the running claim
+    from step to step, the claim against the evaluation the consistency argument proves, the Hyrax argument itself.  mode: "doc" |
+    "hybrid" (None: from the shape); proj=k: nldoc over an aligned chunk of 2^(doc_log - k) symbols; width: bytes per device symbol.
+    Returns the JSON line as a dict; a rejection raises ProofRejected with .phase in LOOKUP_PHASES (as it must with tamper=<phase>)."""
+    if tamper is not None and tamper not in LOOKUP_PHASES:
+        raise ValueError(f"tamper must be one of {LOOKUP_PHASES}")
+    flags = ([f"mode={mode}"] if mode else []) + ([f"proj={int(proj)}"] if proj else []) + [f"width={int(width)}"] + ([f"tamper={tamper}"] if tamper else [])
+    buf = ctypes.create_string_buffer(32768)
+    rc = _load().reef_replay_run_lookup((shapes_path or SHAPES_PATH).encode(), config.encode(), " ".join(flags).encode(), buf, len(buf))
+    text = buf.value.decode(errors="replace")
+    if rc != 0:
+        phase = _phase_of(text)
+        if rc == 1 and phase in LOOKUP_PHASES:
+            raise ProofRejected(f"reef_replay_run_lookup({config}): {text}", phase)
+        raise RuntimeError(f"reef_replay_run_lookup({config}) failed with {rc}: {text}")
+    return json.loads(text)
+
+
+def lookup_selftest(tamper: str | None = None) -> dict:
+    """The lookup leg's checks on a tiny honest transcript made on the host with plain loops (no GPU needed): ell = 4, 3 steps of 3
+    lookups, mode doc and mode hybrid.  Returns the line as a dict -- both transcripts in full, canonical integers as hex strings --
+    when every check accepts; raises ProofRejected naming the phase when one rejects (as it must with tamper=<phase>)."""
+    buf = ctypes.create_string_buffer(65536)
+    rc = _load().reef_replay_lookup_selftest(tamper.encode() if tamper else None, buf, len(buf))
+    text = buf.value.decode(errors="replace")
+    if rc == 1:
+        raise ProofRejected(text, _phase_of(text))
+    if rc != 0:
+        raise RuntimeError(f"reef_replay_lookup_selftest failed with {rc}: {text}")
     return json.loads(text)

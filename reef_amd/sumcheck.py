@@ -153,6 +153,20 @@ class SumCheck(_Handle):
         check(self._lib.reef_sc_read(self._h, which, count, out.ctypes.data))
         return array_to_ints(out)
 
+    def lookup(self, idx: Sequence[int], out=None):
+        """T[idx[j]] of the table as last set (what reset_table restores), however far T has been folded: the v_i of a step's lookups
+        (r1cs.rs:2066-2077).  Does not disturb the rounds: a pending fused round stays pending.  Returns the list of ints, or -- out: a
+        DeviceBuffer of 32 bytes per index -- writes them there as canonical integers and returns None."""
+        q = np.ascontiguousarray(np.array([int(i) for i in idx], dtype=np.uint64))
+        if out is not None:
+            if out.nbytes < 32 * len(q):
+                raise ValueError("device buffer too small")
+            check(self._lib.reef_sc_lookup(self._h, q.ctypes.data, len(q), out.ptr, REEF_DEVICE))
+            return None
+        host = np.zeros((len(q), 4), dtype=np.uint64)
+        check(self._lib.reef_sc_lookup(self._h, q.ctypes.data, len(q), host.ctypes.data, REEF_HOST))
+        return array_to_ints(host)
+
     def reset_table(self) -> None:
         """T <- the table as last set (start of the next folding step)."""
         self._pending = None
