@@ -38,6 +38,8 @@
  *      Later, still 7 (symbols added, none changed): a document's bytes turned into alphabet symbols on the device
  *      (reef_doc_transform, section 3l).
  *      Later, still 7 (symbols added, none changed): entries of the sum-check table as last set, by index (reef_sc_lookup, section 3b).
+ *      Later, still 7 (symbols added, none changed): a batch of IPA openings checked against one key in a single pass
+ *      (reef_ipa_check_batch, reef_ipa_check_batch_last_timing, section 3m).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -847,6 +849,72 @@ reef_status reef_doc_transform(const uint8_t *text, size_t nbytes, int text_loc,
                                const uint32_t *map, size_t map_len,        /* host; NULL = the encoding's own alphabet */
                                uint32_t eof_symbol, uint32_t epsilon_symbol,
                                void *out, uint32_t elem_bytes, size_t out_cap, int out_loc, reef_doc_info *info);
+
+/* ---------------------------------------------------------------------------------------------
+ * (3m) A batch of IPA openings checked against one key in a single pass: a verifier that holds one set of public parameters and
+ * checks a stream of proofs (all proofs for the same regex and document size share gens_v).  With weights rho_i the m checks of 3j
+ * collapse into one equation -- the standard batch verification of inner-product arguments; nothing of the protocol changes and
+ * nothing of what a single call of 3j does:
+ *
+ *   sum_i rho_i (comm_i + c_i q_i + sum_t rs_it^2 L_it + sum_t rs_it^-2 R_it - (a_hat_i b_hat_i) q_i - blind_i h_i)  ==  < S, key >
+ *   S_j = sum_i rho_i a_hat_i s^(i)_j        (s^(i): 3j's s vector of proof i)
+ *
+ * One MSM over the key whatever m is, one MSM over the m (2k + 2) one-off points and the h_i of the blinded proofs, and an O(m n)
+ * field pass that builds S (one launch for any m).  b_hat_i = <s^(i), b^(i)> has a closed form of O(k) products for the eq form and
+ * is formed on the host, so every scalar is known before anything is enqueued.
+ *
+ * A reef_ipa_proof holds what reef_ipa_check_eq takes for one proof, field for field; every pointer in it is HOST memory.
+ * Conventions are 3j's: round 0 pairs with the most significant index bit, is_mont names the form of every scalar (rho included),
+ * points are in pasta Montgomery coordinates, any Z is legal, the identity is legal.  All m proofs are over the same n; the key must
+ * hold at least n points; any kind of key is accepted (plain, pre-shifted, byte tables, small).
+ *
+ * rho: m HOST scalars, each non-zero and below the modulus.  They are the CALLER'S randomness, to be drawn after all m proofs are
+ * fixed (from a transcript over them, or from a random source the provers cannot predict): the library draws no randomness.  An
+ * accepted batch vouches for each proof only up to the usual 1/|F| over that choice; with weights a prover could foresee, errors
+ * of two proofs can cancel (rho = [1, 1] accepts comm_0 + X beside comm_1 - X: that is what the equation says).
+ *
+ * *accept_all   1 iff the combined equation holds.  A batch that does not verify is REEF_OK with *accept_all = 0, not an error.
+ * accept_each   m entries, may be NULL.  The batch accepts: every entry is 1.  The batch rejects: the call then runs the single check
+ *               of 3j on each proof -- m MSMs over the key, paid ONLY on failure -- and fills the array.  NULL: nothing beyond the
+ *               batch runs.
+ * b_hats        m entries, may be NULL: b_hat_i, bit for bit what reef_ipa_check_eq returns for proof i alone (the form is_mont names).
+ * s_comb        n entries, may be NULL: S as canonical integers, in host or device memory (s_loc; a device buffer 16-byte aligned).
+ * d_comb, g_comb   may be NULL: the left and the right side of the combined equation (Jacobian, HOST memory).
+ * Asking for the intermediates changes neither the verdict nor what is launched.
+ *
+ * m = 0: REEF_OK with *accept_all = 1, whatever the key, and no device work.  REEF_ERR_ARG, with no output touched and the key
+ * usable, the message naming the proof's index where there is one: everything 3j rejects, per proof; a rho that is zero or not
+ * below the modulus; a null field of a proof (h and blind excepted: both NULL or both given); npoints outside {1, 2}; a batch beyond
+ * the limits m <= 4096 and m (2k + 3) <= 2^16 one-off points (the message names both numbers); a window split on the key ctx.
+ * S and the MSM over the key run on the key ctx's stream.  The one-off points take 3j's route beside them on a second stream --
+ * made affine, imported into a plain key of the key ctx's own, one MSM -- but on a second side key, sized to the largest batch
+ * seen (grow-only, freed with the ctx); the 64-slot side key of the single calls is not touched.  The comparison needs no
+ * inversion; one host wait, and accept_each's fallback comes after it.
+ * reef_ipa_check_batch_last_timing: how the last batch on the key ctx divided, in device milliseconds, when it ran with the key's
+ * timing on (reef_msm_ctx_enable_timing): the tables and the S pass, the MSM over the key, the one-off points (normalise, import,
+ * MSM).  Each pointer may be NULL.  REEF_ERR_ARG when there was no such batch.
+ * Out of scope: an explicit b vector per proof; proofs of different n in one batch; a batched reef_spartan_eval_matrices; any change
+ * to the replay (its two openings are on different curves and cannot share a key). */
+typedef struct {
+    const reef_jacobian *comm;          /* 1 */
+    const reef_fe *c;                   /* 1 */
+    const reef_affine *q;               /* 1 */
+    const reef_jacobian *L, *R;         /* k = log2(n) each */
+    const reef_fe *rs;                  /* k */
+    const reef_fe *a_hat;               /* 1 */
+    const reef_fe *const *points;       /* b = sum_t weights[t] pad(eq(points[t])): reef_ipa_check_eq's form, npoints 1 or 2 */
+    const size_t *vars;
+    const reef_fe *weights;
+    size_t npoints;
+    const reef_affine *h;               /* both NULL or both given, per proof */
+    const reef_fe *blind;
+} reef_ipa_proof;                       /* 13 pointers/sizes: 104 bytes */
+
+reef_status reef_ipa_check_batch(reef_msm_ctx *key, size_t n, const reef_ipa_proof *proofs, size_t m, const reef_fe *rho, bool is_mont,
+                                 uint32_t *accept_all, uint32_t *accept_each /* m, may be NULL */, reef_fe *b_hats /* m, may be NULL */,
+                                 reef_fe *s_comb /* n, may be NULL */, int s_loc, reef_jacobian *d_comb /* may be NULL */,
+                                 reef_jacobian *g_comb /* may be NULL */);
+reef_status reef_ipa_check_batch_last_timing(reef_msm_ctx *key, float *s_pass_ms, float *key_msm_ms, float *side_ms);
 
 /* ---------------------------------------------------------------------------------------------
  * (4) Runtime plumbing.

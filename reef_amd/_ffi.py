@@ -76,6 +76,11 @@ class DocInfo(ctypes.Structure):     # reef_doc_info: what reef_doc_transform fo
     _fields_ = [(n, c_uint64) for n in ("chars", "kept", "padded", "bad", "first_bad", "malformed_at")]
 
 
+class IpaProof(ctypes.Structure):    # reef_ipa_proof: one proof of a reef_ipa_check_batch, reef_ipa_check_eq's arguments field for field (host memory)
+    _fields_ = [("comm", c_void_p), ("c", c_void_p), ("q", c_void_p), ("L", c_void_p), ("R", c_void_p), ("rs", c_void_p), ("a_hat", c_void_p),
+                ("points", c_void_p), ("vars", c_void_p), ("weights", c_void_p), ("npoints", c_size_t), ("h", c_void_p), ("blind", c_void_p)]
+
+
 DOC_BYTES, DOC_UTF8 = 0, 1
 DOC_DROP, DOC_BAD = 0xFFFFFFFE, 0xFFFFFFFF
 SC_PART_FE, SC_PART_SYMBOLS, SC_PART_FILL = 0, 1, 2
@@ -217,6 +222,8 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_hyrax_read": (c_int, [vp, c_int, c_size_t, vp, c_bool]),
         "reef_ipa_check": (c_int, [vp, c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, c_size_t, c_int, vp, vp, c_bool, POINTER(c_uint32), vp, vp, vp]),
         "reef_ipa_check_eq": (c_int, [vp, c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_size_t, vp, vp, c_bool, POINTER(c_uint32), vp, vp, vp]),
+        "reef_ipa_check_batch": (c_int, [vp, c_size_t, POINTER(IpaProof), c_size_t, vp, c_bool, POINTER(c_uint32), vp, vp, vp, c_int, vp, vp]),
+        "reef_ipa_check_batch_last_timing": (c_int, [vp, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
         "reef_merkle_nodes": (c_uint64, [c_uint64]),
         "reef_merkle_commit": (c_int, [c_int, vp, vp, c_size_t, c_int, c_bool, vp, c_int, vp]),
         "reef_merkle_commit_devices": (c_int, [c_int, vp, vp, c_size_t, c_bool, vp, c_size_t, vp, vp, vp]),

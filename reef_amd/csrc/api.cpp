@@ -655,6 +655,16 @@ reef_status reef_ipa_check_eq(reef_msm_ctx *key, size_t n, const reef_jacobian *
         return v->ipa_check_eq(impl, n, comm, c, q, L, R, rs, a_hat, points, vars, weights, npoints, h, blind, is_mont, accept, p_hat, g_hat, b_hat);
     });
 }
+reef_status reef_ipa_check_batch(reef_msm_ctx *key, size_t n, const reef_ipa_proof *proofs, size_t m, const reef_fe *rho, bool is_mont, uint32_t *accept_all,
+                                 uint32_t *accept_each, reef_fe *b_hats, reef_fe *s_comb, int s_loc, reef_jacobian *d_comb, reef_jacobian *g_comb) {
+    if (m == 0 && accept_all) { *accept_all = 1; return REEF_OK; }     // an empty batch holds, whatever the key: no device work
+    return dispatch<IpaCheckVTable>(key, [&](auto *v, void *impl) {
+        return v->ipa_check_batch(impl, n, proofs, m, rho, is_mont, accept_all, accept_each, b_hats, s_comb, s_loc, d_comb, g_comb);
+    });
+}
+reef_status reef_ipa_check_batch_last_timing(reef_msm_ctx *key, float *s_pass_ms, float *key_msm_ms, float *side_ms) {
+    return dispatch<IpaCheckVTable>(key, [&](auto *v, void *impl) { return v->ipa_check_batch_timing(impl, s_pass_ms, key_msm_ms, side_ms); });
+}
 
 uint64_t reef_merkle_nodes(uint64_t n) {
     uint64_t total = 0, m = (n + 1) / 2;

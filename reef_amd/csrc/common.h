@@ -588,6 +588,9 @@ struct IpaCheckVTable {
                                 const reef_jacobian *R, const reef_fe *rs, const reef_fe *a_hat, const reef_fe *const *points, const size_t *vars,
                                 const reef_fe *weights, size_t npoints, const reef_affine *h, const reef_fe *blind, bool is_mont, uint32_t *accept,
                                 reef_jacobian *p_hat, reef_jacobian *g_hat, reef_fe *b_hat);
+    reef_status (*ipa_check_batch)(void *key_impl, size_t n, const reef_ipa_proof *proofs, size_t m, const reef_fe *rho, bool is_mont, uint32_t *accept_all,
+                                   uint32_t *accept_each, reef_fe *b_hats, reef_fe *s_comb, int s_loc, reef_jacobian *d_comb, reef_jacobian *g_comb);
+    reef_status (*ipa_check_batch_timing)(void *key_impl, float *s_pass_ms, float *key_msm_ms, float *side_ms);
 };
 const IpaCheckVTable *pallas_ipa_check_vtable();
 const IpaCheckVTable *vesta_ipa_check_vtable();

@@ -121,6 +121,9 @@ template <int C> struct Ctx {
     };
     std::vector<GraphEntry> graphs;
     Ctx<C> *side = nullptr;                  // a small plain key of this ctx's own for the one-off points of reef_ipa_check (ipa_check_engine.inc)
+    Ctx<C> *side_batch = nullptr;            // the same for reef_ipa_check_batch: sized to the largest batch seen, grow-only
+    hipEvent_t batch_ev[4] = {};             // a timed batch: S pass begin / end on this ctx's stream, one-off points begin / end on the second
+    bool batch_timed = false;                // the last batch ran with timing on
 };
 // Every entry point that enqueues work holds one of these (under ctx->mu, with the key's device current): the ctx takes the
 // pool stream with the fewest callers at work unless work of its own is still in flight.  When the call returns -- with its
@@ -507,6 +510,9 @@ static reef_status key_build(Ctx<C> *ctx, const reef_affine *bases, size_t n, in
 template <int C> static void ctx_free(Ctx<C> *ctx) {
     if (!ctx) return;
     ctx_free(ctx->side);
+    ctx_free(ctx->side_batch);
+    for (auto &e : ctx->batch_ev)
+        if (e) (void)hipEventDestroy(e);
     graphs_clear(ctx);
     for (DevBuf *b : {&ctx->scalars, &ctx->blinds, &ctx->hpoint, &ctx->dig, &ctx->counts, &ctx->bstart, &ctx->bstart1, &ctx->seg_first,
                       &ctx->seg_counts, &ctx->entries1, &ctx->sym_table, &ctx->sym_tmp, &ctx->sym_u8, &ctx->tile_sums,

@@ -833,6 +833,46 @@ template <int CURVE> struct InnerProductArgument {
                                 blind, true, &accept, nullptr, nullptr, nullptr), "reef_ipa_check_eq");
         return accept == 1;
     }
+
+    // One proof of a batch: what verify takes beside the proof itself.  The vectors must outlive the call.
+    struct Instance {
+        const InnerProductArgument *proof;
+        reef_jacobian comm;
+        reef_fe c;
+        reef_affine q;
+        std::vector<reef_fe> rs;
+        std::vector<std::vector<reef_fe>> points;
+        std::vector<reef_fe> weights;
+        const reef_affine *h = nullptr;
+        const reef_fe *blind = nullptr;
+    };
+    // m proofs over the same n against the one gens_v in a single pass (reef_msm.h 3m): one MSM over the key whatever m is.  rho: one
+    // non-zero weight per proof, the CALLER'S randomness, drawn after every proof is fixed.  each (may be null): resized to m; all true
+    // when the batch accepts, else the single checks run (m MSMs) and say which proofs fail.
+    static bool verify_batch(reef_msm_ctx *gens_v, size_t n, const std::vector<Instance> &batch, const std::vector<reef_fe> &rho,
+                             std::vector<bool> *each = nullptr) {
+        const size_t m = batch.size();
+        if (rho.size() != m) return false;
+        std::vector<reef_ipa_proof> proofs(m);
+        std::vector<std::vector<const reef_fe *>> pts(m);
+        std::vector<std::vector<size_t>> vars(m);
+        for (size_t i = 0; i < m; ++i) {
+            const Instance &in = batch[i];
+            if (!in.proof || in.proof->L.size() != in.rs.size() || in.proof->R.size() != in.rs.size() || in.points.size() != in.weights.size()) return false;
+            for (const auto &p : in.points) {
+                pts[i].push_back(p.data());
+                vars[i].push_back(p.size());
+            }
+            proofs[i] = reef_ipa_proof{&in.comm, &in.c, &in.q, in.proof->L.data(), in.proof->R.data(), in.rs.data(), &in.proof->a_hat, pts[i].data(),
+                                       vars[i].data(), in.weights.data(), in.points.size(), in.h, in.blind};
+        }
+        uint32_t all = 0;
+        std::vector<uint32_t> acc(each ? m : 0);
+        check(reef_ipa_check_batch(gens_v, n, proofs.data(), m, rho.data(), true, &all, each && m ? acc.data() : nullptr, nullptr, nullptr, REEF_HOST, nullptr,
+                                   nullptr), "reef_ipa_check_batch");
+        if (each) each->assign(acc.begin(), acc.end());
+        return all == 1;
+    }
 };
 
 }  // namespace reef_provider

@@ -1,6 +1,8 @@
 // Host side of the IPA check (ipa_check_kernels.inc; include/reef_msm.h 3j); included after ipa_engine.inc (sp_grid).  Two stateless
 // calls on a key ctx that holds gens_v: no handle of their own, no call order.  Everything is enqueued -- the s vector, b_hat and
 // the G_hat MSM on the key ctx's stream, the one-off points beside them on a second pool stream -- and the call waits once.
+// reef_ipa_check_batch (3m) checks m proofs against the one key in a single pass; its host preparation is ipa_batch_host.inc.
+#include "ipa_batch_host.inc"
 namespace reef {
 
 // where b comes from: the caller's vector (reef_ipa_check) or eq tables built on the device (reef_ipa_check_eq)
@@ -280,6 +282,199 @@ static reef_status v_ipa_check_eq(void *key_impl, size_t n, const reef_jacobian 
     return ipa_check_run<C>(key_impl, n, comm, c, q, L, R, rs, a_hat, bs, h, blind, is_mont, accept, p_hat, g_hat, b_hat, "reef_ipa_check_eq");
 }
 
-template <int C> IpaCheckVTable make_ipa_check_vtable() { return IpaCheckVTable{v_ipa_check<C>, v_ipa_check_eq<C>}; }
+// ---------------------------------------------------------------- a batch of checks against one key (include/reef_msm.h 3m)
+// The plain key the one-off points of a batch are summed over: the key ctx's own, sized to the largest batch seen (grow-only), freed
+// with the ctx.  The 64-slot side key of the single calls is another one and stays as it is.
+template <int C> static reef_status ic_side_batch_key(Ctx<C> *key, size_t npts) {
+    if (key->side_batch && key->side_batch->key->n >= npts) return REEF_OK;
+    if (key->side_batch) { v_ctx_destroy<C>(key->side_batch); key->side_batch = nullptr; }
+    size_t cap = 256;
+    while (cap < npts) cap <<= 1;
+    reef_msm_opts o;
+    memset(&o, 0, sizeof o);
+    o.window_bits = 8;
+    o.byte_tables = 2;
+    o.device = key->key->device;
+    std::vector<reef_affine> none(cap);
+    memset(none.data(), 0, none.size() * sizeof(reef_affine));
+    void *impl = nullptr;
+    REEF_TRY(v_ctx_create<C>(&impl, none.data(), cap, REEF_HOST, &o));
+    key->side_batch = (Ctx<C> *)impl;
+    return REEF_OK;
+}
+
+// Everything up to the call's one wait.  prep: the proofs' host preparation; npts: the one-off points of all of them.
+template <int C>
+static reef_status ipa_check_batch_device(Ctx<C> *key, size_t n, u32 k, const reef_ipa_proof *proofs, size_t m, const std::vector<IcBatchProof<1 - C>> &prep,
+                                          size_t npts, uint32_t *accept_all, reef_fe *s_comb, int s_loc, reef_jacobian *d_comb, reef_jacobian *g_comb) {
+    constexpr int F = 1 - C;
+    const char *name = "reef_ipa_check_batch";
+    std::lock_guard<std::mutex> lk(key->mu);
+    if (n > key->key->n) { set_error("%s: n = %zu exceeds the key length %zu", name, n, key->key->n); return REEF_ERR_ARG; }
+    if (key->wsplit_world > 1) { set_error("%s: the key ctx computes a window split of every MSM (reef_msm_ctx_set_window_split)", name); return REEF_ERR_ARG; }
+    REEF_ON_DEVICE(key->key->device);
+    CtxScope<C> scope(key);
+    REEF_TRY(scope.enter());
+    hipStream_t ks = key->stream;
+    ScratchStream ss;
+    REEF_TRY(ss.init());
+    hipEvent_t *ev = nullptr;
+    REEF_TRY(ss.events(&ev));
+    REEF_TRY(ic_side_batch_key<C>(key, npts));
+    const bool timed = key->timing;
+    if (timed && !key->batch_ev[0])
+        for (auto &e : key->batch_ev) REEF_HIP_TRY(hipEventCreate(&e));
+    const u32 hb = k / 2, lo_bits = k - hb, ntab = (1u << hb) + (1u << lo_bits);
+    // one buffer: [uploaded: points | scalars | challenge factors | w] [affine] [D] [G] [accept]
+    const size_t o_pts = 0, o_sc = o_pts + npts * sizeof(jacobian256), o_fac = o_sc + npts * sizeof(fe256), o_w = o_fac + m * 2 * k * sizeof(fe256),
+                 up_bytes = o_w + m * sizeof(fe256), o_aff = up_bytes, o_d = o_aff + npts * sizeof(affine256), o_g = o_d + sizeof(jacobian256),
+                 o_out = o_g + sizeof(jacobian256), total = o_out + 32;
+    void *d_s_ = nullptr, *d_tab_ = nullptr, *d_w_ = nullptr;
+    REEF_TRY(ss.alloc(&d_s_, n * sizeof(fe256)));
+    REEF_TRY(ss.alloc(&d_tab_, m * (size_t)ntab * sizeof(fe256)));
+    REEF_TRY(ss.alloc(&d_w_, total));
+    char *w = (char *)d_w_;
+    std::vector<char> up(up_bytes);
+    {
+        jacobian256 *pts = (jacobian256 *)(up.data() + o_pts);
+        fe256 *sc = (fe256 *)(up.data() + o_sc), *fac = (fe256 *)(up.data() + o_fac), *ws = (fe256 *)(up.data() + o_w);
+        size_t at = 0;
+        for (size_t i = 0; i < m; ++i) {
+            const reef_ipa_proof &pr = proofs[i];
+            const size_t cnt = prep[i].sc.size();
+            pts[at] = ic_lift<C>(pr.q);
+            memcpy(&pts[at + 1], pr.L, k * sizeof(jacobian256));
+            memcpy(&pts[at + 1 + k], pr.R, k * sizeof(jacobian256));
+            memcpy(&pts[at + 1 + 2 * k], pr.comm, sizeof(jacobian256));
+            if (pr.h) pts[at + 2 + 2 * k] = ic_lift<C>(pr.h);
+            memcpy(sc + at, prep[i].sc.data(), cnt * sizeof(fe256));
+            memcpy(fac + i * 2 * k, prep[i].fac.data(), 2 * (size_t)k * sizeof(fe256));
+            ws[i] = fe_to_table<F>(prep[i].w);
+            at += cnt;
+        }
+    }
+    fe256 *d_s = (fe256 *)d_s_, *d_tab = (fe256 *)d_tab_;
+    jacobian256 *d_pts = (jacobian256 *)(w + o_pts), *d_D = (jacobian256 *)(w + o_d), *d_G = (jacobian256 *)(w + o_g);
+    affine256 *d_aff = (affine256 *)(w + o_aff);
+    u32 *d_acc = (u32 *)(w + o_out);
+
+    // ---- the key ctx's stream: the upload, the m pairs of tables, S, the MSM over the key
+    REEF_HIP_TRY(hipMemcpyAsync(w, up.data(), up_bytes, hipMemcpyHostToDevice, ks));
+    REEF_HIP_TRY(hipEventRecord(ev[0], ks));
+    if (timed) REEF_HIP_TRY(hipEventRecord(key->batch_ev[0], ks));
+    hipLaunchKernelGGL(k_ic_tables_batch<F>, dim3((u32)ceil_div(m * (size_t)ntab, 256)), dim3(256), 0, ks, (const fe256 *)(w + o_fac), (const fe256 *)(w + o_w), hb,
+                       lo_bits, (u32)m, d_tab);
+    const u32 grid = (u32)ceil_div(n, SP_THREADS);
+    if (lo_bits >= 6)
+        hipLaunchKernelGGL((k_ic_s_batch<F, true>), dim3(grid), dim3(SP_THREADS), 0, ks, (const fe256 *)d_tab, hb, lo_bits, (u32)n, (u32)m, d_s);
+    else
+        hipLaunchKernelGGL((k_ic_s_batch<F, false>), dim3(grid), dim3(SP_THREADS), 0, ks, (const fe256 *)d_tab, hb, lo_bits, (u32)n, (u32)m, d_s);
+    REEF_HIP_TRY(hipGetLastError());
+    if (timed) REEF_HIP_TRY(hipEventRecord(key->batch_ev[1], ks));
+    // ---- the second stream, beside them: the one-off points made affine, imported as the batch side key's table, one MSM
+    {
+        Ctx<C> *side = key->side_batch;
+        hipStream_t s2 = (hipStream_t)v_ctx_stream<C>(side);
+        if (!s2) return REEF_ERR_HIP;
+        REEF_HIP_TRY(hipStreamWaitEvent(s2, ev[0], 0));
+        std::lock_guard<std::mutex> sl(side->mu);
+        CtxScope<C> sscope(side);
+        REEF_TRY(sscope.enter());
+        if (timed) REEF_HIP_TRY(hipEventRecord(key->batch_ev[2], s2));
+        hipLaunchKernelGGL(k_normalize<C>, dim3(ceil_div(ceil_div(npts, NORM_PER), 256)), dim3(256), 0, s2, (const jacobian256 *)d_pts, (u32)npts, d_aff,
+                           (fe256 *)nullptr);
+        hipLaunchKernelGGL(k_import_key<C>, dim3(ceil_div(npts, 256)), dim3(256), 0, s2, (const affine256 *)d_aff, (u32)npts, side->key->tables);
+        REEF_HIP_TRY(hipGetLastError());
+        REEF_TRY(msm_device_scalars<C>(side, (const fe256 *)(w + o_sc), npts, false, (reef_jacobian *)d_D, REEF_DEVICE, d_D));
+        if (timed) REEF_HIP_TRY(hipEventRecord(key->batch_ev[3], s2));
+        REEF_HIP_TRY(hipEventRecord(ev[1], s2));
+    }
+    REEF_TRY(msm_device_scalars<C>(key, d_s, n, false, (reef_jacobian *)d_G, REEF_DEVICE, d_G));
+    REEF_HIP_TRY(hipStreamWaitEvent(ks, ev[1], 0));
+    hipLaunchKernelGGL(k_ic_final_batch<C>, dim3(1), dim3(64), 0, ks, (const jacobian256 *)d_D, (const jacobian256 *)d_G, d_acc);
+    REEF_HIP_TRY(hipGetLastError());
+    struct { u32 accept, pad[7]; } res;
+    jacobian256 dg[2];
+    REEF_HIP_TRY(hipMemcpyAsync(&res, d_acc, sizeof res, hipMemcpyDeviceToHost, ks));
+    if (d_comb || g_comb) REEF_HIP_TRY(hipMemcpyAsync(dg, d_D, sizeof dg, hipMemcpyDeviceToHost, ks));
+    if (s_comb) REEF_HIP_TRY(hipMemcpyAsync(s_comb, d_s, n * sizeof(fe256), s_loc == REEF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ks));
+    REEF_HIP_TRY(hipStreamSynchronize(ks));                     // the call's one wait
+    key->batch_timed = timed;
+    *accept_all = res.accept;
+    if (d_comb) memcpy(d_comb, &dg[0], sizeof(jacobian256));
+    if (g_comb) memcpy(g_comb, &dg[1], sizeof(jacobian256));
+    return REEF_OK;
+}
+
+template <int C>
+static reef_status v_ipa_check_batch(void *key_impl, size_t n, const reef_ipa_proof *proofs, size_t m, const reef_fe *rho, bool is_mont, uint32_t *accept_all,
+                                     uint32_t *accept_each, reef_fe *b_hats, reef_fe *s_comb, int s_loc, reef_jacobian *d_comb, reef_jacobian *g_comb) {
+    constexpr int F = 1 - C;
+    const char *name = "reef_ipa_check_batch";
+    Ctx<C> *key = (Ctx<C> *)key_impl;
+    if (!key || !accept_all || (m && (!proofs || !rho))) { set_error("null argument"); return REEF_ERR_ARG; }
+    if (m == 0) { *accept_all = 1; return REEF_OK; }
+    u32 k = 0;
+    REEF_TRY(ic_batch_shape(n, m, &k));
+    if (s_comb && s_loc != REEF_HOST && s_loc != REEF_DEVICE) { set_error("%s: unknown location %d of s_comb", name, s_loc); return REEF_ERR_ARG; }
+    if (s_comb && s_loc == REEF_DEVICE && ((uintptr_t)s_comb & 15)) { set_error("%s: a device s_comb must be 16-byte aligned", name); return REEF_ERR_ARG; }
+    // ---- every scalar of every proof through the conversion layer, before anything is touched
+    std::vector<IcBatchProof<F>> prep(m);
+    size_t npts = 0;
+    std::vector<fe> r, rinv;
+    REEF_TRY(ic_batch_challenges<F>(proofs, m, k, is_mont, r, rinv));
+    for (size_t i = 0; i < m; ++i) {
+        REEF_TRY(ic_batch_prepare<F>(proofs[i], i, n, k, r.data() + i * k, rinv.data() + i * k, rho + i, is_mont, prep[i]));
+        npts += prep[i].sc.size();
+    }
+    uint32_t all = 0;
+    REEF_TRY(ipa_check_batch_device<C>(key, n, k, proofs, m, prep, npts, &all, s_comb, s_loc, d_comb, g_comb));
+    *accept_all = all;
+    if (b_hats)
+        for (size_t i = 0; i < m; ++i) {
+            const fe256 o = fe_to_caller<F>(prep[i].b_hat, is_mont);
+            memcpy(b_hats + i, &o, sizeof o);
+        }
+    if (!accept_each) return REEF_OK;
+    if (all) {
+        for (size_t i = 0; i < m; ++i) accept_each[i] = 1;
+        return REEF_OK;
+    }
+    // ---- the batch does not verify and the caller wants to know who: the single check on each proof, m MSMs over the key
+    for (size_t i = 0; i < m; ++i) {
+        const reef_ipa_proof &pr = proofs[i];
+        IcB bs;
+        bs.eq = true;
+        bs.points = pr.points;
+        bs.vars = pr.vars;
+        bs.weights = pr.weights;
+        bs.npoints = pr.npoints;
+        REEF_TRY(ipa_check_run<C>(key_impl, n, pr.comm, pr.c, pr.q, pr.L, pr.R, pr.rs, pr.a_hat, bs, pr.h, pr.blind, is_mont, accept_each + i, nullptr, nullptr,
+                                  nullptr, name));
+    }
+    return REEF_OK;
+}
+
+// How the last batch on this key ctx divided, with the key's timing switched on (reef_msm_ctx_enable_timing) when it ran: the
+// tables and the S pass, the MSM over the key, the one-off points (normalise, import, MSM) on the second stream.
+template <int C> static reef_status v_ipa_check_batch_timing(void *key_impl, float *s_pass_ms, float *key_msm_ms, float *side_ms) {
+    Ctx<C> *key = (Ctx<C> *)key_impl;
+    if (!key) { set_error("null argument"); return REEF_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(key->mu);
+    if (!key->batch_timed || key->ev_last < 0) { set_error("no timed batch yet (reef_msm_ctx_enable_timing, then reef_ipa_check_batch)"); return REEF_ERR_ARG; }
+    REEF_ON_DEVICE(key->key->device);
+    if (s_pass_ms) REEF_HIP_TRY(hipEventElapsedTime(s_pass_ms, key->batch_ev[0], key->batch_ev[1]));
+    if (side_ms) REEF_HIP_TRY(hipEventElapsedTime(side_ms, key->batch_ev[2], key->batch_ev[3]));
+    if (key_msm_ms) {
+        hipEvent_t *q = key->evr[key->ev_last];
+        REEF_HIP_TRY(hipEventSynchronize(q[3]));
+        REEF_HIP_TRY(hipEventElapsedTime(key_msm_ms, q[0], q[3]));
+    }
+    return REEF_OK;
+}
+
+template <int C> IpaCheckVTable make_ipa_check_vtable() {
+    return IpaCheckVTable{v_ipa_check<C>, v_ipa_check_eq<C>, v_ipa_check_batch<C>, v_ipa_check_batch_timing<C>};
+}
 
 }  // namespace reef

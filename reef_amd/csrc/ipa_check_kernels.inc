@@ -177,4 +177,85 @@ __global__ void __launch_bounds__(64) k_ic_final(const jacobian256 *__restrict__
     store_fe256(&out->b_hat, sp_out<F>(fe_from_table(load_fe256(b_hat)), form));
 }
 
+// ---------------------------------------------------------------- a batch of checks against one key (include/reef_msm.h 3m)
+// m proofs over the same n collapse into one equation under the caller's weights rho_i:
+//   sum_i rho_i (comm_i + c_i q_i + sum_t r_it^2 L_it + sum_t r_it^-2 R_it - (a_hat_i b_hat_i) q_i - blind_i h_i)  ==  < S, key >
+//   S_j = sum_i w_i s^(i)_j,  w_i = rho_i a_hat_i
+//   k_ic_tables_batch  the m pairs of challenge tables in one launch, w_i folded into proof i's hi table
+//   k_ic_s_batch       S as the canonical integers the key's MSM reads: one product per proof and entry, five products per
+//                      Montgomery reduction (wide18_mont), the reduced groups summed limb by limb and made canonical once
+//   k_ic_final_batch   the comparison (xyzz_same_point)
+// b_hat_i has a closed form of O(k) products and is formed on the host (ipa_check_engine.inc), so every scalar of every one-off
+// point is known before anything is enqueued: k_ic_eqb, the per-entry products s_j b_j and k_ic_ab have no counterpart here.
+
+// Proof p's tables at tabs + p ntab, ntab = 2^hb + 2^m: hi over its first hb challenges times w[p], as canonical INTEGERS, then lo over
+// its last m, internal form -- the Montgomery product of the two is the canonical-integer residue of w s_j, with no conversion after
+// it.  f[2 (p (hb + m) + i)] = r_i^-1, f[.. + 1] = r_i of proof p; w: internal form.
+template <int F>
+__global__ void __launch_bounds__(256) k_ic_tables_batch(const fe256 *__restrict__ f, const fe256 *__restrict__ w, u32 hb, u32 m, u32 nproofs,
+                                                         fe256 *__restrict__ tabs) {
+    const u32 nh = 1u << hb, ntab = nh + (1u << m);
+    const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (u64)nproofs * ntab) return;
+    const u32 p = (u32)(g / ntab), t = (u32)(g % ntab);
+    const bool lo = t >= nh;
+    const u32 idx = lo ? t - nh : t, bits = lo ? m : hb, off = lo ? hb : 0;
+    const fe256 *fp = f + 2 * (size_t)p * (hb + m);
+    fe acc = lo ? fe_one<F>() : fe_from_table(load_fe256(w + p));
+    for (u32 i = 0; i < bits; ++i) acc = fe_mul<F>(acc, fe_from_table(load_fe256(fp + 2 * (off + i) + ((idx >> (bits - 1 - i)) & 1u))));
+    store_fe256(tabs + g, lo ? fe_to_table<F>(acc) : fe_to_integer<F>(acc));
+}
+
+// s_out[j] = sum_p hi_p[j >> m] lo_p[j & (2^m - 1)] mod M for j < n, canonical integers.  UNI (m >= 6 and n a multiple of 64): the 64
+// entries of a wave share j >> m, so a proof's hi entry is one load per wave.  Limb bounds: the tables are canonical (limbs < 2^29), a
+// product adds 9 terms < 2^58 to a column, the columns are carried after the fourth product of a group and wide18_mont carries again:
+// five products < 5 M^2 give a residue < 2 M with exact limbs.  At most 4096 / 5 + 1 such residues are added limb by limb (< 2^40
+// per limb, value < 2^11 M: fe_from_limb_sums takes 2^30 M).  No scratch, no atomics: an entry is one thread's.
+template <int F, bool UNI>
+__global__ void __launch_bounds__(SP_THREADS) k_ic_s_batch(const fe256 *__restrict__ tabs, u32 hb, u32 m, u32 n, u32 nproofs, fe256 *__restrict__ s_out) {
+    const u32 nh = 1u << hb, ntab = nh + (1u << m), mask = (1u << m) - 1;
+    for (u32 j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
+        u32 jh = j >> m;
+        if constexpr (UNI) jh = (u32)__builtin_amdgcn_readfirstlane((int)jh);
+        const fe256 *hi = tabs + jh, *lo = tabs + nh + (j & mask);
+        fe_wide sums;
+        wide_zero(sums);
+        u32 p = 0;
+        for (; p + 5 <= nproofs; p += 5) {
+            fe_wide18 w;
+            wide18_zero(w);
+#pragma unroll
+            for (int t = 0; t < 5; ++t) {
+                wide18_mac(w, fe_from_table(load_fe256(hi)).l, fe_from_table(load_fe256(lo)).l);
+                if (t == 3) wide18_carry(w);
+                hi += ntab;
+                lo += ntab;
+            }
+            const fe r = wide18_mont<F>(w, 2.0);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) sums.l[i] += r.l[i];
+        }
+        if (p < nproofs) {                                      // the last one to four proofs: no carry between them
+            fe_wide18 w;
+            wide18_zero(w);
+            for (; p < nproofs; ++p) {
+                wide18_mac(w, fe_from_table(load_fe256(hi)).l, fe_from_table(load_fe256(lo)).l);
+                hi += ntab;
+                lo += ntab;
+            }
+            const fe r = wide18_mont<F>(w, 2.0);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) sums.l[i] += r.l[i];
+        }
+        store_fe256(s_out + j, fe_pack(fe_from_limb_sums<F>(sums)));
+    }
+}
+
+// accept = [d == g] as group elements: the two sides of the combined equation.  One thread.
+template <int C>
+__global__ void __launch_bounds__(64) k_ic_final_batch(const jacobian256 *__restrict__ d, const jacobian256 *__restrict__ g, u32 *__restrict__ accept) {
+    if (blockIdx.x | threadIdx.x) return;
+    *accept = xyzz_same_point<C>(xyzz_from_abi_jacobian<C>(load_jacobian256(d)), xyzz_from_abi_jacobian<C>(load_jacobian256(g))) ? 1u : 0u;
+}
+
 }  // namespace reef

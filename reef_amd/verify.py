@@ -10,6 +10,10 @@ check of THIS module, not of the library: pass curve= and a key of another curve
 Scalars cross as Python ints (canonical, or pasta Montgomery form with is_mont=True); points as numpy uint64 arrays in the C-ABI
 layouts: affine (8 limbs) or Jacobian (12 limbs).
 
+`ipa_check_batch` is reef_ipa_check_batch (3m): m proofs over the same n against the one key under caller-drawn weights rho -- one MSM
+over the key whatever m is; `verify_eval_batch` drives m Hyrax arguments through it the way `verify_eval` drives one.  The weights
+are the caller's randomness, drawn after every proof is fixed; neither function draws any.
+
 `matrix_evals` is reef_spartan_eval_matrices: A~, B~, C~ at (r_x, r_y) on the matrices a `Nifs` holds, no witness needed.
 `verify_sumchecks` is the verifier of 3g's transcript -- RelaxedR1CSSNARK::verify [R] up to the opening: O(log n) host arithmetic and that
 one device call -- and `verify_snark` adds `verify_opening` with eval_E = claims_outer[3], eval_W = claims_inner[2].
@@ -21,7 +25,7 @@ from typing import Any, Callable, List, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import REEF_DEVICE, REEF_HOST, ReefError, check
+from ._ffi import REEF_DEVICE, REEF_HOST, IpaProof, ReefError, check
 from ._fe import _arr, _ints
 from .msm import DeviceBuffer, MsmContext, curve_id, decompress, normalize
 from .nifs import Nifs
@@ -94,6 +98,103 @@ def ipa_check_eq(key: MsmContext, n: int, comm, c: int, q, L, R, rs: Sequence[in
     wa = _arr(weights) if len(weights) else np.zeros((1, 4), np.uint64)
     mid = (ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(nvars, ctypes.c_void_p), wa.ctypes.data, len(points))
     return _call(key, key._lib.reef_ipa_check_eq, n, comm, c, q, L, R, rs, a_hat, mid, h, blind, is_mont, intermediates, curve)
+
+
+def eq_b_hat(rs: Sequence[int], points: Sequence[Sequence[int]], weights: Sequence[int], p: int) -> int:
+    """<s, b> for b = sum_t weights[t] pad(eq(points[t])) in O(k) products per point, as reef_ipa_check_batch forms it on the host:
+    with v = len(points[t]), prod_{i < k - v} rs[i]^-1 prod_{j < v} ((1 - p_j) rs[k-v+j]^-1 + p_j rs[k-v+j]).  Canonical ints."""
+    k = len(rs)
+    inv = [pow(r, -1, p) for r in rs]
+    out = 0
+    for pt, w in zip(points, weights):
+        v = len(pt)
+        if v > k:
+            raise ValueError(f"a point of {v} variables against {k} rounds")
+        acc = 1
+        for i in range(k - v):
+            acc = acc * inv[i] % p
+        for j, x in enumerate(pt):
+            acc = acc * ((1 - x) * inv[k - v + j] + x * rs[k - v + j]) % p
+        out = (out + w * acc) % p
+    return out
+
+
+def _marshal_batch(n: int, proofs: Sequence[dict], rho: Sequence[int]):
+    """(reef_ipa_proof array, rho array, what must stay alive until the call returns)"""
+    m = len(proofs)
+    k = _rounds(n)
+    pow2 = n >= 2 and n & (n - 1) == 0
+    structs = (IpaProof * max(m, 1))()
+    keep = []
+    for i, pr in enumerate(proofs):
+        L, R, rs = pr["L"], pr["R"], pr["rs"]
+        if pow2 and (len(rs) != k or len(L) != k or len(R) != k):
+            raise ValueError(f"proof {i}: n = {n} takes {k} rounds: L, R and rs have {len(L)}, {len(R)}, {len(rs)} entries")
+        if not (len(L) and len(R) and len(rs)):
+            L, R, rs = [np.zeros(12, np.uint64)], [np.zeros(12, np.uint64)], [0]  # n < 2: the library says what is wrong with it
+        points, weights = pr["points"], pr["weights"]
+        if len(points) != len(weights):
+            raise ValueError(f"proof {i}: one weight per point")
+        arrs = [_arr(pt) if len(pt) else np.zeros((1, 4), np.uint64) for pt in points]
+        ptrs = (ctypes.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+        nvars = (ctypes.c_size_t * max(len(arrs), 1))(*[len(pt) for pt in points])
+        wa = _arr(weights) if len(weights) else np.zeros((1, 4), np.uint64)
+        own = [_jac([pr["comm"]], 1), _arr([pr["c"]]), _aff(pr["q"]), _jac(L, len(L)), _jac(R, len(R)), _arr(rs), _arr([pr["a_hat"]]), wa]
+        ha = None if pr.get("h") is None else _aff(pr["h"])
+        ba = None if pr.get("blind") is None else _arr([pr["blind"]])
+        keep.append((own, arrs, ptrs, nvars, ha, ba))
+        s = structs[i]
+        s.comm, s.c, s.q, s.L, s.R, s.rs, s.a_hat, s.weights = (a.ctypes.data for a in own)
+        s.points, s.vars, s.npoints = ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(nvars, ctypes.c_void_p), len(points)
+        s.h, s.blind = None if ha is None else ha.ctypes.data, None if ba is None else ba.ctypes.data
+    ra = _arr(rho) if m else np.zeros((1, 4), np.uint64)
+    return structs, ra, keep
+
+
+def ipa_check_batch(key: MsmContext, n: int, proofs: Sequence[dict], rho: Sequence[int], *, is_mont: bool = False, each: bool = False,
+                    intermediates: bool = False, s_comb_out: Optional[DeviceBuffer] = None, curve=None) -> dict:
+    """reef_ipa_check_batch: m proofs over the same n against `key` in one pass.  proofs: dicts with the arguments of `ipa_check_eq`
+    ("comm", "c", "q", "L", "R", "rs", "a_hat", "points", "weights" and, for a blinded one, "h" and "blind").  rho: one non-zero weight
+    per proof, the CALLER'S randomness, drawn after all the proofs are fixed.  {"accept": bool}; with each, "each": a bool per proof
+    (the single checks run only when the batch rejects); with intermediates, "b_hats" (ints), "s_comb" (n ints, canonical),
+    "d_comb" and "g_comb" (Jacobian): the two sides of the combined equation.  s_comb_out: a DeviceBuffer of 32 n bytes that takes S
+    instead of the host."""
+    if curve is not None and curve_id(curve) != key.curve:
+        raise ReefError(1, f"the key is of curve {key.curve}, the check of curve {curve_id(curve)}")
+    m = len(proofs)
+    if len(rho) != m:
+        raise ValueError("one weight per proof")
+    structs, ra, keep = _marshal_batch(n, proofs, rho)
+    accept = ctypes.c_uint32(0xFFFFFFFF)
+    ea = (ctypes.c_uint32 * max(m, 1))(*([0xFFFFFFFF] * max(m, 1))) if each else None
+    bh = np.zeros((max(m, 1), 4), np.uint64) if intermediates else None
+    dc, gc = (np.zeros(12, np.uint64), np.zeros(12, np.uint64)) if intermediates else (None, None)
+    sc, s_ptr, s_loc = None, None, REEF_HOST
+    if s_comb_out is not None:
+        if s_comb_out.nbytes < 32 * n:
+            raise ValueError("s_comb_out needs 32 bytes per entry")
+        s_ptr, s_loc = s_comb_out.ptr, REEF_DEVICE
+    elif intermediates:
+        sc = np.zeros((max(n, 1), 4), np.uint64)
+        s_ptr = sc.ctypes.data
+    check(key._lib.reef_ipa_check_batch(key._h, n, structs, m, ra.ctypes.data, bool(is_mont), ctypes.byref(accept),
+                                        None if ea is None else ctypes.cast(ea, ctypes.c_void_p), None if bh is None else bh.ctypes.data, s_ptr, s_loc,
+                                        None if dc is None else dc.ctypes.data, None if gc is None else gc.ctypes.data))
+    out = {"accept": accept.value == 1}
+    if each:
+        out["each"] = [ea[i] == 1 for i in range(m)]
+    if intermediates:
+        out.update({"b_hats": _ints(bh)[:m], "d_comb": dc, "g_comb": gc})
+        if sc is not None:
+            out["s_comb"] = _ints(sc)[:n]
+    return out
+
+
+def ipa_check_batch_timing(key: MsmContext) -> dict:
+    """reef_ipa_check_batch_last_timing: device milliseconds of the last batch on `key`, run with key.enable_timing() on."""
+    s, g, d = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+    check(key._lib.reef_ipa_check_batch_last_timing(key._h, ctypes.byref(s), ctypes.byref(g), ctypes.byref(d)))
+    return {"s_pass_ms": s.value, "key_msm_ms": g.value, "side_ms": d.value}
 
 
 def _lincomb(curve: int, points, scalars: Sequence[int]) -> np.ndarray:
@@ -176,6 +277,53 @@ def verify_eval(key: MsmContext, q, row_comms32, point: Sequence[int], left: int
     fn = check_fn or ipa_check_eq
     blind = None if blind_total is None else blind_total % p
     return fn(key, n, clz, eval_ % p, q, proof["L"], proof["R"], rs, proof["a_hat"], [list(point[left:])], [1], h=h, blind=blind)["accept"]
+
+
+def verify_eval_batch(key: MsmContext, instances: Sequence[dict], p: int, weights: Callable[[List[List[Any]]], Sequence[int]], *,
+                      each: bool = False, check_fn=None):
+    """m Hyrax arguments over the same gens_v checked in one pass: `verify_eval` for each instance up to its IPA check, then one
+    `ipa_check_batch`.  instances: dicts with verify_eval's arguments -- "q", "row_comms32", "point", "left", "eval", "proof" and,
+    where used, "h", "blind_total", "challenge", "q_of" -- all with the same len(point) - left.  weights(absorbed) -> m non-zero ints
+    below p: the caller's randomness, called once AFTER every proof is fixed, with what each proof contributes ([comm_LZ compressed,
+    eval, a_hat, L and R compressed ...] per instance) for a caller that derives the weights from a transcript.  True / False; with
+    each, (verdict, [bool per instance]).  check_fn stands in for ipa_check_batch (tests)."""
+    curve = key.curve
+    if not instances:
+        return (True, []) if each else True
+    right = len(instances[0]["point"]) - instances[0]["left"]
+    n = 1 << right
+    proofs, absorbed, bad = [], [], False
+    for i, it in enumerate(instances):
+        point, left, proof, challenge, q_of, q = it["point"], it["left"], it["proof"], it.get("challenge"), it.get("q_of"), it.get("q")
+        h, blind_total = it.get("h"), it.get("blind_total")
+        if len(point) - left != right:
+            raise ValueError(f"instance {i}: 2^{len(point) - left} columns, the batch is over 2^{right}")
+        if challenge is None and "rs" not in proof:
+            raise ValueError("verify_eval_batch needs the round challenges: proof['rs'], or a challenge callable to draw them")
+        if q is None and (challenge is None or q_of is None):
+            raise ValueError("verify_eval_batch needs q, or a challenge callable and q_of to form it from the drawn r")
+        if (h is None) != (blind_total is None):
+            raise ValueError("h and blind_total come together or not at all")
+        clz = comm_lz(curve, it["row_comms32"], point[:left], p)
+        cz = compress(key, clz)
+        if challenge is not None:
+            r_ipa = challenge("r", [cz, it["eval"]])
+            if q_of is not None:
+                q = q_of(r_ipa)
+            rs = [challenge("challenge_r", [compress(key, L), compress(key, R)]) for L, R in zip(proof["L"], proof["R"])]
+        else:
+            rs = list(proof["rs"])
+        if len(proof["L"]) != right or len(proof["R"]) != right or len(rs) != right:
+            bad = True
+            continue
+        absorbed.append([cz, it["eval"] % p, proof["a_hat"]] + [compress(key, pt) for pair in zip(proof["L"], proof["R"]) for pt in pair])
+        proofs.append({"comm": clz, "c": it["eval"] % p, "q": q, "L": proof["L"], "R": proof["R"], "rs": rs, "a_hat": proof["a_hat"],
+                       "points": [list(point[left:])], "weights": [1], "h": h, "blind": None if blind_total is None else blind_total % p})
+    if bad:                                                     # a proof of the wrong length verifies nowhere
+        return (False, [False] * len(instances)) if each else False
+    rho = [int(w) % p for w in weights(absorbed)]
+    res = (check_fn or ipa_check_batch)(key, n, proofs, rho, each=each)
+    return (res["accept"], res["each"]) if each else res["accept"]
 
 
 # ---------------------------------------------------------------------------------------------------- 3k and the sum-check verifier
