@@ -40,6 +40,8 @@
  *      Later, still 7 (symbols added, none changed): entries of the sum-check table as last set, by index (reef_sc_lookup, section 3b).
  *      Later, still 7 (symbols added, none changed): a batch of IPA openings checked against one key in a single pass
  *      (reef_ipa_check_batch, reef_ipa_check_batch_last_timing, section 3m).
+ *      Later, still 7 (symbols added, none changed): a verifier's key of a committed document and comm_LZ for many points in one pass
+ *      (reef_hyrax_vk_create, reef_hyrax_vk_destroy, reef_hyrax_vk_comm_lz, section 3n).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -915,6 +917,38 @@ reef_status reef_ipa_check_batch(reef_msm_ctx *key, size_t n, const reef_ipa_pro
                                  reef_fe *s_comb /* n, may be NULL */, int s_loc, reef_jacobian *d_comb /* may be NULL */,
                                  reef_jacobian *g_comb /* may be NULL */);
 reef_status reef_ipa_check_batch_last_timing(reef_msm_ctx *key, float *s_pass_ms, float *key_msm_ms, float *side_ms);
+
+/* ---------------------------------------------------------------------------------------------
+ * (3n) The verifier's key of a committed document: comm_LZ = sum_i eq(point[..left])_i C_i of HyraxPC::verify_eval [R]
+ * (commitment.rs:446-492) over the 2^left row commitments a .cmt file holds, WITHOUT a document.  3i forms the same point on a
+ * reef_hyrax_ctx, which is made from z; a verifier has no z.  The rows are decoded and keyed once; every call then serves any number
+ * of points -- the proofs of a batch (3m) against one document commitment -- in one pass:
+ *
+ *   one launch writes the m x 2^left weights eq(points[t])_i as canonical integers (3i's convention: point[0] pairs with the most
+ *   significant row bit), the m MSMs go through the row pipeline (reef_msm_rows: rows = m, row_len = 2^left) over the resident key
+ *   as one batch of full-width scalars, one launch encodes the m results; one host wait per call.
+ *
+ * row_comms32   2^left_vars x 32 bytes in reef_normalize's encoding, host or device memory (loc; a device buffer 16-byte aligned).
+ *               Decoded on `device` (-1: the calling thread's current device) straight into the buffer the key is built from: no
+ *               affine point visits the host.  Identity rows (32 zero bytes) are legal, as in 3i; so is a key that is all identities.
+ * key_opts      as reef_msm_ctx_create's opts (NULL: the library's default key; .device is ignored).  The key is the vk's own: a
+ *               window split cannot be set on it.
+ * points        m x left_vars scalars, row-major, HOST memory, in the form is_mont names.  Entries 0 and 1 (weights of exactly 0
+ *               and 1) are legal.
+ * comm_lz       m Jacobian points, comm_lz32 their 32-byte encodings (the identity: 32 zero bytes); HOST memory, either may be NULL,
+ *               not both.  The points are the same whatever route the row pipeline takes for a shape.
+ *
+ * m = 0: REEF_OK with nothing written.  REEF_ERR_ARG, the message naming the cause, with nothing written and the vk (if any) still
+ * usable: left_vars outside 1 .. 25; a row that is not the encoding of a point (the message names the first such row and their
+ * count; *out is not written); a point entry not below the modulus; a misaligned device buffer; m 2^left_vars >= 2^31; both outputs
+ * NULL.  The weights and the key's workspace stay on the vk and grow on demand.  A vk serialises the calls made on it; different vks
+ * are independent.  Out of scope: vks over several devices. */
+typedef struct reef_hyrax_vk reef_hyrax_vk;
+reef_status reef_hyrax_vk_create(reef_hyrax_vk **out, int curve, const uint8_t *row_comms32, size_t left_vars, int loc, int device,
+                                 const reef_msm_opts *key_opts);
+void        reef_hyrax_vk_destroy(reef_hyrax_vk *vk);
+reef_status reef_hyrax_vk_comm_lz(reef_hyrax_vk *vk, const reef_fe *points, size_t m, bool is_mont, reef_jacobian *comm_lz /* m, may be NULL */,
+                                  uint8_t *comm_lz32 /* 32 m bytes, may be NULL */);
 
 /* ---------------------------------------------------------------------------------------------
  * (4) Runtime plumbing.

@@ -169,6 +169,7 @@ struct reef_msm_ctx : reef_handle {};
 struct reef_sc_ctx : reef_handle {};
 struct reef_nifs_ctx : reef_handle {};     // rows N6 and N5 and the opening (3f-3h) share it
 struct reef_hyrax_ctx : reef_handle {};
+struct reef_hyrax_vk : reef_handle {};
 struct reef_merkle_ctx : reef_handle {};
 
 // The table of a curve's entry points, one per row (common.h); NULL with the error set for a curve that does not exist.
@@ -181,6 +182,7 @@ template <class VT> static const VT *table(int curve) {
     else if constexpr (std::is_same<VT, OpenVTable>::value) return p ? pallas_open_vtable() : vesta_open_vtable();
     else if constexpr (std::is_same<VT, IpaCheckVTable>::value) return p ? pallas_ipa_check_vtable() : vesta_ipa_check_vtable();
     else if constexpr (std::is_same<VT, MerkleVTable>::value) return p ? pallas_merkle_vtable() : vesta_merkle_vtable();
+    else if constexpr (std::is_same<VT, HyraxVkVTable>::value) return p ? pallas_hyrax_vk_vtable() : vesta_hyrax_vk_vtable();
     else return p ? pallas_hyrax_vtable() : vesta_hyrax_vtable();
 }
 
@@ -636,6 +638,18 @@ reef_status reef_hyrax_read(reef_hyrax_ctx *ctx, int which, size_t count, reef_f
 reef_status reef_hyrax_set_small_key(reef_hyrax_ctx *ctx, size_t n_small) {
     REEF_TRY(check_small_key("reef_hyrax_set_small_key", n_small));
     return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->set_small_key(impl, n_small); });
+}
+
+// ---- the verifier's key of a committed document
+reef_status reef_hyrax_vk_create(reef_hyrax_vk **out, int curve, const uint8_t *row_comms32, size_t left_vars, int loc, int device,
+                                 const reef_msm_opts *key_opts) {
+    return create_handle(out, curve, [&](const CurveVTable *, void **impl) {
+        return table<HyraxVkVTable>(curve)->create(impl, row_comms32, left_vars, loc, device, key_opts);
+    });
+}
+void reef_hyrax_vk_destroy(reef_hyrax_vk *vk) { destroy_handle(vk, &HyraxVkVTable::destroy); }
+reef_status reef_hyrax_vk_comm_lz(reef_hyrax_vk *vk, const reef_fe *points, size_t m, bool is_mont, reef_jacobian *comm_lz, uint8_t *comm_lz32) {
+    return dispatch<HyraxVkVTable>(vk, [&](auto *v, void *impl) { return v->comm_lz(impl, points, m, is_mont, comm_lz, comm_lz32); });
 }
 
 // ---- the verifier's IPA check on a key ctx (the curve is the key's)

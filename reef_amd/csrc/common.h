@@ -578,6 +578,15 @@ struct HyraxVTable {
 const HyraxVTable *pallas_hyrax_vtable();
 const HyraxVTable *vesta_hyrax_vtable();
 
+// The key a verifier holds of a committed document (hyrax_vk_engine.inc; include/reef_msm.h 3n).
+struct HyraxVkVTable {
+    reef_status (*create)(void **impl, const uint8_t *row_comms32, size_t left_vars, int loc, int device, const reef_msm_opts *key_opts);
+    void (*destroy)(void *impl);
+    reef_status (*comm_lz)(void *impl, const reef_fe *points, size_t m, bool is_mont, reef_jacobian *comm_lz, uint8_t *comm_lz32);
+};
+const HyraxVkVTable *pallas_hyrax_vk_vtable();
+const HyraxVkVTable *vesta_hyrax_vk_vtable();
+
 // The verifier's IPA check on a key ctx (ipa_check_engine.inc; include/reef_msm.h 3j).  key_impl: a Ctx impl.
 struct IpaCheckVTable {
     reef_status (*ipa_check)(void *key_impl, size_t n, const reef_jacobian *comm, const reef_fe *c, const reef_affine *q, const reef_jacobian *L,

@@ -810,6 +810,36 @@ template <int CURVE> class HyraxEval {
     size_t num_vars_, left_;
 };
 
+// The verifier's key of a committed document (reef_msm.h 3n): PolyCommit.comm decoded and keyed once, then
+// comm_LZ = sum_i eq(point[..left])_i C_i of HyraxPC::verify_eval [R] for any number of points per call.  Scalars in pasta Montgomery form.
+template <int CURVE> class HyraxVk {
+  public:
+    // row_comms: the 2^left_vars compressed rows (host); device -1: the current one; key_opts: as CommitmentGens' (nullptr: the default key)
+    HyraxVk(const Compressed *row_comms, size_t left_vars, int device = -1, const reef_msm_opts *key_opts = nullptr) : left_(left_vars) {
+        check(reef_hyrax_vk_create(&vk_, CURVE, row_comms->data(), left_vars, REEF_HOST, device, key_opts), "reef_hyrax_vk_create");
+    }
+    // the same from rows already in device memory (16-byte aligned)
+    HyraxVk(const uint8_t *d_row_comms32, size_t left_vars, int device, const reef_msm_opts *key_opts) : left_(left_vars) {
+        check(reef_hyrax_vk_create(&vk_, CURVE, d_row_comms32, left_vars, REEF_DEVICE, device, key_opts), "reef_hyrax_vk_create");
+    }
+    ~HyraxVk() { reef_hyrax_vk_destroy(vk_); }
+    HyraxVk(const HyraxVk &) = delete;
+    HyraxVk &operator=(const HyraxVk &) = delete;
+    size_t left_vars() const { return left_; }
+
+    // points: m x left_vars scalars, row-major.  comm_lz[t] for every point and, when asked for, its encoding: one call, one pass
+    std::vector<reef_jacobian> comm_lz(const reef_fe *points, size_t m, std::vector<Compressed> *compressed = nullptr) const {
+        std::vector<reef_jacobian> out(m);
+        if (compressed) compressed->resize(m);
+        if (m) check(reef_hyrax_vk_comm_lz(vk_, points, m, true, out.data(), compressed ? compressed->data()->data() : nullptr), "reef_hyrax_vk_comm_lz");
+        return out;
+    }
+
+  private:
+    reef_hyrax_vk *vk_ = nullptr;
+    size_t left_;
+};
+
 // InnerProductArgument::verify [R]: the check EE::verify_batch and HyraxPC::verify_eval end with (reef_msm.h 3j).
 // The caller has drawn the round challenges from its transcript; b = sum_t weights[t] pad(eq(points[t])) is built on the device.
 // Scalars in pasta Montgomery form.  A proof that does not verify gives false; bad arguments throw.

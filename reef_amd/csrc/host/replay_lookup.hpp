@@ -4,6 +4,8 @@
 //   bytes -> reef_doc_transform (2n) -> device symbols -> reef_hyrax_create / _commit (2m)  and  reef_sc_set_table_parts (2b)
 //   per step: v = reef_sc_lookup(qs); claim_r; reset, gen_eq_table(prev_running_q reversed), ell x linear_mle_product, read
 //   the last (sc_rs, next_running_v) -> running_q as proof_dot_prod_prover forms it -> reef_hyrax_eval_begin / _eval_comm_own / IPA (2i)
+//   the verifier's half of that argument on the device: reef_hyrax_vk_create over the rows commit produced, reef_hyrax_vk_comm_lz (2o),
+//   reef_ipa_check_eq (2k)
 // After the device symbols exist the host's own copy of them goes into no device call: it serves the checks (lookup_check.hpp) only.
 #pragma once
 #include "lookup_check.hpp"
@@ -195,15 +197,16 @@ static std::string lookup_body(const Shape &shape, const LookupFlags &fl) {
     point.insert(point.end(), q.end() - (doc_log - (size_t)fl.proj), q.end());
     HyraxP::Proof hpf;
     StandinTranscript ht(m, 0xD0C);
-    t0 = clk::now();
-    hyrax.prove_own(row_key, point.data(), ht.fn(), [&](const reef_fe &r) {
+    const auto q_of = [&](const reef_fe &r) {
         const reef_fe d = fmul(m, g1, r);
         reef_jacobian j;
         CK(reef_msm(pc_curve.one, &d, 1, REEF_HOST, true, &j, REEF_HOST));
         reef_affine a;
         CK(reef_normalize(REEF_PALLAS, &j, 1, REEF_HOST, &a, nullptr));
         return a;
-    }, hpf, g_small_key);
+    };
+    t0 = clk::now();
+    hyrax.prove_own(row_key, point.data(), ht.fn(), q_of, hpf, g_small_key);
     const double consistency_ms = ms_since(t0);
 
     // ---- the checks
@@ -219,6 +222,28 @@ static std::string lookup_body(const Shape &shape, const LookupFlags &fl) {
     check_hyrax(m, doc8, doc_log, left, point, hpf, hg, blinds, hd, g1, pcp);
     const double check_ms = ms_since(t0);
 
+    // ---- the verifier's half on the device, from what a verifier holds: the compressed rows, the point, the proof.  comm_LZ through a vk
+    // must be the point reef_hyrax_eval_comm_own gave the prover, and reef_ipa_check_eq must accept the proof against it (the row blinds
+    // leave lz_blind h in comm_LZ; the rounds carry no blinds of their own)
+    t0 = clk::now();
+    const reef_provider::HyraxVk<REEF_PALLAS> vk(comm.data(), left, dev);
+    const double verify_vk_create_ms = ms_since(t0);
+    t0 = clk::now();
+    std::vector<reef_provider::Compressed> vk_lz32;
+    const std::vector<reef_jacobian> vk_lz = vk.comm_lz(point.data(), 1, &vk_lz32);
+    const double verify_comm_lz_ms = ms_since(t0);
+    if (vk_lz32[0] != reef_provider::compress<REEF_PALLAS>(hpf.comm_lz) || vk_lz32[0] != reef_provider::compress<REEF_PALLAS>(vk_lz[0]))
+        reject("verify", "comm_LZ through reef_hyrax_vk_comm_lz differs from reef_hyrax_eval_comm_own's");
+    t0 = clk::now();
+    reef_provider::InnerProductArgument<REEF_PALLAS> ipa;
+    ipa.L = hpf.L;
+    ipa.R = hpf.R;
+    ipa.a_hat = hpf.a_hat;
+    const bool device_verified = ipa.verify(row_key, cols, vk_lz[0], hpf.eval, q_of(hpf.r_q), hpf.r_rounds,
+                                            {std::vector<reef_fe>(point.begin() + left, point.end())}, {m.one}, &h, &hpf.lz_blind);
+    const double verify_ipa_ms = ms_since(t0);
+    if (!device_verified) reject("verify", "reef_ipa_check_eq rejects the consistency argument against the vk's comm_LZ");
+
     const double ns = (double)steps;
     std::vector<char> line(4096);
     snprintf(line.data(), line.size(),
@@ -229,9 +254,10 @@ static std::string lookup_body(const Shape &shape, const LookupFlags &fl) {
              "\"text_bytes\": %zu, \"live_symbols\": %zu, \"table_eval\": \"%s\", \"transform_ms\": %.3f, \"commit_ms\": %.3f, \"set_table_ms\": %.3f, "
              "\"lookup_ms_per_step\": %.3f, \"sumcheck_ms_per_step\": %.3f, \"ms_per_step\": %.3f, \"consistency_ms\": %.3f, \"consistency_rounds\": %zu, \"check_ms\": %.3f, "
              "\"timed\": \"sumcheck_ms_per_step: claim_r, reset, gen_eq_table, ell rounds with the stand-in transcript on the host, the read of next_running_v; "
-             "lookup_ms_per_step: reef_sc_lookup host to host\", \"rounds_checked\": %zu, \"values_checked\": %zu, \"points_checked\": %d, \"proof_checked\": true}",
+             "lookup_ms_per_step: reef_sc_lookup host to host\", \"rounds_checked\": %zu, \"values_checked\": %zu, \"points_checked\": %d, \"proof_checked\": true, "
+             "\"verify_vk_create_ms\": %.3f, \"verify_comm_lz_ms\": %.3f, \"verify_ipa_ms\": %.3f, \"device_verified\": %s}",
              sh->name.c_str(), hybrid ? "hybrid" : "doc", fl.proj, eb, doc_log, ell, steps, nq, nbytes, live, tb.eval_on_host ? "host" : "n3", transform_ms, commit_ms,
              set_table_ms, lookup_ms / ns, sumcheck_ms / ns, (lookup_ms + sumcheck_ms) / ns, consistency_ms, hpf.r_rounds.size(), check_ms, counts.rounds,
-             counts.values, g_checked);
+             counts.values, g_checked, verify_vk_create_ms, verify_comm_lz_ms, verify_ipa_ms, device_verified ? "true" : "false");
     return std::string(line.data());
 }

@@ -22,6 +22,7 @@
 #include "spartan_engine.inc"
 #include "open_engine.inc"
 #include "hyrax_engine.inc"
+#include "hyrax_vk_engine.inc"
 #include "merkle_resident_engine.inc"
 #include "doc_engine.inc"      // once: both curves' tables point at it
 namespace reef {
@@ -43,6 +44,10 @@ const OpenVTable *pallas_open_vtable() {
 }
 const HyraxVTable *pallas_hyrax_vtable() {
     static const HyraxVTable vt = make_hyrax_vtable<0>();
+    return &vt;
+}
+const HyraxVkVTable *pallas_hyrax_vk_vtable() {
+    static const HyraxVkVTable vt = make_hyrax_vk_vtable<0>();
     return &vt;
 }
 const IpaCheckVTable *pallas_ipa_check_vtable() {

@@ -21,6 +21,7 @@
 #include "spartan_engine.inc"
 #include "open_engine.inc"
 #include "hyrax_engine.inc"
+#include "hyrax_vk_engine.inc"
 #include "merkle_resident_engine.inc"
 namespace reef {
 const CurveVTable *vesta_vtable() {
@@ -41,6 +42,10 @@ const OpenVTable *vesta_open_vtable() {
 }
 const HyraxVTable *vesta_hyrax_vtable() {
     static const HyraxVTable vt = make_hyrax_vtable<1>();
+    return &vt;
+}
+const HyraxVkVTable *vesta_hyrax_vk_vtable() {
+    static const HyraxVkVTable vt = make_hyrax_vk_vtable<1>();
     return &vt;
 }
 const IpaCheckVTable *vesta_ipa_check_vtable() {

@@ -44,6 +44,26 @@ __global__ void __launch_bounds__(256) k_mle_eq(MlePoint pt, u32 first, u32 vars
     eq[t] = o;
 }
 
+// k_mle_eq over a batch of points that live in device memory (m x vars, row-major, in the caller's form), written where an MSM reads
+// its scalars: w[t * 2^vars + i] = eq(pts[t])_i as a canonical integer.  Grid: x over the entries, y over the points (a stride loop
+// past 65535 of them).  The products are k_mle_eq's, in its order.
+template <int F>
+__global__ void __launch_bounds__(256) k_mle_eq_batch(const fe256 *__restrict__ pts, u32 m, u32 vars, int is_mont, fe256 *__restrict__ w) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (1u << vars)) return;
+    for (u32 t = blockIdx.y; t < m; t += gridDim.y) {
+        const fe256 *p = pts + (u64)t * vars;
+        fe acc = fe_one<F>();
+        for (u32 k = 0; k < vars; ++k) {
+            const fe r = fe_from_caller<F>(load_fe256(p + k), is_mont);
+            const fe one_minus = fe_sub<F, 2>(fe_one<F>(), r);
+            const bool bit = (i >> (vars - 1 - k)) & 1u;
+            acc = fe_mul<F>(acc, bit ? r : one_minus);
+        }
+        store_fe256(w + ((u64)t << vars) + i, fe_to_integer<F>(fe_canon<F>(acc)));
+    }
+}
+
 template <int EB> struct MleElem;
 template <> struct MleElem<1> { typedef unsigned char type; };
 template <> struct MleElem<2> { typedef unsigned short type; };

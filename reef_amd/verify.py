@@ -14,6 +14,10 @@ layouts: affine (8 limbs) or Jacobian (12 limbs).
 over the key whatever m is; `verify_eval_batch` drives m Hyrax arguments through it the way `verify_eval` drives one.  The weights
 are the caller's randomness, drawn after every proof is fixed; neither function draws any.
 
+`HyraxVk` is the verifier's key of a committed document (3n): the row commitments decoded and keyed once, `.comm_lz(points)` then
+forms comm_LZ for any number of points in one call.  An instance of `verify_eval` / `verify_eval_batch` may carry one in place of
+its rows; the batch makes one call per vk and takes the transcript's encodings from it.
+
 `matrix_evals` is reef_spartan_eval_matrices: A~, B~, C~ at (r_x, r_y) on the matrices a `Nifs` holds, no witness needed.
 `verify_sumchecks` is the verifier of 3g's transcript -- RelaxedR1CSSNARK::verify [R] up to the opening: O(log n) host arithmetic and that
 one device call -- and `verify_snark` adds `verify_opening` with eval_E = claims_outer[3], eval_W = claims_inner[2].
@@ -25,8 +29,9 @@ from typing import Any, Callable, List, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import REEF_DEVICE, REEF_HOST, IpaProof, ReefError, check
-from ._fe import _arr, _ints
+from . import _ffi
+from ._ffi import REEF_DEVICE, REEF_HOST, IpaProof, MsmOpts, ReefError, check
+from ._fe import _Handle, _arr, _ints
 from .msm import DeviceBuffer, MsmContext, curve_id, decompress, normalize
 from .nifs import Nifs
 from .spartan import compress
@@ -248,13 +253,69 @@ def comm_lz(curve, row_comms32, point_left: Sequence[int], p: int) -> np.ndarray
         return ctx.msm(_arr(w), is_mont=False)
 
 
+class HyraxVk(_Handle):
+    """reef_hyrax_vk (3n): the verifier's key of a committed document.  row_comms32: the 2^left rows of 32 bytes a .cmt file holds
+    (bytes or a uint8 array), or a DeviceBuffer of them; decoded and keyed once, on `device` (None: the current one).  The keyword
+    options are MsmContext's (the default: the library's default key)."""
+    _destroy = "reef_hyrax_vk_destroy"
+
+    def __init__(self, curve, row_comms32, left: int, *, device: Optional[int] = None, window_bits: int = 0, bucket_groups: int = 0,
+                 chunk: int = 0, byte_tables: int = 0):
+        self.curve = curve_id(curve)
+        self.left = int(left)
+        self._lib = _ffi.load()
+        self._h = None
+        if not 1 <= self.left <= 25:
+            raise ReefError(1, f"left_vars = {self.left} is outside 1 .. 25")
+        nbytes = 32 << self.left
+        if isinstance(row_comms32, DeviceBuffer):
+            if row_comms32.nbytes < nbytes:
+                raise ValueError(f"expected {1 << self.left} row commitments of 32 bytes, the device buffer holds {row_comms32.nbytes} bytes")
+            loc, ptr, keep = REEF_DEVICE, row_comms32.ptr, row_comms32
+        else:
+            keep = np.frombuffer(bytes(row_comms32), dtype=np.uint8) if isinstance(row_comms32, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(row_comms32, dtype=np.uint8).reshape(-1)
+            if keep.size != nbytes:
+                raise ValueError(f"expected {1 << self.left} row commitments of 32 bytes, got {keep.size} bytes")
+            loc, ptr = REEF_HOST, keep.ctypes.data
+        opts = MsmOpts(window_bits, bucket_groups, chunk, byte_tables, -1, (ctypes.c_uint32 * 3)(0, 0, 0))
+        h = ctypes.c_void_p()
+        check(self._lib.reef_hyrax_vk_create(ctypes.byref(h), self.curve, ptr, self.left, loc, -1 if device is None else int(device),
+                                             ctypes.byref(opts)))
+        self._h = h
+
+    def comm_lz(self, points: Sequence[Sequence[int]], compressed: bool = True, *, is_mont: bool = False):
+        """reef_hyrax_vk_comm_lz: comm_LZ for every point (each `left` ints in the form is_mont names) in one call.  (jacobians,
+        encodings): an (m, 12) uint64 array and a list of m 32-byte strings (None unless compressed)."""
+        m = len(points)
+        for t, pt in enumerate(points):
+            if len(pt) != self.left:
+                raise ValueError(f"point {t} has {len(pt)} entries, the key is over 2^{self.left} rows")
+        jac = np.zeros((m, 12), np.uint64)
+        enc = np.zeros((m, 32), np.uint8) if compressed else None
+        if m:
+            pa = _arr([x for pt in points for x in pt])
+            check(self._lib.reef_hyrax_vk_comm_lz(self._h, pa.ctypes.data, m, bool(is_mont), jac.ctypes.data,
+                                                  None if enc is None else enc.ctypes.data))
+        return jac, (None if enc is None else [enc[t].tobytes() for t in range(m)])
+
+
+def _check_vk(vk: "HyraxVk", curve: int, left: int, who: str, i: Optional[int] = None) -> None:
+    where = "" if i is None else f"instance {i}: "
+    if vk.curve != curve:
+        raise ReefError(1, f"{who}: {where}the vk is of curve {vk.curve}, the key of curve {curve}")
+    if vk.left != left:
+        raise ValueError(f"{who}: {where}the vk is over 2^{vk.left} rows, the instance has left = {left}")
+
+
 def verify_eval(key: MsmContext, q, row_comms32, point: Sequence[int], left: int, eval_: int, proof: dict, p: int, *, h=None,
                 blind_total: Optional[int] = None, challenge: Optional[Callable[[str, List[Any]], int]] = None, q_of=None,
                 check_fn=None) -> bool:
     """HyraxPC::verify_eval [R] for 3i's argument: comm_LZ from the compressed row commitments (comm_lz above), then P_hat = comm_LZ +
     eval q + sum r_k^2 L_k + sum r_k^-2 R_k against a_hat G_hat + a_hat b_hat q (+ blind_total h), b = eq(point[left..]) built on the
     device.  proof: {"L", "R", "a_hat"} and either "rs", or a `challenge` to draw them with: "r" after (comm_LZ, eval) -- q is then
-    q_of(r) -- and "challenge_r" per round, prove_eval's order.  key: gens_v with 2^(len(point) - left) points.  Canonical ints."""
+    q_of(r) -- and "challenge_r" per round, prove_eval's order.  key: gens_v with 2^(len(point) - left) points.  Canonical ints.
+    row_comms32 may be a `HyraxVk` over the rows instead: comm_LZ and its encoding then come from the vk."""
     curve = key.curve
     right = len(point) - left
     n = 1 << right
@@ -264,9 +325,14 @@ def verify_eval(key: MsmContext, q, row_comms32, point: Sequence[int], left: int
         raise ValueError("verify_eval needs q, or a challenge callable and q_of to form it from the drawn r")
     if (h is None) != (blind_total is None):
         raise ValueError("h and blind_total come together or not at all")
-    clz = comm_lz(curve, row_comms32, point[:left], p)
+    if isinstance(row_comms32, HyraxVk):
+        _check_vk(row_comms32, curve, left, "verify_eval")
+        jac, encs = row_comms32.comm_lz([[x % p for x in point[:left]]])
+        clz, cz = jac[0], encs[0]
+    else:
+        clz, cz = comm_lz(curve, row_comms32, point[:left], p), None
     if challenge is not None:
-        r_ipa = challenge("r", [compress(key, clz), eval_])
+        r_ipa = challenge("r", [compress(key, clz) if cz is None else cz, eval_])
         if q_of is not None:
             q = q_of(r_ipa)
         rs = [challenge("challenge_r", [compress(key, L), compress(key, R)]) for L, R in zip(proof["L"], proof["R"])]
@@ -286,13 +352,29 @@ def verify_eval_batch(key: MsmContext, instances: Sequence[dict], p: int, weight
     where used, "h", "blind_total", "challenge", "q_of" -- all with the same len(point) - left.  weights(absorbed) -> m non-zero ints
     below p: the caller's randomness, called once AFTER every proof is fixed, with what each proof contributes ([comm_LZ compressed,
     eval, a_hat, L and R compressed ...] per instance) for a caller that derives the weights from a transcript.  True / False; with
-    each, (verdict, [bool per instance]).  check_fn stands in for ipa_check_batch (tests)."""
+    each, (verdict, [bool per instance]).  check_fn stands in for ipa_check_batch (tests).
+    An instance may carry "vk": a `HyraxVk` over its document's rows, in place of "row_comms32".  Such instances are grouped by vk:
+    ONE `HyraxVk.comm_lz` call per vk forms their comm_LZ, and the encodings it returns go into the transcript (no compress() call
+    for them)."""
     curve = key.curve
     if not instances:
         return (True, []) if each else True
     right = len(instances[0]["point"]) - instances[0]["left"]
     n = 1 << right
     proofs, absorbed, bad = [], [], False
+    by_vk, from_vk = {}, {}                                     # id(vk) -> (vk, [instance index]); instance index -> (comm_LZ, encoding)
+    for i, it in enumerate(instances):
+        vk = it.get("vk")
+        if vk is None:
+            continue
+        if it.get("row_comms32") is not None:
+            raise ValueError(f"instance {i}: \"vk\" stands in place of \"row_comms32\", not beside it")
+        _check_vk(vk, curve, it["left"], "verify_eval_batch", i)
+        by_vk.setdefault(id(vk), (vk, []))[1].append(i)
+    for vk, idx in by_vk.values():
+        jac, encs = vk.comm_lz([[x % p for x in instances[i]["point"][:vk.left]] for i in idx])
+        for k, i in enumerate(idx):
+            from_vk[i] = (jac[k], encs[k])
     for i, it in enumerate(instances):
         point, left, proof, challenge, q_of, q = it["point"], it["left"], it["proof"], it.get("challenge"), it.get("q_of"), it.get("q")
         h, blind_total = it.get("h"), it.get("blind_total")
@@ -304,8 +386,11 @@ def verify_eval_batch(key: MsmContext, instances: Sequence[dict], p: int, weight
             raise ValueError("verify_eval_batch needs q, or a challenge callable and q_of to form it from the drawn r")
         if (h is None) != (blind_total is None):
             raise ValueError("h and blind_total come together or not at all")
-        clz = comm_lz(curve, it["row_comms32"], point[:left], p)
-        cz = compress(key, clz)
+        if i in from_vk:
+            clz, cz = from_vk[i]
+        else:
+            clz = comm_lz(curve, it["row_comms32"], point[:left], p)
+            cz = compress(key, clz)
         if challenge is not None:
             r_ipa = challenge("r", [cz, it["eval"]])
             if q_of is not None:
