@@ -42,6 +42,8 @@
  *      (reef_ipa_check_batch, reef_ipa_check_batch_last_timing, section 3m).
  *      Later, still 7 (symbols added, none changed): a verifier's key of a committed document and comm_LZ for many points in one pass
  *      (reef_hyrax_vk_create, reef_hyrax_vk_destroy, reef_hyrax_vk_comm_lz, section 3n).
+ *      Later, still 7 (symbols added, none changed): the verifier's matrix evaluations at many points in one pass
+ *      (reef_spartan_eval_matrices_batch, reef_nifs_set_eval_workspace, reef_spartan_eval_matrices_batch_last_info, section 3o).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -895,8 +897,8 @@ reef_status reef_doc_transform(const uint8_t *text, size_t nbytes, int text_loc,
  * reef_ipa_check_batch_last_timing: how the last batch on the key ctx divided, in device milliseconds, when it ran with the key's
  * timing on (reef_msm_ctx_enable_timing): the tables and the S pass, the MSM over the key, the one-off points (normalise, import,
  * MSM).  Each pointer may be NULL.  REEF_ERR_ARG when there was no such batch.
- * Out of scope: an explicit b vector per proof; proofs of different n in one batch; a batched reef_spartan_eval_matrices; any change
- * to the replay (its two openings are on different curves and cannot share a key). */
+ * Out of scope: an explicit b vector per proof; proofs of different n in one batch; any change to the replay (its two openings are on
+ * different curves and cannot share a key).  (The matrix evaluations of a batch of proofs: 3o.) */
 typedef struct {
     const reef_jacobian *comm;          /* 1 */
     const reef_fe *c;                   /* 1 */
@@ -949,6 +951,41 @@ reef_status reef_hyrax_vk_create(reef_hyrax_vk **out, int curve, const uint8_t *
 void        reef_hyrax_vk_destroy(reef_hyrax_vk *vk);
 reef_status reef_hyrax_vk_comm_lz(reef_hyrax_vk *vk, const reef_fe *points, size_t m, bool is_mont, reef_jacobian *comm_lz /* m, may be NULL */,
                                   uint8_t *comm_lz32 /* 32 m bytes, may be NULL */);
+
+/* ---------------------------------------------------------------------------------------------
+ * (3o) The verifier's matrix evaluations (3k) at many points in one pass: a verifier that checks m proofs over one shape -- every
+ * proof's secondary circuit; the primary circuit whenever one regex meets many documents -- needs A~, B~, C~ at m points (r_x, r_y) on
+ * the same matrices.  With 3m and 3n this gives each of such a verifier's three device jobs a one-pass form.
+ *
+ * r_x: m x ell_x entries, point after point; r_y: m x ell_y; evals: m x {A~, B~, C~}: HOST memory, in the form is_mont names.
+ * evals[3 t .. 3 t + 2] is bit for bit what reef_spartan_eval_matrices returns for point t alone.  All of 3k holds unchanged: the pad
+ * rule, the matrices-only ctx (no running instance), "at any time, in no call order", no table of a prove or an opening read or
+ * written, and the next call seeing a matrix replaced by reef_nifs_set_matrix.  The single call's results and launches are as before:
+ * the batch keeps buffers of its own.
+ *
+ * m = 0: REEF_OK with no device work and nothing written.  REEF_ERR_ARG, with no output touched and the ctx usable: everything 3k
+ * rejects; an entry not below the modulus (the message names the point's index and whether the entry is in r_x or r_y); m > 4096, 3m's
+ * limit (the message names both numbers).
+ *
+ * One host wait per call, one copy up (every point's 2 (ell_x + ell_y) eq factors) and one copy down (3 m field elements).  The points
+ * are taken two a thread: a matrix entry, its class and its general coefficient are read once for a pair of points (an odd last point
+ * is walked alone, in the same launches).  The eq tables of one point take (num_cons + num_vars + 1 + num_io) x 32 bytes, so the call walks the points in
+ * groups of G = max(1, floor(budget / bytes per point)), rounded down to an even number when above 1 and never more than m; the groups
+ * follow each other on the stream with no host wait between them, each writes its results into one device array of 3 m values, and a
+ * group is four launches -- six when the shape has rows of more than 128 entries -- however many points it holds.
+ * reef_nifs_set_eval_workspace sets the budget in bytes; 0 restores the default of 1 GiB (a choice, not a measurement: whole batches at
+ * Reef's usual shapes, 16 points a group at 2^20 rows).  A budget below one point's tables gives groups of one; it is never an error.
+ * The tables' buffer grows to at most the budget, or one point's tables if that is larger (a buffer made under a larger budget is given
+ * back by the next batch), and is freed with the ctx; beside it the batch keeps the eq factors, 216 bytes of block sums per 256 rows and
+ * point, the long rows' segment sums and the 3 m results.
+ * reef_spartan_eval_matrices_batch_last_info: the last batch on the ctx (m = 0 and failed calls do not count) -- the number of groups,
+ * the points of a full group (G above), the bytes of the tables' buffer as it stands.  Each pointer may be NULL.  REEF_ERR_ARG when
+ * there was no batch.
+ * Out of scope: points in device memory; one batch over different shapes or ctxs; a batched prover. */
+reef_status reef_spartan_eval_matrices_batch(reef_nifs_ctx *ctx, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *r_x /* m ell_x */,
+                                             const reef_fe *r_y /* m ell_y */, size_t m, bool is_mont, reef_fe *evals /* 3 m */);
+reef_status reef_nifs_set_eval_workspace(reef_nifs_ctx *ctx, size_t bytes);
+reef_status reef_spartan_eval_matrices_batch_last_info(reef_nifs_ctx *ctx, size_t *groups, size_t *points_per_group, size_t *workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * (4) Runtime plumbing.

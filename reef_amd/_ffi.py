@@ -203,6 +203,9 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_spartan_inner_round": (c_int, [vp, vp, c_bool, vp]),
         "reef_spartan_inner_claims": (c_int, [vp, vp, c_bool, vp]),
         "reef_spartan_eval_matrices": (c_int, [vp, c_size_t, c_size_t, vp, vp, c_bool, vp]),
+        "reef_spartan_eval_matrices_batch": (c_int, [vp, c_size_t, c_size_t, vp, vp, c_size_t, c_bool, vp]),
+        "reef_nifs_set_eval_workspace": (c_int, [vp, c_size_t]),
+        "reef_spartan_eval_matrices_batch_last_info": (c_int, [vp, POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]),
         "reef_spartan_open_begin": (c_int, [vp, vp, c_bool, vp]),
         "reef_spartan_open_fold": (c_int, [vp, vp, c_bool, vp]),
         "reef_spartan_open_ipa_begin": (c_int, [vp, vp, vp, vp]),

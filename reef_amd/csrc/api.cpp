@@ -566,6 +566,18 @@ reef_status reef_spartan_eval_matrices(reef_nifs_ctx *ctx, size_t num_cons_pad, 
                                        reef_fe evals[3]) {
     return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) { return v->eval_matrices(impl, num_cons_pad, num_vars_pad, r_x, r_y, is_mont, evals); });
 }
+reef_status reef_spartan_eval_matrices_batch(reef_nifs_ctx *ctx, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *r_x, const reef_fe *r_y, size_t m,
+                                             bool is_mont, reef_fe *evals) {
+    return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) {
+        return v->eval_matrices_batch(impl, num_cons_pad, num_vars_pad, r_x, r_y, m, is_mont, evals);
+    });
+}
+reef_status reef_nifs_set_eval_workspace(reef_nifs_ctx *ctx, size_t bytes) {
+    return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) { return v->set_eval_workspace(impl, bytes); });
+}
+reef_status reef_spartan_eval_matrices_batch_last_info(reef_nifs_ctx *ctx, size_t *groups, size_t *points_per_group, size_t *workspace_bytes) {
+    return dispatch<SpartanVTable>(ctx, [&](auto *v, void *impl) { return v->eval_batch_last_info(impl, groups, points_per_group, workspace_bytes); });
+}
 
 // ---- the batched IPA opening of the final SNARK on a NIFS ctx
 reef_status reef_spartan_open_begin(reef_nifs_ctx *ctx, reef_msm_ctx *key, bool is_mont, reef_fe *cross_term) {

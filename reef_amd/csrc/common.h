@@ -541,6 +541,11 @@ struct SpartanVTable {
     reef_status (*inner_claims)(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *claims);
     // the verifier's matrix evaluations (3k): needs the matrices only
     reef_status (*eval_matrices)(void *impl, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *r_x, const reef_fe *r_y, bool is_mont, reef_fe *evals);
+    // the same at m points in one pass (3o), its workspace budget, and how the last batch divided into groups
+    reef_status (*eval_matrices_batch)(void *impl, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *r_x, const reef_fe *r_y, size_t m, bool is_mont,
+                                       reef_fe *evals);
+    reef_status (*set_eval_workspace)(void *impl, size_t bytes);
+    reef_status (*eval_batch_last_info)(void *impl, size_t *groups, size_t *points_per_group, size_t *workspace_bytes);
 };
 const SpartanVTable *pallas_spartan_vtable();
 const SpartanVTable *vesta_spartan_vtable();

@@ -722,6 +722,25 @@ template <int CURVE> class RelaxedR1CSSnark {
         check(reef_spartan_eval_matrices(nifs_.handle(), ncp_, nvp_, r_x.data(), r_y.data(), true, ev.data()), "reef_spartan_eval_matrices");
         return ev;
     }
+    // 3o: the same at many points in one call (one host wait; a matrix entry read once for two points): what a verifier of many proofs
+    // over one shape calls once its host chains have run.  Entry t is bit for bit eval_matrices(r_x[t], r_y[t]).
+    std::vector<std::array<reef_fe, 3>> eval_matrices_batch(const std::vector<std::vector<reef_fe>> &r_x,
+                                                            const std::vector<std::vector<reef_fe>> &r_y) const {
+        if (r_x.size() != r_y.size()) throw std::invalid_argument("eval_matrices_batch: one r_y per r_x");
+        const size_t m = r_x.size(), lx = outer_rounds(), ly = inner_rounds();
+        std::vector<reef_fe> xs, ys;
+        xs.reserve(m * lx);
+        ys.reserve(m * ly);
+        for (size_t t = 0; t < m; ++t) {
+            if (r_x[t].size() != lx || r_y[t].size() != ly) throw std::invalid_argument("eval_matrices_batch: r_x, r_y lengths");
+            xs.insert(xs.end(), r_x[t].begin(), r_x[t].end());
+            ys.insert(ys.end(), r_y[t].begin(), r_y[t].end());
+        }
+        std::vector<std::array<reef_fe, 3>> ev(m);
+        if (m) check(reef_spartan_eval_matrices_batch(nifs_.handle(), ncp_, nvp_, xs.data(), ys.data(), m, true, ev[0].data()),
+                     "reef_spartan_eval_matrices_batch");
+        return ev;
+    }
 
   private:
     Nifs<CURVE> &nifs_;

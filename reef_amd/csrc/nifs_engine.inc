@@ -30,6 +30,12 @@ template <int C> struct NifsCtx : DeviceCtx {   // ev: orders the key ctx's stre
     size_t open_n_small = 0;             // reef_spartan_open_set_small_key: the openings begun from now on move to a folded key at this length (0: never)
     struct EvalWs { DevBuf pts, ex, zy, partial, out; } evw;   // the verifier's matrix evaluations (3k): eq factors, eq(r_x) by row, the column
                                          // weights, block sums, results; empty until the first reef_spartan_eval_matrices
+    struct EvalBatchWs {                 // the same at many points (3o), its own buffers: the single call's workspace and launches stay as they are
+        DevBuf pts, tab, partial, part, out;   // every point's eq factors; the eq tables of one group (ex of its points, then zy); block sums by
+                                         // point; the long rows' segment sums by pair; 3 m results
+        size_t budget = 0;               // reef_nifs_set_eval_workspace: bytes of tab a call may use (0: the default)
+        size_t groups = 0, per_group = 0;   // the last batch (reef_spartan_eval_matrices_batch_last_info); groups == 0: none yet
+    } evb;
     u64 gen = 0;                         // bumped by every call that changes the matrices or the running instance (or commits T)
     DevBuf z1, z2, E, step, run, pts, stage, counters;   // step: the rows W2 and T of the step's commitments, run: W and E (commit_running),
                                          // both two rows of row_len() canonical integers with zero tails; pts: two points
@@ -52,6 +58,7 @@ template <int C> static void nifs_free(NifsCtx<C> *c) {
     spartan_release<C>(c->sp);
     for (DevBuf *b : {&c->z1, &c->z2, &c->E, &c->step, &c->run, &c->pts, &c->stage, &c->counters}) b->release();
     for (DevBuf *b : {&c->evw.pts, &c->evw.ex, &c->evw.zy, &c->evw.partial, &c->evw.out}) b->release();
+    for (DevBuf *b : {&c->evb.pts, &c->evb.tab, &c->evb.partial, &c->evb.part, &c->evb.out}) b->release();
     delete c;
 }
 

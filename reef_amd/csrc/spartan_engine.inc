@@ -2,7 +2,8 @@
 // proof_order.h (the SP_* phases and the call order, the opening's included) and ipa_engine.inc.
 // A prover-side state machine: begin -> outer_round x (ell_x - 1) -> outer_claims -> inner_begin -> inner_round x (ell_y - 1) ->
 // inner_claims, with ell_x = log2(num_cons_pad), ell_y = log2(2 num_vars_pad).  The running instance is read, never written.
-// Beside it, in no order and on no state of the prove: the verifier's matrix evaluations (3k: v_spartan_eval_matrices).
+// Beside it, in no order and on no state of the prove: the verifier's matrix evaluations (3k: v_spartan_eval_matrices; at many points in
+// one pass, 3o: v_spartan_eval_matrices_batch).
 namespace reef {
 
 template <int C> struct SpartanState {
@@ -337,9 +338,130 @@ static reef_status v_spartan_eval_matrices(void *impl, size_t num_cons_pad, size
     return REEF_OK;
 }
 
+// The same at m points in one pass (3o): every point's factors go up in one copy, the points are walked in groups of G whose eq tables fit
+// the workspace budget (c->evb), the groups follow each other on the stream, every group writes its results into one device array of 3 m
+// values, and that array comes back in one copy: one wait.  A group is four launches, six with long rows, however many points it holds
+// (spartan_kernels.inc: the point or the pair of points in blockIdx.y; a group of ONE point has no pair to share entries with and takes
+// the single call's row kernels in the same three places).  Its buffers are the batch's own: c->evw and c->rows.part, which the
+// single call and a prove use, are not touched.
+static constexpr size_t SP_BATCH_MAX = 4096;                    // 3m's limit on a batch
+static constexpr size_t SP_BATCH_BUDGET = (size_t)1 << 30;      // the default budget: a choice, not a measurement (3o)
+template <int C>
+static reef_status v_spartan_eval_matrices_batch(void *impl, size_t num_cons_pad, size_t num_vars_pad, const reef_fe *r_x, const reef_fe *r_y, size_t m,
+                                                 bool is_mont, reef_fe *evals) {
+    constexpr int F = NifsCtx<C>::F;
+    constexpr const char *name = "reef_spartan_eval_matrices_batch";
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    if (m == 0) return REEF_OK;
+    if (m > SP_BATCH_MAX) { set_error("%s: m = %zu points, at most %zu in one call", name, m, SP_BATCH_MAX); return REEF_ERR_ARG; }
+    if (!r_x || !r_y || !evals) { set_error("null argument"); return REEF_ERR_ARG; }
+    REEF_TRY(sp_check_pads(c, name, num_cons_pad, num_vars_pad));
+    const u32 ell_x = sp_log2(num_cons_pad), ell_y = sp_log2(2 * num_vars_pad), ell = ell_x + ell_y;
+    std::vector<fe256> f(m * 2 * ell);                        // per point {1 - p_j, p_j}: r_x's factors, then r_y's
+    {
+        std::vector<fe> p(ell);
+        char what[48];
+        for (size_t t = 0; t < m; ++t) {
+            snprintf(what, sizeof what, "point %zu's r_x", t);
+            REEF_TRY(fe_import_all<F>(r_x + t * ell_x, ell_x, is_mont, name, what, p.data()));
+            snprintf(what, sizeof what, "point %zu's r_y", t);
+            REEF_TRY(fe_import_all<F>(r_y + t * ell_y, ell_y, is_mont, name, what, p.data() + ell_x));
+            for (size_t j = 0; j < ell; ++j) {
+                f[2 * (t * ell + j)] = fe_to_table<F>(fe_sub<F, 2>(fe_one<F>(), p[j]));
+                f[2 * (t * ell + j) + 1] = fe_to_table<F>(p[j]);
+            }
+        }
+    }
+    DeviceCall call(c, OnExit::WAIT_AND_IDLE);
+    if (!c->has[0] || !c->has[1] || !c->has[2]) {
+        set_error("%s: set the matrices A, B and C first (reef_nifs_set_matrix)", name);
+        return REEF_ERR_ARG;
+    }
+    REEF_TRY(call.enter());
+    REEF_TRY(nifs_prepare(c));
+    auto &w = c->evb;
+    // groups: G points' tables inside the budget, an even number of them (whole pairs) when more than one; one point always goes
+    const size_t per_point = (c->num_cons + c->nz) * sizeof(fe256), budget = w.budget ? w.budget : SP_BATCH_BUDGET;
+    size_t G = std::max<size_t>(1, budget / per_point);
+    if (G > 1) G &= ~(size_t)1;
+    G = std::min(G, m);
+    const u32 nblocks = (u32)ceil_div(c->num_cons, SP_THREADS), nlong = c->rows.nlong, nseg = c->rows.nseg, rows = nblocks + nlong;
+    if (w.tab.cap > std::max(budget, per_point)) w.tab.release();   // a budget lowered since the workspace was made
+    REEF_TRY(w.tab.ensure_exact(G * per_point));
+    REEF_TRY(w.pts.ensure(f.size() * sizeof(fe256)));
+    REEF_TRY(w.partial.ensure(G * rows * 27 * sizeof(unsigned long long)));
+    REEF_TRY(w.part.ensure(std::max<size_t>(1, (G + 1) / 2 * nseg) * 6 * sizeof(fe_limbs)));
+    REEF_TRY(w.out.ensure(3 * m * sizeof(fe256)));
+    REEF_HIP_TRY(hipMemcpyAsync(w.pts.p, f.data(), f.size() * sizeof(fe256), hipMemcpyHostToDevice, c->stream));
+    NifsArgs a = nifs_args(c);
+    a.z1 = a.z2 = nullptr;                                    // the column tables come with the pair (SpBatch)
+    const u32 *seg_row = c->rows.seg_row.template as<u32>(), *seg_first = c->rows.seg_first.template as<u32>();
+    const int form = is_mont ? (int)SP_FORM_MONT : (int)SP_FORM_INTEGER;
+    size_t ngroups = 0;
+    for (size_t first = 0; first < m; first += G, ++ngroups) {
+        const u32 np = (u32)std::min(G, m - first), pairs = (np + 1) / 2;
+        SpBatch g;
+        g.f = w.pts.template as<fe256>() + first * 2 * ell;
+        g.ex = w.tab.template as<fe256>();
+        g.zy = g.ex + G * c->num_cons;
+        g.partial = w.partial.template as<unsigned long long>();
+        g.part = w.part.template as<fe_limbs>();
+        g.npts = np;
+        g.fstride = 2 * ell;
+        g.ell_x = ell_x;
+        g.ell_y = ell_y;
+        g.nz = (u32)c->nz;
+        g.rows = rows;
+        g.nseg = nseg;
+        hipLaunchKernelGGL(k_sp_eq_batch<F>, dim3(nblocks, np), dim3(256), 0, c->stream, g, (u32)c->num_cons);
+        hipLaunchKernelGGL(k_sp_eq_cols_batch<F>, dim3(ceil_div(c->nz, 256), np), dim3(256), 0, c->stream, g, (u32)c->num_vars,
+                           (u32)(num_vars_pad - c->num_vars));
+        if (np == 1) {                                        // a group of one: the single call's row kernels on the batch's buffers, launch for launch
+            NifsArgs a1 = a;
+            a1.z1 = a1.z2 = g.zy;
+            hipLaunchKernelGGL(k_sp_eval_short<F>, dim3(nblocks), dim3(SP_THREADS), 0, c->stream, a1, (const fe256 *)g.ex, g.partial);
+            if (nlong) {
+                hipLaunchKernelGGL((k_nifs_rows_long<F, NIFS_MODE_SPARTAN>), dim3(nseg), dim3(256), 0, c->stream, a1, seg_row, seg_first, g.part);
+                hipLaunchKernelGGL(k_sp_eval_long<F>, dim3(nlong), dim3(64), 0, c->stream, a1, seg_first, (const fe_limbs *)g.part, (const fe256 *)g.ex,
+                                   g.partial + (size_t)nblocks * 27);
+            }
+        } else {
+            hipLaunchKernelGGL(k_sp_eval_short_pair<F>, dim3(nblocks, pairs), dim3(SP_THREADS), 0, c->stream, a, g);
+            if (nlong) {
+                hipLaunchKernelGGL(k_sp_rows_long_pair<F>, dim3(nseg, pairs), dim3(256), 0, c->stream, a, seg_row, seg_first, g);
+                hipLaunchKernelGGL(k_sp_eval_long_pair<F>, dim3(nlong, pairs), dim3(64), 0, c->stream, a, seg_first, g);
+            }
+        }
+        hipLaunchKernelGGL(k_sp_finish_batch<F>, dim3(np), dim3(SP_THREADS), 0, c->stream, (const unsigned long long *)g.partial, rows, form,
+                           w.out.template as<fe256>() + 3 * first);
+        REEF_HIP_TRY(hipGetLastError());
+    }
+    REEF_HIP_TRY(hipMemcpyAsync(evals, w.out.p, 3 * m * sizeof(fe256), hipMemcpyDeviceToHost, c->stream));
+    REEF_HIP_TRY(hipStreamSynchronize(c->stream));             // the one wait; f goes out of scope
+    w.groups = ngroups;
+    w.per_group = G;
+    return REEF_OK;
+}
+template <int C> static reef_status v_spartan_set_eval_workspace(void *impl, size_t bytes) {
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->evb.budget = bytes;
+    return REEF_OK;
+}
+template <int C> static reef_status v_spartan_eval_batch_last_info(void *impl, size_t *groups, size_t *points_per_group, size_t *workspace_bytes) {
+    NifsCtx<C> *c = (NifsCtx<C> *)impl;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->evb.groups) { set_error("reef_spartan_eval_matrices_batch_last_info: no batch has run on this ctx"); return REEF_ERR_ARG; }
+    if (groups) *groups = c->evb.groups;
+    if (points_per_group) *points_per_group = c->evb.per_group;
+    if (workspace_bytes) *workspace_bytes = c->evb.tab.cap;
+    return REEF_OK;
+}
+
 template <int C> SpartanVTable make_spartan_vtable() {
     return SpartanVTable{v_spartan_begin<C>, v_spartan_outer_round<C>, v_spartan_outer_claims<C>, v_spartan_inner_begin<C>, v_spartan_inner_round<C>,
-                         v_spartan_inner_claims<C>, v_spartan_eval_matrices<C>};
+                         v_spartan_inner_claims<C>, v_spartan_eval_matrices<C>, v_spartan_eval_matrices_batch<C>, v_spartan_set_eval_workspace<C>,
+                         v_spartan_eval_batch_last_info<C>};
 }
 
 }  // namespace reef

@@ -9,6 +9,7 @@
 //   inner rounds sum ABC z at 0 and 2                                                              (k_sp_round<F, 0>)
 //   inner claims ABC(r_y), z(r_y): the last bind; eval_W = W . eq(r_y[1..])
 // and, for the verifier, without a prove (3k): A~, B~, C~ at (r_x, r_y) over the CSR      (k_sp_eq_cols, k_sp_eval_short, k_sp_eval_long)
+// and the same at many points in one pass (3o), two points a thread          (k_sp_eq_batch, k_sp_eq_cols_batch, k_sp_*_pair, k_sp_finish_batch)
 //
 // Tables hold the resident internal form, canonical and packed (fe_to_table), like the NIFS vectors.  Round sums are lazy: each
 // term is one product (< 2M, exact 29-bit limbs) whose limbs go into 64-bit column sums per thread, then per wave (DPP), per block
@@ -155,8 +156,7 @@ template <int F> __device__ __forceinline__ fe256 sp_out(const fe &x, int form) 
 // out[k] = the sum over nblocks blocks of value k (k < nv), in `form`.  One block: every thread adds its blocks' 9 nv slots, LDS
 // atomics add the threads; value k's limb sums (< 2^24 terms of < 2^29 each) are reduced once.
 template <int F>
-__global__ void __launch_bounds__(SP_THREADS) k_sp_finish(const unsigned long long *__restrict__ partial, u32 nblocks, u32 nv, int form,
-                                                          fe256 *__restrict__ out) {
+__device__ __forceinline__ void sp_finish_body(const unsigned long long *__restrict__ partial, u32 nblocks, u32 nv, int form, fe256 *__restrict__ out) {
     __shared__ unsigned long long tot[27];
     if (threadIdx.x < 27) tot[threadIdx.x] = 0;
     __syncthreads();
@@ -176,6 +176,11 @@ __global__ void __launch_bounds__(SP_THREADS) k_sp_finish(const unsigned long lo
 #pragma unroll
     for (int i = 0; i < 9; ++i) w.l[i] = tot[9 * threadIdx.x + i];
     store_fe256(out + threadIdx.x, sp_out<F>(fe_from_limb_sums<F>(w), form));
+}
+template <int F>
+__global__ void __launch_bounds__(SP_THREADS) k_sp_finish(const unsigned long long *__restrict__ partial, u32 nblocks, u32 nv, int form,
+                                                          fe256 *__restrict__ out) {
+    sp_finish_body<F>(partial, nblocks, nv, form, out);
 }
 
 // The last bind (two entries left): t[k][0] = t[k][0] + r (t[k][1] - t[k][0]) for k < nt, and out[k] = that value in `form`
@@ -245,6 +250,151 @@ __global__ void __launch_bounds__(64) k_sp_eval_long(NifsArgs a, const u32 *__re
 #pragma unroll
         for (int i = 0; i < 9; ++i) partial[(size_t)l * 27 + 9 * k + i] = p.l[i];
     }
+}
+
+// ---- the same at many points in one pass (include/reef_msm.h 3o).  A group of npts points has plain tables per point -- ex[t][row],
+// zy[t][col], partial[t][rows][27] -- and is walked two points a thread: pair q = blockIdx.y holds the points 2q and 2q + 1, and every
+// CSR entry, its class and its general coefficient are read once for both (nifs_dot<F, 1>, as a folding step reads them for z1 and
+// z2).  An odd last point is a pair with t1 = t0: the row kernels walk it with one vector (nifs_dot<F, 0>, a branch on blockIdx alone),
+// so it costs what the single call's row pass costs, and nothing is written for a second point.  Entries of the tables and every sum
+// are what the single call forms for the point alone: the results are bit-identical.  The launches of a group do not depend on npts.
+struct SpBatch {
+    const fe256 *f;              // eq factors of point t at f + t fstride: r_x's 2 ell_x, then r_y's 2 ell_y
+    fe256 *ex, *zy;              // ex + t num_cons, zy + t nz
+    unsigned long long *partial; // partial + t rows 27: a row per block of the row pass, then a row per long row
+    fe_limbs *part;              // the long rows' segment sums of pair q at part + q nseg 6 (k_nifs_rows_long's MODE_T layout)
+    u32 npts, fstride, ell_x, ell_y, nz, rows, nseg;
+};
+__device__ __forceinline__ u32 sp_pair_second(const SpBatch &g, u32 t0) { return t0 + 1 < g.npts ? t0 + 1 : t0; }
+
+// k_sp_eq and k_sp_eq_cols with the point in blockIdx.y (as k_mle_eq_batch beside k_mle_eq): the same sp_eq_at per entry
+template <int F>
+__global__ void __launch_bounds__(256) k_sp_eq_batch(SpBatch g, u32 n) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    if (i >= n) return;
+    store_fe256(g.ex + (size_t)t * n + i, sp_eq_at<F>(g.f + (size_t)t * g.fstride, g.ell_x, i));
+}
+template <int F>
+__global__ void __launch_bounds__(256) k_sp_eq_cols_batch(SpBatch g, u32 num_vars, u32 shift) {
+    const u32 c = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    if (c >= g.nz) return;
+    store_fe256(g.zy + (size_t)t * g.nz + c, sp_eq_at<F>(g.f + (size_t)t * g.fstride + 2 * g.ell_x, g.ell_y, c + (c >= num_vars ? shift : 0u)));
+}
+
+// k_sp_eval_short for the pair blockIdx.y: a row's three dot products with BOTH column tables from one walk over its entries, then the
+// six products with the pair's two ex[row], summed per point as sp_block_sums does.  The predicate-not-return rule holds as there; the
+// branch around the second block sum is on blockIdx alone, so whole blocks take it.
+// Bound, per point: as k_sp_eval_short's -- a thread adds one product (limbs < 2^29) to each of the point's 27 columns.
+template <int F>
+__global__ void __launch_bounds__(SP_THREADS) k_sp_eval_short_pair(NifsArgs a, SpBatch g) {
+    const u32 row = blockIdx.x * blockDim.x + threadIdx.x;
+    const u32 t0 = 2 * blockIdx.y, t1 = sp_pair_second(g, t0);
+    u64 acc[2][3][9];
+#pragma unroll
+    for (int v = 0; v < 2; ++v)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int i = 0; i < 9; ++i) acc[v][k][i] = 0;
+    u32 b[3] = {0, 0, 0}, e[3] = {0, 0, 0};
+    if (row < a.num_cons) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { b[k] = a.m[k].rowptr[row]; e[k] = a.m[k].rowptr[row + 1]; }
+    }
+    const u32 len = (e[0] - b[0]) + (e[1] - b[1]) + (e[2] - b[2]);
+    if (len != 0 && len <= NIFS_LONG_ROW) {                 // a predicate, not a return
+        const fe k254 = fe_from_table(a.k254);
+        const fe256 *z1 = g.zy + (size_t)t0 * g.nz, *z2 = g.zy + (size_t)t1 * g.nz;
+        const fe w0 = fe_from_table(load_fe256(g.ex + (size_t)t0 * a.num_cons + row));
+        const fe w1 = fe_from_table(load_fe256(g.ex + (size_t)t1 * a.num_cons + row));
+        if (t1 != t0) {                                     // on blockIdx alone: whole blocks go one way
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                fe d[2];
+                nifs_dot<F, 1>(a.m[k], b[k], e[k], 1, z1, z2, k254, d);
+                sp_acc(acc[0][k], fe_mul<F>(w0, d[0]));
+                sp_acc(acc[1][k], fe_mul<F>(w1, d[1]));
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                fe d;
+                nifs_dot<F, 0>(a.m[k], b[k], e[k], 1, z1, z1, k254, &d);
+                sp_acc(acc[0][k], fe_mul<F>(w0, d));
+            }
+        }
+    }
+    sp_block_sums<3>(acc[0], g.partial + (size_t)t0 * g.rows * 27);
+    if (t1 != t0) sp_block_sums<3>(acc[1], g.partial + (size_t)t1 * g.rows * 27);
+}
+// The long rows' segment pass for the pair blockIdx.y: k_nifs_rows_long<F, NIFS_MODE_T> on the pair's column tables, six sums a segment
+// (d[2 k + v]: matrix k, point v) into the pair's own slice of part.  Its text is that kernel's, not a body shared with it: behind a shared
+// __device__ function k_nifs_rows_long compiled to ten more SGPRs, and it is a kernel of every folding step.
+template <int F>
+__global__ void __launch_bounds__(256) k_sp_rows_long_pair(NifsArgs a, const u32 *__restrict__ seg_row, const u32 *__restrict__ seg_first, SpBatch g) {
+    __shared__ fe_limbs wsum[4][6];
+    const u32 t0 = 2 * blockIdx.y, t1 = sp_pair_second(g, t0);
+    const fe256 *z1 = g.zy + (size_t)t0 * g.nz, *z2 = g.zy + (size_t)t1 * g.nz;
+    fe_limbs *part = g.part + (size_t)blockIdx.y * g.nseg * 6;
+    const u32 l = seg_row[blockIdx.x], row = a.long_rows[l], seg = blockIdx.x - seg_first[l];
+    const u32 lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    const fe k254 = fe_from_table(a.k254);
+    fe d[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const u32 b = a.m[k].rowptr[row], e = a.m[k].rowptr[row + 1];
+        const u32 sb = min(e, b + seg * NIFS_SEG), se = min(e, sb + NIFS_SEG);
+        if (t1 != t0) nifs_dot<F, 1>(a.m[k], sb + threadIdx.x, se, blockDim.x, z1, z2, k254, d + 2 * k);
+        else {                                              // the odd last point: one vector, its twin's sums are zero and are not read
+            nifs_dot<F, 0>(a.m[k], sb + threadIdx.x, se, blockDim.x, z1, z1, k254, d + 2 * k);
+            d[2 * k + 1] = fe_zero();
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        nifs_wave_sum<F>(d[j]);
+        if (lane == 0) wsum[wave][j] = fe_to_limbs(d[j]);
+    }
+    __syncthreads();
+    if (threadIdx.x >= 6) return;
+    fe v = fe_from_limbs(wsum[0][threadIdx.x], 1.0);
+    for (int w = 1; w < (int)(blockDim.x / WAVE); ++w) v = fe_canon<F>(fe_add<F>(v, fe_from_limbs(wsum[w][threadIdx.x], 1.0)));
+    part[(size_t)blockIdx.x * 6 + threadIdx.x] = fe_to_limbs(v);
+}
+// k_sp_eval_long for the pair blockIdx.y: the six sums of long row l (d[2 k + v]: matrix k, point v of the pair), times each point's
+// eq(r_x)[row], as row (rows - nlong) + l of each point's partial
+template <int F>
+__global__ void __launch_bounds__(64) k_sp_eval_long_pair(NifsArgs a, const u32 *__restrict__ seg_first, SpBatch g) {
+    const u32 l = blockIdx.x, row = a.long_rows[l];
+    const u32 t0 = 2 * blockIdx.y, t1 = sp_pair_second(g, t0);
+    const u32 s0 = seg_first[l], s1 = seg_first[l + 1];
+    const fe_limbs *part = g.part + (size_t)blockIdx.y * g.nseg * 6;
+    fe d[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        d[j] = fe_zero();
+        for (u32 s = s0 + threadIdx.x; s < s1; s += WAVE) d[j] = fe_canon<F>(fe_add<F>(d[j], fe_from_limbs(part[(size_t)s * 6 + j], 1.0)));
+        nifs_wave_sum<F>(d[j]);
+    }
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+        const u32 t = v ? t1 : t0;
+        if (v && t1 == t0) continue;
+        const fe w = fe_from_table(load_fe256(g.ex + (size_t)t * a.num_cons + row));
+        unsigned long long *dst = g.partial + ((size_t)t * g.rows + (g.rows - a.nlong) + l) * 27;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const fe p = fe_mul<F>(w, d[2 * k + v]);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) dst[9 * k + i] = p.l[i];
+        }
+    }
+}
+// k_sp_finish with one block per point of the group: out[3 t ..] = the three sums of point t's partial, in `form`
+template <int F>
+__global__ void __launch_bounds__(SP_THREADS) k_sp_finish_batch(const unsigned long long *__restrict__ partial, u32 rows, int form, fe256 *__restrict__ out) {
+    sp_finish_body<F>(partial + (size_t)blockIdx.x * rows * 27, rows, 3u, form, out + 3 * (size_t)blockIdx.x);
 }
 
 }  // namespace reef

@@ -113,3 +113,15 @@ class Nifs(_Handle):
         v, f = ctypes.c_uint64(), ctypes.c_uint64()
         check(self._lib.reef_nifs_check_relaxed(self._h, ctypes.byref(v), ctypes.byref(f)))
         return v.value, (None if v.value == 0 else f.value)
+
+    def set_eval_workspace(self, nbytes: int) -> None:
+        """The budget of the eq tables a `verify.matrix_evals_batch` call may hold (reef_nifs_set_eval_workspace): the batch walks its
+        points in groups whose tables fit it.  0: the default of 1 GiB.  A budget below one point's tables gives groups of one."""
+        check(self._lib.reef_nifs_set_eval_workspace(self._h, nbytes))
+
+    def eval_batch_last_info(self) -> dict:
+        """How the last `verify.matrix_evals_batch` on this ctx divided (reef_spartan_eval_matrices_batch_last_info): "groups",
+        "points_per_group" and "workspace_bytes" (the tables' buffer as it stands).  ReefError when there was no batch."""
+        g, k, b = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+        check(self._lib.reef_spartan_eval_matrices_batch_last_info(self._h, ctypes.byref(g), ctypes.byref(k), ctypes.byref(b)))
+        return {"groups": g.value, "points_per_group": k.value, "workspace_bytes": b.value}

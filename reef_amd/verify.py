@@ -21,6 +21,8 @@ its rows; the batch makes one call per vk and takes the transcript's encodings f
 `matrix_evals` is reef_spartan_eval_matrices: A~, B~, C~ at (r_x, r_y) on the matrices a `Nifs` holds, no witness needed.
 `verify_sumchecks` is the verifier of 3g's transcript -- RelaxedR1CSSNARK::verify [R] up to the opening: O(log n) host arithmetic and that
 one device call -- and `verify_snark` adds `verify_opening` with eval_E = claims_outer[3], eval_W = claims_inner[2].
+`matrix_evals_batch` is reef_spartan_eval_matrices_batch (3o): the same three values at many points in one call, and
+`verify_sumchecks_batch` verifies many proofs over one shape with one such call.
 """
 from __future__ import annotations
 
@@ -426,6 +428,34 @@ def matrix_evals(nifs: Nifs, num_cons_pad: int, num_vars_pad: int, r_x: Sequence
     return _ints(out)
 
 
+def matrix_evals_batch(nifs: Nifs, num_cons_pad: int, num_vars_pad: int, points: Sequence[Sequence[Sequence[int]]], *,
+                       is_mont: bool = False) -> List[List[int]]:
+    """reef_spartan_eval_matrices_batch (3o): [A~, B~, C~] at every (r_x, r_y) of `points` in one call -- one host wait, a matrix entry
+    read once for two points.  Entry t is bit for bit `matrix_evals` at points[t].  An empty list makes no call."""
+    m = len(points)
+    if any(len(pt) != 2 for pt in points):
+        raise ValueError("a point is a pair (r_x, r_y)")
+    if m == 0:
+        return []
+    lx, ly = len(points[0][0]), len(points[0][1])
+    for t, (r_x, r_y) in enumerate(points):
+        if len(r_x) != lx or len(r_y) != ly:
+            raise ValueError(f"point {t} has {len(r_x)} and {len(r_y)} entries, point 0 has {lx} and {ly}")
+
+    def pow2(n):
+        return n >= 2 and n & (n - 1) == 0
+    if pow2(num_cons_pad) and pow2(num_vars_pad) and (lx != _rounds(num_cons_pad) or ly != _rounds(2 * num_vars_pad)):
+        raise ValueError(f"pads ({num_cons_pad}, {num_vars_pad}) take {_rounds(num_cons_pad)} and {_rounds(2 * num_vars_pad)} point entries: "
+                         f"r_x and r_y have {lx}, {ly}")
+    xa = _arr([x for r_x, _ in points for x in r_x]) if lx else np.zeros((1, 4), np.uint64)   # illegal pads: the library says what is wrong
+    ya = _arr([y for _, r_y in points for y in r_y]) if ly else np.zeros((1, 4), np.uint64)
+    out = np.zeros((3 * m, 4), dtype=np.uint64)
+    check(nifs._lib.reef_spartan_eval_matrices_batch(nifs._h, num_cons_pad, num_vars_pad, xa.ctypes.data, ya.ctypes.data, m, bool(is_mont),
+                                                     out.ctypes.data))
+    flat = _ints(out)
+    return [flat[3 * t:3 * t + 3] for t in range(m)]
+
+
 def _interp(ys: Sequence[int], r: int, p: int) -> int:
     """the polynomial through (0, ys[0]), (1, ys[1]), ... at r"""
     out = 0
@@ -447,13 +477,14 @@ def _eq_entry(point: Sequence[int], i: int, p: int) -> int:
     return out
 
 
-def _sumchecks(nifs, num_cons_pad, num_vars_pad, u, X, proof, challenge, p, evals_fn):
+def _sumchecks_host(num_cons_pad, num_vars_pad, u, X, proof, challenge, p):
+    """The host part of `_sumchecks`, up to the matrix evaluations: (ok, r_x, r_y, what `_sumchecks_final` needs)."""
     ell_x, ell_y = _rounds(num_cons_pad), _rounds(2 * num_vars_pad)
     outer, inner, co, ci = proof["outer"], proof["inner"], list(proof["claims_outer"]), list(proof["claims_inner"])
     if len(outer) != ell_x or len(inner) != ell_y or len(co) != 4 or len(ci) != 3 or 1 + len(X) > num_vars_pad:
-        return False, [], []
+        return False, [], [], None
     if any(len(ev) != 3 for ev in outer) or any(len(ev) != 2 for ev in inner):
-        return False, [], []
+        return False, [], [], None
     tau = [challenge("t", []) for _ in range(ell_x)]
     claim, r_x = 0, []
     for e0, e2, e3 in outer:
@@ -472,13 +503,26 @@ def _sumchecks(nifs, num_cons_pad, num_vars_pad, u, X, proof, challenge, p, eval
     for name, drawn in (("tau", tau), ("r_x", r_x), ("r", r), ("r_y", r_y)):         # a transcript that records its challenges must agree
         ok = ok and (name not in proof or proof[name] == drawn)
     if not ok:
-        return False, r_x, r_y
+        return False, r_x, r_y, None
     eval_w = ci[2] % p
     eval_x = sum(_eq_entry(r_y[1:], j, p) * v for j, v in enumerate([u] + list(X))) % p
     z_ry = ((1 - r_y[0]) * eval_w + r_y[0] * eval_x) % p
-    ea, eb, ec = (evals_fn or matrix_evals)(nifs, num_cons_pad, num_vars_pad, r_x, r_y)
+    return True, r_x, r_y, (claim, r, z_ry, ci)
+
+
+def _sumchecks_final(rest, evals: Sequence[int], p: int) -> bool:
+    """The final comparisons of `_sumchecks` on [A~, B~, C~] at the proof's (r_x, r_y)."""
+    claim, r, z_ry, ci = rest
+    ea, eb, ec = evals
     abc = (ea + r * eb + r * r * ec) % p
-    return claim == abc * z_ry % p and ci[0] == abc and ci[1] == z_ry, r_x, r_y
+    return claim == abc * z_ry % p and ci[0] == abc and ci[1] == z_ry
+
+
+def _sumchecks(nifs, num_cons_pad, num_vars_pad, u, X, proof, challenge, p, evals_fn):
+    ok, r_x, r_y, rest = _sumchecks_host(num_cons_pad, num_vars_pad, u, X, proof, challenge, p)
+    if not ok:
+        return False, r_x, r_y
+    return _sumchecks_final(rest, (evals_fn or matrix_evals)(nifs, num_cons_pad, num_vars_pad, r_x, r_y), p), r_x, r_y
 
 
 def verify_sumchecks(nifs: Optional[Nifs], num_cons_pad: int, num_vars_pad: int, u: int, X: Sequence[int], proof: dict,
@@ -493,6 +537,25 @@ def verify_sumchecks(nifs: Optional[Nifs], num_cons_pad: int, num_vars_pad: int,
     evals_fn(nifs, num_cons_pad, num_vars_pad, r_x, r_y) stands in for the device call (tests).  Canonical ints; False, never an
     exception, for a transcript that does not verify."""
     return _sumchecks(nifs, num_cons_pad, num_vars_pad, u % p, [x % p for x in X], proof, challenge, p, evals_fn)[0]
+
+
+def verify_sumchecks_batch(nifs: Optional[Nifs], num_cons_pad: int, num_vars_pad: int, instances: Sequence[dict], p: int, *,
+                           evals_fn=None) -> List[bool]:
+    """`verify_sumchecks` for many proofs over one shape: a bool per instance.  instances: dicts with "u", "X", "proof" and "challenge"
+    (each proof's own transcript).  The host part runs per proof; ONE `matrix_evals_batch` call then covers the proofs whose host
+    checks passed (none is made when none passed), and the final comparisons run per proof.
+    evals_fn(nifs, num_cons_pad, num_vars_pad, points) stands in for the device call (tests)."""
+    out, live, points = [False] * len(instances), [], []
+    for i, it in enumerate(instances):
+        ok, r_x, r_y, rest = _sumchecks_host(num_cons_pad, num_vars_pad, it["u"] % p, [x % p for x in it["X"]], it["proof"], it["challenge"], p)
+        if ok:
+            live.append((i, rest))
+            points.append((r_x, r_y))
+    if live:
+        evals = (evals_fn or matrix_evals_batch)(nifs, num_cons_pad, num_vars_pad, points)
+        for (i, rest), ev in zip(live, evals):
+            out[i] = _sumchecks_final(rest, ev, p)
+    return out
 
 
 def verify_snark(nifs: Optional[Nifs], key: MsmContext, gens_s, comm_e, comm_w, num_cons_pad: int, num_vars_pad: int, u: int, X: Sequence[int],
