@@ -9,15 +9,12 @@ Every test but the last (pure Python: the extreme values are what they claim) ne
 
 import pytest
 
+from merkle_drivers import table_max
 from oracle import mle_oracle
 from oracle.pasta_oracle import CURVES, P, Q
 from oracle.sumcheck_oracle import gen_eq_table, linear_mle_coeffs, linear_mle_fold
 
 R256 = 1 << 256
-
-
-def table_max(mod):
-    return ((1 << 254) - 1) * pow(2, -261, mod) % mod
 
 
 def values(kind, mod, n):

@@ -1,8 +1,6 @@
 """The resident Poseidon Merkle tree on the GPU (include/reef_msm.h 3d: reef_merkle_create / _info / _open / _read_level / _check_paths)
 against the oracle, bit for bit: the stand-in constants of oracle.merkle_oracle, canonical integers on Pallas's scalar field and the pasta
-Montgomery form on Vesta's.  The oracle's trees are computed once per (field, size) and shared."""
-import ctypes
-import functools
+Montgomery form on Vesta's.  The oracle's trees are computed once per (field, size) and shared (tests/merkle_drivers.py)."""
 import json
 import os
 import subprocess
@@ -10,109 +8,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from merkle_drivers import FIELDS, Raw, expected_open, limbs, oracle_tree, params, path_alterations
 from oracle import merkle_oracle as M
 
 pytestmark = pytest.mark.gpu
-
-FIELDS = {"pallas": (M.Q, False), "vesta": (M.P, True)}      # curve -> (its scalar field, the form the test hands field elements over in)
-R = 1 << 256
-
-
-@functools.lru_cache(maxsize=None)
-def params(curve):
-    return M.standin_params(FIELDS[curve][0])
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_tree(curve, n, mul=31, add=7):
-    doc = [(mul * i + add) % 131 for i in range(n)]
-    root, tree = M.commit(doc, params(curve))
-    return doc, root, tree
-
-
-def limbs(x):
-    return [(x >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
-
-
-class Raw:
-    """The C ABI itself, field elements in either form: Python integers in and out, converted here (x * 2^256 mod m is the Montgomery form)."""
-
-    def __init__(self, curve, doc, device=0):
-        from reef_amd import _ffi, merkle, msm
-        self.lib, self.m, self.mont = _ffi.load(), FIELDS[curve][0], FIELDS[curve][1]
-        self.rinv = pow(R, -1, self.m)
-        p = params(curve)
-        self._rc, self._mds = self.fe_array(p.rc), self.fe_array([x for row in p.mds for x in row])
-        pp = merkle.PoseidonParams(p.t, p.rf, p.rp, 0, self._rc.ctypes.data, self._mds.ctypes.data, (ctypes.c_uint64 * 4)(*limbs(self.to_form(p.tag_leaf))),
-                                   (ctypes.c_uint64 * 4)(*limbs(self.to_form(p.tag_node))))
-        d = np.ascontiguousarray(np.asarray(doc, dtype=np.uint32))
-        self.h = ctypes.c_void_p()
-        _ffi.check(self.lib.reef_merkle_create(ctypes.byref(self.h), msm.curve_id(curve), ctypes.byref(pp), d.ctypes.data, d.shape[0], 0, self.mont, device))
-        n, lv, nodes = ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
-        root = np.zeros((1, 4), dtype=np.uint64)
-        _ffi.check(self.lib.reef_merkle_info(self.h, ctypes.byref(n), ctypes.byref(lv), ctypes.byref(nodes), root.ctypes.data))
-        self.n, self.levels, self.nodes, self.root = n.value, lv.value, nodes.value, self.ints(root)[0]
-
-    def to_form(self, x):
-        return x * R % self.m if self.mont else x
-
-    def fe_array(self, xs):
-        return np.array([limbs(self.to_form(x)) for x in xs], dtype=np.uint64).reshape(-1, 4)
-
-    def ints(self, arr):
-        out = [int(r[0]) | int(r[1]) << 64 | int(r[2]) << 128 | int(r[3]) << 192 for r in arr]
-        return [x * self.rinv % self.m for x in out] if self.mont else out
-
-    def open(self, idx, want_sym=True, want_oidx=True, want_path=True, fill=0):
-        """-> (status, symbols, opposite_idx, opposite ints, path ints); outputs start as `fill` so that an untouched one shows"""
-        idx = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64))
-        k, L = idx.shape[0], self.levels
-        sym = np.full(max(k, 1), fill, dtype=np.uint32)
-        oidx = np.full(max(k, 1), fill, dtype=np.uint64)
-        opp = np.full((max(k * L, 1), 4), fill, dtype=np.uint64)
-        path = np.full((max(k * L, 1), 4), fill, dtype=np.uint64)
-        st = self.lib.reef_merkle_open(self.h, idx.ctypes.data, k, sym.ctypes.data if want_sym else None, oidx.ctypes.data if want_oidx else None, opp.ctypes.data,
-                                       path.ctypes.data if want_path else None)
-        self.raw_out = (sym, oidx, opp, path)
-        return st, sym[:k].tolist(), oidx[:k].tolist(), self.ints(opp[:k * L]), self.ints(path[:k * L])
-
-    def read_level(self, level, first, count):
-        out = np.zeros((max(count, 1), 4), dtype=np.uint64)
-        st = self.lib.reef_merkle_read_level(self.h, level, first, count, out.ctypes.data, 0)
-        return st, self.ints(out[:count])
-
-    def check_paths(self, idx, sym, oidx, opp, raw_opp=None):
-        idx = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64))
-        sym = np.ascontiguousarray(np.asarray(sym, dtype=np.uint32))
-        oidx = np.ascontiguousarray(np.asarray(oidx, dtype=np.uint64))
-        o = raw_opp if raw_opp is not None else self.fe_array(opp)
-        accept = np.full(max(idx.shape[0], 1), 7, dtype=np.uint32)
-        st = self.lib.reef_merkle_check_paths(self.h, idx.ctypes.data, sym.ctypes.data, oidx.ctypes.data, o.ctypes.data, idx.shape[0], accept.ctypes.data)
-        return st, accept[:idx.shape[0]].tolist()
-
-    def error(self):
-        return self.lib.reef_last_error().decode()
-
-    def close(self):
-        if self.h:
-            self.lib.reef_merkle_destroy(self.h)
-            self.h = None
-
-
-def expected_open(doc, tree, idx):
-    """reef_merkle_open's arrays from the oracle's tree: (symbols, opposite_idx, opposite, path), the last two query-major."""
-    n, L = len(doc), len(tree)
-    sym, oidx, opp, path = [], [], [], []
-    for q in idx:
-        sib = q ^ 1
-        sym.append(doc[q])
-        oidx.append(sib if sib < n else 0)
-        opp.append(doc[sib] if sib < n else 0)
-        for h in range(L - 1):
-            s = (q >> (h + 1)) ^ 1
-            opp.append(tree[h][s] if s < len(tree[h]) else 0)
-        path += [tree[h][q >> (h + 1)] for h in range(L)]
-    return sym, oidx, opp, path
 
 
 @pytest.mark.parametrize("curve", ["pallas", "vesta"])
@@ -187,8 +86,8 @@ def test_open_order_and_shape(gpu_lib):
 
 def alterations(L):
     """(name, depth) of the fields of one opening that the check must notice: the issue's list, the depths deduplicated for short trees"""
-    out = [("symbols", None), ("opposite_idx", None), ("idx_bit0", None)]
-    return out + [("opposite", d) for d in sorted({0, L // 2, L - 1})]
+    out = path_alterations(L)                                               # the symbol, the sibling's index, the sibling at three depths
+    return out[:2] + [("idx_bit0", None)] + out[2:]
 
 
 @pytest.mark.parametrize("curve", ["pallas", "vesta"])
@@ -236,13 +135,15 @@ def test_recomputing_the_root_from_openings(n, curve, gpu_lib):
         t.close()
 
 
-def test_the_thread_per_path_form_of_the_check(gpu_lib):
-    """More paths than the five-lane form takes (POS_SPREAD_MAX_NODES = 16384, merkle_kernels.inc): 16385 paths of depth 3."""
+@pytest.mark.parametrize("curve", ["pallas", "vesta"])
+def test_the_thread_per_path_form_of_the_check(curve, gpu_lib):
+    """More paths than the five-lane form takes (POS_SPREAD_MAX_NODES = 16384, merkle_kernels.inc): 16385 paths of depth 3.  On Vesta the claimed
+    siblings cross in Montgomery form."""
     n, k = 8, 16385
-    doc, root, tree = oracle_tree("pallas", n)
+    doc, root, tree = oracle_tree(curve, n)
     L = len(tree)
     assert L == 3
-    t = Raw("pallas", doc)
+    t = Raw(curve, doc)
     try:
         idx = [(3 * j + 1) % n for j in range(k)]
         sym, oidx, opp, _ = expected_open(doc, tree, idx)
@@ -250,7 +151,7 @@ def test_the_thread_per_path_form_of_the_check(gpu_lib):
         assert st == 0 and accept == [1] * k, t.error()
         for victim, slot in ((k // 2, 1), (k - 1, 2), (0, 0)):
             p2 = list(opp)
-            p2[victim * L + slot] = (p2[victim * L + slot] + 1) % M.Q
+            p2[victim * L + slot] = (p2[victim * L + slot] + 1) % FIELDS[curve][0]
             st, accept = t.check_paths(idx, sym, oidx, p2)
             assert st == 0 and accept.count(0) == 1 and accept[victim] == 0, (victim, slot)
         s2 = list(sym)
