@@ -44,6 +44,8 @@
  *      (reef_hyrax_vk_create, reef_hyrax_vk_destroy, reef_hyrax_vk_comm_lz, section 3n).
  *      Later, still 7 (symbols added, none changed): the verifier's matrix evaluations at many points in one pass
  *      (reef_spartan_eval_matrices_batch, reef_nifs_set_eval_workspace, reef_spartan_eval_matrices_batch_last_info, section 3o).
+ *      Later, still 7 (symbols added, none changed): the Hyrax consistency arguments of many proofs over one resident document in
+ *      lock-step (reef_hyrax_batch_*, section 3p).
  *   6  round 6: the drop-in symbols build a returning key's resident copy on a builder thread (no call pays for it: reef_key_cache_wait,
  *      reef_key_cache_stats.spares in place of .reserved); REEF_SC_FENCE defaults to the release-ordered ticket; device groups report where a
  *      call's time went (reef_msm_group_enable_timing / _last_timing) and take REEF_SCALARS_FANOUT (reef_msm_group_opts.scalars, was reserved[0]).
@@ -747,6 +749,51 @@ reef_status reef_hyrax_finish(reef_hyrax_ctx *ctx, const reef_fe *r_last, bool i
 reef_status reef_hyrax_read(reef_hyrax_ctx *ctx, int which, size_t count, reef_fe *out, bool to_mont);
 /* The same switch as reef_spartan_open_set_small_key for the arguments begun (reef_hyrax_eval_begin) after the call. */
 reef_status reef_hyrax_set_small_key(reef_hyrax_ctx *ctx, size_t n_small);
+
+/* ---------------------------------------------------------------------------------------------
+ * (3p) The Hyrax consistency arguments (3i) of many proofs over ONE resident document, advanced in lock-step: a prover that keeps a
+ * committed document resident and proves m regexes over it runs m arguments whose rounds are independent given their own challenges.
+ * A batch advances all of them one round per call, with one host wait per call for the whole batch: the folds of all proofs are one
+ * launch (the proof index in the grid), the 2 m cross terms L_i, R_i one pass of the row pipeline (reef_msm_rows' route for the key's
+ * kind, rows = 2 m over the original key), the blind terms one launch.
+ *
+ * Proof i of a batch is, output for output, what 3i returns for points[i] alone with the same q, h, blinds and challenges: evals,
+ * lz_blinds, a_hat, b_hat and read bit for bit, L and R as points (their 32-byte encodings).  All conventions are 3i's.
+ *
+ * reef_hyrax_batch_create      borrows doc's resident document -- z, the row blinds, the factoring, the device -- and copies none of
+ *                              it: doc must outlive the batch.  The batch keeps buffers of its own (a and b as m_max x 2^right
+ *                              entries, the expanded scalars, the block sums, the per-proof tables; they only grow) and never touches
+ *                              doc's single-argument state: an argument in flight through reef_hyrax_* on the same ctx continues bit
+ *                              for bit, reef_hyrax_commit stays legal at any time, and calls on a batch and on its doc serialise.
+ *                              REEF_ERR_ARG: m_max > 4096; m_max 2^right > 2^24 entries (the message names both numbers).
+ * reef_hyrax_batch_eval_begin  points: m x num_vars entries, point after point; key as reef_hyrax_eval_begin takes it (same curve and
+ *                              device, exactly 2^right points, any kind, no window split).  evals[i] = <LZ_i, R_i>, lz_blinds[i] =
+ *                              sum_j L_ij blind_j (either may be NULL).  One upload, the document pass of one point after the other
+ *                              on the stream, one wait.  May come at any time: it starts the batch over, with any m <= m_max.
+ * reef_hyrax_batch_ipa_begin   q: one point per proof (each proof's own transcript challenge); h: ONE point for the whole batch (the
+ *                              key's blinding generator) or NULL; with h, blinds holds 2 m entries (blinds[2 i], blinds[2 i + 1]:
+ *                              proof i's for L and R), here and in every round call (NULL there: zeros).  L[i], R[i]: round 0's.
+ * reef_hyrax_batch_ipa_round   r: one non-zero challenge per proof; exactly right - 1 calls.
+ * reef_hyrax_batch_finish      the last fold with r_last[i]; a_hat[i] = a_i[0], b_hat[i] = b_i[0] (b_hat may be NULL).
+ * reef_hyrax_batch_read        which: 0 a, 1 b of proof `proof` as they stand; the first `count` to the host.  From eval_begin on.
+ *
+ * m = 0: REEF_OK with no device work and nothing written.  REEF_ERR_ARG writes nothing, leaves the batch usable and names the proof
+ * index where there is one: everything 3i rejects, per proof; m > m_max; a key of another curve, device or length; a window split on
+ * the key; h without blinds.  A call out of order is REEF_ERR_ARG naming the next call, and changes nothing.
+ * Out of scope: the folded small key (reef_hyrax_set_small_key: folded keys differ per proof); comm_LZ of the batch (the prover holds
+ * the rows: reef_hyrax_vk_comm_lz serves it); points, q or challenges in device memory; batches over several documents or devices. */
+typedef struct reef_hyrax_batch reef_hyrax_batch;
+reef_status reef_hyrax_batch_create(reef_hyrax_batch **out, reef_hyrax_ctx *doc, size_t m_max);
+void reef_hyrax_batch_destroy(reef_hyrax_batch *b);
+reef_status reef_hyrax_batch_eval_begin(reef_hyrax_batch *b, reef_msm_ctx *key, const reef_fe *points /* m x num_vars */, size_t m, bool is_mont,
+                                        reef_fe *evals /* m */, reef_fe *lz_blinds /* m, may be NULL */);
+reef_status reef_hyrax_batch_ipa_begin(reef_hyrax_batch *b, const reef_affine *q /* m */, const reef_affine *h /* one, may be NULL */,
+                                       const reef_fe *blinds /* 2 m, with h */, bool is_mont, reef_jacobian *L /* m */, reef_jacobian *R /* m */);
+reef_status reef_hyrax_batch_ipa_round(reef_hyrax_batch *b, const reef_fe *r /* m */, const reef_fe *blinds /* 2 m or NULL */, bool is_mont,
+                                       reef_jacobian *L /* m */, reef_jacobian *R /* m */);
+reef_status reef_hyrax_batch_finish(reef_hyrax_batch *b, const reef_fe *r_last /* m */, bool is_mont, reef_fe *a_hat /* m */,
+                                    reef_fe *b_hat /* m, may be NULL */);
+reef_status reef_hyrax_batch_read(reef_hyrax_batch *b, size_t proof, int which, size_t count, reef_fe *out, bool to_mont);
 
 /* ---------------------------------------------------------------------------------------------
  * (3j) The verifier's half of an inner-product argument: the check EE::verify_batch ends CompressedSNARK::verify with [R] and

@@ -223,6 +223,13 @@ def _bind(path: str) -> ctypes.CDLL:
         "reef_hyrax_ipa_round": (c_int, [vp, vp, vp, c_bool, vp, vp]),
         "reef_hyrax_finish": (c_int, [vp, vp, c_bool, vp, vp]),
         "reef_hyrax_read": (c_int, [vp, c_int, c_size_t, vp, c_bool]),
+        "reef_hyrax_batch_create": (c_int, [POINTER(vp), vp, c_size_t]),
+        "reef_hyrax_batch_destroy": (None, [vp]),
+        "reef_hyrax_batch_eval_begin": (c_int, [vp, vp, vp, c_size_t, c_bool, vp, vp]),
+        "reef_hyrax_batch_ipa_begin": (c_int, [vp, vp, vp, vp, c_bool, vp, vp]),
+        "reef_hyrax_batch_ipa_round": (c_int, [vp, vp, vp, c_bool, vp, vp]),
+        "reef_hyrax_batch_finish": (c_int, [vp, vp, c_bool, vp, vp]),
+        "reef_hyrax_batch_read": (c_int, [vp, c_size_t, c_int, c_size_t, vp, c_bool]),
         "reef_hyrax_vk_create": (c_int, [POINTER(vp), c_int, vp, c_size_t, c_int, c_int, POINTER(MsmOpts)]),
         "reef_hyrax_vk_destroy": (None, [vp]),
         "reef_hyrax_vk_comm_lz": (c_int, [vp, vp, c_size_t, c_bool, vp, vp]),

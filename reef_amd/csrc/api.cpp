@@ -170,6 +170,7 @@ struct reef_sc_ctx : reef_handle {};
 struct reef_nifs_ctx : reef_handle {};     // rows N6 and N5 and the opening (3f-3h) share it
 struct reef_hyrax_ctx : reef_handle {};
 struct reef_hyrax_vk : reef_handle {};
+struct reef_hyrax_batch : reef_handle {};
 struct reef_merkle_ctx : reef_handle {};
 
 // The table of a curve's entry points, one per row (common.h); NULL with the error set for a curve that does not exist.
@@ -183,6 +184,7 @@ template <class VT> static const VT *table(int curve) {
     else if constexpr (std::is_same<VT, IpaCheckVTable>::value) return p ? pallas_ipa_check_vtable() : vesta_ipa_check_vtable();
     else if constexpr (std::is_same<VT, MerkleVTable>::value) return p ? pallas_merkle_vtable() : vesta_merkle_vtable();
     else if constexpr (std::is_same<VT, HyraxVkVTable>::value) return p ? pallas_hyrax_vk_vtable() : vesta_hyrax_vk_vtable();
+    else if constexpr (std::is_same<VT, HyraxBatchVTable>::value) return p ? pallas_hyrax_batch_vtable() : vesta_hyrax_batch_vtable();
     else return p ? pallas_hyrax_vtable() : vesta_hyrax_vtable();
 }
 
@@ -650,6 +652,33 @@ reef_status reef_hyrax_read(reef_hyrax_ctx *ctx, int which, size_t count, reef_f
 reef_status reef_hyrax_set_small_key(reef_hyrax_ctx *ctx, size_t n_small) {
     REEF_TRY(check_small_key("reef_hyrax_set_small_key", n_small));
     return dispatch<HyraxVTable>(ctx, [&](auto *v, void *impl) { return v->set_small_key(impl, n_small); });
+}
+
+// ---- the Hyrax arguments of many proofs over one resident document, in lock-step
+reef_status reef_hyrax_batch_create(reef_hyrax_batch **out, reef_hyrax_ctx *doc, size_t m_max) {
+    if (!doc) { set_error("null argument"); return REEF_ERR_ARG; }
+    return create_handle(out, doc->curve, [&](const CurveVTable *, void **impl) {
+        return table<HyraxBatchVTable>(doc->curve)->create(impl, doc->impl, m_max);
+    });
+}
+void reef_hyrax_batch_destroy(reef_hyrax_batch *b) { destroy_handle(b, &HyraxBatchVTable::destroy); }
+reef_status reef_hyrax_batch_eval_begin(reef_hyrax_batch *b, reef_msm_ctx *key, const reef_fe *points, size_t m, bool is_mont, reef_fe *evals,
+                                        reef_fe *lz_blinds) {
+    REEF_TRY(require_same_curve(b, key, "reef_hyrax_batch_eval_begin", "Hyrax"));
+    return dispatch<HyraxBatchVTable>(b, [&](auto *v, void *impl) { return v->eval_begin(impl, key->impl, points, m, is_mont, evals, lz_blinds); });
+}
+reef_status reef_hyrax_batch_ipa_begin(reef_hyrax_batch *b, const reef_affine *q, const reef_affine *h, const reef_fe *blinds, bool is_mont,
+                                       reef_jacobian *L, reef_jacobian *R) {
+    return dispatch<HyraxBatchVTable>(b, [&](auto *v, void *impl) { return v->ipa_begin(impl, q, h, blinds, is_mont, L, R); });
+}
+reef_status reef_hyrax_batch_ipa_round(reef_hyrax_batch *b, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R) {
+    return dispatch<HyraxBatchVTable>(b, [&](auto *v, void *impl) { return v->ipa_round(impl, r, blinds, is_mont, L, R); });
+}
+reef_status reef_hyrax_batch_finish(reef_hyrax_batch *b, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat) {
+    return dispatch<HyraxBatchVTable>(b, [&](auto *v, void *impl) { return v->finish(impl, r_last, is_mont, a_hat, b_hat); });
+}
+reef_status reef_hyrax_batch_read(reef_hyrax_batch *b, size_t proof, int which, size_t count, reef_fe *out, bool to_mont) {
+    return dispatch<HyraxBatchVTable>(b, [&](auto *v, void *impl) { return v->read(impl, proof, which, count, out, to_mont); });
 }
 
 // ---- the verifier's key of a committed document

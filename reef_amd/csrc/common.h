@@ -592,6 +592,21 @@ struct HyraxVkVTable {
 const HyraxVkVTable *pallas_hyrax_vk_vtable();
 const HyraxVkVTable *vesta_hyrax_vk_vtable();
 
+// The Hyrax arguments of many proofs over one resident document in lock-step (hyrax_batch_engine.inc; include/reef_msm.h 3p).
+// doc_impl: a HyraxCtx impl; key_impl: a Ctx impl.
+struct HyraxBatchVTable {
+    reef_status (*create)(void **impl, void *doc_impl, size_t m_max);
+    void (*destroy)(void *impl);
+    reef_status (*eval_begin)(void *impl, void *key_impl, const reef_fe *points, size_t m, bool is_mont, reef_fe *evals, reef_fe *lz_blinds);
+    reef_status (*ipa_begin)(void *impl, const reef_affine *q, const reef_affine *h, const reef_fe *blinds, bool is_mont, reef_jacobian *L,
+                             reef_jacobian *R);
+    reef_status (*ipa_round)(void *impl, const reef_fe *r, const reef_fe *blinds, bool is_mont, reef_jacobian *L, reef_jacobian *R);
+    reef_status (*finish)(void *impl, const reef_fe *r_last, bool is_mont, reef_fe *a_hat, reef_fe *b_hat);
+    reef_status (*read)(void *impl, size_t proof, int which, size_t count, reef_fe *out, bool to_mont);
+};
+const HyraxBatchVTable *pallas_hyrax_batch_vtable();
+const HyraxBatchVTable *vesta_hyrax_batch_vtable();
+
 // The verifier's IPA check on a key ctx (ipa_check_engine.inc; include/reef_msm.h 3j).  key_impl: a Ctx impl.
 struct IpaCheckVTable {
     reef_status (*ipa_check)(void *key_impl, size_t n, const reef_jacobian *comm, const reef_fe *c, const reef_affine *q, const reef_jacobian *L,

@@ -11,6 +11,7 @@
 #include "spartan_kernels.inc"
 #include "open_kernels.inc"
 #include "hyrax_kernels.inc"
+#include "hyrax_batch_kernels.inc"
 #include "ipa_check_kernels.inc"
 #include "doc_kernels.inc"
 #include "engine.inc"
@@ -23,6 +24,7 @@
 #include "open_engine.inc"
 #include "hyrax_engine.inc"
 #include "hyrax_vk_engine.inc"
+#include "hyrax_batch_engine.inc"
 #include "merkle_resident_engine.inc"
 #include "doc_engine.inc"      // once: both curves' tables point at it
 namespace reef {
@@ -44,6 +46,10 @@ const OpenVTable *pallas_open_vtable() {
 }
 const HyraxVTable *pallas_hyrax_vtable() {
     static const HyraxVTable vt = make_hyrax_vtable<0>();
+    return &vt;
+}
+const HyraxBatchVTable *pallas_hyrax_batch_vtable() {
+    static const HyraxBatchVTable vt = make_hyrax_batch_vtable<0>();
     return &vt;
 }
 const HyraxVkVTable *pallas_hyrax_vk_vtable() {

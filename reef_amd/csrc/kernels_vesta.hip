@@ -11,6 +11,7 @@
 #include "spartan_kernels.inc"
 #include "open_kernels.inc"
 #include "hyrax_kernels.inc"
+#include "hyrax_batch_kernels.inc"
 #include "ipa_check_kernels.inc"
 #include "engine.inc"
 #include "fe_host.inc"
@@ -22,6 +23,7 @@
 #include "open_engine.inc"
 #include "hyrax_engine.inc"
 #include "hyrax_vk_engine.inc"
+#include "hyrax_batch_engine.inc"
 #include "merkle_resident_engine.inc"
 namespace reef {
 const CurveVTable *vesta_vtable() {
@@ -42,6 +44,10 @@ const OpenVTable *vesta_open_vtable() {
 }
 const HyraxVTable *vesta_hyrax_vtable() {
     static const HyraxVTable vt = make_hyrax_vtable<1>();
+    return &vt;
+}
+const HyraxBatchVTable *vesta_hyrax_batch_vtable() {
+    static const HyraxBatchVTable vt = make_hyrax_batch_vtable<1>();
     return &vt;
 }
 const HyraxVkVTable *vesta_hyrax_vk_vtable() {

@@ -90,4 +90,25 @@ inline OrderVerdict hy_check(const char *name, int phase, uint32_t rounds, uint3
     return strcmp(want, name) == 0 ? v : v.refuse("%s: out of order, the next call is %s", name, want);
 }
 
+// The same for a batch of arguments in lock-step (3p: hyrax_batch_engine.inc), whose phases are 3i's and whose rounds are the
+// challenges the whole batch has taken.  reef_hyrax_batch_eval_begin may always come and starts the batch over; reef_hyrax_batch_read
+// needs the vectors it set and nothing else; the IPA calls go in order.
+inline const char *hyb_next(int phase, uint32_t rounds, uint32_t right) {
+    switch (phase) {
+    case HY_EVAL: return "reef_hyrax_batch_ipa_begin";
+    case HY_IPA: return rounds + 1 < right ? "reef_hyrax_batch_ipa_round" : "reef_hyrax_batch_finish";
+    default: return "reef_hyrax_batch_eval_begin";
+    }
+}
+inline OrderVerdict hyb_check(const char *name, int phase, uint32_t rounds, uint32_t right) {
+    OrderVerdict v;
+    if (strcmp(name, "reef_hyrax_batch_eval_begin") == 0) return v;
+    if (strcmp(name, "reef_hyrax_batch_read") == 0) {
+        if (phase != HY_NONE) return v;
+        return v.refuse("%s: a and b exist from reef_hyrax_batch_eval_begin on, the next call", name);
+    }
+    const char *want = hyb_next(phase, rounds, right);
+    return strcmp(want, name) == 0 ? v : v.refuse("%s: out of order, the next call is %s", name, want);
+}
+
 }  // namespace reef

@@ -182,6 +182,76 @@ class HyraxEval(_Handle):
         check(self._lib.reef_hyrax_set_small_key(self._h, n_small))
 
 
+class HyraxBatch(_Handle):
+    """The arguments of up to m_max proofs over the resident document of `doc`, advanced in lock-step (include/reef_msm.h 3p): every
+    call takes and returns one entry per proof and has one host wait for the whole batch.  The batch borrows doc's document and keeps
+    doc alive; an argument in flight on doc itself is not disturbed.  Proof i's outputs are what HyraxEval returns for its point
+    alone."""
+    _destroy = "reef_hyrax_batch_destroy"
+
+    def __init__(self, doc: HyraxEval, m_max: int):
+        self._lib = doc._lib
+        self.doc, self.m_max, self.m = doc, m_max, 0
+        self.num_vars, self.left, self.right = doc.num_vars, doc.left, doc.right
+        h = ctypes.c_void_p()
+        check(self._lib.reef_hyrax_batch_create(ctypes.byref(h), doc._h, m_max))
+        self._h = h
+
+    def _points(self, fn, *args) -> Tuple[np.ndarray, np.ndarray]:
+        L, R = np.zeros((max(self.m, 1), 12), dtype=np.uint64), np.zeros((max(self.m, 1), 12), dtype=np.uint64)
+        check(fn(self._h, *args, L.ctypes.data, R.ctypes.data))
+        return L[:self.m], R[:self.m]
+
+    def _per_proof(self, vals: Sequence[int], per: int, what: str) -> np.ndarray:
+        if len(vals) != per * self.m:
+            raise ValueError(f"expected {per * self.m} {what} for {self.m} proofs, got {len(vals)}")
+        return _arr(vals) if len(vals) else np.zeros((1, 4), dtype=np.uint64)
+
+    def eval_begin(self, key: MsmContext, points: Sequence[Sequence[int]], *, is_mont: bool = False) -> Tuple[List[int], List[int]]:
+        """a_i = LZ_i, b_i = eq(points[i][left..]) on the device; returns (evals, lz_blinds), one entry per point.  Starts the batch
+        over with m = len(points) proofs."""
+        m = len(points)
+        for p in points:
+            if len(p) != self.num_vars:
+                raise ValueError(f"expected {self.num_vars} point entries, got {len(p)}")
+        pa = _arr([x for p in points for x in p]) if m else np.zeros((1, 4), dtype=np.uint64)
+        ev, lb = np.zeros((max(m, 1), 4), dtype=np.uint64), np.zeros((max(m, 1), 4), dtype=np.uint64)
+        check(self._lib.reef_hyrax_batch_eval_begin(self._h, key._h, pa.ctypes.data, m, is_mont, ev.ctypes.data, lb.ctypes.data))
+        if m:
+            self.m = m
+        return _ints(ev[:m]), _ints(lb[:m])
+
+    def ipa_begin(self, q: np.ndarray, h: Optional[np.ndarray] = None, blinds: Optional[Sequence[int]] = None, *,
+                  is_mont: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """Round 0's L and R of every proof, (m, 12) each.  q: (m, 8) affine points, one per proof; h: one point for the batch;
+        blinds: 2 m entries, (bl, br) of proof 0, of proof 1, ..."""
+        qa = np.ascontiguousarray(q, dtype=np.uint64).reshape(-1, 8)
+        if qa.shape[0] != self.m:
+            raise ValueError(f"expected {self.m} points q, got {qa.shape[0]}")
+        ha = None if h is None else np.ascontiguousarray(h, dtype=np.uint64).reshape(8)
+        ba = None if blinds is None else self._per_proof(blinds, 2, "blinds")
+        return self._points(self._lib.reef_hyrax_batch_ipa_begin, qa.ctypes.data, None if ha is None else ha.ctypes.data,
+                            None if ba is None else ba.ctypes.data, is_mont)
+
+    def ipa_round(self, r: Sequence[int], blinds: Optional[Sequence[int]] = None, *, is_mont: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        ra = self._per_proof(r, 1, "challenges")
+        ba = None if blinds is None else self._per_proof(blinds, 2, "blinds")
+        return self._points(self._lib.reef_hyrax_batch_ipa_round, ra.ctypes.data, None if ba is None else ba.ctypes.data, is_mont)
+
+    def finish(self, r_last: Sequence[int], *, is_mont: bool = False) -> Tuple[List[int], List[int]]:
+        """(a_hats, b_hats), one entry per proof"""
+        ra = self._per_proof(r_last, 1, "challenges")
+        a, b = np.zeros((max(self.m, 1), 4), dtype=np.uint64), np.zeros((max(self.m, 1), 4), dtype=np.uint64)
+        check(self._lib.reef_hyrax_batch_finish(self._h, ra.ctypes.data, is_mont, a.ctypes.data, b.ctypes.data))
+        return _ints(a[:self.m]), _ints(b[:self.m])
+
+    def read(self, proof: int, which: int, count: int, *, to_mont: bool = False) -> List[int]:
+        """which: 0 a, 1 b of proof `proof`, as they stand now."""
+        out = np.zeros((max(count, 1), 4), dtype=np.uint64)
+        check(self._lib.reef_hyrax_batch_read(self._h, proof, which, count, out.ctypes.data, to_mont))
+        return _ints(out[:count])
+
+
 def prove_eval(hx: HyraxEval, key: MsmContext, point: Sequence[int], challenge: Callable[[str, List[Any]], int], p: int,
                q_of: Callable[[int], np.ndarray], *, row_comms: Optional[np.ndarray] = None, row_comms_compressed=None,
                h: Optional[np.ndarray] = None,
