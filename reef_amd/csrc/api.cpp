@@ -1218,7 +1218,10 @@ struct Builder {
         o.byte_tables = 2;                             // never for a key the caller did not create: 256 KiB per point would dwarf the budget
         o.device = k.device;
         reef_msm_ctx *master = nullptr;
-        if (reef_msm_ctx_create(&master, k.curve, (const reef_affine *)j.copy, k.n, REEF_HOST, &o) != REEF_OK) { fail_build(j, 4); return; }
+        tl_packed_tables_only = true;                  // the budget was reserved for the packed tables (schedule_build): the key holds nothing else
+        const reef_status built = reef_msm_ctx_create(&master, k.curve, (const reef_affine *)j.copy, k.n, REEF_HOST, &o);
+        tl_packed_tables_only = false;
+        if (built != REEF_OK) { fail_build(j, 4); return; }
         k.host_copy = j.copy;
         k.master = master;                             // (nobody reads it before state 2)
         j.copy = nullptr;

@@ -49,6 +49,11 @@ inline const char *exp_env(const char *name) {
 #endif
 }
 
+// Set by a thread while it builds a key that must stay in the packed tables alone (engine.inc: key_build gives a pre-shifted key a second,
+// loop-form copy of its tables, twice their size, otherwise).  The drop-in symbols' builder thread sets it: the keys of the process-wide
+// table are charged to REEF_MSM_KEY_CACHE_MB as 64 bytes per table point, and that is then all they hold.
+inline thread_local bool tl_packed_tables_only = false;
+
 // Allocations and launches of a context must target the device its key lives on, whatever the calling thread's current device is.  A
 // hipSetDevice that FAILS must not go unnoticed -- the work that follows would silently go to the caller's device: entry points
 // open the scope with REEF_ON_DEVICE and return REEF_ERR_HIP.

@@ -115,9 +115,9 @@ template <int C> REEF_HD xyzz xyzz_dbl(const xyzz &p) {
 
 // acc + P, P affine with x < 1, y < 2 (madd-2008-s).  Handles acc = O, P = O, P = -acc
 // (falls out as ZZ = 0) and P = acc (doubling branch).
-template <int C> REEF_HD xyzz xyzz_madd_flag(const xyzz &a, bool a_known_empty, const affine &p) {
+// p_inf: whether P is the identity, for callers that know it without looking at the limbs (key_limbs' flag word).
+template <int C> REEF_HD xyzz xyzz_madd_flags(const xyzz &a, bool a_known_empty, const affine &p, bool p_inf) {
     const bool a_inf = a_known_empty || xyzz_is_inf<C>(a);
-    const bool p_inf = affine_is_inf(p);
     const fe pp_ = fe_mul_sub<C, 8>(p.x, a.zz, a.x);          // U2 - X1: 1.02 + 8   -> < 9.02   (X1 < 8)
     const fe rr = fe_mul_sub<C, 4>(p.y, a.zzz, a.y);          // S2 - Y1: 1.04 + 4   -> < 5.04   (Y1 < 4)
     xyzz r;
@@ -144,6 +144,10 @@ template <int C> REEF_HD xyzz xyzz_madd_flag(const xyzz &a, bool a_known_empty, 
     }
     if (REEF_ANY(p_inf)) r = xyzz_select(p_inf, a, r);        // acc + O = acc
     return r;
+}
+
+template <int C> REEF_HD xyzz xyzz_madd_flag(const xyzz &a, bool a_known_empty, const affine &p) {
+    return xyzz_madd_flags<C>(a, a_known_empty, p, affine_is_inf(p));
 }
 
 template <int C> REEF_HD xyzz xyzz_madd(const xyzz &a, const affine &p) { return xyzz_madd_flag<C>(a, false, p); }
@@ -182,6 +186,51 @@ REEF_HD affine affine_from_table(const affine256 &m) {
     affine r;
     r.x = fe_from_table(m.x);
     r.y = fe_from_table(m.y);
+    return r;
+}
+// Loop form of a key table entry (128 B): what the bucket accumulation would otherwise compute per entry from the packed
+// form, stored once per key -- x and y as fe_from_table returns them, -y as fe_neg<C, 2>(y) returns it (zero for the
+// identity, which the loop never reads), and a word that is non-zero for the identity.  Words:
+//      0 ..  7   x limbs 0-7
+//      8 .. 11   x limb 8, y limb 8, -y limb 8, identity flag
+//     12 .. 19   y limbs 0-7
+//     20 .. 27   -y limbs 0-7
+//     28 .. 31   zero
+// so that an entry is five aligned 16-byte loads: words 0-11 and, by the digit's sign, words 12-19 or 20-27.
+struct alignas(16) affine_limbs {
+    u32 w[32];
+};
+static constexpr int LIMBS_X = 0, LIMBS_TOP = 8, LIMBS_Y = 12, LIMBS_NEG_Y = 20;
+template <int C> REEF_HD affine_limbs affine_limbs_from_table(const affine256 &m) {
+    const affine p = affine_from_table(m);
+    const bool inf = affine_is_inf(p);
+    const fe ny = fe_select(inf, fe_zero(), fe_neg<C, 2>(p.y));
+    affine_limbs r;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        r.w[LIMBS_X + i] = p.x.l[i];
+        r.w[LIMBS_Y + i] = p.y.l[i];
+        r.w[LIMBS_NEG_Y + i] = ny.l[i];
+    }
+    r.w[LIMBS_TOP] = p.x.l[8]; r.w[LIMBS_TOP + 1] = p.y.l[8]; r.w[LIMBS_TOP + 2] = ny.l[8]; r.w[LIMBS_TOP + 3] = inf ? 1u : 0u;
+#pragma unroll
+    for (int i = 28; i < 32; ++i) r.w[i] = 0;
+    return r;
+}
+// The part of a record one entry reads -- head = words 0-11, ysel = words 12-19 (neg false) or 20-27 (neg true) -- as the
+// operand of the mixed addition: x < 1, y < 2 as from affine_from_table and a conditional negation.
+struct limbs_entry {
+    u32 head[12], ysel[8];
+};
+REEF_HD affine affine_from_limbs(const limbs_entry &e, bool neg, bool *inf) {
+    affine r;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { r.x.l[i] = e.head[i]; r.y.l[i] = e.ysel[i]; }
+    r.x.l[8] = e.head[8];
+    r.y.l[8] = neg ? e.head[10] : e.head[9];
+    REEF_SET_BOUND(r.x, 1.0);
+    REEF_SET_BOUND(r.y, neg ? 2.0 : 1.0);
+    *inf = e.head[11] != 0;
     return r;
 }
 template <int C> REEF_HD affine256 affine_to_table(const affine &p) {

@@ -60,6 +60,8 @@ template <int C> struct Key {
     affine256 *tables = nullptr;  // T tables of n points each
     size_t n = 0, cap = 0;     // points per table, allocated points per table
     u32 c = 0, W = 0, G = 0, T = 0;
+    affine_limbs *limb_tables = nullptr;   // the same T * n points in the accumulation loop's own form (ec.h: affine_limbs, 128 B each), for k_accum0 alone;
+    size_t limb_cap = 0;                   // null: the loop reads `tables` (plain, nibble- and byte-table keys; no room on the device).  limb_cap: allocated records
     affine256 *small_tab = nullptr;   // nibble tables of a small pre-shifted key (k_small_msm), 960 points per key point
     size_t small_n = 0;               // points the nibble tables cover (0: none)
     affine256 *wide_tab = nullptr;    // byte tables of a mid-size pre-shifted key (k_wide_accum), 4096 points per key point
@@ -184,6 +186,7 @@ template <int C> static void wide_drop(Key<C> *k) {
 template <int C> static void key_release(Key<C> *k) {
     if (k && --k->refs == 0) {
         if (k->tables) (void)hipFree(k->tables);
+        if (k->limb_tables) (void)hipFree(k->limb_tables);
         if (k->small_tab) (void)hipFree(k->small_tab);
         wide_drop(k);
         delete k;
@@ -448,6 +451,16 @@ static reef_status run_wide(Ctx<C> *ctx, const fe256 *d_scalars, size_t n, bool 
 }
 
 // -------------------------------------------------------------- key setup ----
+// Which keys get a second copy of their tables in the accumulation loop's form (Key::limb_tables: 128 B per table point beside the
+// packed 64 B, so a key's device memory triples): pre-shifted keys that the bucket pipeline serves.  Not plain keys (T = 1: their
+// tables are as often as not rebuilt per call), not keys served from nibble or byte tables, not the keys of the drop-in symbols'
+// process-wide table (tl_packed_tables_only).  REEF_MSM_LIMB_TABLES=0 (experiment build) keeps every key packed, for A/B runs.
+static inline bool limb_tables_wanted(size_t n, u32 G, u32 T, u32 opt_tables) {
+    if (n == 0 || T <= 1 || (u64)T * n >= (1ull << 31) || tl_packed_tables_only) return false;
+    if (G == 1 && (n <= SMALL_N_MAX || (wide_enabled(opt_tables) && n <= wide_n_max()))) return false;
+    const char *e = exp_env("REEF_MSM_LIMB_TABLES");
+    return !(e && atoi(e) == 0);
+}
 template <int C>
 static reef_status key_build(Ctx<C> *ctx, const reef_affine *bases, size_t n, int loc) {
     Key<C> *key = ctx->key;
@@ -463,6 +476,12 @@ static reef_status key_build(Ctx<C> *ctx, const reef_affine *bases, size_t n, in
     key->n = n; key->c = c; key->W = W; key->G = G; key->T = T;
     ctx->sym_bits = ctx->symw_bits = 0;   // block tables belong to the previous bases
     graphs_clear(ctx);   // captured launches read the previous tables and plan
+    const bool limbs = limb_tables_wanted(n, G, T, ctx->opt_tables);
+    if (key->limb_tables && (!limbs || need > key->limb_cap)) { (void)hipFree(key->limb_tables); key->limb_tables = nullptr; key->limb_cap = 0; }
+    if (limbs && !key->limb_tables) {                  // no room for them is never fatal: the loop reads the packed tables then
+        if (hipMalloc((void **)&key->limb_tables, need * sizeof(affine_limbs)) == hipSuccess) key->limb_cap = need;
+        else { (void)hipGetLastError(); key->limb_tables = nullptr; }
+    }
     if (n == 0) return REEF_OK;
     // ABI points -> key-table form (internal Montgomery radix, canonical): one pass, once per key
     const affine256 *src = (const affine256 *)bases;
@@ -489,6 +508,9 @@ static reef_status key_build(Ctx<C> *ctx, const reef_affine *bases, size_t n, in
                                ctx->tmp_xyzz.template as<xyzz_mem>(), (u32)((size_t)cnt * n), key->tables + (size_t)j * n);
         }
     }
+    if (key->limb_tables)                              // every table in the loop's form, from the packed ones, once
+        hipLaunchKernelGGL(k_limb_tables<C>, dim3(ceil_div((size_t)T * n, 256)), dim3(256), 0, ctx->stream, (const affine256 *)key->tables, (u32)((size_t)T * n),
+                           key->limb_tables);
     key->small_n = 0;
     if (G == 1 && n <= SMALL_N_MAX) {   // a small resident commitment key: nibble tables for the sort-free path (k_small_msm)
         if (key->small_tab) { (void)hipFree(key->small_tab); key->small_tab = nullptr; }
@@ -986,10 +1008,15 @@ static reef_status run_core(Ctx<C> *ctx, const fe256 *d_scalars, const CorePlan 
         xyzz_mem *bacc = ctx->bucket_acc.template as<xyzz_mem>();
         u32 *ok = ctx->lkeys[fused ? 1 : 0].template as<u32>();
         xyzz_mem *ov = ctx->lvals[fused ? 1 : 0].template as<xyzz_mem>();
-        if (fused && word_entries) hipLaunchKernelGGL((k_accum0<C, true, true>), ag, ab, 0, st, ctx->key->tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, NBT);
-        else if (fused) hipLaunchKernelGGL((k_accum0<C, true, false>), ag, ab, 0, st, ctx->key->tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, 0u);
-        else if (word_entries) hipLaunchKernelGGL((k_accum0<C, false, true>), ag, ab, 0, st, ctx->key->tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, NBT);
-        else hipLaunchKernelGGL((k_accum0<C, false, false>), ag, ab, 0, st, ctx->key->tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, 0u);
+        auto launch_accum0 = [&](const auto *tables) {   // the key's packed tables, or its loop-form copy: the same indices
+            using TABLE = std::remove_cv_t<std::remove_pointer_t<decltype(tables)>>;
+            if (fused && word_entries) hipLaunchKernelGGL((k_accum0<C, true, true, TABLE>), ag, ab, 0, st, tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, NBT);
+            else if (fused) hipLaunchKernelGGL((k_accum0<C, true, false, TABLE>), ag, ab, 0, st, tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, 0u);
+            else if (word_entries) hipLaunchKernelGGL((k_accum0<C, false, true, TABLE>), ag, ab, 0, st, tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, NBT);
+            else hipLaunchKernelGGL((k_accum0<C, false, false, TABLE>), ag, ab, 0, st, tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, 0u);
+        };
+        if (ctx->key->limb_tables) launch_accum0((const affine_limbs *)ctx->key->limb_tables);
+        else launch_accum0((const affine256 *)ctx->key->tables);
     }
     if (ctx->timing) REEF_HIP_TRY(hipEventRecord(ctx->ev[2], st));
     launch_partial_merge<C>(ctx, nchunks0, ctx->bucket_acc.template as<xyzz_mem>(), fused);

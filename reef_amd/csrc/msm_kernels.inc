@@ -22,6 +22,8 @@
 // Reference semantics: Group::vartime_multiscalar_mul of nova-snark's pasta provider
 // (-> pasta_msm::pallas/vesta), reached from src/backend/framework.rs:668,695 and
 // src/backend/commitment.rs:187,350,361,371,383,422,430 of eniac/Reef.
+#include <type_traits>
+
 #include "ec.h"
 #include "ec_coop.h"
 #include "glv_consts.h"
@@ -85,6 +87,25 @@ __device__ __forceinline__ void store_jacobian256(jacobian256 *p, const jacobian
 }
 // key-table entry -> registers
 __device__ __forceinline__ affine load_table_point(const affine256 *p) { return affine_from_table(load_affine256(p)); }
+// loop-form key-table entry (ec.h: affine_limbs) -> the words one entry needs: x, the top limbs and the flag, and the y block
+// the digit's sign picks by address
+__device__ __forceinline__ limbs_entry load_limbs_entry(const affine_limbs *p, bool neg) {
+    const u32x4 *q = reinterpret_cast<const u32x4 *>(p);
+    const u32x4 *qy = q + (neg ? LIMBS_NEG_Y / 4 : LIMBS_Y / 4);
+    const u32x4 a = q[0], b = q[1], c = q[2], d = qy[0], e = qy[1];
+    limbs_entry r;
+    r.head[0] = a.x; r.head[1] = a.y; r.head[2] = a.z; r.head[3] = a.w;
+    r.head[4] = b.x; r.head[5] = b.y; r.head[6] = b.z; r.head[7] = b.w;
+    r.head[8] = c.x; r.head[9] = c.y; r.head[10] = c.z; r.head[11] = c.w;
+    r.ysel[0] = d.x; r.ysel[1] = d.y; r.ysel[2] = d.z; r.ysel[3] = d.w;
+    r.ysel[4] = e.x; r.ysel[5] = e.y; r.ysel[6] = e.z; r.ysel[7] = e.w;
+    return r;
+}
+// what k_accum0 keeps of a table entry between its load and its use, by the table's form
+__device__ __forceinline__ affine256 load_accum_entry(const affine256 *tables, u32 pay) { return load_affine256(tables + (pay & 0x7fffffffu)); }
+__device__ __forceinline__ limbs_entry load_accum_entry(const affine_limbs *tables, u32 pay) {
+    return load_limbs_entry(tables + (pay & 0x7fffffffu), (pay >> 31) != 0);
+}
 __device__ __forceinline__ xyzz load_xyzz(const xyzz_mem *p) {
     const u32x4 *q = reinterpret_cast<const u32x4 *>(p);
     xyzz_mem m;
@@ -664,8 +685,11 @@ __device__ __forceinline__ u32 bucket_of(const u32 *__restrict__ bs, u32 nbt, u3
     }
     return lo;
 }
-template <int C, bool FUSED, bool WORD = false>
-__global__ void __launch_bounds__(256) k_accum0(const affine256 *__restrict__ tables, const void *__restrict__ entries_,
+// TABLE: affine256 -- the packed key tables: every entry is unpacked, and negated when its digit is negative, in the loop; or
+// affine_limbs -- a pre-shifted key's loop-form tables (Key::limb_tables): the entry's operand is loaded as it stands, its sign
+// picks the y block by address and the record's flag word says whether the point is the identity.  Same operands bit for bit.
+template <int C, bool FUSED, bool WORD = false, typename TABLE = affine256>
+__global__ void __launch_bounds__(256) k_accum0(const TABLE *__restrict__ tables, const void *__restrict__ entries_,
                                                const u32 *__restrict__ m_ptr, u32 L0,
                                                u32 nchunks, xyzz_mem *__restrict__ bucket_acc, u32 *__restrict__ out_keys,
                                                xyzz_mem *__restrict__ out_vals, u32 nbt = 0) {
@@ -706,31 +730,37 @@ __global__ void __launch_bounds__(256) k_accum0(const affine256 *__restrict__ ta
             pay = e0.y;
             lo_open = prev_key == cur_key;
         }
-        affine256 raw = load_affine256(tables + (pay & 0x7fffffffu));
+        auto raw = load_accum_entry(tables, pay);
         xyzz acc = xyzz_identity();
         bool acc_empty = true;
         bool first_run = true;
         for (u32 k = 0; k < cnt; ++k) {
-            // prefetch the next entry while this one is being added
-            u32 nkey = cur_key, npay = 0;
-            affine256 nraw = raw;
-            if (k + 1 < cnt) {
-                if constexpr (WORD) {
-                    npay = mine1[k + 1];
-                    if (start + k + 1 == boundary) {                           // the next entry opens another bucket
-                        nkey = cur_key + 1;
-                        if (bs[nkey + 1] == boundary) nkey = bucket_of(bs, nbt, boundary);   // empty buckets in between (sparse digits)
-                    }
-                } else {
-                    const u32x2 e = mine[k + 1];
-                    nkey = e.x;
-                    npay = e.y;
+            // prefetch the next entry while this one is being added.  The chunk's last entry fetches itself once more (one load
+            // in L0, never used): with the loads under a branch the registers they land in were copied from the current entry's
+            // first, every iteration, for the one in which nothing is loaded.
+            const u32 kn = k + 1 < cnt ? k + 1 : k;
+            u32 nkey = cur_key, npay;
+            if constexpr (WORD) {
+                npay = mine1[kn];
+                if (k + 1 < cnt && start + k + 1 == boundary) {                // the next entry opens another bucket
+                    nkey = cur_key + 1;
+                    if (bs[nkey + 1] == boundary) nkey = bucket_of(bs, nbt, boundary);   // empty buckets in between (sparse digits)
                 }
-                nraw = load_affine256(tables + (npay & 0x7fffffffu));
+            } else {
+                const u32x2 e = mine[kn];
+                nkey = e.x;                                                    // (its own key again at the chunk's end)
+                npay = e.y;
             }
-            affine pt = affine_from_table(raw);
-            pt.y = fe_select((pay >> 31) != 0 && !affine_is_inf(pt), fe_neg<C, 2>(pt.y), pt.y);
-            acc = xyzz_madd_flag<C>(acc, acc_empty, pt);
+            const auto nraw = load_accum_entry(tables, npay);
+            if constexpr (std::is_same<TABLE, affine_limbs>::value) {
+                bool pt_inf;
+                const affine pt = affine_from_limbs(raw, (pay >> 31) != 0, &pt_inf);
+                acc = xyzz_madd_flags<C>(acc, acc_empty, pt, pt_inf);
+            } else {
+                affine pt = affine_from_table(raw);
+                pt.y = fe_select((pay >> 31) != 0 && !affine_is_inf(pt), fe_neg<C, 2>(pt.y), pt.y);
+                acc = xyzz_madd_flag<C>(acc, acc_empty, pt);
+            }
             acc_empty = false;
             const bool last = (k + 1 == cnt);
             if (last || nkey != cur_key) {
@@ -1812,6 +1842,18 @@ __global__ void __launch_bounds__(256) k_import_key(const affine256 *__restrict_
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     store_affine256(dst + i, affine_to_table<C>(affine_from_abi<C>(load_affine256(src + i))));
+}
+
+// dst[i] = the loop form of the packed table entry src[i] (ec.h: affine_limbs), for all the tables of a pre-shifted key at
+// once: what k_accum0 would otherwise work out again for every entry of every MSM on the key.  Runs once per key.
+template <int C>
+__global__ void __launch_bounds__(256) k_limb_tables(const affine256 *__restrict__ src, u32 count, affine_limbs *__restrict__ dst) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const affine_limbs r = affine_limbs_from_table<C>(load_affine256(src + i));
+    u32x4 *q = reinterpret_cast<u32x4 *>(dst + i);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) q[k] = mk_u32x4(r.w[4 * k], r.w[4 * k + 1], r.w[4 * k + 2], r.w[4 * k + 3]);
 }
 
 // tmp[j*n + i] = 2^(shift*(j + 1 - first)) * src[i] for j < count (XYZZ; with `first` tmp[i] is src[i] itself): the
