@@ -504,7 +504,8 @@ reef_status reef_merkle_check_paths(reef_merkle_ctx *ctx, const uint64_t *idx, c
  * coefficients of the isogeny (x_num[4], x_den[2], y_num[4], y_den[3]: highest degree first, the monic leading terms
  * of the denominators left out), the domain separation string and the byte order hash_to_field reads its 64-byte
  * strings in.  Field elements of the parameters are canonical integers of the curve's BASE field, or pasta
- * Montgomery form when is_mont.  out: n affine points in the ABI form (identity = (0, 0)), host or device. */
+ * Montgomery form when is_mont; in either form each of the 16 is below that field's modulus, and a call with one that
+ * is not is refused with REEF_ERR_ARG.  out: n affine points in the ABI form (identity = (0, 0)), host or device. */
 typedef struct {
     reef_fe a, b, z;             /* E' and the SWU constant Z (a non-square with g(b/(Z a)) square, RFC 9380 6.6.2) */
     reef_fe iso[13];             /* x_num[4], x_den[2], y_num[4], y_den[3] */

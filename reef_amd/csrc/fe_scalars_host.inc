@@ -1,6 +1,7 @@
 // The scalar checks of the conversion layer's host side (fe_host.inc includes this first): a caller's field element is below the
 // modulus, and comes in as internal form or as a canonical integer.  Plain host arithmetic over field.h: no HIP, no state, so a host
 // program can compile it alone (host/ipa_batch_selftest.cpp).  Needs reef_status, REEF_TRY and set_error (common.h).
+#pragma once                     // keygen_engine.inc (inside engine.inc) takes fe_valid before fe_host.inc includes this
 namespace reef {
 
 static bool fe_valid(const reef_fe *x, int field) {              // canonical: below the modulus

@@ -1,5 +1,6 @@
 // Host side of commitment-key derivation (row N1); included after merkle_engine.inc.
 #include "keccak.h"
+#include "fe_scalars_host.inc"   // fe_valid
 namespace reef {
 
 // out[i] = hash_to_curve(SHAKE256(label)[32 i .. 32 i + 32)) for i < n, affine ABI points of curve C (identity = (0, 0)).
@@ -9,6 +10,11 @@ static reef_status v_derive_generators(const uint8_t *label, size_t label_len, s
     if (!kp || !out || (label_len && !label) || (kp->dst_len && !kp->dst)) { set_error("null argument"); return REEF_ERR_ARG; }
     if (kp->dst_len > 255) { set_error("domain separation string longer than 255 bytes (RFC 9380 5.3.3 asks for a hashed tag then)"); return REEF_ERR_ARG; }
     if (n == 0 || n >= (1ull << 27)) { set_error("generator count out of range"); return REEF_ERR_ARG; }
+    const reef_fe *const named[3] = {&kp->a, &kp->b, &kp->z};      // the 16 field elements, in either form, are below the modulus of field C
+    for (u32 i = 0; i < 3; ++i)
+        if (!fe_valid(named[i], C)) { set_error("reef_derive_generators: %s is not below the modulus", i == 0 ? "a" : i == 1 ? "b" : "z"); return REEF_ERR_ARG; }
+    for (u32 i = 0; i < 13; ++i)
+        if (!fe_valid(kp->iso + i, C)) { set_error("reef_derive_generators: iso[%u] is not below the modulus", i); return REEF_ERR_ARG; }
     ScratchStream ss;
     REEF_TRY(ss.init());
     constexpr u32 NCONST = 16;                     // a, b, z, iso[13]

@@ -35,19 +35,23 @@ def shake256(data: bytes, out_len: int) -> bytes:
 
 
 def derive_generators(curve, label: bytes, n: int, a: int, b: int, z: int, iso: Sequence[int], dst: bytes,
-                      little_endian: bool = False, device: bool = False):
+                      little_endian: bool = False, device: bool = False, is_mont: bool = False):
     """-> (n, 8) uint64: n affine points in the ABI form (what reef_msm_ctx_create takes as a key), or with `device` a
-    DeviceBuffer holding them (the key never visits the host).  Parameters as canonical integers of the curve's base field."""
+    DeviceBuffer holding them (the key never visits the host).  Parameters as canonical integers of the curve's base field; with
+    `is_mont` they cross the ABI in pasta Montgomery form (times 2^256 mod p), the form a Rust caller's constants are stored in."""
     assert len(iso) == 13
     lib = _ffi.load()
+    if is_mont:
+        p = BASE_MODULUS[curve_id(curve)]
+        a, b, z, *iso = [(v << 256) % p for v in (a, b, z, *iso)]
     kp = KeygenParams(_fe(a), _fe(b), _fe(z), ((ctypes.c_uint64 * 4) * 13)(*[_fe(c) for c in iso]), dst, len(dst), 1 if little_endian else 0)
     if device:
         from .msm import DeviceBuffer
         buf = DeviceBuffer(64 * n)
-        check(lib.reef_derive_generators(curve_id(curve), label, len(label), n, ctypes.byref(kp), False, buf.ptr, REEF_DEVICE))
+        check(lib.reef_derive_generators(curve_id(curve), label, len(label), n, ctypes.byref(kp), bool(is_mont), buf.ptr, REEF_DEVICE))
         return buf
     out = np.zeros((n, 8), dtype=np.uint64)
-    check(lib.reef_derive_generators(curve_id(curve), label, len(label), n, ctypes.byref(kp), False, out.ctypes.data, REEF_HOST))
+    check(lib.reef_derive_generators(curve_id(curve), label, len(label), n, ctypes.byref(kp), bool(is_mont), out.ctypes.data, REEF_HOST))
     return out
 
 

@@ -101,13 +101,13 @@ class CommitmentGens:
 
     @classmethod
     def new(cls, curve, label: bytes, n: int, *, a: int, b: int, z: int, iso: Sequence[int], dst: bytes, little_endian: bool = False,
-            h: Optional[np.ndarray] = None, **kw) -> "CommitmentGens":
+            is_mont: bool = False, h: Optional[np.ndarray] = None, **kw) -> "CommitmentGens":
         """CommitmentGens::new(label, n) [R] (src/backend/framework.rs:297-303, commitment.rs:146-149, :176-180): the n generators are
         derived from the label on the GPU (row N1, reef_derive_generators: SHAKE256 stream on the host, the 2n maps to the curve and the
         batch normalisation on the device).  pasta_curves' hash-to-curve constants (a, b, z of the isogenous curve, the 13 isogeny
         coefficients, the domain separation string) are inputs: they live in an un-vendored crate."""
         from . import keygen
-        return cls(curve, keygen.derive_generators(curve, label, n, a, b, z, iso, dst, little_endian), h, **kw)
+        return cls(curve, keygen.derive_generators(curve, label, n, a, b, z, iso, dst, little_endian, is_mont=is_mont), h, **kw)
 
     @classmethod
     def new_with_blinding_gen(cls, curve, label: bytes, n: int, blinding_gen: np.ndarray, **kw) -> "CommitmentGens":

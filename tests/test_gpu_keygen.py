@@ -6,6 +6,7 @@ import hashlib
 import numpy as np
 import pytest
 
+from keygen_inputs import seam_indices
 from oracle import keygen_oracle as K
 from oracle import pasta_oracle as O
 
@@ -40,10 +41,10 @@ def test_key_sized_derivation_properties(gpu_lib):
     p = k.p
     xs = np.array([pt[0] % (1 << 64) for pt in pts], dtype=np.uint64)
     assert all(pt is not None for pt in pts) and len(np.unique(xs)) == n
-    for i in (0, 1, 77, 4095, 65536, n - 1):
-        assert (pts[i][1] ** 2 - pts[i][0] ** 3 - 5) % p == 0
-    for i in (0, 1, 77, n - 1):                                        # sampled against the oracle
-        assert pts[i] == K.hash_to_curve(K.shake256_chunks(b"ck", n)[i], k)
+    assert all((y * y - x * x * x - 5) % p == 0 for x, y in pts)
+    chunks = K.shake256_chunks(b"ck", n)
+    for i in sorted({0, 1, 77, n - 1} | set(seam_indices(n))):         # sampled against the oracle, and on both sides of every piece of the engine
+        assert pts[i] == K.hash_to_curve(chunks[i], k)
     _, short = _derive(curve, b"ck", 100, k)
     assert short == pts[:100]
     # the derived key is a valid MSM key: sum of the first 64 generators through the engine = oracle sum

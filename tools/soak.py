@@ -67,12 +67,14 @@ while time.time() < t_end:
                 h = R.gen_bases_ap(cid, 0xB11D, 1, 1)[0].copy()
                 wr = R.compress(cid, R.row_msm(cid, bases[:row_len].copy(), rsc, rows, row_len, h=h, blinds=bl, threads=16))
                 assert msm.compress(cid, g.msm_rows(rsc, rows, row_len, blinds=bl, h=h)) == wr, ("group-rows", cid, rows, row_len, members)
-    elif shape == 7:    # key derivation (stand-in parameter sets)
+    elif shape == 7:    # key derivation (stand-in parameter sets; any domain separation string the ABI takes, either form of the parameters)
         name = "pallas" if cid == 0 else "vesta"
         k = KO.standin_params(name, int(rng.integers(0, 3)), bool(rng.integers(0, 2)))
+        k.dst = rng.bytes(int(rng.integers(0, 256)))
+        is_mont = bool(rng.integers(0, 2))
         label, n = rng.bytes(int(rng.integers(0, 40))), int(rng.integers(1, 48))
-        raw = keygen.derive_generators(name, label, n, k.a, k.b, k.z, k.iso, k.dst, k.little_endian)
-        assert keygen.points_to_ints(name, raw) == KO.from_label(label, n, k), ("keygen", name, n)
+        raw = keygen.derive_generators(name, label, n, k.a, k.b, k.z, k.iso, k.dst, k.little_endian, is_mont=is_mont)
+        assert keygen.points_to_ints(name, raw) == KO.from_label(label, n, k), ("keygen", name, n, len(k.dst), is_mont)
     elif shape == 8:    # Poseidon Merkle tree (stand-in constants, any number of partial rounds)
         p = MO.standin_params(MO.Q if cid == 0 else MO.P, 5, int(rng.choice([2, 4, 8])), int(rng.integers(0, 60)))
         doc = [int(v) for v in rng.integers(0, 1 << 32, size=int(rng.integers(1, 120)), dtype=np.uint64)]
