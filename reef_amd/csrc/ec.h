@@ -10,6 +10,8 @@
 //      XYZZ:                     X < 6, Y < 3.6, ZZ < 1.6, ZZZ < 1.6   (loose: X < 8, Y < 4, Z* < 2)
 // The bound of each intermediate is written next to it; tests/test_host_math.py replays
 // the formulas on the host with the bounds tracked and asserted (REEF_BOUNDS build).
+// Their device twin, tools/ec_check.hip with tests/test_gpu_ec_bounds.py, checks the values realised on gfx950 against the
+// same bounds, from operands anywhere inside the loose ones.
 //
 // Data layouts at the C ABI are those of fil_pasta_curves `repr-c` (Cargo.toml:14):
 //   EpAffine/EqAffine {x, y} 64 B, identity = (0, 0);   Ep/Eq {x, y, z} 96 B Jacobian.

@@ -65,6 +65,8 @@ __device__ __forceinline__ void coop_jitter(int role, int site) {
 // wide accesses as HIP's uint4 structs (field.h), so every access is a dword instruction, and result slots and operands
 // loaded from memory still go through coop_launder (coop_get_result here, load_xyzz_coop in msm_kernels.inc; 1-3 %) in case
 // a build turns the passes back on.  tests/test_gpu_parity.py::test_group_law runs every pair and triple of operations.
+// tests/test_gpu_ec_bounds.py runs the single operations on every operand representation and in every lane layout (whole
+// workgroups of P + P lanes, a single one, ragged ends), through tools/ec_check.hip.
 __device__ __forceinline__ void coop_put(CoopLds &L, int slot, int lane, const fe &v) {
     L.q[slot][0][lane] = mk_u32x4(v.l[0], v.l[1], v.l[2], v.l[3]);
     L.q[slot][1][lane] = mk_u32x4(v.l[4], v.l[5], v.l[6], v.l[7]);

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../ec.h"
+#include "ec_ops.h"
 #include "../glv_host.h"
 #include "../host_combine.h"
 #include <chrono>
@@ -90,7 +91,74 @@ template <int C> static void window_combine(const affine256 *pts, u32 G, u32 c, 
     *us_old = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() / reps;
 }
 
+// Raw-limb entry points, of the same shape as those of tools/ec_check.hip (the device twin).  Each operand comes with the multiple of M the
+// caller vouches for, which becomes its tracked bound, so that a violated bound comment still aborts.
+template <int C> static void raw_pred(int op, const u32 *in, size_t stride, const double *bounds, u32 *out, size_t n) {
+    for (size_t i = 0; i < n; ++i) out[i] = ec_pred<C>(op, in + stride * i, bounds + 4 * i);
+}
+template <int C> static void raw_one_wave(int op, const u32 *a, const double *ab, const u32 *b, const double *bb, const u32 *flags, u32 *out, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        raw_store(out + 36 * i, ec_one_wave<C>(op, raw_xyzz(a + 36 * i, ab + 4 * i), raw_xyzz(b + 36 * i, bb + 4 * i), raw_affine(b + 36 * i, bb + 4 * i), flags[i]));
+}
+template <int C> static void raw_entry(const u32 *table, const u32 *pay, const u32 *acc, const double *accb, const u32 *empty, u32 *out_limbs,
+                                       u32 *out_packed, u32 *records, size_t entries, size_t n) {
+    std::vector<affine_limbs> rec(entries);
+    for (size_t e = 0; e < entries; ++e) {
+        rec[e] = affine_limbs_from_table<C>(raw_affine256(table + 16 * e));
+        memcpy(records + 32 * e, rec[e].w, sizeof rec[e].w);
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const size_t e = pay[i] & 0x7fffffffu;
+        const bool neg = (pay[i] >> 31) != 0;
+        const xyzz a = raw_xyzz(acc + 36 * i, accb + 4 * i);
+        raw_store(out_limbs + 36 * i, ec_entry_limbs<C>(a, empty[i] != 0, limbs_entry_of(rec[e], neg), neg));
+        raw_store(out_packed + 36 * i, ec_entry_packed<C>(a, empty[i] != 0, raw_affine256(table + 16 * e), neg));
+    }
+}
+template <int C> static void raw_chain(const u32 *table, const u32 *pay, size_t len, u32 *out, size_t nchains) {
+    for (size_t j = 0; j < nchains; ++j) {
+        xyzz acc = xyzz_identity();
+        bool acc_empty = true;
+        for (size_t k = 0; k < len; ++k) {
+            const u32 p = pay[j * len + k];
+            const bool neg = (p >> 31) != 0;
+            const affine_limbs rec = affine_limbs_from_table<C>(raw_affine256(table + 16 * (size_t)(p & 0x7fffffffu)));
+            acc = ec_entry_limbs<C>(acc, acc_empty, limbs_entry_of(rec, neg), neg);
+            acc_empty = false;
+            raw_store(out + 36 * (j * len + k), acc);
+            acc = xyzz_from_mem(xyzz_to_mem(acc));    // the engine's memory form: asserts the result invariant of every step
+        }
+    }
+}
+template <int C> static void raw_convert(int op, const u32 *in, const double *bounds, u32 *out, size_t n) {
+    for (size_t i = 0; i < n; ++i) ec_convert<C>(op, in + 36 * i, bounds + 4 * i, out + 36 * i);
+}
+
 extern "C" {
+// bounds: 4 doubles per operand (X, Y, ZZ, ZZZ; x, y for an affine one; the first for a field element)
+void host_ec_raw_pred(int curve, int op, const uint32_t *in, size_t stride, const double *bounds, uint32_t *out, size_t n) {
+    if (curve == 0) raw_pred<0>(op, in, stride, bounds, out, n);
+    else raw_pred<1>(op, in, stride, bounds, out, n);
+}
+void host_ec_raw_one_wave(int curve, int op, const uint32_t *a, const double *a_bounds, const uint32_t *b, const double *b_bounds,
+                          const uint32_t *flags, uint32_t *out, size_t n) {
+    if (curve == 0) raw_one_wave<0>(op, a, a_bounds, b, b_bounds, flags, out, n);
+    else raw_one_wave<1>(op, a, a_bounds, b, b_bounds, flags, out, n);
+}
+// pay[i] = entry index | sign << 31 must lie inside the table (the caller checks)
+void host_ec_raw_entry(int curve, const uint32_t *table, size_t entries, const uint32_t *pay, const uint32_t *acc, const double *acc_bounds,
+                       const uint32_t *empty, uint32_t *out_limbs, uint32_t *out_packed, uint32_t *records, size_t n) {
+    if (curve == 0) raw_entry<0>(table, pay, acc, acc_bounds, empty, out_limbs, out_packed, records, entries, n);
+    else raw_entry<1>(table, pay, acc, acc_bounds, empty, out_limbs, out_packed, records, entries, n);
+}
+void host_ec_raw_chain(int curve, const uint32_t *table, const uint32_t *pay, size_t len, uint32_t *out, size_t nchains) {
+    if (curve == 0) raw_chain<0>(table, pay, len, out, nchains);
+    else raw_chain<1>(table, pay, len, out, nchains);
+}
+void host_ec_raw_convert(int curve, int op, const uint32_t *in, const double *bounds, uint32_t *out, size_t n) {
+    if (curve == 0) raw_convert<0>(op, in, bounds, out, n);
+    else raw_convert<1>(op, in, bounds, out, n);
+}
 void host_window_combine_check(int curve, const void *pts, unsigned G, unsigned c, void *out_new, void *out_old, double *us) {
     if (curve == 0) window_combine<0>((const affine256 *)pts, G, c, (jacobian256 *)out_new, (jacobian256 *)out_old, us, us + 1);
     else window_combine<1>((const affine256 *)pts, G, c, (jacobian256 *)out_new, (jacobian256 *)out_old, us, us + 1);

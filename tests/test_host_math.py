@@ -21,7 +21,7 @@ CID = {"pallas": 0, "vesta": 1}
 @pytest.fixture(scope="module")
 def host():
     src = os.path.join(CSRC, "tools", "host_check.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("field.h", "ec.h", "field_consts.h", "glv_host.h", "glv_consts.h", "host_combine.h")]
+    deps = [src, os.path.join(CSRC, "tools", "ec_ops.h")] + [os.path.join(CSRC, f) for f in ("field.h", "ec.h", "field_consts.h", "glv_host.h", "glv_consts.h", "host_combine.h")]
     if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
         os.makedirs(os.path.dirname(SO), exist_ok=True)
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-DREEF_BOUNDS", "-shared", "-fPIC", src, "-o", SO])
