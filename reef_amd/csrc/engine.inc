@@ -18,14 +18,10 @@ static_assert(sizeof(affine256) == sizeof(reef_affine), "affine256 layout");
 static_assert(sizeof(jacobian256) == sizeof(reef_jacobian), "jacobian256 layout");
 static_assert(sizeof(xyzz_mem) == 144, "xyzz_mem layout");
 
-static constexpr u32 MAX_LDS_KEYS = 32768;     // 128 KiB of LDS counters per workgroup
-static constexpr u32 MAX_SCAN_KEYS = SCAN_TILE * 1024;
-static constexpr u32 SORT_SHIFT = 8;                       // two-level sort: 256 buckets per coarse bin
-static constexpr u64 TWO_LEVEL_MIN_ENTRIES = 1u << 20;     // below this the one-level sort's shorter kernel chain wins
-static constexpr u32 DEFAULT_L0 = 0;   // chunk length chosen per call
+static_assert(sizeof(xyzz_mem) == XYZZ_BYTES && sizeof(u32x2) == ENTRY_BYTES, "msm_plan.h sizes the workspace with these");
 
-static inline u32 ceil_div(u64 a, u64 b) { return (u32)((a + b - 1) / b); }
-static inline u64 round_up(u64 a, u64 b) { return (a + b - 1) / b * b; }
+static constexpr u32 DEFAULT_L0 = 0;   // chunk length chosen per call (msm_plan.h, with the pipeline's other constants)
+
 static inline u32 windows_for(u32 c) { return (256 + c - 1) / c; }
 
 // Relative cost model (unit: one mixed add) used to pick the window size.
@@ -116,9 +112,9 @@ template <int C> struct Ctx {
     int rowcol_force = -1;                   // row / column sums of a coop ctx: -1 by the rule (rowcol_lanes), 0 always four waves per sum, 16 / 32 / 64 always
                                              // that many lanes per sum (REEF_MSM_ROWCOL)
     u64 rowcol_calls[2] = {};                // MSMs of a coop ctx whose row / column sums took the latency form [0] / the throughput form [1]
-    // hipGraphs of the bucket pipeline, one per (scalars pointer, result pointer, n, ...) this ctx keeps seeing (REEF_MSM_GRAPH=1)
+    // hipGraphs of the bucket pipeline, one per (scalars pointer, result pointer, launch plan, ...) this ctx keeps seeing (REEF_MSM_GRAPH=1)
     struct GraphEntry {
-        const void *scalars; void *out; size_t n; bool is_mont; u32 wr, ww; int rowcol; uint64_t gen; int seen;
+        const void *scalars; void *out; bool is_mont; u32 wr, ww; CoreLaunch plan; uint64_t gen; int seen;
         hipGraph_t graph; hipGraphExec_t exec;
     };
     std::vector<GraphEntry> graphs;
@@ -759,53 +755,46 @@ template <int C> static reef_status v_ctx_plan(void *impl, uint32_t *c, uint32_t
 }
 
 // ------------------------------------------------------------ the pipeline ----
-struct CorePlan {
-    u32 c, W, G;       // window bits, windows used, bucket groups per result
-    u32 rows, row_len; // rows == 1: single MSM over N = row_len scalars
-    u32 n_ctx;         // table stride
-    bool slice_sort = false;  // rows > 1 only: long rows, sorted by the sliced K1 sort (a batch of MSMs)
-};
+// One MSM through the buckets is a plan and four stages.  core_launch_plan (msm_plan.h: pure integer arithmetic, tested on the host)
+// decides everything -- chunk length, sort levels and entry forms, scan route, fusions, merge levels, row / column split -- and sizes
+// every workspace buffer; ensure_core_workspace grows what is too small BEFORE the first launch; launch_sort, launch_accumulate,
+// launch_partial_merge and launch_reduce enqueue what the plan says and decide nothing.
 
-// Partial merge after k_accum0: the two slots per chunk -> bucket sums.  First level with a chunk per lane
-// (k_merge_chunks), then k_accumN levels on the two slots per wave until one wave is left.
-// Does the accumulation kernel run the first merge level itself (k_accum0<C, true>)?  Mid-size inputs only: one wave per SIMD
-// (up to 65536 chunks), where the merged kernel's registers cost no occupancy, and only where the first level would run one
-// wave per 64 chunks anyway (beyond 384 waves; below, four waves share each addition).  REEF_MSM_FUSE_MERGE=0 keeps two kernels.
-template <int C> static bool merge_is_fused(const Ctx<C> *ctx, u32 nchunks0) {
-    static const bool on = !(exp_env("REEF_MSM_FUSE_MERGE") && atoi(exp_env("REEF_MSM_FUSE_MERGE")) == 0);
-    static const bool merge1 = !(exp_env("REEF_MSM_MERGE1") && atoi(exp_env("REEF_MSM_MERGE1")) == 0);
-    static const u32 max_chunks = [] { const char *e = exp_env("REEF_MSM_FUSE_MAX_CHUNKS"); return e ? (u32)atoi(e) : 65536u; }();
-    const u32 waves = ceil_div(nchunks0, 64);
-    return on && merge1 && nchunks0 <= max_chunks && !(ctx->coop && waves <= 384);
+// The experiment switches of the bucket pipeline (common.h: exp_env), read once per process.
+static const CoreSwitches &core_switches() {
+    static const CoreSwitches sw = [] {
+        CoreSwitches s;
+        auto off = [](const char *name) { const char *e = exp_env(name); return e && atoi(e) == 0; };
+        s.fuse_merge = !off("REEF_MSM_FUSE_MERGE");        // 0: k_accum0 and the first merge level stay two kernels
+        s.merge1 = !off("REEF_MSM_MERGE1");                // 0: slot-per-lane first merge level
+        if (const char *e = exp_env("REEF_MSM_FUSE_MAX_CHUNKS")) s.fuse_max_chunks = (u32)atoi(e);
+        s.fuse_recode = !off("REEF_MSM_FUSE_RECODE");      // 0: k_recode and k_count stay two kernels
+        s.sort_compact = !off("REEF_MSM_SORT_COMPACT");    // 0: 8-byte entries between the two sort levels
+        s.sort_word = !off("REEF_MSM_SORT_WORD");          // 0: 8-byte sorted entries
+        // TIMING ONLY -- the result is garbage: 1 leaves the whole bucket reduction out, 2 its row / column sums only.  What a window would be
+        // worth if its bucket reduction were free: the upper bound on anything a faster reduction can buy
+        // (profiles/r06_free_reduction_bound.txt: VERDICT r5 item 3's kill criterion, measured before any kernel was written).
+        if (const char *e = exp_env("REEF_MSM_SKIP_REDUCE")) s.skip_reduce = atoi(e);
+        return s;
+    }();
+    return sw;
 }
+
+// Partial merge after k_accum0 (msm_plan.h: merge_plan): the two slots per chunk -> bucket sums.
 template <int C>
-static void launch_partial_merge(Ctx<C> *ctx, u32 nchunks0, xyzz_mem *acc, bool first_level_done = false) {
+static void launch_partial_merge(Ctx<C> *ctx, const MergePlan &m, u32 nchunks0, xyzz_mem *acc) {
     hipStream_t st = ctx->stream;
-    u32 waves = ceil_div(nchunks0, 64);
-    static const bool merge1 = !(exp_env("REEF_MSM_MERGE1") && atoi(exp_env("REEF_MSM_MERGE1")) == 0);   // experiment switch: 0 = slot-per-lane first level
-    u32 len = 2 * waves;
-    int cur = 1;
-    if (!merge1) { len = 2 * nchunks0; cur = 0; waves = 2; }
-    else if (first_level_done) {}                      // k_accum0<C, true> has written the level-1 lists
-    else
-    // four waves per addition pay while the chip is not full of them; beyond that plain waves have the better throughput
-    if (ctx->coop && waves <= 384)
-        hipLaunchKernelGGL((k_merge_chunks<C, true>), dim3(waves), dim3(256), 0, st, ctx->lkeys[0].template as<u32>(), ctx->lvals[0].template as<xyzz_mem>(),
-                           nchunks0, acc, ctx->lkeys[1].template as<u32>(), ctx->lvals[1].template as<xyzz_mem>());
-    else
-        hipLaunchKernelGGL((k_merge_chunks<C, false>), dim3(ceil_div(waves, 4)), dim3(256), 0, st, ctx->lkeys[0].template as<u32>(),
-                           ctx->lvals[0].template as<xyzz_mem>(), nchunks0, acc, ctx->lkeys[1].template as<u32>(), ctx->lvals[1].template as<xyzz_mem>());
-    if (waves <= 1) return;
-    for (;;) {
-        if (ctx->coop)
-            hipLaunchKernelGGL(k_accumN_coop<C>, dim3(ceil_div(len, 64)), dim3(256), 0, st, ctx->lkeys[cur].template as<u32>(),
-                               ctx->lvals[cur].template as<xyzz_mem>(), len, acc, ctx->lkeys[cur ^ 1].template as<u32>(), ctx->lvals[cur ^ 1].template as<xyzz_mem>());
-        else
-            hipLaunchKernelGGL(k_accumN<C>, dim3(ceil_div(len, 256)), dim3(256), 0, st, ctx->lkeys[cur].template as<u32>(),
-                               ctx->lvals[cur].template as<xyzz_mem>(), len, acc, ctx->lkeys[cur ^ 1].template as<u32>(), ctx->lvals[cur ^ 1].template as<xyzz_mem>());
-        if (len <= 64) break;
-        len = 2 * ceil_div(len, 64);
-        cur ^= 1;
+    u32 *keys[2] = {ctx->lkeys[0].template as<u32>(), ctx->lkeys[1].template as<u32>()};
+    xyzz_mem *vals[2] = {ctx->lvals[0].template as<xyzz_mem>(), ctx->lvals[1].template as<xyzz_mem>()};
+    if (m.first == MERGE_FIRST_COOP)
+        hipLaunchKernelGGL((k_merge_chunks<C, true>), dim3(m.first_grid), dim3(256), 0, st, keys[0], vals[0], nchunks0, acc, keys[1], vals[1]);
+    else if (m.first == MERGE_FIRST_PLAIN)
+        hipLaunchKernelGGL((k_merge_chunks<C, false>), dim3(m.first_grid), dim3(256), 0, st, keys[0], vals[0], nchunks0, acc, keys[1], vals[1]);
+    u32 cur = m.cur;
+    for (u32 i = 0; i < m.nlevels; ++i, cur ^= 1) {
+        const u32 len = m.len[i];
+        if (ctx->coop) hipLaunchKernelGGL(k_accumN_coop<C>, dim3(ceil_div(len, 64)), dim3(256), 0, st, keys[cur], vals[cur], len, acc, keys[cur ^ 1], vals[cur ^ 1]);
+        else hipLaunchKernelGGL(k_accumN<C>, dim3(ceil_div(len, 256)), dim3(256), 0, st, keys[cur], vals[cur], len, acc, keys[cur ^ 1], vals[cur ^ 1]);
     }
 }
 
@@ -820,8 +809,6 @@ static void launch_partial_merge(Ctx<C> *ctx, u32 nchunks0, xyzz_mem *acc, bool 
 // longer chain in full.  (A caller counts from its first enqueue to the wait that finds it idle: a ctx whose device-side result was never
 // waited for through the library still counts, and the rule then errs towards the throughput form.)  Both forms return the same group
 // element.  A ctx without coop tails (REEF_MSM_COOP=0) keeps every tail on one wave: 64 lanes per sum.
-static constexpr u32 ROWCOL_SHARED_MIN_BUCKETS = 1u << 16;
-static constexpr int ROWCOL_SHARED_LANES = 32;
 template <int C> static int rowcol_lanes(const Ctx<C> *ctx, u32 NB) {
     if (!ctx->coop) return 64;
     if (ctx->rowcol_force >= 0) return ctx->rowcol_force;
@@ -830,241 +817,180 @@ template <int C> static int rowcol_lanes(const Ctx<C> *ctx, u32 NB) {
     return shared ? ROWCOL_SHARED_LANES : 0;
 }
 
+// The plan of one call: the shape, what the ctx adds (the form of the row / column sums as of now), the switches.
 template <int C>
-static reef_status run_core(Ctx<C> *ctx, const fe256 *d_scalars, const CorePlan &pl, bool is_mont, const fe256 *d_blinds,
-                            const affine256 *d_h, jacobian256 *d_out, const xyzz_mem **group_sums_out = nullptr, int rowcol = -1) {
-    hipStream_t st = ctx->stream;
-    const u64 N = (u64)pl.rows * pl.row_len;
-    const u32 NB = 1u << (pl.c - 1);
-    const u32 groups_total = pl.rows * pl.G;
-    const u64 NBT64 = (u64)groups_total * NB;
-    if (NBT64 > MAX_SCAN_KEYS) { set_error("too many buckets (%llu)", (unsigned long long)NBT64); return REEF_ERR_ARG; }
-    if (N >= (1ull << 31) || N * pl.W >= (1ull << 32)) { set_error("too many digits"); return REEF_ERR_ARG; }
-    const u32 NBT = (u32)NBT64;
-    const u64 Mmax = N * pl.W;
-    // entries per accumulation thread: about one bucket's worth (few runs cut by chunk edges),
-    // but enough threads to fill the chip
-    u32 L0 = ctx->L0;
-    if (L0 == 0) {
-        // k_accum0 is bound by integer issue and a lone wave saturates its SIMD: while the input is too small to keep two
-        // waves per SIMD in long chunks, the shortest chain is one wave per SIMD (1024 waves = 65536 chunks) -- more threads
-        // would only share the SIMDs and leave more partial sums to merge.  Large inputs: long chunks, two waves per SIMD.
-        // The grid is a whole number of waves per SIMD: 65536 chunks (one wave on each of the 1024 SIMDs) up to 48 entries
-        // per chunk, 131072 chunks (two waves per SIMD, which hides the table gathers better) beyond.
-        if (Mmax <= 48ull * 65536) L0 = (u32)std::max<u64>(4, ceil_div(Mmax, 65536));
-        else L0 = (u32)std::min<u64>(128, ceil_div(Mmax, 131072));
+static reef_status core_plan(const Ctx<C> *ctx, const CorePlan &pl, bool group_sums_out, CoreLaunch *p) {
+    const CoreCtxOpts o{ctx->L0, ctx->coop, ctx->two_level, rowcol_lanes<C>(ctx, 1u << (pl.c - 1)), group_sums_out};
+    const char *why = nullptr;
+    const reef_status rs = core_launch_plan(pl, o, core_switches(), p, &why);
+    if (rs != REEF_OK) set_error("%s (%llu buckets, %llu digits)", why, (unsigned long long)p->groups_total * p->NB, (unsigned long long)p->Mmax);
+    return rs;
+}
+
+// Every buffer the chain touches, sized before its first launch: a buffer that has to grow is freed and allocated here, not between
+// two kernels of the chain (and not under an open graph capture).  Steady state allocates nothing.
+template <int C> static reef_status ensure_core_workspace(Ctx<C> *ctx, const CoreBytes &b) {
+    REEF_TRY(ctx->dig.ensure(b.dig));
+    REEF_TRY(ctx->counts.ensure(b.counts));
+    REEF_TRY(ctx->tile_sums.ensure(b.tile_sums));
+    REEF_TRY(ctx->bstart.ensure(b.bstart));
+    REEF_TRY(ctx->entries.ensure(b.entries));
+    REEF_TRY(ctx->bstart1.ensure(b.bstart1));
+    REEF_TRY(ctx->seg_first.ensure(b.seg_first));
+    REEF_TRY(ctx->seg_counts.ensure(b.seg_counts));
+    REEF_TRY(ctx->entries1.ensure(b.entries1));
+    REEF_TRY(ctx->bucket_acc.ensure(b.bucket_acc));
+    for (int i = 0; i < 2; ++i) {
+        REEF_TRY(ctx->lkeys[i].ensure(b.lkeys[i]));
+        REEF_TRY(ctx->lvals[i].ensure(b.lvals[i]));
     }
-    const u32 nchunks0 = (u32)round_up(ceil_div(Mmax, L0), 64);
-    const u64 entries_padded = (u64)nchunks0 * L0;
+    REEF_TRY(ctx->rowcol.ensure(b.rowcol));
+    REEF_TRY(ctx->group_sums.ensure(b.group_sums));
+    REEF_TRY(ctx->wsum.ensure(b.wsum));
+    return REEF_OK;
+}
 
-    REEF_TRY(ctx->dig.ensure(Mmax * sizeof(u32)));
-    REEF_TRY(ctx->bstart.ensure(((u64)NBT + 1) * sizeof(u32)));
-    REEF_TRY(ctx->tile_sums.ensure(1024 * sizeof(u32)));
-    REEF_TRY(ctx->entries.ensure(entries_padded * sizeof(u32x2)));
-    REEF_TRY(ctx->bucket_acc.ensure((u64)NBT * sizeof(xyzz_mem)));
-    const u32 len1 = 2 * nchunks0;
-    const u32 len2 = 2 * ceil_div(len1, 64);
-    REEF_TRY(ctx->lkeys[0].ensure((u64)len1 * sizeof(u32)));
-    REEF_TRY(ctx->lvals[0].ensure((u64)len1 * sizeof(xyzz_mem)));
-    REEF_TRY(ctx->lkeys[1].ensure((u64)len2 * sizeof(u32)));
-    REEF_TRY(ctx->lvals[1].ensure((u64)len2 * sizeof(xyzz_mem)));
-    REEF_TRY(ctx->rowcol.ensure((u64)groups_total * ((1ull << ((pl.c - 1) / 2)) + (1ull << (pl.c / 2))) * sizeof(xyzz_mem)));
-    REEF_TRY(ctx->group_sums.ensure((u64)groups_total * sizeof(xyzz_mem)));
+// ---- digits, then the counting sort by bucket: ctx->entries in bucket order, ctx->bstart the buckets' first entries
+template <int C>
+static void launch_sort(Ctx<C> *ctx, const CorePlan &pl, const CoreLaunch &p, const fe256 *d_scalars, bool is_mont) {
+    hipStream_t st = ctx->stream;
+    u32 *dig = ctx->dig.template as<u32>(), *bstart = ctx->bstart.template as<u32>(), *counts = ctx->counts.template as<u32>();
+    u32 *tile_sums = ctx->tile_sums.template as<u32>();
+    u32 *bstart_c = p.two_level ? ctx->bstart1.template as<u32>() : bstart;     // scan output of the (coarse) histogram pass
+    void *entries = (void *)ctx->entries.template as<u32x2>();
+    const u32 NBTc = p.NBTc, S = p.S;
+    auto launch_recode = [&] {
+        hipLaunchKernelGGL(k_recode<C>, dim3(ceil_div(p.N, 256)), dim3(256), 0, st, d_scalars, (u32)p.N, (int)is_mont, pl.c, pl.W, ctx->wsplit_rank,
+                           ctx->wsplit_world, dig);
+    };
+    SortShape sh{};
+    RowSortShape rsh{};
+    u32 *totals_src = counts;
+    if (!p.row_mode) {
+        sh.n = pl.row_len; sh.B = pl.rows; sh.W = pl.W; sh.G = pl.G; sh.NB = p.NBc; sh.shift = p.shift; sh.KB = p.KB; sh.per = p.per;
+        sh.NBT = NBTc; sh.row_len = 0; sh.n_ctx = pl.n_ctx; sh.L0 = p.L0;
+        if (p.recode_fused) {
+            hipLaunchKernelGGL(k_recode_count<C>, dim3(S), dim3(1024), p.KB * sizeof(u32), st, d_scalars, (int)is_mont, pl.c, ctx->wsplit_rank, ctx->wsplit_world, sh,
+                               dig, counts);
+        } else {
+            launch_recode();
+            hipLaunchKernelGGL(k_count, dim3(S, p.groups_total, p.P), dim3(1024), p.KB * sizeof(u32), st, dig, sh, counts);
+        }
+        totals_src = counts + (size_t)S * NBTc;
+    } else {
+        rsh.rows = pl.rows; rsh.row_len = pl.row_len; rsh.W = pl.W; rsh.G = pl.G; rsh.NB = p.NB;
+        rsh.rows_per_block = p.rows_per_block; rsh.n_ctx = pl.n_ctx; rsh.L0 = p.L0;
+        launch_recode();
+        hipLaunchKernelGGL(k_row_count, dim3(ceil_div(pl.rows, p.rows_per_block)), dim3(1024), p.rows_per_block * p.keys_per_row * sizeof(u32), st, dig, rsh,
+                           totals_src);
+    }
+    if (p.scan == SCAN_SMALL) {
+        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, counts, S, NBTc, bstart_c);
+    } else {
+        const bool wave = p.scan == SCAN_WAVE;              // a wave per key, or a thread
+        if (wave) hipLaunchKernelGGL(k_slice_totals_w, dim3(ceil_div(NBTc, 4)), dim3(256), 0, st, counts, S, NBTc, totals_src);
+        else if (!p.row_mode) hipLaunchKernelGGL(k_slice_totals, dim3(ceil_div(NBTc, 256)), dim3(256), 0, st, counts, S, NBTc, totals_src);
+        hipLaunchKernelGGL(k_scan_tiles, dim3(p.ntiles), dim3(SCAN_BLOCK), 0, st, totals_src, NBTc, bstart_c, tile_sums);
+        hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, st, tile_sums, p.ntiles, bstart_c + NBTc);
+        if (wave) hipLaunchKernelGGL(k_scan_finish_w, dim3(ceil_div(NBTc, 4)), dim3(256), 0, st, bstart_c, tile_sums, counts, S, NBTc);
+        else hipLaunchKernelGGL(k_scan_finish, dim3(ceil_div(NBTc, 256)), dim3(256), 0, st, bstart_c, tile_sums, counts, p.row_mode ? 0u : S, NBTc);
+    }
+    if (p.two_level) {
+        // coarse bins into entries1, then each bin by its low key bits into entries; the entry forms (msm_plan.h) are template arguments
+        auto two_level_sort = [&](auto compact, auto word) {
+            constexpr bool COMPACT = decltype(compact)::value, WORD = decltype(word)::value;
+            const void *e1 = (const void *)ctx->entries1.template as<u32x2>();
+            u32 *seg_first = ctx->seg_first.template as<u32>(), *seg_counts = ctx->seg_counts.template as<u32>();
+            const size_t fine_lds = p.fine * sizeof(u32);
+            hipLaunchKernelGGL(k_scatter<COMPACT>, dim3(S, p.groups_total, p.P), dim3(1024), p.KB * sizeof(u32), st, dig, sh, counts, (void *)e1);
+            hipLaunchKernelGGL(k_seg_plan, dim3(1), dim3(1024), 0, st, bstart_c, NBTc, seg_first);
+            hipLaunchKernelGGL(k_fine_count<COMPACT>, dim3(p.nseg_max), dim3(1024), fine_lds, st, e1, bstart_c, seg_first, NBTc, p.shift, seg_counts);
+            hipLaunchKernelGGL(k_fine_offsets, dim3(NBTc), dim3(p.fine), 0, st, bstart_c, seg_first, NBTc, p.shift, seg_counts, bstart);
+            hipLaunchKernelGGL((k_fine_scatter<COMPACT, WORD>), dim3(p.nseg_max), dim3(1024), fine_lds, st, e1, bstart_c, seg_first, NBTc, p.shift, seg_counts, entries);
+        };
+        if (p.word_entries) two_level_sort(std::true_type{}, std::true_type{});
+        else if (p.compact) two_level_sort(std::true_type{}, std::false_type{});
+        else two_level_sort(std::false_type{}, std::false_type{});
+    } else if (!p.row_mode) {
+        hipLaunchKernelGGL(k_scatter<false>, dim3(S, p.groups_total, p.P), dim3(1024), p.KB * sizeof(u32), st, dig, sh, counts, entries);
+    } else {
+        hipLaunchKernelGGL(k_row_scatter, dim3(ceil_div(pl.rows, p.rows_per_block)), dim3(1024), p.rows_per_block * p.keys_per_row * sizeof(u32), st, dig, rsh,
+                           bstart, ctx->entries.template as<u32x2>());
+    }
+}
 
-    u32 *dig = ctx->dig.template as<u32>();
-    u32 *bstart = ctx->bstart.template as<u32>();
+// ---- bucket accumulation: a chunk of L0 sorted entries per thread; k_accum0's (first merge level fused, one-word entries, table form)
+template <int C> static void launch_accumulate(Ctx<C> *ctx, const CoreLaunch &p) {
+    hipStream_t st = ctx->stream;
+    const bool fused = p.merge.fused, word = p.word_entries;
+    const u32 NBT = p.NBT, L0 = p.L0, nchunks0 = p.nchunks0;
+    const dim3 ag(ceil_div(nchunks0, 256)), ab(256);
+    const void *ent = (const void *)ctx->entries.template as<u32x2>();
+    const u32 *bend = ctx->bstart.template as<u32>() + NBT;
+    xyzz_mem *bacc = ctx->bucket_acc.template as<xyzz_mem>();
+    u32 *ok = ctx->lkeys[fused ? 1 : 0].template as<u32>();
+    xyzz_mem *ov = ctx->lvals[fused ? 1 : 0].template as<xyzz_mem>();
+    auto launch_accum0 = [&](const auto *tables) {   // the key's packed tables, or its loop-form copy: the same indices
+        using TABLE = std::remove_cv_t<std::remove_pointer_t<decltype(tables)>>;
+        if (fused && word) hipLaunchKernelGGL((k_accum0<C, true, true, TABLE>), ag, ab, 0, st, tables, ent, bend, L0, nchunks0, bacc, ok, ov, NBT);
+        else if (fused) hipLaunchKernelGGL((k_accum0<C, true, false, TABLE>), ag, ab, 0, st, tables, ent, bend, L0, nchunks0, bacc, ok, ov, 0u);
+        else if (word) hipLaunchKernelGGL((k_accum0<C, false, true, TABLE>), ag, ab, 0, st, tables, ent, bend, L0, nchunks0, bacc, ok, ov, NBT);
+        else hipLaunchKernelGGL((k_accum0<C, false, false, TABLE>), ag, ab, 0, st, tables, ent, bend, L0, nchunks0, bacc, ok, ov, 0u);
+    };
+    if (ctx->key->limb_tables) launch_accum0((const affine_limbs *)ctx->key->limb_tables);
+    else launch_accum0((const affine256 *)ctx->key->tables);
+}
 
+// ---- bucket reduction (row/column sums, two short weighted sums), final Horner over groups
+template <int C>
+static void launch_reduce(Ctx<C> *ctx, const CorePlan &pl, const CoreLaunch &p, jacobian256 *d_out, const xyzz_mem **group_sums_out) {
+    hipStream_t st = ctx->stream;
+    const u32 c1 = p.c1, c2 = p.c2, groups_total = p.groups_total;
+    const xyzz_mem *bacc = ctx->bucket_acc.template as<xyzz_mem>();
+    const u32 *bstart = ctx->bstart.template as<u32>();
+    xyzz_mem *rowcol = ctx->rowcol.template as<xyzz_mem>(), *wsum = ctx->wsum.template as<xyzz_mem>();
+    xyzz_mem *gsum = ctx->group_sums.template as<xyzz_mem>();
+    if (group_sums_out && ctx->pinned && (size_t)groups_total * sizeof(xyzz_mem) <= Ctx<C>::PINNED_POINTS * sizeof(jacobian256))
+        gsum = (xyzz_mem *)ctx->pinned;                // host finishes the combine: let the kernel store where the host reads
+    jacobian256 *direct_out = p.direct ? d_out : (jacobian256 *)nullptr;
+    if (group_sums_out) *group_sums_out = gsum;        // the caller finishes the window combine on the host
+    if (p.skip_reduce == 1) return;
+    auto launch_rowcol = [&](auto lps) {
+        constexpr int LPS = decltype(lps)::value;
+        hipLaunchKernelGGL((k_reduce_rowcol<C, LPS>), dim3(ceil_div(ceil_div(p.rc_waves, 64u / LPS), 4)), dim3(256), 0, st, bacc, bstart, c1, c2, groups_total, rowcol);
+    };
+    if (ctx->coop) {
+        const int lanes = p.rowcol_lanes;
+        ++ctx->rowcol_calls[lanes != 0];
+        if (p.skip_reduce == 2) {}
+        else if (lanes == 16) launch_rowcol(std::integral_constant<int, 16>{});
+        else if (lanes == 32) launch_rowcol(std::integral_constant<int, 32>{});
+        else if (lanes == 64) launch_rowcol(std::integral_constant<int, 64>{});
+        else hipLaunchKernelGGL(k_reduce_rowcol_coop<C>, dim3(p.rc_waves), dim3(256), 0, st, bacc, bstart, c1, c2, groups_total, rowcol);
+        hipLaunchKernelGGL(k_reduce_weighted_coop<C>, dim3(groups_total, 2), dim3(256), 0, st, rowcol, c1, c2, wsum);
+        hipLaunchKernelGGL(k_reduce_combine_coop<C>, dim3(groups_total), dim3(256), 0, st, wsum, c2, gsum, direct_out);
+    } else {
+        if (p.skip_reduce != 2) launch_rowcol(std::integral_constant<int, 64>{});
+        hipLaunchKernelGGL(k_reduce_weighted<C>, dim3(groups_total), dim3(128), 0, st, rowcol, c1, c2, gsum, direct_out);
+    }
+    if (!group_sums_out && !p.direct) hipLaunchKernelGGL(k_final<C>, dim3(ceil_div(pl.rows, 64)), dim3(64), 0, st, gsum, pl.G, pl.c, pl.rows, d_out);
+}
+
+template <int C>
+static reef_status run_core(Ctx<C> *ctx, const fe256 *d_scalars, const CorePlan &pl, const CoreLaunch &p, bool is_mont, const fe256 *d_blinds,
+                            const affine256 *d_h, jacobian256 *d_out, const xyzz_mem **group_sums_out = nullptr) {
+    hipStream_t st = ctx->stream;
+    REEF_TRY(ensure_core_workspace<C>(ctx, p.bytes));
     if (ctx->timing) {
         REEF_TRY(ctx_begin_timing<C>(ctx));
         REEF_HIP_TRY(hipEventRecord(ctx->ev[0], st));
     }
-    auto launch_recode = [&] {
-        hipLaunchKernelGGL(k_recode<C>, dim3(ceil_div(N, 256)), dim3(256), 0, st, d_scalars, (u32)N, (int)is_mont, pl.c, pl.W, ctx->wsplit_rank,
-                           ctx->wsplit_world, dig);
-    };
-    // a single MSM with one bucket group whose (coarse) histogram fits one LDS part: the thread that recodes a scalar counts
-    // its digits too (k_recode_count); REEF_MSM_FUSE_RECODE=0 keeps two kernels
-    static const bool fuse_recode_env = !(exp_env("REEF_MSM_FUSE_RECODE") && atoi(exp_env("REEF_MSM_FUSE_RECODE")) == 0);
-
-    // ---- counting sort by bucket
-    u32 *totals_src;
-    u32 S = 0;
-    SortShape sh{};
-    RowSortShape rsh{};
-    const bool row_mode = pl.rows > 1 && !pl.slice_sort;
-    // large inputs: two-level sort (coarse bins of 2^SORT_SHIFT buckets, then each bin by its low key bits)
-    const bool two_level = !row_mode && ctx->two_level != 0 && NB >= (64u << SORT_SHIFT) &&
-                           (ctx->two_level > 0 || Mmax >= TWO_LEVEL_MIN_ENTRIES);
-    // one-word entries between the two levels when the point index, the low key bits and the sign fit in 32 bits: with
-    // SORT_SHIFT low bits, or with one fewer (twice the coarse bins) -- 2^20 points x 16 tables need the latter
-    static const bool compact_env = !(exp_env("REEF_MSM_SORT_COMPACT") && atoi(exp_env("REEF_MSM_SORT_COMPACT")) == 0);
-    static const bool word_env = !(exp_env("REEF_MSM_SORT_WORD") && atoi(exp_env("REEF_MSM_SORT_WORD")) == 0);
-    bool word_entries = false;
-    const u64 index_span = (u64)ceil_div(pl.W, pl.G) * pl.n_ctx;       // payloads are j * n_ctx + i, j < tables per group
-    u32 shift = two_level ? SORT_SHIFT : 0u;
-    bool compact = false;
-    if (two_level && compact_env) {
-        if (index_span <= (1ull << (31 - SORT_SHIFT))) compact = true;
-        else if (index_span <= (1ull << (32 - SORT_SHIFT))) { compact = true; shift = SORT_SHIFT - 1; }
-    }
-    const u32 NBc = NB >> shift;                       // keys per group seen by the (coarse) histogram
-    const u32 NBTc = groups_total * NBc;
-    u32 *bstart_c = bstart;                            // scan output of the histogram pass
-    if (two_level) {
-        REEF_TRY(ctx->bstart1.ensure(((u64)NBTc + 1) * sizeof(u32)));
-        bstart_c = ctx->bstart1.template as<u32>();
-    }
-    if (!row_mode) {
-        const u32 KB = std::min(NBc, MAX_LDS_KEYS);
-        const u32 P = NBc / KB;
-        S = std::max<u32>(1, std::min<u32>(ceil_div(256, groups_total * P), ceil_div(pl.row_len, 1024)));   // one workgroup per CU
-        sh.n = pl.row_len; sh.B = pl.rows; sh.W = pl.W; sh.G = pl.G; sh.NB = NBc; sh.shift = shift; sh.KB = KB; sh.per = ceil_div(pl.row_len, S);
-        sh.NBT = NBTc; sh.row_len = 0; sh.n_ctx = pl.n_ctx; sh.L0 = L0;
-        S = ceil_div(pl.row_len, sh.per);
-        REEF_TRY(ctx->counts.ensure(((u64)S + 1) * NBTc * sizeof(u32)));
-        u32 *counts = ctx->counts.template as<u32>();
-        if (fuse_recode_env && groups_total == 1 && P == 1) {       // the grid is the slices
-            hipLaunchKernelGGL(k_recode_count<C>, dim3(S), dim3(1024), KB * sizeof(u32), st, d_scalars, (int)is_mont, pl.c, ctx->wsplit_rank, ctx->wsplit_world, sh,
-                               dig, counts);
-        } else {
-            launch_recode();
-            hipLaunchKernelGGL(k_count, dim3(S, groups_total, P), dim3(1024), KB * sizeof(u32), st, dig, sh, counts);
-        }
-        totals_src = counts + (size_t)S * NBTc;
-    } else {
-        const u32 keys_per_row = pl.G * NB;
-        if (keys_per_row > MAX_LDS_KEYS) { set_error("row MSM: window too large for the LDS sort"); return REEF_ERR_ARG; }
-        rsh.rows = pl.rows; rsh.row_len = pl.row_len; rsh.W = pl.W; rsh.G = pl.G; rsh.NB = NB;
-        // whole rows per workgroup: bounded by LDS keys and ~64Ki digits of work
-        u32 rpb = std::max<u32>(1, MAX_LDS_KEYS / keys_per_row);
-        rpb = std::min<u32>(rpb, std::max<u32>(1, 65536 / std::max<u32>(1, pl.row_len)));
-        rsh.rows_per_block = rpb; rsh.n_ctx = pl.n_ctx; rsh.L0 = L0;
-        REEF_TRY(ctx->counts.ensure((u64)NBT * sizeof(u32)));
-        totals_src = ctx->counts.template as<u32>();
-        launch_recode();
-        hipLaunchKernelGGL(k_row_count, dim3(ceil_div(pl.rows, rpb)), dim3(1024), rpb * keys_per_row * sizeof(u32), st, dig, rsh,
-                           totals_src);
-    }
-    const u32 ntiles = ceil_div(NBTc, SCAN_TILE);
-    if (!row_mode && NBTc <= 4096 && (NBTc & 3u) == 0 && S <= SCAN_SMALL_SLICES) {
-        // few keys: slice totals + scan + cursors in one workgroup
-        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, ctx->counts.template as<u32>(), S, NBTc, bstart_c);
-    } else {
-        if (!row_mode) {
-            if (NBTc <= 4096) hipLaunchKernelGGL(k_slice_totals_w, dim3(ceil_div(NBTc, 4)), dim3(256), 0, st, ctx->counts.template as<u32>(), S, NBTc, totals_src);
-            else hipLaunchKernelGGL(k_slice_totals, dim3(ceil_div(NBTc, 256)), dim3(256), 0, st, ctx->counts.template as<u32>(), S, NBTc, totals_src);
-        }
-        hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(SCAN_BLOCK), 0, st, totals_src, NBTc, bstart_c, ctx->tile_sums.template as<u32>());
-        hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, st, ctx->tile_sums.template as<u32>(), ntiles, bstart_c + NBTc);
-        if (!row_mode && NBTc <= 4096)
-            hipLaunchKernelGGL(k_scan_finish_w, dim3(ceil_div(NBTc, 4)), dim3(256), 0, st, bstart_c, ctx->tile_sums.template as<u32>(),
-                               ctx->counts.template as<u32>(), S, NBTc);
-        else
-            hipLaunchKernelGGL(k_scan_finish, dim3(ceil_div(NBTc, 256)), dim3(256), 0, st, bstart_c, ctx->tile_sums.template as<u32>(),
-                               ctx->counts.template as<u32>(), row_mode ? 0u : S, NBTc);
-    }
-    if (two_level) {
-        REEF_TRY(ctx->entries1.ensure(entries_padded * sizeof(u32x2)));
-        REEF_TRY(ctx->seg_first.ensure(((u64)NBTc + 1) * sizeof(u32)));
-        const u32 nseg_max = (u32)ceil_div(Mmax, SORT_SEG) + NBTc;
-        const u32 fine = 1u << shift;
-        REEF_TRY(ctx->seg_counts.ensure((u64)nseg_max * fine * sizeof(u32)));
-        u32x2 *e1 = ctx->entries1.template as<u32x2>();
-        u32 *seg_first = ctx->seg_first.template as<u32>(), *seg_counts = ctx->seg_counts.template as<u32>();
-        word_entries = compact && word_env;              // one-word sorted entries: k_accum0 takes its keys from bucket_start[]
-        if (compact) {
-            hipLaunchKernelGGL(k_scatter<true>, dim3(S, groups_total, NBc / sh.KB), dim3(1024), sh.KB * sizeof(u32), st, dig, sh, ctx->counts.template as<u32>(), (void *)e1);
-            hipLaunchKernelGGL(k_seg_plan, dim3(1), dim3(1024), 0, st, bstart_c, NBTc, seg_first);
-            hipLaunchKernelGGL(k_fine_count<true>, dim3(nseg_max), dim3(1024), fine * sizeof(u32), st, (const void *)e1, bstart_c, seg_first, NBTc, shift, seg_counts);
-            hipLaunchKernelGGL(k_fine_offsets, dim3(NBTc), dim3(fine), 0, st, bstart_c, seg_first, NBTc, shift, seg_counts, bstart);
-            if (word_entries)
-                hipLaunchKernelGGL((k_fine_scatter<true, true>), dim3(nseg_max), dim3(1024), fine * sizeof(u32), st, (const void *)e1, bstart_c, seg_first, NBTc, shift, seg_counts,
-                                   (void *)ctx->entries.template as<u32x2>());
-            else
-                hipLaunchKernelGGL((k_fine_scatter<true, false>), dim3(nseg_max), dim3(1024), fine * sizeof(u32), st, (const void *)e1, bstart_c, seg_first, NBTc, shift, seg_counts,
-                                   (void *)ctx->entries.template as<u32x2>());
-        } else {
-            hipLaunchKernelGGL(k_scatter<false>, dim3(S, groups_total, NBc / sh.KB), dim3(1024), sh.KB * sizeof(u32), st, dig, sh, ctx->counts.template as<u32>(), (void *)e1);
-            hipLaunchKernelGGL(k_seg_plan, dim3(1), dim3(1024), 0, st, bstart_c, NBTc, seg_first);
-            hipLaunchKernelGGL(k_fine_count<false>, dim3(nseg_max), dim3(1024), fine * sizeof(u32), st, (const void *)e1, bstart_c, seg_first, NBTc, shift, seg_counts);
-            hipLaunchKernelGGL(k_fine_offsets, dim3(NBTc), dim3(fine), 0, st, bstart_c, seg_first, NBTc, shift, seg_counts, bstart);
-            hipLaunchKernelGGL((k_fine_scatter<false, false>), dim3(nseg_max), dim3(1024), fine * sizeof(u32), st, (const void *)e1, bstart_c, seg_first, NBTc, shift, seg_counts,
-                               (void *)ctx->entries.template as<u32x2>());
-        }
-    } else if (!row_mode) {
-        hipLaunchKernelGGL(k_scatter<false>, dim3(S, groups_total, NB / sh.KB), dim3(1024), sh.KB * sizeof(u32), st, dig, sh, ctx->counts.template as<u32>(),
-                           (void *)ctx->entries.template as<u32x2>());
-    } else {
-        hipLaunchKernelGGL(k_row_scatter, dim3(ceil_div(pl.rows, rsh.rows_per_block)), dim3(1024),
-                           rsh.rows_per_block * pl.G * NB * sizeof(u32), st, dig, rsh, bstart, ctx->entries.template as<u32x2>());
-    }
-
-    // ---- bucket accumulation
+    launch_sort<C>(ctx, pl, p, d_scalars, is_mont);
     if (ctx->timing) REEF_HIP_TRY(hipEventRecord(ctx->ev[1], st));
-    const bool fused = merge_is_fused<C>(ctx, nchunks0);
-    {
-        const dim3 ag(ceil_div(nchunks0, 256)), ab(256);
-        const void *ent = (const void *)ctx->entries.template as<u32x2>();
-        xyzz_mem *bacc = ctx->bucket_acc.template as<xyzz_mem>();
-        u32 *ok = ctx->lkeys[fused ? 1 : 0].template as<u32>();
-        xyzz_mem *ov = ctx->lvals[fused ? 1 : 0].template as<xyzz_mem>();
-        auto launch_accum0 = [&](const auto *tables) {   // the key's packed tables, or its loop-form copy: the same indices
-            using TABLE = std::remove_cv_t<std::remove_pointer_t<decltype(tables)>>;
-            if (fused && word_entries) hipLaunchKernelGGL((k_accum0<C, true, true, TABLE>), ag, ab, 0, st, tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, NBT);
-            else if (fused) hipLaunchKernelGGL((k_accum0<C, true, false, TABLE>), ag, ab, 0, st, tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, 0u);
-            else if (word_entries) hipLaunchKernelGGL((k_accum0<C, false, true, TABLE>), ag, ab, 0, st, tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, NBT);
-            else hipLaunchKernelGGL((k_accum0<C, false, false, TABLE>), ag, ab, 0, st, tables, ent, bstart + NBT, L0, nchunks0, bacc, ok, ov, 0u);
-        };
-        if (ctx->key->limb_tables) launch_accum0((const affine_limbs *)ctx->key->limb_tables);
-        else launch_accum0((const affine256 *)ctx->key->tables);
-    }
+    launch_accumulate<C>(ctx, p);
     if (ctx->timing) REEF_HIP_TRY(hipEventRecord(ctx->ev[2], st));
-    launch_partial_merge<C>(ctx, nchunks0, ctx->bucket_acc.template as<xyzz_mem>(), fused);
-
-    // ---- bucket reduction (row/column sums, two short weighted sums), final Horner over groups
-    const u32 lg = pl.c - 1;                       // NB = 2^lg
-    const u32 c2 = (lg + 1) / 2, c1 = lg - c2;
-    const u32 per_group = (1u << c1) + (1u << c2);
-    const u32 rc_waves = groups_total * per_group;
-    xyzz_mem *gsum = ctx->group_sums.template as<xyzz_mem>();
-    if (group_sums_out && ctx->pinned && (size_t)groups_total * sizeof(xyzz_mem) <= Ctx<C>::PINNED_POINTS * sizeof(jacobian256))
-        gsum = (xyzz_mem *)ctx->pinned;                // host finishes the combine: let the kernel store where the host reads
-    const bool direct = !group_sums_out && pl.G == 1;   // one group per result: no Horner, no separate conversion kernel
-    // REEF_MSM_SKIP_REDUCE (experiment build, TIMING ONLY -- the result is garbage): 1 leaves the whole bucket reduction out, 2 its row / column sums
-    // only.  What a window would be worth if its bucket reduction were free: the upper bound on anything a faster reduction can buy
-    // (profiles/r06_free_reduction_bound.txt: VERDICT r5 item 3's kill criterion, measured before any kernel was written).
-    static const int skip_reduce = [] { const char *e = exp_env("REEF_MSM_SKIP_REDUCE"); return e ? atoi(e) : 0; }();
-    const int lanes = rowcol >= 0 ? rowcol : rowcol_lanes<C>(ctx, NB);   // rc_waves sums: on four waves each (0), or `lanes` lanes each
-    auto launch_rowcol = [&](auto lps) {
-        constexpr int LPS = decltype(lps)::value;
-        hipLaunchKernelGGL((k_reduce_rowcol<C, LPS>), dim3(ceil_div(ceil_div(rc_waves, 64u / LPS), 4)), dim3(256), 0, st, ctx->bucket_acc.template as<xyzz_mem>(),
-                           bstart, c1, c2, groups_total, ctx->rowcol.template as<xyzz_mem>());
-    };
-    if (skip_reduce == 1) {
-        if (group_sums_out) *group_sums_out = gsum;
-    } else if (ctx->coop) {
-        REEF_TRY(ctx->wsum.ensure((u64)groups_total * 4 * sizeof(xyzz_mem)));
-        ++ctx->rowcol_calls[lanes != 0];
-        if (skip_reduce == 2) {}
-        else if (lanes == 16) launch_rowcol(std::integral_constant<int, 16>{});
-        else if (lanes == 32) launch_rowcol(std::integral_constant<int, 32>{});
-        else if (lanes == 64) launch_rowcol(std::integral_constant<int, 64>{});
-        else
-        hipLaunchKernelGGL(k_reduce_rowcol_coop<C>, dim3(rc_waves), dim3(256), 0, st, ctx->bucket_acc.template as<xyzz_mem>(), bstart, c1, c2,
-                           groups_total, ctx->rowcol.template as<xyzz_mem>());
-        hipLaunchKernelGGL(k_reduce_weighted_coop<C>, dim3(groups_total, 2), dim3(256), 0, st, ctx->rowcol.template as<xyzz_mem>(), c1, c2,
-                           ctx->wsum.template as<xyzz_mem>());
-        hipLaunchKernelGGL(k_reduce_combine_coop<C>, dim3(groups_total), dim3(256), 0, st, ctx->wsum.template as<xyzz_mem>(), c2, gsum,
-                           direct ? d_out : (jacobian256 *)nullptr);
-    } else {
-        if (skip_reduce != 2) launch_rowcol(std::integral_constant<int, 64>{});
-        hipLaunchKernelGGL(k_reduce_weighted<C>, dim3(groups_total), dim3(128), 0, st, ctx->rowcol.template as<xyzz_mem>(), c1, c2, gsum,
-                           direct ? d_out : (jacobian256 *)nullptr);
-    }
-    const xyzz_mem *gs = gsum;
-    if (skip_reduce == 1) {}
-    else if (group_sums_out) *group_sums_out = gs;  // the caller finishes the window combine on the host
-    else if (!direct) hipLaunchKernelGGL(k_final<C>, dim3(ceil_div(pl.rows, 64)), dim3(64), 0, st, gs, pl.G, pl.c, pl.rows, d_out);
+    launch_partial_merge<C>(ctx, p.merge, p.nchunks0, ctx->bucket_acc.template as<xyzz_mem>());
+    launch_reduce<C>(ctx, pl, p, d_out, group_sums_out);
     if (d_blinds && (ctx->wsplit_world <= 1 || ctx->wsplit_rank == 0))   // window split: the blind term belongs to one partial sum only
         REEF_TRY(launch_blind<C>(ctx, d_out, d_blinds, d_h, is_mont, pl.rows));
     if (ctx->timing) {
@@ -1073,6 +999,13 @@ static reef_status run_core(Ctx<C> *ctx, const fe256 *d_scalars, const CorePlan 
     }
     REEF_HIP_TRY(hipGetLastError());
     return REEF_OK;
+}
+template <int C>
+static reef_status run_core(Ctx<C> *ctx, const fe256 *d_scalars, const CorePlan &pl, bool is_mont, const fe256 *d_blinds,
+                            const affine256 *d_h, jacobian256 *d_out, const xyzz_mem **group_sums_out = nullptr) {
+    CoreLaunch p;
+    REEF_TRY(core_plan<C>(ctx, pl, group_sums_out != nullptr, &p));
+    return run_core<C>(ctx, d_scalars, pl, p, is_mont, d_blinds, d_h, d_out, group_sums_out);
 }
 
 // Where the kernels write `count` results: the caller's device buffer, the host-mapped landing zone
@@ -1129,7 +1062,8 @@ template <int C>
 static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const CorePlan &pl, bool is_mont, jacobian256 *d_out) {
     hipStream_t st = ctx->stream;
     const uint64_t gen = g_devbuf_gen.load();
-    const int rowcol = rowcol_lanes<C>(ctx, 1u << (pl.c - 1));     // a captured chain holds ONE form of the row / column sums: part of the key
+    CoreLaunch plan;                                          // a captured chain IS one plan: the whole of it is part of the key, and the
+    REEF_TRY(core_plan<C>(ctx, pl, false, &plan));            // plan compared here is the one run_core launches, at capture and at replay
     typename Ctx<C>::GraphEntry *hit = nullptr;
     for (size_t i = 0; i < ctx->graphs.size();) {
         auto &e = ctx->graphs[i];
@@ -1139,11 +1073,11 @@ static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const C
             ctx->graphs.erase(ctx->graphs.begin() + i);
             continue;
         }
-        if (e.scalars == d_scalars && e.out == d_out && e.n == pl.row_len && e.is_mont == is_mont && e.wr == ctx->wsplit_rank && e.ww == ctx->wsplit_world && e.rowcol == rowcol) hit = &e;
+        if (e.scalars == d_scalars && e.out == d_out && e.is_mont == is_mont && e.wr == ctx->wsplit_rank && e.ww == ctx->wsplit_world && same_plan(e.plan, plan)) hit = &e;
         ++i;
     }
     if (hit && hit->exec) {
-        if (ctx->coop) ++ctx->rowcol_calls[rowcol != 0];
+        if (ctx->coop) ++ctx->rowcol_calls[plan.rowcol_lanes != 0];
         REEF_HIP_TRY(hipGraphLaunch(hit->exec, st));
         return REEF_OK;
     }
@@ -1155,7 +1089,7 @@ static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const C
         // reserved stream to nobody, and a context pinned to it waits the microseconds the capture lasts (common.h).  Otherwise this
         // call runs the plain path and the capture is tried again at the next one.
         PoolStream *ps = ctx->lease.ps;
-        if (!ps || ctx->lease.bg || !stream_pool().try_reserve(ps, ctx->lease.pinned ? 1 : 0)) return run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out, nullptr, rowcol);
+        if (!ps || ctx->lease.bg || !stream_pool().try_reserve(ps, ctx->lease.pinned ? 1 : 0)) return run_core<C>(ctx, d_scalars, pl, plan, is_mont, nullptr, nullptr, d_out);
         hit->seen = 2;
         struct Reserve {                                      // until the capture has ended
             PoolStream *p;
@@ -1163,7 +1097,7 @@ static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const C
             ~Reserve() { StreamPool::unreserve(p); }
         } reserve(ps);
         if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const reef_status rs = run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out, nullptr, rowcol);
+            const reef_status rs = run_core<C>(ctx, d_scalars, pl, plan, is_mont, nullptr, nullptr, d_out);
             hipGraph_t g = nullptr;
             const hipError_t ee = hipStreamEndCapture(st, &g);
             if (rs == REEF_OK && ee == hipSuccess && g && g_devbuf_gen.load() == gen && hipGraphInstantiate(&hit->exec, g, nullptr, nullptr, 0) == hipSuccess) {
@@ -1177,9 +1111,9 @@ static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const C
         } else {
             (void)hipGetLastError();
         }
-        return run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out, nullptr, rowcol);   // capture refused: the plain path, from now on
+        return run_core<C>(ctx, d_scalars, pl, plan, is_mont, nullptr, nullptr, d_out);   // capture refused: the plain path, from now on
     }
-    REEF_TRY(run_core<C>(ctx, d_scalars, pl, is_mont, nullptr, nullptr, d_out, nullptr, rowcol));
+    REEF_TRY(run_core<C>(ctx, d_scalars, pl, plan, is_mont, nullptr, nullptr, d_out));
     if (!hit) {
         if (ctx->graphs.size() >= 4) {
             auto &v = ctx->graphs.front();
@@ -1187,7 +1121,7 @@ static reef_status run_core_graphed(Ctx<C> *ctx, const fe256 *d_scalars, const C
             if (v.graph) (void)hipGraphDestroy(v.graph);
             ctx->graphs.erase(ctx->graphs.begin());
         }
-        ctx->graphs.push_back({d_scalars, d_out, pl.row_len, is_mont, ctx->wsplit_rank, ctx->wsplit_world, rowcol, g_devbuf_gen.load(), 1, nullptr, nullptr});
+        ctx->graphs.push_back({d_scalars, d_out, is_mont, ctx->wsplit_rank, ctx->wsplit_world, plan, g_devbuf_gen.load(), 1, nullptr, nullptr});
     }
     return REEF_OK;
 }
@@ -1318,7 +1252,7 @@ static reef_status sym_rows_sum(Ctx<C> *ctx, u64 M, u32 blocks, size_t rows, boo
     hipLaunchKernelGGL((k_accum0<C, false, false>), dim3(ceil_div(nchunks0, 256)), dim3(256), 0, st, ctx->sym_table.template as<affine256>(), (const void *)entries, bstart + rows, L0,
                        nchunks0, row_acc, ctx->lkeys[0].template as<u32>(), ctx->lvals[0].template as<xyzz_mem>(), 0u);
     if (ctx->timing) REEF_HIP_TRY(hipEventRecord(ctx->ev[2], st));
-    launch_partial_merge<C>(ctx, nchunks0, row_acc);
+    launch_partial_merge<C>(ctx, merge_plan(nchunks0, ctx->coop, core_switches(), false), nchunks0, row_acc);
     hipLaunchKernelGGL(k_final<C>, dim3(ceil_div(rows, 64)), dim3(64), 0, st, row_acc, 1u, 0u, (u32)rows, d_out);   // XYZZ row sums -> Jacobian
     if (d_blinds) REEF_TRY(launch_blind<C>(ctx, d_out, d_blinds, d_h, is_mont, rows));
     if (ctx->timing) {

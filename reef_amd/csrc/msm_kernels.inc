@@ -27,6 +27,7 @@
 #include "ec.h"
 #include "ec_coop.h"
 #include "glv_consts.h"
+#include "msm_plan.h"     // the constants the launch plan and the kernels share: SCAN_*, SORT_SEG
 
 namespace reef {
 
@@ -276,8 +277,6 @@ static __global__ void __launch_bounds__(256) k_slice_totals(const u32 *__restri
     totals[key] = t;
 }
 
-static constexpr u32 SCAN_BLOCK = 1024, SCAN_ITEMS = 4, SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS;
-
 // Few keys, many slices (coarse pass of the two-level sort): one wave per key, lanes over the slices.
 static __global__ void __launch_bounds__(256) k_slice_totals_w(const u32 *__restrict__ counts, u32 S, u32 NBT, u32 *__restrict__ totals) {
     latency_critical();
@@ -394,8 +393,7 @@ static __global__ void __launch_bounds__(256) k_scan_finish(u32 *__restrict__ bu
 // Small key spaces (mid-size MSMs, the coarse pass of the two-level sort): slice totals, the exclusive scan and the
 // per-slice cursors in ONE workgroup -- the four-kernel scan above costs ~20 us of launches for 4096 keys.  Thread i
 // owns the four keys 4i..4i+3 and reads them from every slice as one 16-byte load, all slices in flight together
-// (NBT <= 4096, a multiple of 4; S <= SCAN_SMALL_SLICES).
-static constexpr u32 SCAN_SMALL_SLICES = 64;
+// (NBT <= 4096, a multiple of 4; S <= SCAN_SMALL_SLICES, msm_plan.h).
 static __global__ void __launch_bounds__(1024) k_scan_small(u32 *__restrict__ counts, u32 S, u32 NBT, u32 *__restrict__ bucket_start) {
     latency_critical();
     __shared__ u32 lds[192];
@@ -467,7 +465,6 @@ static __global__ void __launch_bounds__(1024) k_scatter(const u32 *__restrict__
 // entries into coarse bins of FINE = 2^shift buckets; level 2 sorts each bin by the low key bits.
 // A bin is cut into segments of <= SORT_SEG entries, one workgroup each (a giant bucket -- witness-like
 // scalars -- simply becomes many segments).
-static constexpr u32 SORT_SEG = 16384;
 __device__ __forceinline__ u32 ceil_div_u32(u32 a, u32 b) { return (a + b - 1u) / b; }
 
 // seg_first[bin] = number of segments of all earlier bins (exclusive scan of ceil(count/SORT_SEG)); one workgroup.

@@ -110,9 +110,10 @@ def _thresholds():
     """(MAX_SCAN_KEYS, the row_len from which rows are sorted as whole MSMs, rows per batch there, bucket keys per row of a plain key's
     rows of 2 entries, of a pre-shifted key's rows, of a plain key's rows of 2^11 entries): the arithmetic of v_msm_rows for full-width scalars, from the sources' constants"""
     eng = open(os.path.join(ROOT, "reef_amd", "csrc", "engine.inc")).read()
-    ker = open(os.path.join(ROOT, "reef_amd", "csrc", "msm_kernels.inc")).read()
+    ker = open(os.path.join(ROOT, "reef_amd", "csrc", "msm_plan.h")).read()         # the pipeline's constants, kernels' and engine's alike
     max_scan = _const("SCAN_BLOCK", ker) * _const("SCAN_ITEMS", ker) * 1024
-    assert "MAX_SCAN_KEYS = SCAN_TILE * 1024" in eng and "SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS" in ker
+    assert "MAX_SCAN_KEYS = SCAN_TILE * 1024" in ker and "SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS" in ker
+    assert "MAX_SCAN_KEYS =" not in eng and "SCAN_TILE =" not in eng + open(os.path.join(ROOT, "reef_amd", "csrc", "msm_kernels.inc")).read()
     long_rows = int(re.search(r"rows > 1 && row_len >= (\d+) && bits \+ 1 > 13", eng).group(1))
     per_batch = int(re.search(r"\(size_t\)\(\(\(1ull << 31\) - 1\) / \(\(u64\)row_len \* key->W\)\), \(size_t\)(\d+)\}\)", eng).group(1))
 

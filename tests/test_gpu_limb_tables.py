@@ -1,7 +1,7 @@
 """A pre-shifted key that the bucket pipeline serves keeps a second copy of its tables in the accumulation loop's own form
 (engine.inc: Key::limb_tables, ec.h: affine_limbs) and k_accum0 reads its operands from there.  Everything here is checked against
 the C oracle or the discrete-logarithm closed form on arithmetic-progression bases, as compressed encodings, on both curves and for
-scalars in both conventions.  Which k_accum0 a shape reaches (engine.inc: run_core, merge_is_fused): the first merge level is fused into
+scalars in both conventions.  Which k_accum0 a shape reaches (msm_plan.h: core_launch_plan, merge_plan): the first merge level is fused into
 it between 385 and 1024 waves of chunks, entries are one word each from 2^20 entries on; `chunk` (entries per thread) moves a shape of
 a given size from one side to the other, so every instantiation over the loop-form tables is reached at sizes the oracle can handle:
     4096 points, 20 tables, default chunk   320 waves    two-word entries

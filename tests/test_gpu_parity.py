@@ -437,6 +437,31 @@ def test_shipped_plan_either_side_of_the_window_thresholds_dlog_property(n, c, g
                 assert msm.compress("pallas", ctx.msm(sc_dev, upto)) == C.compress(C.mul(acc % C.order, C.gen)), (kind, upto)
 
 
+@pytest.mark.parametrize("key_n,n,c,route", [
+    (1 << 20, 1 << 16, 15, "two levels, 8-byte entries between them"),      # 18 tables x 2^20 points: an index beyond 2^24 leaves no room for the low key bits
+    (1500, 1500, 17, "one level, two LDS parts per group, k_slice_totals"),  # 65536 buckets = 2 x 32768 counters; 16 scan tiles
+    (70000, 70000, 13, "one level, k_slice_totals_w / k_scan_finish_w")])    # 4096 keys but 69 slices: more than k_scan_small takes
+def test_plan_routes_no_other_test_reaches_dlog_property(key_n, n, c, route, gpu_lib):
+    """Routes of the launch plan (msm_plan.h: core_launch_plan; tests/test_core_plan_host.py checks the decisions) at the smallest shapes that
+    reach them, on a pre-shifted key: uniform and witness-like scalars, the whole prefix and a ragged one; expected: the discrete-log closed form."""
+    from reef_amd import msm
+    C = CURVES["pallas"]
+    k0, d = 0x5A17C3, 0x2F1
+    bases = msm.gen_bases("pallas", k0, d, key_n, device=True)
+    idx = np.arange(n, dtype=object)
+    with msm.MsmContext("pallas", bases, key_n, bucket_groups=1, window_bits=c) as ctx:
+        assert ctx.plan()["window_bits"] == c and ctx.plan()["bucket_groups"] == 1
+        for kind in (0, 1):
+            sc_dev = msm.gen_scalars("pallas", 0xD1CE + kind, n, kind=kind, mont=True, device=True)
+            canon = msm.gen_scalars("pallas", 0xD1CE + kind, n, kind=kind, mont=False)
+            cols = [canon[:, j].astype(object) for j in range(4)]
+            for upto in (n, n - 321):
+                acc = 0
+                for j in range(4):
+                    acc += (int(np.sum(cols[j][:upto])) * k0 + int(np.sum(cols[j][:upto] * idx[:upto])) * d) << (64 * j)
+                assert msm.compress("pallas", ctx.msm(sc_dev, upto)) == C.compress(C.mul(acc % C.order, C.gen)), (route, kind, upto)
+
+
 def test_linearity_and_clone_threads(gpu_lib, cref):
     """MSM(a) + MSM(b) == MSM(a+b); clones of one key used from several threads agree."""
     from reef_amd import msm

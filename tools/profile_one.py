@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """One MSM configuration, repeated, for rocprofv3 --kernel-trace: per-kernel timeline of a single MSM.
    python tools/profile_one.py run LOGN C G [REPS]          # the workload (run it under rocprofv3 --kernel-trace)
+   python tools/profile_one.py rows ROWS ROW_LEN C G [REPS] # reef_msm_rows of full-width scalars: the LDS row sort, or the sliced sort of long rows
    python tools/profile_one.py show TRACE.csv [SKIP]        # timeline of the last MSM in the trace (durations and gaps, us)
 """
 import csv
@@ -29,6 +30,18 @@ def run(logn, c, g, reps=8, kind=0, chunk=0):
     print(f"logn={logn} c={c} G={g} chunk={chunk} plan={ctx.plan()} total_ms={st['total_ms'] / st['calls']:.4f} accum_ms={st['accumulate_ms'] / st['calls']:.4f}")
 
 
+def run_rows(rows, row_len, c, g, reps=2):
+    from reef_amd import msm
+    bases = msm.gen_bases("pallas", 12345, 7, row_len, device=True)
+    sc = msm.gen_scalars("pallas", 99, rows * row_len, device=True)
+    out = msm.DeviceBuffer(96 * rows)
+    with msm.MsmContext("pallas", bases, row_len, window_bits=c, bucket_groups=g, byte_tables=2) as ctx:
+        for _ in range(reps):
+            ctx.msm_rows(sc, rows, row_len, out=out)
+            ctx.sync()
+        print(f"rows={rows} row_len={row_len} c={c} G={g} plan={ctx.plan()}")
+
+
 def show(path):
     rows = list(csv.DictReader(open(path)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
@@ -50,5 +63,7 @@ def show(path):
 if __name__ == "__main__":
     if sys.argv[1] == "run":
         run(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]) if len(sys.argv) > 5 else 8, chunk=int(os.environ.get("CHUNK", "0")))
+    elif sys.argv[1] == "rows":
+        run_rows(*(int(a) for a in sys.argv[2:]))
     else:
         show(sys.argv[2])
