@@ -1,4 +1,6 @@
-// Host side of the sum-check vector kernels (row N2); included after engine.inc.
+// Host side of the sum-check vector kernels (row N2); included after engine.inc.  What a call decides -- switches, grids, row lists, the
+// route of a round -- is sumcheck_plan.h's, pure and tested on the host; this file holds the ctx, the launches and the state changes.
+#include "sumcheck_plan.h"
 namespace reef {
 
 template <int C> struct ScCtx : DeviceCtx {   // device: where the tables live; no event
@@ -22,14 +24,8 @@ template <int C> struct ScCtx : DeviceCtx {   // device: where the tables live; 
     // view of gen_eq_table's split (2^(ell - ell/2) rows), the 4-byte copy of its entries, the row lists of round one
     bool st_ok = false;
     DevBuf st_s32, st_flags, st_lists, st_k, st_sumfl;   // st_k: KA, KC (fe_limbs) and the S masks of the first fold
-    struct StList { u32 off = 0, n = 0; };
-    StList st_sum[2][3];                 // round-one sums: [side][class W, S, K] -> pair rows h < H/2
-    StList st_fast, st_gen;              // first fold: h < H/4 whose four sources are all K or S / the others
-    // first fold deferred by one round (sumcheck_kernels.inc): g < H/8 with both quadruples g, g + H/8 fast (st_f8), the same rows
-    // as a list of quadruples (st_f8x), the fast quadruples that are not among them (st_frest), the g that are not in st_f8 (st_g8)
-    StList st_f8, st_f8x, st_frest, st_g8;
-    StList st_d8[4][2];                  // the rows of st_f8x by source block b (row h + b * H/4) and class: [b][0] S rows, [b][1] K rows
-    bool defer_on = false;               // the rows of st_f8x have not been written: the next call is their second fold, or they are flushed
+    ScRowLists st;                       // the row lists of round one and of the first fold, deferred or not (sumcheck_plan.h): stretches of st_lists
+    bool defer_on = false;               // the rows of st.f8x have not been written: the next call is their second fold, or they are flushed
     fe256 defer_r1 = {};
     size_t defer_pow = 0;                // the pow of that next call
     u32 defer_hq = 0;
@@ -45,55 +41,37 @@ template <int C> struct ScCtx : DeviceCtx {   // device: where the tables live; 
     u32 seq = 0;                         // sequence number of the last one-launch round (the kernel posts it after the coefficients)
     // The tuning switches (environment) are read when the ctx is created, when a table is set and when a step starts
     // (gen_eq_table) -- never per round: a step runs under ONE setting, and no getenv sits on the per-round path (ADVICE r3).
-    struct Switches {
-        bool one_launch = true, rank1 = true, structured = true, identity = true, defer = true;
-        size_t r1_min_pow = (size_t)1 << 21;
-        u32 floor_blocks = 256;
-        u32 one_launch_max = 64;         // REEF_SC_ONE_LAUNCH_MAX: a round of at most this many blocks finishes its sums itself (the last block to arrive)
-        size_t split_max = (size_t)1 << 14;   // REEF_SC_SPLIT_MAX: rounds of at most this many pairs spread an item over four waves (0: never)
-        u32 split_blocks = 64;             // REEF_SC_SPLIT_BLOCKS: the most workgroups of such a round (every one adds 27 words to the shared sums: 256 of them cost the 2^14-pair round 7 us)
-        u32 items = 8;                   // pairs a thread of a dense round takes at least (its three lazy reductions and the block's sums are per thread)
-        u32 order = 2;                   // REEF_SC_FENCE: how a multi-block one-launch round orders its additions before the ticket (sumcheck_kernels.inc: SC_ORDER_*)
-        u32 set_sub = 8;                 // REEF_SC_SET_SUB: the most 128-entry tiles a wave of k_sc_set_parts takes (two entries per lane and tile)
-    } sw;
+    ScSwitches sw;
 };
-// REEF_SC_ONE_LAUNCH=0: the sums of a round are finished by a second kernel and copied back (rounds 1-2 form), for A/B runs.
-// REEF_SC_RANK1=0: gen_eq_table writes the EQ table out, as rounds 1-2 did.  REEF_SC_STRUCT=0: the first round of a step reads
-// the pristine table as dense field elements whatever it holds.  REEF_SC_IDENTITY=0: all three sums of a fused rank-one round
-// are accumulated.  REEF_SC_RANK1_MIN_POW: rounds below this many entries per half are launch-latency-bound; there the dense fused
-// kernel (one launch and the final sums) is shorter than the rank-one round (row factors, pass, final sums), so EQ is written out
-// once the tables have shrunk to it (measured: 2^21-entry tables 1.18 ms dense, 1.27 ms rank-one; 2^24: 2.31 / 2.02; 2^26: 5.67 / 3.68).
+// sumcheck_plan.h has what each switch means and its bounds; this is the one place of row N2 that reads the environment.
 template <int C> static void sc_read_switches(ScCtx<C> *c) {
-    auto off = [](const char *name) { const char *e = exp_env(name); return e && e[0] == '0'; };
-    c->sw.one_launch = !off("REEF_SC_ONE_LAUNCH");
-    c->sw.rank1 = !off("REEF_SC_RANK1");
-    c->sw.structured = !off("REEF_SC_STRUCT");
-    c->sw.identity = !off("REEF_SC_IDENTITY");
-    c->sw.defer = !off("REEF_SC_DEFER");         // REEF_SC_DEFER=0: the first fold of a structured table is written out at once (round 3 form)
-    const char *e = exp_env("REEF_SC_RANK1_MIN_POW");
-    c->sw.r1_min_pow = (e && *e) ? (size_t)std::max<long long>(1, atoll(e)) : (size_t)1 << 21;
-    e = exp_env("REEF_SC_ITEMS");
-    c->sw.items = (e && *e) ? (u32)std::min<long long>(64, std::max<long long>(1, atoll(e))) : 8u;
-    e = exp_env("REEF_SC_SPLIT_MAX");
-    c->sw.split_max = (e && *e) ? (size_t)std::max<long long>(0, atoll(e)) : (size_t)1 << 14;
-    e = exp_env("REEF_SC_SPLIT_BLOCKS");
-    c->sw.split_blocks = (e && *e) ? (u32)std::min<long long>(1024, std::max<long long>(1, atoll(e))) : 64u;
-    e = exp_env("REEF_SC_ONE_LAUNCH_MAX");
-    c->sw.one_launch_max = (e && *e) ? (u32)std::min<long long>(8192, std::max<long long>(1, atoll(e))) : 64u;
-    e = getenv("REEF_SC_FENCE");             // 2 (default since round 6): acq_rel ticket; 1: __threadfence before the ticket; 0: returning atomics + s_waitcnt only
-    c->sw.order = (e && *e) ? (u32)std::min<long long>(2, std::max<long long>(0, atoll(e))) : 2u;
-    e = exp_env("REEF_SC_SET_SUB");
-    c->sw.set_sub = (e && *e) ? (u32)std::min<long long>(64, std::max<long long>(1, atoll(e))) : 8u;
-    e = exp_env("REEF_SC_FLOOR");
-    c->sw.floor_blocks = (e && *e) ? (u32)std::min<long long>(8192, std::max<long long>(1, atoll(e))) : 256u;
+    ScSwitchText t = {};
+    t.one_launch = exp_env("REEF_SC_ONE_LAUNCH");
+    t.rank1 = exp_env("REEF_SC_RANK1");
+    t.structured = exp_env("REEF_SC_STRUCT");
+    t.identity = exp_env("REEF_SC_IDENTITY");
+    t.defer = exp_env("REEF_SC_DEFER");
+    t.r1_min_pow = exp_env("REEF_SC_RANK1_MIN_POW");
+    t.floor_blocks = exp_env("REEF_SC_FLOOR");
+    t.one_launch_max = exp_env("REEF_SC_ONE_LAUNCH_MAX");
+    t.split_max = exp_env("REEF_SC_SPLIT_MAX");
+    t.split_blocks = exp_env("REEF_SC_SPLIT_BLOCKS");
+    t.items = exp_env("REEF_SC_ITEMS");
+    t.order = getenv("REEF_SC_FENCE");
+    t.set_sub = exp_env("REEF_SC_SET_SUB");
+    t.blocks_cap = exp_env("REEF_SC_BLOCKS");
+    c->sw = sc_parse_switches(t);
 }
-// Blocks of a dense round over `work` pairs: a thread pays ~7 products of fixed work (three lazy reductions, the wave's sums)
-// against ~5 per pair, so a mid-sized round is spread over fewer, longer threads (2^20 pairs: 109 -> 74 us with 8 pairs each).
-template <int C> static u32 sc_dense_blocks(const ScCtx<C> *c, size_t work) {
-    const size_t one_each = std::max<size_t>(1, ceil_div(work, 256));      // a pair per thread: the shortest chain
-    const size_t longer = std::max<size_t>(c->sw.floor_blocks, ceil_div(work, (size_t)256 * c->sw.items));   // never fewer blocks than CUs for it
-    return (u32)std::min<size_t>(c->nblocks, std::min(one_each, longer));
+// what the decisions of a round read of the ctx
+template <int C> static ScState sc_state(const ScCtx<C> *c) {
+    ScState s;
+    s.len = c->len; s.valid_t = c->valid_t; s.valid_e = c->valid_e; s.nblocks = c->nblocks;
+    s.r1 = c->r1; s.r1_hi = c->r1_hi; s.r1_hi0 = c->r1_hi0; s.r1_lo = c->r1_lo; s.r1_nq = c->r1_nq; s.r1_prev_pow = c->r1_prev_pow;
+    s.fresh = c->fresh; s.st_ok = c->st_ok; s.defer_on = c->defer_on; s.defer_pow = c->defer_pow; s.defer_hq = c->defer_hq;
+    s.st = c->st;
+    return s;
 }
+static inline dim3 sc_dim3(ScGrid g) { return dim3(g.x, g.y); }
 
 template <int C> static void sc_free(ScCtx<C> *c) {
     if (!c) return;
@@ -118,9 +96,7 @@ template <int C> static reef_status v_sc_create(void **impl, size_t len) {
         c->len = len;
         c->valid_t = c->valid_e = len;
         REEF_TRY(c->lease.enter(c->device, &c->stream));
-        size_t cap = 2048;                   // REEF_SC_BLOCKS: the most blocks a round is spread over (A/B runs)
-        if (const char *e = exp_env("REEF_SC_BLOCKS")) if (*e) cap = (size_t)std::min<long long>(8192, std::max<long long>(1, atoll(e)));
-        c->nblocks = (u32)std::min<size_t>(cap, std::max<size_t>(1, len / 2 / 256));
+        c->nblocks = sc_nblocks(len, c->sw.blocks_cap);
         for (DevBuf *b : {&c->T, &c->T0, &c->E}) REEF_TRY(b->ensure(len * sizeof(fe256)));
         REEF_TRY(c->partial.ensure((size_t)c->nblocks * 27 * sizeof(u64)));
         REEF_TRY(c->out3.ensure(3 * sizeof(fe256)));
@@ -140,9 +116,6 @@ template <int C> static reef_status v_sc_create(void **impl, size_t len) {
 }
 template <int C> static void v_sc_destroy(void *impl) { sc_free((ScCtx<C> *)impl); }
 
-// One-launch rounds only for rounds of a few blocks: 2048 blocks adding 27 limbs each to the same 27 words serialise (2^20-entry
-// round: 58 -> 103 us), a small round saves its second kernel and its copy (46 -> 37 us per round, 16 of the 21 rounds of a 2^21 step).
-template <int C> static bool sc_one_launch(const ScCtx<C> *c, u32 blocks) { return c->sw.one_launch && blocks <= c->sw.one_launch_max; }
 // The kernel posts the call's sequence number (c->seq) to pinned memory after the coefficients: poll briefly (a round that is
 // still streaming gigabytes is waited for the ordinary way), 12 -> 6.6 us per launch-and-wait.
 template <int C> static reef_status sc_wait_posted(ScCtx<C> *c) {
@@ -181,17 +154,13 @@ template <int C> struct R1View {
         fd = f1 + half;
     }
 };
-// a round with `pow` can stay rank-one: both tables have exactly 2*pow live entries and the bit it folds is an FH bit
-template <int C> static bool sc_r1_round(const ScCtx<C> *c, size_t pow) {
-    return c->r1 && c->r1_hi >= 1 && c->valid_e == 2 * pow && c->valid_t == 2 * pow && pow >= c->sw.r1_min_pow;
-}
 // EQ written out where the dense kernels expect it (the live 2^(r1_hi + r1_lo) entries); leaves rank-one mode unless `keep`
 template <int C> static reef_status sc_r1_materialize(ScCtx<C> *c, bool keep = false) {
     constexpr int F = ScCtx<C>::F;
     const R1View<C> v(c);
     const u32 ell_cur = c->r1_hi + c->r1_lo;
     const size_t n = (size_t)1 << ell_cur;
-    hipLaunchKernelGGL(k_sc_eq_table<F>, dim3((u32)std::min<size_t>(4096, ceil_div(n, 256))), dim3(256), 0, c->stream, (const fe256 *)v.fh,
+    hipLaunchKernelGGL(k_sc_eq_table<F>, dim3(sc_fold_blocks(n)), dim3(256), 0, c->stream, (const fe256 *)v.fh,
                        (const fe256 *)v.fl, ell_cur, c->r1_lo, c->E.template as<fe256>());
     if (c->r1_nq)
         hipLaunchKernelGGL(k_sc_r1_masses<F>, dim3(ceil_div(c->r1_nq, 256)), dim3(256), 0, c->stream, (const u32 *)c->r1mq.template as<u32>(),
@@ -209,27 +178,17 @@ template <int C> static reef_status sc_r1_prep(ScCtx<C> *c, const fe256 *r, size
     const u32 hn_next = rows_after >> 1;
     fe256 rr = {};
     if (r) rr = *r;
-    const u32 threads = std::max<u32>(std::max<u32>(hn_next, r ? c->r1_nq : 0u), 1u);
-    hipLaunchKernelGGL(k_sc_r1_prep<F>, dim3(ceil_div(threads, 256)), dim3(256), 0, c->stream, v.fh, hc, r ? 1 : 0, rr, hn_next, v.f0, v.f1, v.fd,
+    hipLaunchKernelGGL(k_sc_r1_prep<F>, dim3(sc_r1_prep_blocks(c->r1_hi, r != nullptr, c->r1_nq)), dim3(256), 0, c->stream, v.fh, hc, r ? 1 : 0, rr, hn_next, v.f0, v.f1, v.fd,
                        c->r1mq.template as<u32>(), c->r1mw.template as<fe256>(), c->r1_nq, (u32)pow);
     REEF_HIP_TRY(hipGetLastError());
     if (r) c->r1_hi -= 1;
     return REEF_OK;
 }
-// grid of the column kernels for `hn` pair rows: blocks over the columns x row groups, at most 1024 blocks (every block
-// leaves 36 limb sums for k_sc_r1_final to add up: 2048 of them cost it 25 us)
-template <int C> static reef_status sc_r1_grid(ScCtx<C> *c, u32 hn, dim3 *grid, u32 *rows_per_chunk) {
-    const u32 gx = ceil_div((size_t)1 << c->r1_lo, 256);
-    const u32 chunks = std::max<u32>(1u, std::min<u32>(hn, std::max<u32>(1u, 1024u / gx)));
-    *rows_per_chunk = ceil_div(hn, chunks);
-    *grid = dim3(gx, ceil_div(hn, *rows_per_chunk));
-    return REEF_OK;
-}
-template <int C> static reef_status sc_r1_finish(ScCtx<C> *c, u32 blocks, size_t pow, reef_fe *out3_host, const fe256 *ident_r = nullptr) {
+// the sums kernels of a rank-one round have left their limb sums in r1acc; hand the coefficients of the round with `pow` to the caller
+template <int C> static reef_status sc_r1_finish(ScCtx<C> *c, size_t pow, reef_fe *out3_host, const fe256 *ident_r = nullptr) {
     constexpr int F = ScCtx<C>::F;
     fe256 rr = {};
     if (ident_r) rr = *ident_r;
-    (void)blocks;
     hipLaunchKernelGGL(k_sc_r1_final<F>, dim3(1), dim3(1024), 0, c->stream, c->r1acc.template as<unsigned long long>(),
                        (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(), (u32)pow, (const u32 *)c->r1mq.template as<u32>(),
                        (const fe256 *)c->r1mw.template as<fe256>(), c->r1_nq, ident_r ? 1 : 0, rr, c->out3.template as<fe256>(), c->pinned3, ++c->seq);
@@ -248,12 +207,9 @@ template <int C> static reef_status sc_struct_open(ScCtx<C> *c, u32 *lo_bits, u3
     c->defer_on = false;                 // the table is replaced
     *rows = 0;
     sc_read_switches<C>(c);
-    size_t ell = 0;
-    while (((size_t)1 << ell) < c->len) ++ell;
-    const u32 lo = (u32)(ell / 2), hi = (u32)ell - lo;
-    *lo_bits = lo;
-    if (!c->sw.rank1 || !c->sw.structured || hi < 2 || c->len / 2 < c->sw.r1_min_pow) return REEF_OK;
-    const u32 H = 1u << hi;
+    *lo_bits = sc_lo_bits(c->len);
+    const u32 H = sc_struct_rows(c->len, c->sw);
+    if (!H) return REEF_OK;
     REEF_TRY(c->st_s32.ensure(c->len * sizeof(u32)));
     REEF_TRY(c->st_flags.ensure((size_t)H * sizeof(u32)));
     {
@@ -268,56 +224,9 @@ template <int C> static reef_status sc_struct_lists(ScCtx<C> *c, u32 H) {
     std::vector<u32> flags(H);
     REEF_HIP_TRY(hipMemcpyAsync(flags.data(), c->st_flags.p, (size_t)H * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));
-    auto cls = [&](u32 row) { return (flags[row] & 2u) ? 2u : (flags[row] & 1u) ? 1u : 0u; };   // K, S, W
-    size_t plain = 0;
-    for (u32 r = 0; r < H; ++r) plain += cls(r) != 0;
-    if (2 * plain < H) return REEF_OK;
     std::vector<u32> lists;
-    const u32 hn = H / 2, hq = H / 4;
-    for (u32 side = 0; side < 2; ++side)
-        for (u32 k = 0; k < 3; ++k) {
-            c->st_sum[side][k].off = (u32)lists.size();
-            for (u32 h = 0; h < hn; ++h)
-                if (cls(h + side * hn) == k) lists.push_back(h);
-            c->st_sum[side][k].n = (u32)lists.size() - c->st_sum[side][k].off;
-        }
-    auto fast = [&](u32 h) { return cls(h) && cls(h + hq) && cls(h + 2 * hq) && cls(h + 3 * hq); };
-    c->st_fast.off = (u32)lists.size();
-    for (u32 h = 0; h < hq; ++h)
-        if (fast(h)) lists.push_back(h);
-    c->st_fast.n = (u32)lists.size() - c->st_fast.off;
-    c->st_gen.off = (u32)lists.size();
-    for (u32 h = 0; h < hq; ++h)
-        if (!fast(h)) lists.push_back(h);
-    c->st_gen.n = (u32)lists.size() - c->st_gen.off;
-    {
-        const u32 h8 = hq / 2;
-        auto fast8 = [&](u32 g) { return h8 && fast(g) && fast(g + h8); };
-        c->st_f8.off = (u32)lists.size();
-        for (u32 g = 0; g < h8; ++g)
-            if (fast8(g)) lists.push_back(g);
-        c->st_f8.n = (u32)lists.size() - c->st_f8.off;
-        c->st_f8x.off = (u32)lists.size();
-        for (u32 h = 0; h < hq; ++h)
-            if (h8 && fast8(h % h8)) lists.push_back(h);
-        c->st_f8x.n = (u32)lists.size() - c->st_f8x.off;
-        c->st_frest.off = (u32)lists.size();
-        for (u32 h = 0; h < hq; ++h)
-            if (fast(h) && !(h8 && fast8(h % h8))) lists.push_back(h);
-        c->st_frest.n = (u32)lists.size() - c->st_frest.off;
-        c->st_g8.off = (u32)lists.size();
-        for (u32 g = 0; g < h8; ++g)
-            if (!fast8(g)) lists.push_back(g);
-        c->st_g8.n = (u32)lists.size() - c->st_g8.off;
-        for (u32 b = 0; b < 4; ++b)
-            for (u32 k = 0; k < 2; ++k) {                  // cls: 1 = S, 2 = K
-                c->st_d8[b][k].off = (u32)lists.size();
-                for (u32 h = 0; h < hq; ++h)
-                    if (h8 && fast8(h % h8) && cls(h + b * hq) == k + 1) lists.push_back(h);
-                c->st_d8[b][k].n = (u32)lists.size() - c->st_d8[b][k].off;
-            }
-    }
-    lists.push_back(0);
+    if (!sc_build_row_lists(flags.data(), H, &c->st, &lists)) return REEF_OK;
+    const u32 hq = H / 4;
     REEF_TRY(c->st_lists.ensure(lists.size() * sizeof(u32)));
     REEF_HIP_TRY(hipMemcpyAsync(c->st_lists.p, lists.data(), lists.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
     REEF_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -336,68 +245,15 @@ template <int C> static reef_status sc_struct_build(ScCtx<C> *c, const fe256 *sr
     REEF_HIP_TRY(hipGetLastError());
     return sc_struct_lists<C>(c, H);
 }
-// the first round of a step on a structured table: tables are whole (2*pow = len), T is pristine, EQ is rank-one with all its FH bits
-template <int C> static bool sc_struct_round(const ScCtx<C> *c, size_t pow) {
-    return c->st_ok && c->fresh && 2 * pow == c->len && c->r1_hi == c->r1_hi0 && c->sw.structured;
-}
-// grid of a list-driven column kernel: blocks over the columns x row groups (at most 2048 blocks, at most 256 rows per thread)
-template <int C> static dim3 sc_list_grid(const ScCtx<C> *c, u32 nlist) {
-    const u32 gx = ceil_div((size_t)1 << c->r1_lo, 256);
-    const u32 gy = std::max<u32>(1u, std::min<u32>(nlist, std::max<u32>(std::max<u32>(1u, 1024u / gx), ceil_div(nlist, 256))));
-    return dim3(gx, gy);
-}
-// round-one sums of a structured table: per side, the S rows, the W rows and the K rows; returns the number of partial blocks
-template <int C> static reef_status sc_struct_sums(ScCtx<C> *c, u32 *blocks_out) {
-    constexpr int F = ScCtx<C>::F;
-    const R1View<C> v(c);
-    const u32 hn = 1u << (c->r1_hi - 1);
-    const u32 *lists = c->st_lists.template as<u32>();
-    size_t total = 0;
-    for (u32 side = 0; side < 2; ++side) {
-        for (u32 k = 0; k < 2; ++k) {
-            const dim3 g = sc_list_grid<C>(c, c->st_sum[side][k].n);
-            if (c->st_sum[side][k].n) total += (size_t)g.x * g.y;
-        }
-        total += std::max(ceil_div(c->st_sum[0][2].n, 256), ceil_div(c->st_sum[1][2].n, 256));   // the merged launch: the larger set's blocks, per side
-    }
-    (void)total;
-    unsigned long long *part = c->r1acc.template as<unsigned long long>();
-    const fe256 *T0 = c->T0.template as<fe256>();
-    u32 at = 0;
-    for (u32 side = 0; side < 2; ++side) {
-        const fe_limbs *fa = side ? v.f1 : v.f0;
-        const auto &W = c->st_sum[side][0], &S = c->st_sum[side][1];
-        if (S.n) {
-            const dim3 g = sc_list_grid<C>(c, S.n);
-            hipLaunchKernelGGL((k_sc_r1s_rows<F, false>), g, dim3(256), 0, c->stream, T0, (const u32 *)c->st_s32.template as<u32>(), c->r1_lo, side ? hn : 0u, side,
-                               lists + S.off, S.n, fa, (const fe_limbs *)v.fd, (const fe256 *)v.fl, part);
-            at += g.x * g.y;
-        }
-        if (W.n) {
-            const dim3 g = sc_list_grid<C>(c, W.n);
-            hipLaunchKernelGGL((k_sc_r1s_rows<F, true>), g, dim3(256), 0, c->stream, T0, (const u32 *)c->st_s32.template as<u32>(), c->r1_lo, side ? hn : 0u, side,
-                               lists + W.off, W.n, fa, (const fe_limbs *)v.fd, (const fe256 *)v.fl, part);
-            at += g.x * g.y;
-        }
-    }
-    {                                                         // the constant rows of both sides: one launch
-        ScConstSets sets = {};
-        u32 kb = 0;
-        for (u32 side = 0; side < 2; ++side) {
-            const auto &K = c->st_sum[side][2];
-            sets.row_off[side] = side ? hn : 0u; sets.side[side] = side; sets.nlist[side] = K.n; sets.list[side] = lists + K.off;
-            sets.fa[side] = side ? v.f1 : v.f0; sets.fd[side] = v.fd;
-            kb = std::max(kb, ceil_div(K.n, 256));
-        }
-        if (kb) {
-            hipLaunchKernelGGL(k_sc_r1s_const<F>, dim3(kb, 2), dim3(256), 0, c->stream, T0, c->r1_lo, sets, (const fe256 *)c->st_sumfl.template as<fe256>(),
-                               part);
-            at += 2 * kb;
-        }
-    }
-    REEF_HIP_TRY(hipGetLastError());
-    *blocks_out = at;
-    return REEF_OK;
+// k_sc_r1_fold_coeffs_cs (any of its forms) over one row list: the rows' fold from their 4-byte sources and their share of the next
+// sums; hn: pair rows after the fold, which KA, KC and the S masks in st_k are laid out by
+template <int C, class K>
+static void sc_launch_cs(ScCtx<C> *c, const R1View<C> &v, K kernel, ScGrid g, u32 hn, const ScList &L, const fe256 &r, unsigned long long *out) {
+    fe_limbs *ka = c->st_k.template as<fe_limbs>(), *kc = ka + hn;
+    u32 *smask = reinterpret_cast<u32 *>(kc + hn);
+    hipLaunchKernelGGL(kernel, sc_dim3(g), dim3(256), 0, c->stream, (const u32 *)c->st_s32.template as<u32>(), c->T.template as<fe256>(), c->r1_lo, hn,
+                       c->st_lists.template as<u32>() + L.off, L.n, r, (const fe_limbs *)ka, (const fe_limbs *)kc, (const u32 *)smask, (const fe_limbs *)v.f0,
+                       (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl, out);
 }
 
 // The deferred first fold (k_sc_r1_fold_coeffs_cs<.., WRITE = false>) written out after all: any call that is not the second fold
@@ -405,17 +261,10 @@ template <int C> static reef_status sc_struct_sums(ScCtx<C> *c, u32 *blocks_out)
 template <int C> static reef_status sc_defer_flush(ScCtx<C> *c) {
     if (!c->defer_on) return REEF_OK;
     c->defer_on = false;
-    const u32 hq = c->defer_hq;
     const R1View<C> v(c);
-    const u32 *lists = c->st_lists.template as<u32>();
-    fe_limbs *ka = c->st_k.template as<fe_limbs>(), *kc = ka + hq;
-    u32 *smask = reinterpret_cast<u32 *>(kc + hq);
-    const dim3 g = sc_list_grid<C>(c, c->st_f8x.n);
     REEF_TRY(c->stage.ensure((size_t)R1_GROUPS * R1_SLOTS * sizeof(u64)));   // scratch accumulators: nobody reads these sums
-    hipLaunchKernelGGL((k_sc_r1_fold_coeffs_cs<ScCtx<C>::F, true, true>), g, dim3(256), 0, c->stream, (const u32 *)c->st_s32.template as<u32>(),
-                       c->T.template as<fe256>(), c->r1_lo, hq, lists + c->st_f8x.off, c->st_f8x.n, c->defer_r1, (const fe_limbs *)ka, (const fe_limbs *)kc,
-                       (const u32 *)smask, (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl,
-                       c->stage.template as<unsigned long long>());
+    sc_launch_cs<C>(c, v, k_sc_r1_fold_coeffs_cs<ScCtx<C>::F, true, true>, sc_list_grid(c->r1_lo, c->st.f8x.n), c->defer_hq, c->st.f8x, c->defer_r1,
+                    c->stage.template as<unsigned long long>());
     REEF_HIP_TRY(hipGetLastError());
     return REEF_OK;
 }
@@ -519,10 +368,9 @@ template <int C> static reef_status v_sc_set_parts(void *impl, const reef_sc_par
     a.start[SC_MAX_PARTS] = (u32)start;
     u32 lo = 0, H = 0;
     REEF_TRY(sc_struct_open<C>(c, &lo, &H));
-    // tiles per wave: 8 (16 entries per lane) where that still leaves 8192 waves -- by measurement at 2^26 entries, where the kernel
-    // alone takes a quarter less time with 4 tiles than with 1 (the sweep: profiles/r12_sc_set_parts_timing.txt)
-    const u32 tiles = (u32)ceil_div(c->len, 128), sub = std::max<u32>(1u, std::min<u32>(c->sw.set_sub, tiles / 8192u));
-    hipLaunchKernelGGL(k_sc_set_parts<ScCtx<C>::F>, dim3(ceil_div(ceil_div(tiles, sub), 4)), dim3(256), 0, c->stream, a, (u32)c->len, lo, sub,
+    u32 sub = 0;
+    const u32 blocks = sc_set_parts_blocks(c->len, c->sw, &sub);
+    hipLaunchKernelGGL(k_sc_set_parts<ScCtx<C>::F>, dim3(blocks), dim3(256), 0, c->stream, a, (u32)c->len, lo, sub,
                        c->T0.template as<fe256>(), H ? c->st_flags.template as<u32>() : nullptr, H ? c->st_s32.template as<u32>() : nullptr);
     REEF_HIP_TRY(hipGetLastError());
     c->fresh = c->has_table = true;
@@ -585,38 +433,96 @@ template <int C> static reef_status v_sc_lookup(void *impl, const uint64_t *idx,
     return REEF_OK;
 }
 
+// ---- The rounds.  An entry point checks its arguments, asks sc_round_plan (sumcheck_plan.h) which route the round takes and with which
+// grids, and hands over to the route's launch function below; the state changes are theirs, in their order among the launches.
+
+// the plan of this call from the state `s`, a deferred fold written out where the plan says so; REEF_ERR_ARG: too few live entries
+template <int C> static reef_status sc_plan_call(ScCtx<C> *c, ScCall call, size_t pow, const ScState &s, ScRoundPlan *p) {
+    const reef_status rs = sc_round_plan(call, pow, s, c->sw, p);
+    if (p->flush) REEF_TRY(sc_defer_flush<C>(c));
+    if (rs != REEF_OK)
+        set_error("%s with pow = %zu needs %zu live entries per table; T has %zu, EQ has %zu", call == SC_COEFFS ? "round" : "fold", pow, 2 * pow, c->valid_t, c->valid_e);
+    return rs;
+}
+// The kernels of a fused rank-one round come with the sum t1 e1 (template argument S11) and without: the sum-check identity gives it
+// where the coefficients of THIS round are still in out3 and r is its challenge (REEF_SC_IDENTITY=0: all three sums are accumulated).
+template <class K> static K sc_s11(bool ident, K with_sum, K without) { return ident ? without : with_sum; }
+// k_sc_r1_fold_coeffs over a row list (list == nullptr: over all hn rows): fold and the next sums in one pass over T
+template <int C>
+static void sc_launch_general(ScCtx<C> *c, const R1View<C> &v, const ScRoundPlan &p, ScGrid g, const u32 *list, u32 nlist, const fe256 &rr) {
+    constexpr int F = ScCtx<C>::F;
+    hipLaunchKernelGGL((sc_s11(p.ident, k_sc_r1_fold_coeffs<F, true>, k_sc_r1_fold_coeffs<F, false>)), sc_dim3(g), dim3(256), 0, c->stream,
+                       (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(), c->T.template as<fe256>(), c->r1_lo, p.hn, list, nlist, rr,
+                       (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl, c->r1acc.template as<unsigned long long>());
+}
+// k_sc_coeffs over `pairs` pairs of the tables as they stand, and the coefficients to the caller
+template <int C> static reef_status sc_dense_sums(ScCtx<C> *c, const ScRoundPlan &p, size_t pairs, reef_fe *out3_host) {
+    const bool one = p.one_launch;
+    hipLaunchKernelGGL(k_sc_coeffs<ScCtx<C>::F>, dim3(p.blocks), dim3(256), 0, c->stream, (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(),
+                       (const fe256 *)c->E.template as<fe256>(), (u32)pairs, c->partial.template as<unsigned long long>(),
+                       one ? c->gacc.template as<unsigned long long>() : nullptr, c->pinned3, one ? ++c->seq : 0u, c->sw.order);
+    return sc_dense_finish<C>(c, one, p.blocks, out3_host);
+}
+// FH folded with r, then T (EQ's share of the fold is k_sc_r1_prep)
+template <int C> static reef_status sc_r1_fold(ScCtx<C> *c, const ScRoundPlan &p, size_t pow, const fe256 &rr) {
+    REEF_TRY(sc_r1_prep<C>(c, &rr, pow));
+    hipLaunchKernelGGL(k_sc_r1_fold<ScCtx<C>::F>, dim3(p.fold_blocks), dim3(256), 0, c->stream, (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(),
+                       c->T.template as<fe256>(), (u32)pow, rr);
+    c->fresh = false;
+    c->valid_t = c->valid_e = pow;
+    return REEF_OK;
+}
+
+// SC_SUMS_STRUCT: per side, the S rows and the W rows; then the constant rows of both sides in one launch
+template <int C> static reef_status sc_sums_struct(ScCtx<C> *c, const ScRoundPlan &p, size_t pow, reef_fe *out3_host) {
+    constexpr int F = ScCtx<C>::F;
+    const R1View<C> v(c);
+    const u32 hn = p.hn;
+    const u32 *lists = c->st_lists.template as<u32>();
+    unsigned long long *part = c->r1acc.template as<unsigned long long>();
+    const fe256 *T0 = c->T0.template as<fe256>();
+    ScConstSets sets = {};
+    for (u32 side = 0; side < 2; ++side) {
+        const fe_limbs *fa = side ? v.f1 : v.f0;
+        const ScList &W = c->st.sum[side][0], &S = c->st.sum[side][1], &K = c->st.sum[side][2];
+        if (S.n)
+            hipLaunchKernelGGL((k_sc_r1s_rows<F, false>), sc_dim3(p.g_sum[side][1]), dim3(256), 0, c->stream, T0, (const u32 *)c->st_s32.template as<u32>(), c->r1_lo,
+                               side ? hn : 0u, side, lists + S.off, S.n, fa, (const fe_limbs *)v.fd, (const fe256 *)v.fl, part);
+        if (W.n)
+            hipLaunchKernelGGL((k_sc_r1s_rows<F, true>), sc_dim3(p.g_sum[side][0]), dim3(256), 0, c->stream, T0, (const u32 *)c->st_s32.template as<u32>(), c->r1_lo,
+                               side ? hn : 0u, side, lists + W.off, W.n, fa, (const fe_limbs *)v.fd, (const fe256 *)v.fl, part);
+        sets.row_off[side] = side ? hn : 0u; sets.side[side] = side; sets.nlist[side] = K.n; sets.list[side] = lists + K.off;
+        sets.fa[side] = fa; sets.fd[side] = v.fd;
+    }
+    if (p.const_blocks)
+        hipLaunchKernelGGL(k_sc_r1s_const<F>, dim3(p.const_blocks, 2), dim3(256), 0, c->stream, T0, c->r1_lo, sets, (const fe256 *)c->st_sumfl.template as<fe256>(), part);
+    REEF_HIP_TRY(hipGetLastError());
+    return sc_r1_finish<C>(c, pow, out3_host);
+}
+template <int C> static reef_status sc_sums_r1(ScCtx<C> *c, const ScRoundPlan &p, size_t pow, reef_fe *out3_host) {
+    const R1View<C> v(c);
+    hipLaunchKernelGGL(k_sc_r1_coeffs<ScCtx<C>::F>, sc_dim3(p.grid), dim3(256), 0, c->stream, (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(), c->r1_lo,
+                       p.hn, p.rows_per_chunk, (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl,
+                       c->r1acc.template as<unsigned long long>());
+    return sc_r1_finish<C>(c, pow, out3_host);
+}
+
 // linear_mle_product, first half: out = (xsq, x, con)
 template <int C> static reef_status v_sc_coeffs(void *impl, size_t pow, reef_fe *out3_host) {
     ScCtx<C> *c = (ScCtx<C> *)impl;
     if (!c || !out3_host || pow == 0 || 2 * pow > c->len) { set_error("bad argument"); return REEF_ERR_ARG; }
     DeviceCall call(c, OnExit::STAY);
     REEF_TRY(call.enter());
-    REEF_TRY(sc_defer_flush<C>(c));        // rows whose first fold was deferred are written out: this is not their second fold
-    if (2 * pow > std::min(c->valid_t, c->valid_e)) { set_error("round with pow = %zu needs %zu live entries per table; T has %zu, EQ has %zu", pow, 2 * pow, c->valid_t, c->valid_e); return REEF_ERR_ARG; }
-    if (sc_r1_round<C>(c, pow) && sc_struct_round<C>(c, pow)) {
-        u32 blocks = 0;
-        REEF_TRY(sc_struct_sums<C>(c, &blocks));
-        return sc_r1_finish<C>(c, blocks, pow, out3_host);
-    }
-    if (sc_r1_round<C>(c, pow)) {
-        const R1View<C> v(c);
-        const u32 hn = 1u << (c->r1_hi - 1);
-        dim3 grid;
-        u32 rpc;
-        REEF_TRY(sc_r1_grid<C>(c, hn, &grid, &rpc));
-        hipLaunchKernelGGL(k_sc_r1_coeffs<ScCtx<C>::F>, grid, dim3(256), 0, c->stream, (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(), c->r1_lo,
-                           hn, rpc, (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl,
-                           c->r1acc.template as<unsigned long long>());
-        return sc_r1_finish<C>(c, grid.x * grid.y, pow, out3_host);
+    ScRoundPlan p;
+    REEF_TRY(sc_plan_call<C>(c, SC_COEFFS, pow, sc_state<C>(c), &p));
+    switch (p.route) {
+    case SC_SUMS_STRUCT: return sc_sums_struct<C>(c, p, pow, out3_host);
+    case SC_SUMS_R1: return sc_sums_r1<C>(c, p, pow, out3_host);
+    default: break;
     }
     c->r1_prev_pow = 0;
-    if (c->r1) REEF_TRY(sc_r1_materialize<C>(c));
-    const u32 blocks = sc_dense_blocks<C>(c, pow);
-    const bool one = sc_one_launch<C>(c, blocks);
-    hipLaunchKernelGGL(k_sc_coeffs<ScCtx<C>::F>, dim3(blocks), dim3(256), 0, c->stream, (c->fresh ? c->T0 : c->T).template as<fe256>(),
-                       c->E.template as<fe256>(), (u32)pow, c->partial.template as<unsigned long long>(),
-                       one ? c->gacc.template as<unsigned long long>() : nullptr, c->pinned3, one ? ++c->seq : 0u, c->sw.order);
-    return sc_dense_finish<C>(c, one, blocks, out3_host);
+    if (p.materialize) REEF_TRY(sc_r1_materialize<C>(c));
+    return sc_dense_sums<C>(c, p, pow, out3_host);
 }
 
 // linear_mle_product, second half
@@ -625,30 +531,108 @@ template <int C> static reef_status v_sc_fold(void *impl, size_t pow, const reef
     if (!c || !r || pow == 0 || 2 * pow > c->len) { set_error("bad argument"); return REEF_ERR_ARG; }
     DeviceCall call(c, OnExit::STAY);
     REEF_TRY(call.enter());
-    REEF_TRY(sc_defer_flush<C>(c));        // rows whose first fold was deferred are written out: this is not their second fold
     c->r1_prev_pow = 0;                  // the tables change: no coefficients on the device describe them any more
-    if (2 * pow > std::min(c->valid_t, c->valid_e)) { set_error("fold with pow = %zu needs %zu live entries per table; T has %zu, EQ has %zu", pow, 2 * pow, c->valid_t, c->valid_e); return REEF_ERR_ARG; }
+    ScRoundPlan p;
+    REEF_TRY(sc_plan_call<C>(c, SC_FOLD, pow, sc_state<C>(c), &p));
     fe256 rr;
     memcpy(&rr, r, sizeof rr);
-    if (sc_r1_round<C>(c, pow)) {
-        REEF_TRY(sc_r1_prep<C>(c, &rr, pow));
-        const u32 fb = (u32)std::min<size_t>(4096, std::max<size_t>(1, ceil_div(pow, 256)));
-        hipLaunchKernelGGL(k_sc_r1_fold<ScCtx<C>::F>, dim3(fb), dim3(256), 0, c->stream, (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(),
-                           c->T.template as<fe256>(), (u32)pow, rr);
-        c->fresh = false;
-        c->valid_t = c->valid_e = pow;
+    if (p.route == SC_FOLD_R1) {
+        REEF_TRY(sc_r1_fold<C>(c, p, pow, rr));
         REEF_HIP_TRY(hipGetLastError());
-        if (c->r1_hi == 0) REEF_TRY(sc_r1_materialize<C>(c));      // the FH bits are used up: 2^lo entries, dense from here
+        if (p.materialize) REEF_TRY(sc_r1_materialize<C>(c));      // the FH bits are used up: 2^lo entries, dense from here
         return REEF_OK;
     }
-    if (c->r1) REEF_TRY(sc_r1_materialize<C>(c));
+    if (p.materialize) REEF_TRY(sc_r1_materialize<C>(c));
     c->valid_t = c->valid_e = pow;
-    const u32 blocks = (u32)std::min<size_t>(4096, std::max<size_t>(1, ceil_div(pow, 256)));
-    hipLaunchKernelGGL(k_sc_fold<ScCtx<C>::F>, dim3(blocks), dim3(256), 0, c->stream, (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(),
+    hipLaunchKernelGGL(k_sc_fold<ScCtx<C>::F>, dim3(p.fold_blocks), dim3(256), 0, c->stream, (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(),
                        c->T.template as<fe256>(), c->E.template as<fe256>(), (u32)pow, rr);
     c->fresh = false;
     REEF_HIP_TRY(hipGetLastError());
     return REEF_OK;   // ordered before the next call on the ctx's stream
+}
+
+// SC_FC_DEFER, after k_sc_r1_kprep: sums of the next round from the structure.  The rows of st.f8x are not written (their second fold
+// will write a quarter-size table from the sources): their share of the sums comes straight from the pristine rows, block by block, with
+// the scaled row factors -- 18 multiply-adds per 4-byte entry, no t' anywhere.  The other fast rows and the general ones as in SC_FC_STRUCT.
+template <int C> static void sc_fc_defer(ScCtx<C> *c, const ScRoundPlan &p, const R1View<C> &v, size_t pow, const fe256 &rr) {
+    constexpr int F = ScCtx<C>::F;
+    const u32 hn = p.hn;
+    const u32 *lists = c->st_lists.template as<u32>();
+    fe_limbs *ka = c->st_k.template as<fe_limbs>(), *kc = ka + hn;
+    u32 *smask = reinterpret_cast<u32 *>(kc + hn);
+    unsigned long long *part = c->r1acc.template as<unsigned long long>();
+    fe_limbs *fa4 = reinterpret_cast<fe_limbs *>(smask + hn) + hn, *fd4 = fa4 + 4 * (size_t)hn;   // after K2A, K2C
+    hipLaunchKernelGGL(k_sc_r2s_factors<F>, dim3(p.prep_blocks), dim3(256), 0, c->stream, (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, hn,
+                       rr, fa4, fd4);
+    const fe256 *T0 = c->T0.template as<fe256>();
+    ScConstSets sets = {};
+    for (u32 b = 0; b < 4; ++b) {
+        const ScList &S = c->st.d8[b][0], &K = c->st.d8[b][1];
+        const fe_limbs *fab = fa4 + (size_t)b * hn, *fdb = fd4 + (size_t)b * hn;
+        if (S.n)
+            hipLaunchKernelGGL((k_sc_r1s_rows<F, false>), sc_dim3(p.g_d8[b]), dim3(256), 0, c->stream, T0, (const u32 *)c->st_s32.template as<u32>(), c->r1_lo, b * hn,
+                               b & 1u, lists + S.off, S.n, fab, fdb, (const fe256 *)v.fl, part);
+        sets.row_off[b] = b * hn; sets.side[b] = b & 1u; sets.nlist[b] = K.n; sets.list[b] = lists + K.off;
+        sets.fa[b] = fab; sets.fd[b] = fdb;
+    }
+    if (p.const_blocks)
+        hipLaunchKernelGGL(k_sc_r1s_const<F>, dim3(p.const_blocks, 4), dim3(256), 0, c->stream, T0, c->r1_lo, sets, (const fe256 *)c->st_sumfl.template as<fe256>(), part);
+    if (c->st.frest.n)
+        sc_launch_cs<C>(c, v, sc_s11(p.ident, k_sc_r1_fold_coeffs_cs<F, true, true>, k_sc_r1_fold_coeffs_cs<F, false, true>), p.g_frest, hn, c->st.frest, rr, part);
+    if (c->st.gen.n) sc_launch_general<C>(c, v, p, p.g_gen, lists + c->st.gen.off, c->st.gen.n, rr);
+    if (p.points_blocks)                     // the few entries of t' the masses of the next round read
+        hipLaunchKernelGGL(k_sc_defer_points<F>, dim3(p.points_blocks), dim3(256), 0, c->stream, (const u32 *)c->st_s32.template as<u32>(), c->T.template as<fe256>(),
+                           c->r1_lo, hn, (u32)(pow / 2), (const u32 *)c->r1mq.template as<u32>(), c->r1_nq, rr, (const fe_limbs *)ka, (const fe_limbs *)kc,
+                           (const u32 *)smask);
+    c->defer_on = true;
+    c->defer_r1 = rr;
+    c->defer_pow = pow / 2;
+    c->defer_hq = hn;
+}
+// SC_FC_STRUCT, SC_FC_DEFER: rows whose four sources are constant or small: 4-byte reads; the few others through the general kernel
+template <int C> static void sc_fc_struct(ScCtx<C> *c, const ScRoundPlan &p, const R1View<C> &v, size_t pow, const fe256 &rr) {
+    constexpr int F = ScCtx<C>::F;
+    const u32 hn = p.hn;
+    fe_limbs *ka = c->st_k.template as<fe_limbs>(), *kc = ka + hn;
+    u32 *smask = reinterpret_cast<u32 *>(kc + hn);
+    hipLaunchKernelGGL(k_sc_r1_kprep<F>, dim3(p.prep_blocks), dim3(256), 0, c->stream, (const fe256 *)c->T0.template as<fe256>(),
+                       (const u32 *)c->st_flags.template as<u32>(), c->r1_lo, hn, rr, ka, kc, smask);
+    if (p.route == SC_FC_DEFER) return sc_fc_defer<C>(c, p, v, pow, rr);
+    if (c->st.fast.n)
+        sc_launch_cs<C>(c, v, sc_s11(p.ident, k_sc_r1_fold_coeffs_cs<F, true>, k_sc_r1_fold_coeffs_cs<F, false>), p.g_fast, hn, c->st.fast, rr,
+                        c->r1acc.template as<unsigned long long>());
+    if (c->st.gen.n) sc_launch_general<C>(c, v, p, p.g_gen, c->st_lists.template as<u32>() + c->st.gen.off, c->st.gen.n, rr);
+}
+// SC_FC_SECOND: the first fold was deferred for the rows of st.f8x and this call is their SECOND fold -- straight from the 4-byte
+// sources.  hn = an eighth of the pristine rows = half of defer_hq: g < hn; st.f8 from the sources, st.g8 from the dense rows
+template <int C> static void sc_fc_second(ScCtx<C> *c, const ScRoundPlan &p, const R1View<C> &v, const fe256 &rr) {
+    constexpr int F = ScCtx<C>::F;
+    c->defer_on = false;
+    const u32 hn = p.hn, hq = p.hq;
+    const u32 *lists = c->st_lists.template as<u32>();
+    fe_limbs *ka = c->st_k.template as<fe_limbs>(), *kc = ka + hq;
+    u32 *smask = reinterpret_cast<u32 *>(kc + hq);
+    fe_limbs *k2a = reinterpret_cast<fe_limbs *>(smask + hq), *k2c = k2a + hn;
+    hipLaunchKernelGGL(k_sc_r2_kprep<F>, dim3(p.prep_blocks), dim3(256), 0, c->stream, (const fe_limbs *)ka, (const fe_limbs *)kc, hn, rr, k2a, k2c);
+    hipLaunchKernelGGL((sc_s11(p.ident, k_sc_r2_fold_coeffs_cs<F, true>, k_sc_r2_fold_coeffs_cs<F, false>)), sc_dim3(p.g_f8), dim3(256), 0, c->stream,
+                       (const u32 *)c->st_s32.template as<u32>(), c->T.template as<fe256>(), c->r1_lo, hq, lists + c->st.f8.off, c->st.f8.n, c->defer_r1, rr,
+                       (const fe_limbs *)k2a, (const fe_limbs *)k2c, (const u32 *)smask, (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd,
+                       (const fe256 *)v.fl, c->r1acc.template as<unsigned long long>());
+    if (c->st.g8.n) sc_launch_general<C>(c, v, p, p.g_gen, lists + c->st.g8.off, c->st.g8.n, rr);
+}
+// SC_FC_R1 and the three above: the next round stays rank-one: fold and its sums in one pass over T
+template <int C> static reef_status sc_fc_rank1(ScCtx<C> *c, const ScRoundPlan &p, size_t pow, const fe256 &rr, reef_fe *out3_host) {
+    REEF_TRY(sc_r1_prep<C>(c, &rr, pow));
+    const R1View<C> v(c);
+    switch (p.route) {
+    case SC_FC_STRUCT:
+    case SC_FC_DEFER: sc_fc_struct<C>(c, p, v, pow, rr); break;
+    case SC_FC_SECOND: sc_fc_second<C>(c, p, v, rr); break;
+    default: sc_launch_general<C>(c, v, p, p.grid, nullptr, 0, rr);
+    }
+    c->fresh = false;
+    c->valid_t = c->valid_e = pow;
+    return sc_r1_finish<C>(c, pow / 2, out3_host, p.ident ? &rr : nullptr);
 }
 
 // fold with `pow` and return the coefficients of the next round (pow/2) from the same pass
@@ -657,189 +641,33 @@ template <int C> static reef_status v_sc_fold_coeffs(void *impl, size_t pow, con
     if (!c || !r || !out3_host || pow < 2 || 2 * pow > c->len) { set_error("bad argument"); return REEF_ERR_ARG; }
     DeviceCall call(c, OnExit::STAY);
     REEF_TRY(call.enter());
-    const size_t prev_pow = c->r1_prev_pow;
+    const ScState s = sc_state<C>(c);    // with r1_prev_pow: do the coefficients on the device describe the tables this call folds?
     c->r1_prev_pow = 0;
-    if (2 * pow > std::min(c->valid_t, c->valid_e)) { set_error("fold with pow = %zu needs %zu live entries per table; T has %zu, EQ has %zu", pow, 2 * pow, c->valid_t, c->valid_e); return REEF_ERR_ARG; }
+    ScRoundPlan p;
+    REEF_TRY(sc_plan_call<C>(c, SC_FOLD_COEFFS, pow, s, &p));
     fe256 rr;
     memcpy(&rr, r, sizeof rr);
-    if (c->defer_on && !(pow == c->defer_pow && sc_r1_round<C>(c, pow) && c->r1_hi >= 2 && pow / 2 >= c->sw.r1_min_pow)) REEF_TRY(sc_defer_flush<C>(c));
-    if (sc_r1_round<C>(c, pow)) {
-        if (c->r1_hi >= 2 && pow / 2 >= c->sw.r1_min_pow) {      // the next round stays rank-one: fold and its sums in one pass over T
-            const u32 hn = 1u << (c->r1_hi - 2);
-            const bool structured = sc_struct_round<C>(c, pow);
-            // the first fold was deferred for the rows of st_f8x: this call is their SECOND fold -- straight from the 4-byte sources
-            const bool second = c->defer_on;
-            // ... or it is the first fold of a structured table and the next round will be of this kind too: defer what can be
-            const bool defer = structured && c->sw.defer && c->r1_hi >= 3 && pow / 4 >= c->sw.r1_min_pow && c->st_f8.n > 0;
-            REEF_TRY(sc_r1_prep<C>(c, &rr, pow));
-            const R1View<C> v(c);
-            dim3 grid;
-            u32 rpc;
-            REEF_TRY(sc_r1_grid<C>(c, hn, &grid, &rpc));
-            // the coefficients of THIS round are still in out3 and r is its challenge: sum t1 e1 of the next round follows from
-            // the sum-check identity (REEF_SC_IDENTITY=0: all three sums are accumulated)
-            const bool ident = prev_pow == pow && c->sw.identity;
-            const fe256 *Tsrc = (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>();
-            unsigned long long *part = c->r1acc.template as<unsigned long long>();
-            u32 blocks = 0;
-            auto general = [&](const u32 *list, u32 nlist, dim3 g, unsigned long long *out) {
-                if (ident)
-                    hipLaunchKernelGGL((k_sc_r1_fold_coeffs<ScCtx<C>::F, false>), g, dim3(256), 0, c->stream, Tsrc, c->T.template as<fe256>(), c->r1_lo, hn, list, nlist,
-                                       rr, (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl, out);
-                else
-                    hipLaunchKernelGGL((k_sc_r1_fold_coeffs<ScCtx<C>::F, true>), g, dim3(256), 0, c->stream, Tsrc, c->T.template as<fe256>(), c->r1_lo, hn, list, nlist,
-                                       rr, (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl, out);
-            };
-            if (structured) {
-                // rows whose four sources are constant or small: 4-byte reads; the few others through the dense kernel
-                const u32 *lists = c->st_lists.template as<u32>();
-                fe_limbs *ka = c->st_k.template as<fe_limbs>(), *kc = ka + hn;
-                u32 *smask = reinterpret_cast<u32 *>(kc + hn);
-                const dim3 gf = sc_list_grid<C>(c, c->st_fast.n), gg = sc_list_grid<C>(c, c->st_gen.n);
-                hipLaunchKernelGGL(k_sc_r1_kprep<ScCtx<C>::F>, dim3(ceil_div(hn, 256)), dim3(256), 0, c->stream, (const fe256 *)c->T0.template as<fe256>(),
-                                   (const u32 *)c->st_flags.template as<u32>(), c->r1_lo, hn, rr, ka, kc, smask);
-                if (defer) {
-                    // sums of the next round from the structure; rows of st_f8x are not written (their second fold will write a
-                    // quarter-size table from the sources), the other fast rows and the general ones as before
-                    const dim3 gr = sc_list_grid<C>(c, c->st_frest.n);
-                    size_t nblk = (size_t)gr.x * gr.y + (size_t)gg.x * gg.y;
-                    for (u32 b = 0; b < 4; ++b) {
-                        const dim3 gs = sc_list_grid<C>(c, c->st_d8[b][0].n);
-                        nblk += (c->st_d8[b][0].n ? (size_t)gs.x * gs.y : 0) + 4 * (size_t)ceil_div(c->st_d8[b][1].n, 256);   // the merged launch has 4 x the largest set's blocks at most
-                    }
-                    auto cs = [&](auto kernel, const typename ScCtx<C>::StList &L, dim3 g) {
-                        hipLaunchKernelGGL(kernel, g, dim3(256), 0, c->stream, (const u32 *)c->st_s32.template as<u32>(), c->T.template as<fe256>(), c->r1_lo, hn,
-                                           lists + L.off, L.n, rr, (const fe_limbs *)ka, (const fe_limbs *)kc, (const u32 *)smask, (const fe_limbs *)v.f0,
-                                           (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl, part);
-                        blocks += g.x * g.y;
-                    };
-                    // the deferred rows: their share of the next round's sums straight from the pristine rows, block by block, with
-                    // the scaled row factors -- 18 multiply-adds per 4-byte entry, no t' anywhere
-                    {
-                        fe_limbs *fa4 = reinterpret_cast<fe_limbs *>(smask + hn) + hn, *fd4 = fa4 + 4 * (size_t)hn;   // after K2A, K2C
-                        hipLaunchKernelGGL(k_sc_r2s_factors<ScCtx<C>::F>, dim3(ceil_div(hn, 256)), dim3(256), 0, c->stream, (const fe_limbs *)v.f0, (const fe_limbs *)v.f1,
-                                           (const fe_limbs *)v.fd, hn, rr, fa4, fd4);
-                        const fe256 *T0 = c->T0.template as<fe256>();
-                        for (u32 b = 0; b < 4; ++b) {
-                            const auto &S = c->st_d8[b][0];
-                            const fe_limbs *fab = fa4 + (size_t)b * hn, *fdb = fd4 + (size_t)b * hn;
-                            if (S.n) {
-                                const dim3 gs = sc_list_grid<C>(c, S.n);
-                                hipLaunchKernelGGL((k_sc_r1s_rows<ScCtx<C>::F, false>), gs, dim3(256), 0, c->stream, T0, (const u32 *)c->st_s32.template as<u32>(), c->r1_lo,
-                                                   b * hn, b & 1u, lists + S.off, S.n, fab, fdb, (const fe256 *)v.fl, part);
-                                blocks += gs.x * gs.y;
-                            }
-                        }
-                        ScConstSets sets = {};
-                        u32 kb = 0;
-                        for (u32 b = 0; b < 4; ++b) {
-                            const auto &K = c->st_d8[b][1];
-                            sets.row_off[b] = b * hn; sets.side[b] = b & 1u; sets.nlist[b] = K.n; sets.list[b] = lists + K.off;
-                            sets.fa[b] = fa4 + (size_t)b * hn; sets.fd[b] = fd4 + (size_t)b * hn;
-                            kb = std::max(kb, ceil_div(K.n, 256));
-                        }
-                        if (kb) {
-                            hipLaunchKernelGGL(k_sc_r1s_const<ScCtx<C>::F>, dim3(kb, 4), dim3(256), 0, c->stream, T0, c->r1_lo, sets,
-                                               (const fe256 *)c->st_sumfl.template as<fe256>(), part);
-                            blocks += 4 * kb;
-                        }
-                    }
-                    if (c->st_frest.n) {
-                        if (ident) cs(k_sc_r1_fold_coeffs_cs<ScCtx<C>::F, false, true>, c->st_frest, gr);
-                        else cs(k_sc_r1_fold_coeffs_cs<ScCtx<C>::F, true, true>, c->st_frest, gr);
-                    }
-                    if (c->st_gen.n) {
-                        general(lists + c->st_gen.off, c->st_gen.n, gg, part);
-                        blocks += gg.x * gg.y;
-                    }
-                    if (c->r1_nq)                        // the few entries of t' the masses of the next round read
-                        hipLaunchKernelGGL(k_sc_defer_points<ScCtx<C>::F>, dim3(ceil_div(2 * c->r1_nq, 256)), dim3(256), 0, c->stream, (const u32 *)c->st_s32.template as<u32>(),
-                                           c->T.template as<fe256>(), c->r1_lo, hn, (u32)(pow / 2), (const u32 *)c->r1mq.template as<u32>(), c->r1_nq, rr,
-                                           (const fe_limbs *)ka, (const fe_limbs *)kc, (const u32 *)smask);
-                    c->defer_on = true;
-                    c->defer_r1 = rr;
-                    c->defer_pow = pow / 2;
-                    c->defer_hq = hn;
-                } else {
-                if (c->st_fast.n) {
-                    if (ident)
-                        hipLaunchKernelGGL((k_sc_r1_fold_coeffs_cs<ScCtx<C>::F, false>), gf, dim3(256), 0, c->stream, (const u32 *)c->st_s32.template as<u32>(),
-                                           c->T.template as<fe256>(), c->r1_lo, hn, lists + c->st_fast.off, c->st_fast.n, rr, (const fe_limbs *)ka, (const fe_limbs *)kc,
-                                           (const u32 *)smask, (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl, part);
-                    else
-                        hipLaunchKernelGGL((k_sc_r1_fold_coeffs_cs<ScCtx<C>::F, true>), gf, dim3(256), 0, c->stream, (const u32 *)c->st_s32.template as<u32>(),
-                                           c->T.template as<fe256>(), c->r1_lo, hn, lists + c->st_fast.off, c->st_fast.n, rr, (const fe_limbs *)ka, (const fe_limbs *)kc,
-                                           (const u32 *)smask, (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl, part);
-                    blocks += gf.x * gf.y;
-                }
-                if (c->st_gen.n) {
-                    general(lists + c->st_gen.off, c->st_gen.n, gg, part);
-                    blocks += gg.x * gg.y;
-                }
-                }
-            } else if (second) {
-                // hn = an eighth of the pristine rows = half of defer_hq: g < hn; st_f8 from the sources, st_g8 from the dense rows
-                c->defer_on = false;
-                const u32 hq = c->defer_hq;
-                const u32 *lists = c->st_lists.template as<u32>();
-                fe_limbs *ka = c->st_k.template as<fe_limbs>(), *kc = ka + hq;
-                u32 *smask = reinterpret_cast<u32 *>(kc + hq);
-                fe_limbs *k2a = reinterpret_cast<fe_limbs *>(smask + hq), *k2c = k2a + hn;
-                const dim3 g8 = sc_list_grid<C>(c, c->st_f8.n), gg = sc_list_grid<C>(c, c->st_g8.n);
-                hipLaunchKernelGGL(k_sc_r2_kprep<ScCtx<C>::F>, dim3(ceil_div(hn, 256)), dim3(256), 0, c->stream, (const fe_limbs *)ka, (const fe_limbs *)kc, hn, rr, k2a, k2c);
-                if (ident)
-                    hipLaunchKernelGGL((k_sc_r2_fold_coeffs_cs<ScCtx<C>::F, false>), g8, dim3(256), 0, c->stream, (const u32 *)c->st_s32.template as<u32>(), c->T.template as<fe256>(),
-                                       c->r1_lo, hq, lists + c->st_f8.off, c->st_f8.n, c->defer_r1, rr, (const fe_limbs *)k2a, (const fe_limbs *)k2c, (const u32 *)smask,
-                                       (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl, part);
-                else
-                    hipLaunchKernelGGL((k_sc_r2_fold_coeffs_cs<ScCtx<C>::F, true>), g8, dim3(256), 0, c->stream, (const u32 *)c->st_s32.template as<u32>(), c->T.template as<fe256>(),
-                                       c->r1_lo, hq, lists + c->st_f8.off, c->st_f8.n, c->defer_r1, rr, (const fe_limbs *)k2a, (const fe_limbs *)k2c, (const u32 *)smask,
-                                       (const fe_limbs *)v.f0, (const fe_limbs *)v.f1, (const fe_limbs *)v.fd, (const fe256 *)v.fl, part);
-                blocks += g8.x * g8.y;
-                if (c->st_g8.n) {
-                    general(lists + c->st_g8.off, c->st_g8.n, gg, part);
-                    blocks += gg.x * gg.y;
-                }
-            } else {
-                general(nullptr, 0, grid, part);
-                blocks = grid.x * grid.y;
-            }
-            c->fresh = false;
-            c->valid_t = c->valid_e = pow;
-            return sc_r1_finish<C>(c, blocks, pow / 2, out3_host, ident ? &rr : nullptr);
-        }
-        // last rank-one round (FH bits used up, or the tables are small now): fold T, write the live entries of EQ out, and
-        // take the next sums with the dense kernel
-        REEF_TRY(sc_r1_prep<C>(c, &rr, pow));
-        const u32 fb = (u32)std::min<size_t>(4096, std::max<size_t>(1, ceil_div(pow, 256)));
-        hipLaunchKernelGGL(k_sc_r1_fold<ScCtx<C>::F>, dim3(fb), dim3(256), 0, c->stream, (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(),
-                           c->T.template as<fe256>(), (u32)pow, rr);
-        c->fresh = false;
-        c->valid_t = c->valid_e = pow;
+    switch (p.route) {
+    case SC_FC_R1: case SC_FC_STRUCT: case SC_FC_DEFER: case SC_FC_SECOND: return sc_fc_rank1<C>(c, p, pow, rr, out3_host);
+    case SC_FC_LAST_R1:                  // fold T, write the live entries of EQ out, and take the next sums with the dense kernel
+        REEF_TRY(sc_r1_fold<C>(c, p, pow, rr));
         REEF_TRY(sc_r1_materialize<C>(c));
-        const u32 cb = sc_dense_blocks<C>(c, pow / 2);
-        const bool one = sc_one_launch<C>(c, cb);
-        hipLaunchKernelGGL(k_sc_coeffs<ScCtx<C>::F>, dim3(cb), dim3(256), 0, c->stream, (const fe256 *)c->T.template as<fe256>(),
-                           (const fe256 *)c->E.template as<fe256>(), (u32)(pow / 2), c->partial.template as<unsigned long long>(),
-                           one ? c->gacc.template as<unsigned long long>() : nullptr, c->pinned3, one ? ++c->seq : 0u, c->sw.order);
-        return sc_dense_finish<C>(c, one, cb, out3_host);
+        return sc_dense_sums<C>(c, p, pow / 2, out3_host);
+    default: break;
     }
-    if (c->r1) REEF_TRY(sc_r1_materialize<C>(c));
+    if (p.materialize) REEF_TRY(sc_r1_materialize<C>(c));
     c->valid_t = c->valid_e = pow;
-    if (c->sw.one_launch && pow / 2 <= c->sw.split_max) {   // a small round: an item over four waves, always one launch
-        const u32 sb = (u32)std::min<size_t>(c->sw.split_blocks, std::max<size_t>(1, ceil_div(pow / 2, 64)));
-        hipLaunchKernelGGL(k_sc_fold_coeffs_split<ScCtx<C>::F>, dim3(sb), dim3(256), 0, c->stream, (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(),
-                           c->T.template as<fe256>(), c->E.template as<fe256>(), (u32)pow, rr, c->gacc.template as<unsigned long long>(), c->pinned3, ++c->seq, c->sw.order);
-        c->fresh = false;
-        return sc_dense_finish<C>(c, true, sb, out3_host);
-    }
-    const u32 blocks = sc_dense_blocks<C>(c, pow / 2);
-    const bool one = sc_one_launch<C>(c, blocks);
-    hipLaunchKernelGGL(k_sc_fold_coeffs<ScCtx<C>::F>, dim3(blocks), dim3(256), 0, c->stream, (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>(),
-                       c->T.template as<fe256>(), c->E.template as<fe256>(), (u32)pow, rr, c->partial.template as<unsigned long long>(),
-                       one ? c->gacc.template as<unsigned long long>() : nullptr, c->pinned3, one ? ++c->seq : 0u, c->sw.order);
+    const fe256 *Tsrc = (const fe256 *)(c->fresh ? c->T0 : c->T).template as<fe256>();
+    const bool one = p.one_launch;
+    if (p.route == SC_FC_SPLIT)
+        hipLaunchKernelGGL(k_sc_fold_coeffs_split<ScCtx<C>::F>, dim3(p.blocks), dim3(256), 0, c->stream, Tsrc, c->T.template as<fe256>(), c->E.template as<fe256>(),
+                           (u32)pow, rr, c->gacc.template as<unsigned long long>(), c->pinned3, ++c->seq, c->sw.order);
+    else
+        hipLaunchKernelGGL(k_sc_fold_coeffs<ScCtx<C>::F>, dim3(p.blocks), dim3(256), 0, c->stream, Tsrc, c->T.template as<fe256>(), c->E.template as<fe256>(), (u32)pow,
+                           rr, c->partial.template as<unsigned long long>(), one ? c->gacc.template as<unsigned long long>() : nullptr, c->pinned3,
+                           one ? ++c->seq : 0u, c->sw.order);
     c->fresh = false;
-    return sc_dense_finish<C>(c, one, blocks, out3_host);
+    return sc_dense_finish<C>(c, one, p.blocks, out3_host);
 }
 
 // gen_eq_table into the ctx's EQ table: rs has nq + 1 entries, last_q has ell = log2(len) entries
@@ -891,7 +719,7 @@ static reef_status v_sc_gen_eq(void *impl, const reef_fe *rs, const uint32_t *qs
     hipLaunchKernelGGL(k_sc_eq_factors<ScCtx<C>::F>, dim3(ceil_div(nfac, 256)), dim3(256), 0, c->stream, d_lq, (u32)ell, lo_bits, rs_last, fac_hi,
                        fac_lo);
     c->r1 = false;
-    if (hi_bits >= 1 && c->sw.rank1 && c->len / 2 >= c->sw.r1_min_pow) {
+    if (sc_eq_rank1(c->len, c->sw)) {
         // EQ stays FH (x) FL + masses (sumcheck_kernels.inc): nothing of 2^ell entries is written here
         c->r1_lo = lo_bits;
         c->r1_hi = c->r1_hi0 = hi_bits;
@@ -907,7 +735,7 @@ static reef_status v_sc_gen_eq(void *impl, const reef_fe *rs, const uint32_t *qs
         c->r1 = true;
         REEF_TRY(sc_r1_prep<C>(c, nullptr, c->len / 2));
     } else {
-        hipLaunchKernelGGL(k_sc_eq_table<ScCtx<C>::F>, dim3((u32)std::min<size_t>(4096, ceil_div(c->len, 256))), dim3(256), 0, c->stream, fac_hi, fac_lo,
+        hipLaunchKernelGGL(k_sc_eq_table<ScCtx<C>::F>, dim3(sc_fold_blocks(c->len)), dim3(256), 0, c->stream, fac_hi, fac_lo,
                            (u32)ell, lo_bits, c->E.template as<fe256>());
         if (nq) hipLaunchKernelGGL(k_sc_eq_points<ScCtx<C>::F>, dim3(ceil_div(nq, 64)), dim3(64), 0, c->stream, d_rs, (const u32 *)d_qs, (u32)nq,
                                    c->E.template as<fe256>());

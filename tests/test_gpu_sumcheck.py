@@ -440,6 +440,44 @@ def test_deferred_first_fold(kind, ell, nq, interrupt, gpu_lib, either_build, mo
                 assert sc.read(0, 1) == [tt[0]] and sc.read(1, 1) == [ee[0]], (kind, defer, step)
 
 
+@pytest.mark.parametrize("case", ["fold-while-deferred", "coeffs-after-second-fold", "last-rank-one-round-two-launches"])
+def test_round_plans_no_other_test_reaches(case, gpu_lib, experiment_build, monkeypatch):
+    """Three plans of sc_round_plan (sumcheck_plan.h) that the cases above do not reach, by the host walk of tests/test_sc_plan_host.py: the
+    unfused fold arriving while a first fold is deferred (flush, then the rank-one fold), stand-alone coefficients right after the second
+    fold (so the fused call that follows spares a sum by the identity), and the last rank-one round of a step whose dense sums take a second
+    kernel (REEF_SC_ONE_LAUNCH=0).  The hybrid table at ell = 7 is the smallest whose deferred fold leaves both st.f8 and st.g8 with rows
+    (16 rows: a W row in one eighth).  Every round's coefficients against the oracle."""
+    from reef_amd.sumcheck import SumCheck
+    monkeypatch.setenv("REEF_SC_RANK1_MIN_POW", "1")
+    if case == "last-rank-one-round-two-launches":
+        monkeypatch.setenv("REEF_SC_ONE_LAUNCH", "0")
+    kind, ell, nq, q = "hybrid", 7, 3, Q
+    rng = SplitMix64(ell * 7919 + nq)
+    t = _structured_table(kind, ell, rng, q)
+    n = 1 << ell
+    qs = [n - 1, rng.next() % n, n // 2 + 1]                    # masses in the (small / constant) second half
+    rs = [uniform_scalar(rng, q) for _ in range(nq + 1)]
+    last_q = [uniform_scalar(rng, q) for _ in range(ell)]
+    tt, ee = list(t), gen_eq_table(rs, qs, last_q, q)
+    with SumCheck("pallas", ell) as sc:
+        sc.set_table(0, t)
+        sc.gen_eq_table(rs, qs, last_q)
+        g = sc.round_coeffs(1)
+        for i in range(1, ell + 1):
+            assert g == linear_mle_coeffs(tt, ee, ell, i, q), (case, i)
+            r = uniform_scalar(rng, q)
+            linear_mle_fold(tt, ee, ell, i, r, q)
+            if i == ell or (i == 2 and case == "fold-while-deferred"):
+                sc.fold(i, r)
+                if i < ell:
+                    g = sc.round_coeffs(i + 1)
+            else:
+                g = sc.fold_and_next_coeffs(i, r)
+            if i == 2 and case == "coeffs-after-second-fold":
+                assert sc.round_coeffs(3) == g
+        assert sc.read(0, 1) == [tt[0]] and sc.read(1, 1) == [ee[0]], case
+
+
 @pytest.mark.parametrize("kind,ell,nq", [("hybrid", 10, 7), ("mixed", 9, 4)])
 def test_gen_eq_before_set_table_gives_the_same_step(kind, ell, nq, gpu_lib, experiment_build, monkeypatch):
     """The results do not depend on the order of the calls (include/reef_msm.h 3b): gen_eq_table FIRST, then a structured table --
